@@ -9,12 +9,17 @@ IC_Angle, rBRIEF) plus the brute-force Hamming match against the previous frame 
 ratio 0.9, rotation check) — batch 1, the tracking-thread regime. value = frames/s summed over
 ranks (weak scaling: every rank streams its own frames, no collective on the data path).
 
-Extra lines in the same JSON object (rank 0): C3 (1280x720 batch 64 extract + 63-pair match),
+A plain run sets up the camera streams, warms up, times the K steps, writes the last step's
+outputs when --dump-outputs DIR is given, and prints the headline line. Everything else is
+behind --full, as extra entries of the same JSON object (rank 0): the strict batch-1 and
+one-camera figures, C3 (1280x720 batch 64 extract + 63-pair match),
 C4 LocalBundleAdjustment (50 KF / 2000 pts / 8000 obs, 10 LM iterations, host API incl.
-H2D/D2H) in LBA/s == KF/s, the roofline of the dominant kernel measured live with HIP events
-on its launch stream, and the CPU baseline (oracle/ restatement timed on this host's cores).
+H2D/D2H) in LBA/s == KF/s, C5, the 8f rows, the roofline of the dominant kernel measured live
+with HIP events on its launch stream, and the CPU baseline (oracle/ restatement timed on this
+host's cores).
 
-Usage: python bench.py [--gpus N --steps K --warmup W]  (torchrun for N > 1)
+Usage: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+(torchrun for N > 1)
 """
 from __future__ import annotations
 
@@ -45,13 +50,19 @@ def kernel_symbol(stage, batch):
             6: "k_match_finish"}[stage]
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200, help="timed steps (one frame per camera each)")
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-extra", action="store_true", help="skip the C3 / LBA extra lines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (every camera's keypoints, descriptors and "
+                         "matches) as DIR/<name>.npy (float32; rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure the stage replay and roofline, the batch-1 and "
+                         "one-camera figures, C3 / C4 / C5 / 8f and the CPU baselines (the options below)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the C3 / LBA extra lines")
     ap.add_argument("--c3-steps", type=int, default=10)
     ap.add_argument("--c3-inflight", type=int, default=8,
                     help="C3 batches in flight (each its own context and stream)")
@@ -66,7 +77,10 @@ def parse():
                     help="seconds for the extras (C3/C4/C5/8f) before the watchdog prints the headline")
     ap.add_argument("--detail", default=os.path.join("gpurun_out", "bench_detail.json"),
                     help="file for the full record (counters, stage tables); '' for none")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 # ORBHIP_BENCH_REHEARSAL=1: the N-rank flow on fewer GPUs than ranks (ranks share GPUs by LOCAL_RANK
@@ -253,11 +267,10 @@ class FrontendC2:
 
     def __init__(self, rank, inflight=1, cameras=1):
         import torch
-        from orb_slam3_ros2_amd import ORBextractor
         from orb_slam3_ros2_amd.frontend import FrameStream
         self.S, self.C = max(1, int(inflight)), max(1, int(cameras))
         self.fss = [FrameStream(self.W, self.H, self.S, 1000, 1.2, 8, 20, 7, 50, 0.9, True) for _ in range(self.C)]
-        self.ext = ORBextractor(1000, 1.2, 8, 20, 7)   # level tables for the roofline bytes only
+        self._ext = None
         self.frames_np = make_stream_frames(self.NF, self.W, self.H, 1000 * rank + 1)
         self.frames = torch.from_numpy(self.frames_np).to("cuda")
         p = [self.frames[i].data_ptr() for i in range(self.NF)]
@@ -270,6 +283,14 @@ class FrontendC2:
     @property
     def frames_per_step(self):
         return self.C
+
+    @property
+    def ext(self):
+        """Level tables for the roofline bytes, and the context of the --full extras."""
+        if self._ext is None:
+            from orb_slam3_ros2_amd import ORBextractor
+            self._ext = ORBextractor(1000, 1.2, 8, 20, 7)
+        return self._ext
 
     def push_one(self, c):
         slot = self.pushes[c](self.p_frames[c][self.k % self.NF], self.W)
@@ -287,6 +308,31 @@ class FrontendC2:
         c, slot = self.last
         self.fss[c].wait(slot)
         return int(self.fss[c].view(slot)["nmatch"].item())
+
+    def last_outputs(self):
+        """What the last step computed, as a caller of the front-end receives it: for every camera
+        the slot of its last frame (keypoints (cap, 6): x, y, size, angle, response, octave;
+        descriptors (cap, 32), their count n, the mono count) and that frame's match against the
+        camera's previous frame (per query, i.e. per keypoint of the previous frame: matched
+        index, best and second distance; nmatch).
+        Arrays over the cameras; rows past n and queries past the previous frame's n, which the
+        library leaves as they were, are written as 0 and -1."""
+        import torch
+        torch.cuda.synchronize()
+        names = ("kps", "desc", "n", "mono", "match", "best", "second", "nmatch")
+        out = {k: [] for k in names}
+        for fs in self.fss:
+            slot = (self.k - 1) % fs.slots
+            v = {k: t.cpu().numpy() for k, t in fs.view(slot).items() if k in names}
+            n = int(v["n"][0])
+            nq = int(fs.view((slot - 1) % fs.slots)["n"].item()) if self.k >= 2 else 0
+            v["kps"][:, 5] = v["kps"][:, 5].view(np.int32)   # the record's octave field is an int32
+            v["kps"][n:], v["desc"][n:] = 0, 0
+            for k in ("match", "best", "second"):
+                v[k][nq:] = -1
+            for k in names:
+                out[k].append(v[k])
+        return {k: np.stack(a) for k, a in out.items()}
 
     def mean_keypoints(self):
         import torch
@@ -758,17 +804,11 @@ class Watchdog:
 
 
 def c2_headline(args, ws, rank):
-    """C2 camera streams: K timed steps of one frame per camera; then a stage replay of the same
-    16-camera stream, untimed, in which camera c's contexts time stage (c mod 5) + 1 with the
-    stage timer (execution-only: the kernels carry the events, StageTimer in orbhip_kernels.h),
-    so every stage's average kernel duration comes from launches under the timed region's own
-    concurrency and the dominant kernel is the one rocprofv3's kernel trace of this C2 section
-    ranks first; then the strict batch-1 figure (one camera, one frame at a time) and one camera
-    with 8 frames in flight."""
+    """C2 camera streams: K timed steps of one frame per camera, then (--dump-outputs) the last
+    step's outputs. Returns the headline figures and the camera streams, still open."""
     import torch
     K, W = args.steps, args.warmup
     c2 = FrontendC2(rank, args.inflight, args.cameras)
-    seq = FrontendC2(rank, 1, 1)
     # ---- timed region (no stage timer open: the frames replay as launch graphs) ----
     for _ in range(W):
         c2.step()
@@ -781,6 +821,31 @@ def c2_headline(args, ws, rank):
     _barrier(ws)
     elapsed = _max_over_ranks(ws, time.perf_counter() - t0)
     frames_total = _sum_over_ranks(ws, float(K * c2.frames_per_step))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, c2.last_outputs())
+    r = {"value": frames_total / elapsed, "elapsed": elapsed, "frames_per_step": c2.frames_per_step,
+         "cameras": c2.C, "inflight": c2.S, "host_submit_ms_per_frame": 1e3 * t_enq / (K * c2.frames_per_step)}
+    return r, c2
+
+
+def dump_outputs(path, arrays):
+    """arrays as path/<name>.npy, float32 (every value is an integer below 2^24 or a float32)."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
+def c2_detail(args, ws, rank, c2, r):
+    """--full, after the timed region: a stage replay of the same
+    16-camera stream, untimed, in which camera c's contexts time stage (c mod 5) + 1 with the
+    stage timer (execution-only: the kernels carry the events, StageTimer in orbhip_kernels.h),
+    so every stage's average kernel duration comes from launches under the timed region's own
+    concurrency and the dominant kernel is the one rocprofv3's kernel trace of this C2 section
+    ranks first; then the strict batch-1 figure (one camera, one frame at a time) and one camera
+    with 8 frames in flight. Adds its figures to r and closes the camera streams."""
+    import torch
+    K, W = args.steps, args.warmup
+    seq = FrontendC2(rank, 1, 1)
     # ---- stage replay: K more steps of the same stream, every stage timed on its own cameras ----
     profs = []
     for c, fs in enumerate(c2.fss):
@@ -801,10 +866,8 @@ def c2_headline(args, ws, rank):
         a[1] += n
     stage_ms = {st: a[0] / a[1] for st, a in sorted(acc.items()) if a[1]}
     dom = max(stage_ms, key=stage_ms.get)
-    r = {"value": frames_total / elapsed, "elapsed": elapsed, "frames_per_step": c2.frames_per_step,
-         "cameras": c2.C, "inflight": c2.S, "host_submit_ms_per_frame": 1e3 * t_enq / (K * c2.frames_per_step),
-         "keypoints": c2.mean_keypoints(), "nmatch": c2.last_matches(), "stage_ms": stage_ms, "dom": dom,
-         "dom_avg_ms": stage_ms[dom], "dom_n": acc[dom][1]}
+    r.update({"keypoints": c2.mean_keypoints(), "nmatch": c2.last_matches(), "stage_ms": stage_ms, "dom": dom,
+              "dom_avg_ms": stage_ms[dom], "dom_n": acc[dom][1]})
     r["dom_bytes"] = c2.stage_bytes()[dom]
     r["octree_candidates_per_frame"] = c2.n_cand
     r["frames_np"] = c2.frames_np
@@ -1072,23 +1135,15 @@ def c4_lba(args, ws, rank, ctx):
     return out
 
 
-def main():
-    args = parse()
+def main(argv=None):
+    args = parse(argv)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(_spawn_ranks(args))
     ws, rank, local = _dist_setup(args)
     if ws != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={ws}")
-    r = c2_headline(args, ws, rank)
-    K, W, dom = args.steps, args.warmup, r["dom"]
-    # algorithmic bytes per frame = A0 + 2 sum_{l>=1} A_l + N * 56 (1,649,864 B at
-    # 640x480 and N = 1000), one frame per launch of the dominant kernel; the kernel's own bytes
-    # (stage_bytes) ride along as kernel_own_bytes
-    frame_bytes = survey_frame_bytes(r["ext"], StreamC2.W, StreamC2.H, r["keypoints"] or 1000.0)
-    achieved = frame_bytes / (r["dom_avg_ms"] * 1e-3) / 1e9
-    own = r["dom_bytes"] / (r["dom_avg_ms"] * 1e-3) / 1e9
-    ks = kernel_symbol(dom, 1)
-    host = host_cpus()
+    r, c2 = c2_headline(args, ws, rank)
+    K, W = args.steps, args.warmup
     out = {
         "metric": "frames/sec ORB extract+match @640×480; KF/sec LocalBA (50 KF, 2k pts)",
         "value": round(r["value"], 2),
@@ -1102,19 +1157,45 @@ def main():
         "vs_baseline": None,
         "dtype": "u8",
         "data": "synthetic (SURVEY.md 8d rectangles + sigma-4 noise; a camera panning over one static scene, seeded)",
-        "batch1_frames_per_s": round(1e3 / r["batch1_ms"], 1),
-        "batch1_latency_ms": round(r["batch1_ms"], 4),
         "config": {"workload": "C2: 640x480, 8-level pyramid, 1000 feat/frame, FAST 20/7, batch=1 per camera stream; "
                                "ORBextractor::operator() + brute-force Hamming match to the camera's previous frame",
                    "step": f"one frame on each of {r['cameras']} independent camera streams",
                    "frames_per_step": r["frames_per_step"],
                    "parallelism": f"replicas x{ws} (no collective); {r['cameras']} camera streams per GPU, batch 1 each",
                    "cameras": r["cameras"], "frames_in_flight_per_camera": r["inflight"],
-                   "batch1_latency_ms": round(r["batch1_ms"], 4),
-                   "batch1_frames_per_s": round(1e3 / r["batch1_ms"], 1),
-                   "one_camera_8_in_flight_frames_per_s": round(r["one_camera_inflight_fps"], 1),
-                   "host_submit_ms_per_frame": round(r["host_submit_ms_per_frame"], 4),
-                   "keypoints_per_frame": round(r["keypoints"], 1), "matches_last_pair": r["nmatch"]},
+                   "host_submit_ms_per_frame": round(r["host_submit_ms_per_frame"], 4)},
+    }
+    detail = None
+    if args.full:
+        full_record(args, ws, rank, c2, r, out)
+        if rank == 0:
+            detail = write_detail(out, args.detail)
+    else:
+        c2.close()
+    if rank == 0:
+        print(json.dumps(compact_line(out, detail)), flush=True)
+    if ws > 1:
+        import torch.distributed as dist
+        dist.destroy_process_group()
+
+
+def full_record(args, ws, rank, c2, r, out):
+    """--full: everything the bench measures beside the headline, added to `out`: the stage replay
+    and roofline of the C2 streams, the batch-1 and one-camera figures, the extras (C5, C3, C4, 8f)
+    under a watchdog, and the CPU baselines (one rank, unless --no-cpu)."""
+    c2_detail(args, ws, rank, c2, r)
+    dom = r["dom"]
+    # SURVEY.md §8(d): algorithmic bytes per frame = A0 + 2 sum_{l>=1} A_l + N * 56 (1,649,864 B at
+    # 640x480 and N = 1000), one frame per launch of the dominant kernel; the kernel's own bytes
+    # (stage_bytes) ride along as kernel_own_bytes
+    frame_bytes = survey_frame_bytes(r["ext"], StreamC2.W, StreamC2.H, r["keypoints"] or 1000.0)
+    achieved = frame_bytes / (r["dom_avg_ms"] * 1e-3) / 1e9
+    own = r["dom_bytes"] / (r["dom_avg_ms"] * 1e-3) / 1e9
+    ks = kernel_symbol(dom, 1)
+    host = host_cpus()
+    out.update({
+        "batch1_frames_per_s": round(1e3 / r["batch1_ms"], 1),
+        "batch1_latency_ms": round(r["batch1_ms"], 4),
         "roofline": {"kernel": ks, "bound": headline_bound(ks), "achieved": round(achieved, 3), "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 6),
                      "traffic": load_traffic(ks, "c2"), "counters": load_counters(ks, "c2"),
@@ -1132,7 +1213,11 @@ def main():
                      "stage_avg_ms": {STAGES[k]: round(v, 5) for k, v in r["stage_ms"].items()},
                      "stage_avg_ms_one_frame_stream": {STAGES[k]: round(v, 5)
                                                        for k, v in r["stage_ms_one_frame"].items()}},
-    }
+    })
+    out["config"].update({"batch1_latency_ms": round(r["batch1_ms"], 4),
+                          "batch1_frames_per_s": round(1e3 / r["batch1_ms"], 1),
+                          "one_camera_8_in_flight_frames_per_s": round(r["one_camera_inflight_fps"], 1),
+                          "keypoints_per_frame": round(r["keypoints"], 1), "matches_last_pair": r["nmatch"]})
     if not args.no_extra:
         wd = Watchdog(out, rank, args.extra_timeout, args.detail)
         extra = {}
@@ -1174,12 +1259,6 @@ def main():
             out["cpu_baseline"]["c3_sample"] = (f"{c3c['frames']} 1280x720 frames (16-frame stream, seed 5000), each "
                                                 f"extract + match to the previous frame, {c3c['cores']} threads, "
                                                 f"{c3c['wall']:.1f}s wall")
-    if rank == 0:
-        detail = write_detail(out, args.detail)
-        print(json.dumps(compact_line(out, detail)), flush=True)
-    if ws > 1:
-        import torch.distributed as dist
-        dist.destroy_process_group()
 
 
 def write_detail(out, path):
@@ -1208,10 +1287,11 @@ def compact_line(out, detail):
     cfg = out["config"]
     line["config"] = _pick(cfg, ("workload", "step", "frames_per_step", "parallelism", "cameras",
                                  "one_camera_8_in_flight_frames_per_s", "keypoints_per_frame"))
-    rf = out["roofline"]
-    line["roofline"] = _pick(rf, ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic",
-                                  "algorithmic_bytes_per_launch", "bytes_rule", "avg_launch_ms", "launches_timed",
-                                  "kernel_own_bytes"))
+    rf = out.get("roofline")
+    if rf is not None:
+        line["roofline"] = _pick(rf, ("kernel", "bound", "achieved", "peak", "unit", "frac", "traffic",
+                                      "algorithmic_bytes_per_launch", "bytes_rule", "avg_launch_ms", "launches_timed",
+                                      "kernel_own_bytes"))
     ex = out.get("extra")
     if ex is not None:
         e = {}

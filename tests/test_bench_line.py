@@ -52,6 +52,23 @@ def test_compact_line_keeps_figures_and_fits_the_tail():
     assert cb["value"] == 1180.0 and cb["cores"] == 16 and cb["kind"] == "port" and cb["c4_lba_kf_per_s"] == 770.0
 
 
+def test_plain_run_options_and_line():
+    """A plain run measures the headline only: --full is off unless given, and the line of a
+    record without the --full entries still carries the contract fields."""
+    args = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert (args.steps, args.warmup, args.full, args.dump_outputs) == (7, 3, False, None)
+    args = bench.parse(["--full", "--dump-outputs", "d"])
+    assert args.full and args.dump_outputs == "d"
+    plain = {k: v for k, v in _full_record().items()
+             if k not in ("roofline", "extra", "cpu_baseline", "batch1_frames_per_s", "batch1_latency_ms")}
+    line = bench.compact_line(plain, None)
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype",
+              "config"):
+        assert line[k] == plain[k] or k == "config"
+    assert line["detail"] is None and not {"roofline", "extra", "cpu_baseline"} & set(line)
+    json.dumps(line)
+
+
 def test_survey_frame_bytes_c2():
     """1,649,864 B per 640x480 frame at N = 1000 (the level areas of the
     ORBextractor ctor tables, checked against the oracle's own level geometry)."""

@@ -3,10 +3,11 @@
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
-mkdir -p gpurun_out
+O=${ORBHIP_OUT:-bench_out}
+mkdir -p $O
 for m in default 0; do
   if [ $m = default ]; then unset ORBHIP_DESC_MODE; else export ORBHIP_DESC_MODE=$m; fi
-  timeout -k 10 200 python3 -u bench.py --no-cpu --no-extra --steps 300 > gpurun_out/dm.log 2>&1 || exit 1
-  grep -v amdgpu.ids gpurun_out/dm.log | tail -1 | python3 -c "
+  timeout -k 10 200 python3 -u bench.py --full --no-cpu --no-extra --steps 300 > $O/dm.log 2>&1 || exit 1
+  grep -v amdgpu.ids $O/dm.log | tail -1 | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('desc_mode $m', d['value'], d['batch1_frames_per_s'])"
 done

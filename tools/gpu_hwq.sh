@@ -3,10 +3,11 @@
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 export TMPDIR=/tmp
-mkdir -p gpurun_out/hwq
+O=${ORBHIP_OUT:-bench_out}
+mkdir -p $O/hwq
 for q in 4 16 8 4 16; do
-  GPU_MAX_HW_QUEUES=$q timeout -k 10 200 python3 -u bench.py --no-cpu --no-extra > gpurun_out/hwq/q$q.log 2>&1 || { tail gpurun_out/hwq/q$q.log; exit 1; }
-  grep -v amdgpu.ids gpurun_out/hwq/q$q.log | tail -1 | python3 -c "
+  GPU_MAX_HW_QUEUES=$q timeout -k 10 200 python3 -u bench.py --full --no-cpu --no-extra > $O/hwq/q$q.log 2>&1 || { tail $O/hwq/q$q.log; exit 1; }
+  grep -v amdgpu.ids $O/hwq/q$q.log | tail -1 | python3 -c "
 import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']
 print('hwq $q value', d['value'], 'batch1_ms', d['batch1_latency_ms'], r['kernel'], r['avg_launch_ms'])
 print('  stages', r['stage_avg_ms'])"

@@ -10,7 +10,7 @@ rc=$?; tail -3 $O/pytest.log; [ $rc -eq 0 ] || { grep -E "FAILED|Error|assert" $
 timeout -k 10 180 rocprofv3 --kernel-trace --stats --output-format csv -d $O/c3prof -o c3 -- python3 tools/pmc_workload.py c3 > $O/c3prof.log 2>&1 || { tail -5 $O/c3prof.log; exit 1; }
 python3 tools/prof_summary.py stats "$(ls $O/c3prof/*kernel_stats.csv | head -1)" $O/c3_kernel_stats.md "tools/pmc_workload.py c3" || exit 1
 head -14 $O/c3_kernel_stats.md | tail -8
-timeout -k 10 400 python3 -u bench.py --no-cpu > $O/bench.log 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
+timeout -k 10 400 python3 -u bench.py --full --no-cpu > $O/bench.log 2> $O/bench.err || { tail -20 $O/bench.err; exit 1; }
 grep -v amdgpu.ids $O/bench.log | tail -1 > $O/bench.json
 python3 -c "
 import json; d=json.load(open('$O/bench.json')); r=d['roofline']; e=d['extra']

@@ -68,7 +68,7 @@ def sections(trace_csv, dst, warmup, steps):
     """Append to `dst` the C2 section's per-kernel averages split by bench phase.
 
     The camera streams are the streams with warmup + 2 * steps launches of a kernel (bench.py
-    c2_headline: W warmup frames, K timed frames, K stage-replay frames per camera); their
+    --full, c2_headline and c2_detail: W warmup frames, K timed frames, K stage-replay frames per camera); their
     launches are split in issue order. Everything else (the one-camera figures) is one row."""
     per = defaultdict(lambda: defaultdict(list))
     for r in csv.DictReader(open(trace_csv)):
