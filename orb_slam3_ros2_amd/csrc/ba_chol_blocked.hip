@@ -137,13 +137,17 @@ __device__ __forceinline__ void update_tile(double* __restrict__ S, int n, int r
     double av[8];
 #pragma unroll
     for (int kk = 0; kk < 8; kk++) av[kk] = -LI[(16 * wid + cc) * 34 + 4 * kk + rq];
+    // the panel's 32 products are summed from zero and meet C in one addition: summed into C itself
+    // each was rounded at C's magnitude (n roundings per entry over the factorization, not n / 32)
+    double4_t d[4];
 #pragma unroll
     for (int u = 0; u < 4; u++) {
+        d[u] = double4_t{0, 0, 0, 0};
         if (diag && u > wid) continue;   // strictly-upper 16x16 blocks of a diagonal tile
 #pragma unroll
         for (int kk = 0; kk < 8; kk++) {
             const double bv = LJ[(16 * u + cc) * 34 + 4 * kk + rq];
-            acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[kk], bv, acc[u], 0, 0, 0);
+            d[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[kk], bv, d[u], 0, 0, 0);
         }
     }
 #pragma unroll
@@ -152,7 +156,7 @@ __device__ __forceinline__ void update_tile(double* __restrict__ S, int n, int r
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             const int row = ri + 16 * wid + rq + 4 * q, col = rj + 16 * u + cc;
-            if (row < n && col < n) S[(size_t)row * n + col] = acc[u][q];
+            if (row < n && col < n) S[(size_t)row * n + col] = acc[u][q] + d[u][q];
         }
     }
 }

@@ -411,7 +411,12 @@ __device__ void dag_helper(const DagK& a, const Lay& L, __amdgpu_buffer_rsrc_t r
         const int type = upd ? 3 : (dRC >= 3 ? 2 : (dRC == 0 ? 0 : 1));
         const int ps = max(a.rf[R], a.rf[C]),
                   pe = upd ? a.nti : (dRC >= 3 ? C : (dRC == 2 ? C - 1 : (dRC == 1 ? C - 2 : C - 3)));
-        double4_t acc = s_quad(a, R, C, rq, cq);
+        // the columns' products are summed from zero and meet the tile of S in ONE addition below:
+        // summed into the tile itself, each of the 32 (pe - ps) products was rounded at the tile's
+        // magnitude (S's diagonal), a backward error growing with n (8.3 u at n = 2394 on a
+        // diagonally dominant S, where fp64 LAPACK has 2.1 u)
+        const double4_t a_rc = s_quad(a, R, C, rq, cq);
+        double4_t acc = {0, 0, 0, 0};
         const bool dg = type == 0 || (upd && dRC == 0);   // a diagonal tile: with its right-hand side
         const bool rhs = dg && cq == 0;
         const bool skip = dg && quad == 1;   // the upper quadrant of a diagonal tile: unused
@@ -447,6 +452,7 @@ __device__ void dag_helper(const DagK& a, const Lay& L, __amdgpu_buffer_rsrc_t r
             p += m;
         }
         if (fail) break;
+        acc += a_rc;
         int* target;
         if (type == 2) {
             if (wg_prefix(L.fCh + C, nullptr, nullptr, 1) == 0) break;

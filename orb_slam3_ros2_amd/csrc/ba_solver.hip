@@ -3161,12 +3161,14 @@ int ba_test_cholesky(const double* A, const double* b, double* x, int n, unsigne
     BAOK(hipEventRecord(e1, nullptr));
     BAOK(hipDeviceSynchronize());
     BAOK(hipEventElapsedTime(ms, e0, e1));
+    int fl = 0;
+    BAOK(hipMemcpy(&fl, df, sizeof(int), hipMemcpyDeviceToHost));
     BAOK(hipMemcpy(x, dx, sizeof(double) * n, hipMemcpyDeviceToHost));
     BAOK(hipMemcpy(phases5, dd, sizeof(unsigned long long) * 5, hipMemcpyDeviceToHost));
     (void)hipFree(dS); (void)hipFree(db_); (void)hipFree(dx); (void)hipFree(df); (void)hipFree(dd);
     (void)hipFree(dL);
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    return ORBHIP_OK;
+    return fl ? ORBHIP_OK : ORBHIP_ERR_NOT_PD;
 }
 
 }  // namespace orbhip

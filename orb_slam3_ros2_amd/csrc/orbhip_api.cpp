@@ -1522,7 +1522,7 @@ int orbhip_search_bow(orbhip_ctx* c, const uint8_t* kf_desc, const float* kf_ang
 // ---- test hooks (not part of the reference surface) ----
 int orbhip_test_cholesky(const double* A, const double* b, double* x, int n, unsigned long long* phases5,
                          float* ms) {
-    if (!A || !b || !x || n <= 0 || n > 480) return ORBHIP_ERR_ARG;
+    if (!A || !b || !x || !phases5 || !ms || n <= 0 || n > 480) return ORBHIP_ERR_ARG;
     return ba_test_cholesky(A, b, x, n, phases5, ms);
 }
 int orbhip_test_cholesky_reg(const double* A, const double* b, double* x, int n, int reps, float* ms,

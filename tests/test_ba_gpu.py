@@ -7,41 +7,17 @@ import numpy as np
 import pytest
 
 from orb_slam3_ros2_amd.synthetic import synthetic_ba_problem
+from tests.helpers import BAND_COND, REL, band_spd, check_solve, spd_with_spectrum
+from tests.helpers import compare_ba as _compare
+from tests.helpers import qsign as _qsign
 
 pytestmark = pytest.mark.gpu
-
-REL = 1e-4
 
 
 @pytest.fixture(scope="module")
 def opt():
     from orb_slam3_ros2_amd import Optimizer
     return Optimizer()
-
-
-def _qsign(q):
-    q = q.astype(np.float64)
-    return q * np.where(q[:, 3:4] < 0, -1.0, 1.0)
-
-
-def _compare(g, o, prob, exact_schedule=True):
-    # Run to full convergence, g2o stops on rho == 0 (bit-equal chi2 of two trials): where that
-    # happens depends on the last bits of the sums, so the schedule is compared only for runs
-    # that stop on the iteration budget (the LocalBundleAdjustment case, optimize(10)).
-    if exact_schedule:
-        assert g.iterations_done == o["iterations_done"] and g.lm_trials == o["lm_trials"]
-    assert abs(g.final_chi2 - o["final_chi2"]) <= REL * abs(o["final_chi2"])
-    dq = np.abs(_qsign(g.pose_q) - _qsign(o["pose_q"])).max()
-    tscale = max(1.0, np.abs(o["pose_t"]).max())
-    dt = np.abs(g.pose_t.astype(np.float64) - o["pose_t"]).max() / tscale
-    pscale = max(1.0, np.abs(o["points"]).max())
-    dp = np.abs(g.points.astype(np.float64) - o["points"]).max() / pscale
-    assert dq < REL and dt < REL and dp < REL, (dq, dt, dp)
-    gout = (g.edge_chi2 > 5.991) | (g.edge_depth_ok == 0)
-    oout = (o["edge_chi2"] > 5.991) | (o["edge_depth_ok"] == 0)
-    # flags may only differ for edges whose chi2 sits within rounding of the threshold
-    diff = np.nonzero(gout != oout)[0]
-    assert all(abs(o["edge_chi2"][e] - 5.991) < 1e-3 for e in diff)
 
 
 def test_lba_c4_parity(opt, oracle):
@@ -180,9 +156,12 @@ def test_batch_matches_single(opt, oracle):
 
 @pytest.mark.parametrize("n_kf,n_pts,window", [(100, 3000, 20), (90, 2500, 90)])
 def test_gba_blocked_cholesky_parity(opt, oracle, n_kf, n_pts, window):
-    """GlobalBundleAdjustment-sized reduced systems (n = 6*(n_kf-1) > 480) go through the blocked
-    multi-workgroup Cholesky: a keyframe loop with a 20-KF co-visibility window (banded S with a
-    loop-closure corner, tiles skipped by the envelope) and a fully co-visible set (dense S)."""
+    """GlobalBundleAdjustment-sized reduced systems (n = 6*(n_kf-1) = 594 / 534 > 480) solved alone:
+    since the persistent DAG solver became the default these sizes go through k_chol_dag (the name
+    dates from the blocked solver, which test_ba_dispatch_gpu.py::test_forced_blocked_solver_paths
+    now reaches through ORBHIP_CHOL_BLOCKED): a keyframe loop with a 20-KF co-visibility window
+    (banded S with a loop-closure corner, tiles skipped by the envelope) and a fully co-visible
+    set (dense S)."""
     from orb_slam3_ros2_amd.optimizer import BAProblem
     prob, _ = synthetic_ba_problem(n_kf=n_kf, n_pts=n_pts, layout="loop", window=window, seed=11)
     p = BAProblem(**{**prob.__dict__, "iterations": 10, "huber_delta": float(np.sqrt(5.99))})
@@ -214,16 +193,15 @@ def test_gba_c5_eight_landmark_shards_parity(opt, c5_case):
 def test_register_cholesky_solves_spd(n):
     """The register-resident LL^T (ba_chol_reg.hip, the C4 solver) on random SPD systems, well and
     badly conditioned (eigenvalues over 8 decades, like S + lambda I late in an LM run), against
-    numpy's fp64 solve: relative residual at rounding level."""
+    numpy's fp64 solve: relative residual at rounding level; and the yardstick of
+    tests/helpers.py::check_solve (backward error <= 8 u, forward error against a long-double
+    solve <= 8 cond u)."""
     import ctypes
     from orb_slam3_ros2_amd._lib import lib
     L = lib()
     rng = np.random.default_rng(n)
     for cond in (1e2, 1e8):
-        Q, _ = np.linalg.qr(rng.normal(size=(n, n)))
-        ev = np.geomspace(1.0, cond, n) * 1e3
-        A = (Q * ev) @ Q.T
-        A = 0.5 * (A + A.T)
+        A = spd_with_spectrum(n, cond, rng)
         b = rng.normal(size=n)
         x = np.zeros(n)
         ms = ctypes.c_float(0)
@@ -232,39 +210,34 @@ def test_register_cholesky_solves_spd(n):
         ref = np.linalg.solve(A, b)
         assert np.abs(A @ x - b).max() <= 1e-9 * np.abs(b).max() * cond / 1e2 + 1e-12
         assert np.abs(x - ref).max() <= 1e-13 * cond * np.abs(ref).max()
+        check_solve(A, x, b, cond)
 
 
-@pytest.mark.parametrize("n,shape", [(100, "dense"), (600, "dense"), (1201, "dense"), (900, "band"), (2394, "loop")])
+@pytest.mark.parametrize("n,shape", [(100, "dense"), (600, "dense"), (1201, "dense"), (900, "band"), (2394, "loop"),
+                                     (600, "cond1e8")])
 def test_blocked_cholesky_solves_spd(n, shape):
     """The multi-workgroup blocked solver (ba_chol_blocked.hip: one launch per 32-column panel,
     the panel rows recomputed by each update tile, the factor's panels transposed into the upper
     triangle, the backward solve over the envelope) on random SPD systems: dense, banded, and a
-    band plus a loop-closure corner (C5's shape), against numpy's fp64 solve."""
+    band plus a loop-closure corner (C5's shape), against numpy's fp64 solve; one system with
+    eigenvalues over 8 decades. Every case: backward error <= 8 u; n <= 600: forward error against
+    a long-double solve <= 8 cond u (check_solve)."""
     import ctypes
     from orb_slam3_ros2_amd._lib import lib
     L = lib()
     rng = np.random.default_rng(n)
-    if shape == "dense":
-        M = rng.normal(size=(n, n))
-        A = M @ M.T + n * np.eye(n)
-    else:
-        bw = 120
-        M = np.zeros((n, n))
-        for i in range(n):
-            lo = max(0, i - bw)
-            M[i, lo:i + 1] = rng.normal(size=i + 1 - lo)
-        if shape == "loop":   # the last 120 rows also couple to the first 120 columns
-            M[n - 120:, :120] = rng.normal(size=(120, 120)) * 0.3
-        A = M @ M.T + n * np.eye(n)
-    A = 0.5 * (A + A.T)
+    A = spd_with_spectrum(n, 1e8, rng) if shape == "cond1e8" else band_spd(n, shape, rng)
     b = rng.normal(size=n)
     x = np.zeros(n)
     ms = ctypes.c_float(0)
-    L.orbhip_test_cholesky_blocked.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_void_p]
     rc = L.orbhip_test_cholesky_blocked(A.ctypes.data, b.ctypes.data, x.ctypes.data, n, ctypes.byref(ms))
     assert rc == 0
+    if shape == "cond1e8":
+        check_solve(A, x, b, 1e8)
+        return
     ref = np.linalg.solve(A, b)
     assert np.abs(x - ref).max() <= 1e-10 * np.abs(ref).max()
+    check_solve(A, x, b, BAND_COND if n <= 600 else None)
 
 
 @pytest.mark.parametrize("n,shape,helpers,pback", [(31, "dense", 0, None), (64, "dense", 0, None),
@@ -276,7 +249,10 @@ def test_blocked_cholesky_solves_spd(n, shape):
                                                    (600, "band", 0, "1"), (1201, "dense", 0, None),
                                                    (1201, "dense", 5, None), (1201, "dense", 0, "0"),
                                                    (2394, "loop", 0, None), (2394, "loop", 7, None),
-                                                   (2394, "loop", 0, "1"), (2394, "dense", 0, None)])
+                                                   (2394, "loop", 0, "1"), (2394, "dense", 0, None),
+                                                   (96, "cond1e8", 0, None), (96, "cond1e8", 1, None),
+                                                   (294, "cond1e8", 0, None), (294, "cond1e8", 1, None),
+                                                   (600, "cond1e8", 0, None), (600, "cond1e8", 1, None)])
 def test_dag_cholesky_solves_spd(n, shape, helpers, pback, monkeypatch):
     """The persistent tiled-DAG solver (ba_chol_dag.hip: one launch, a chain workgroup on the
     diagonal path, helper workgroups on the off-diagonal tiles, flag hand-offs) on random SPD
@@ -286,52 +262,52 @@ def test_dag_cholesky_solves_spd(n, shape, helpers, pback, monkeypatch):
     rows go to the helpers). The chain's backward (r06: column copies written by the helpers' tasks,
     the last interval's operands from LDS, owner waves per column residue) at NT = 3 (the first
     copy task), with few helpers, and on band / loop envelopes whose rows skip columns. Against
-    numpy's fp64 solve; three solves in a row reuse the flags through the per-solve epoch."""
+    numpy's fp64 solve; three solves in a row reuse the flags through the per-solve epoch.
+    Systems with eigenvalues over 8 decades (S + lambda I late in an LM run) exercise the pivots'
+    reciprocal square roots (ORBHIP_DAG_NEWTON) where their rounding shows. Every case: backward
+    error <= 8 u; n <= 600: forward error against a long-double solve <= 8 cond u (check_solve)."""
     import ctypes
     from orb_slam3_ros2_amd._lib import lib
     if pback is not None:
         monkeypatch.setenv("ORBHIP_DAG_PBACK", pback)
     L = lib()
     rng = np.random.default_rng(n + helpers)
-    if shape == "dense":
-        M = rng.normal(size=(n, n))
-        A = M @ M.T + n * np.eye(n)
-    else:
-        bw = 120
-        M = np.zeros((n, n))
-        for i in range(n):
-            lo = max(0, i - bw)
-            M[i, lo:i + 1] = rng.normal(size=i + 1 - lo)
-        if shape == "loop":
-            M[n - 120:, :120] = rng.normal(size=(120, 120)) * 0.3
-        A = M @ M.T + n * np.eye(n)
-    A = 0.5 * (A + A.T)
+    A = spd_with_spectrum(n, 1e8, rng) if shape == "cond1e8" else band_spd(n, shape, rng)
     b = rng.normal(size=n)
     x = np.zeros(n)
     ms = ctypes.c_float(0)
     rc = L.orbhip_test_cholesky_dag(A.ctypes.data, b.ctypes.data, x.ctypes.data, n, 3, helpers, ctypes.byref(ms),
                                     None)
     assert rc == 0
+    if shape == "cond1e8":
+        check_solve(A, x, b, 1e8)
+        return
     ref = np.linalg.solve(A, b)
     assert np.abs(x - ref).max() <= 1e-11 * np.abs(ref).max()
+    check_solve(A, x, b, BAND_COND if n <= 600 else None)
 
 
 def test_dag_cholesky_non_spd_rejected():
-    """A matrix that is not positive definite: flag 0 (the LM rejects the trial), x = 0."""
+    """A matrix that is not positive definite: flag 0 (the LM rejects the trial), x = 0. The bad
+    pivot inside the chain's intervals (150), in the prologue's tile (0) and in the last column
+    (n - 1, the partial last tile). A bad pivot stops no hand-off: the chain runs every interval
+    and publishes every flag whatever the values, only its `ok` word clears flag[0] at the end."""
     import ctypes
     from orb_slam3_ros2_amd._lib import lib
     L = lib()
     n = 200
     rng = np.random.default_rng(5)
     M = rng.normal(size=(n, n))
-    A = M @ M.T + n * np.eye(n)
-    A[150, 150] = -1e6
+    A0 = M @ M.T + n * np.eye(n)
     b = rng.normal(size=n)
-    x = np.ones(n)
-    ms = ctypes.c_float(0)
-    rc = L.orbhip_test_cholesky_dag(A.ctypes.data, b.ctypes.data, x.ctypes.data, n, 1, 0, ctypes.byref(ms), None)
-    assert rc == -4
-    assert not x.any()
+    for pos in (150, 0, n - 1):
+        A = A0.copy()
+        A[pos, pos] = -1e6
+        x = np.ones(n)
+        ms = ctypes.c_float(0)
+        rc = L.orbhip_test_cholesky_dag(A.ctypes.data, b.ctypes.data, x.ctypes.data, n, 1, 0, ctypes.byref(ms), None)
+        assert rc == -4, pos
+        assert not x.any(), pos
 
 
 def test_device_lm_rejections_and_pops(opt, oracle):
