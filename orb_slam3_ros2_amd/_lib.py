@@ -203,6 +203,8 @@ def lib():
     L.orbhip_test_cholesky_reg.argtypes = [vp, vp, vp, i32, i32, ctypes.POINTER(f32), vp]
     L.orbhip_test_cholesky_blocked.argtypes = [vp, vp, vp, i32, ctypes.POINTER(f32)]
     L.orbhip_test_cholesky_dag.argtypes = [vp, vp, vp, i32, i32, i32, ctypes.POINTER(f32), vp]
+    # host only: the matcher's dispatch decision for a call shape (tests assert the route they mean to reach)
+    L.orbhip_test_match_route.argtypes = [i32, i32, i32, i32, vp]
     _lib = L
     return L
 

@@ -39,7 +39,6 @@ struct MatchView {
 
 constexpr int kTC = 256;     // train descriptors per workgroup chunk (64 per wave): batches
 constexpr int kTCSmall = 64; // 16 per wave: one pair (C2), where 256-chunks leave the chip idle
-constexpr int kFusedMaxPairs = 4;   // k_match_fused up to this many pairs (the sync scratch holds 64 ints each)
 
 // A chunk partial {best | second << 16, index} (8 B), or packed in 4 B while every train index
 // fits 14 bits (pk): best | second << 9 | index << 18 (index 0x3FFF when there is no best), which
@@ -464,18 +463,11 @@ static bool match_xcd_on() {
     return !(e && e[0] == '0');
 }
 
-static void run_match(const MatchView& v, int npairs, int max_q, int max_t, int th_low, float ratio,
-                      int check_orientation, int32_t* match, int32_t* best, int32_t* second, int32_t* nmatch,
-                      uint2* part, hipStream_t st, StageTimer* timer = nullptr, int* sync = nullptr) {
-    if (npairs <= 0) return;
+// Every dispatch threshold of the matcher lives here (run_match only follows the result).
+MatchRoute match_route(int npairs, int max_q, int max_t, bool fused_allowed) {
+    constexpr int kFusedMaxPairs = 4;   // k_match_fused up to this many pairs (the sync scratch holds 64 ints each)
     const char* unf = std::getenv("ORBHIP_MATCH_UNFUSED");   // A/B switch (read per call: tests flip it)
-    if (sync && npairs <= kFusedMaxPairs && !(unf && unf[0] && unf[0] != '0')) {
-        if (timer) timer->begin(5, st);
-        ORBHIP_LAUNCH(k_match_fused, dim3((unsigned)std::max(1, (max_q + kFQ - 1) / kFQ), npairs), dim3(1024),
-                           0, st, v, th_low, ratio, check_orientation, match, best, second, nmatch, sync);
-        if (timer) timer->end(5, st);
-        return;
-    }
+    if (fused_allowed && npairs <= kFusedMaxPairs && !(unf && unf[0] && unf[0] != '0')) return MatchRoute{0, 0, 0, 0};
     const int qblocks = (max_q + 63) / 64;
     // 16 trains per wave while 64 per wave would leave most of the chip idle (one pair)
     const bool small = (int64_t)npairs * qblocks * ((max_t + kTC - 1) / kTC) < 512;
@@ -483,27 +475,43 @@ static void run_match(const MatchView& v, int npairs, int max_q, int max_t, int 
     // chunks write fewer (query, chunk) partials
     const char* e_tc = std::getenv("ORBHIP_MATCH_TC");
     const int tcb = e_tc ? std::atoi(e_tc) : kTC;
-    const int tc = small ? kTCSmall : (tcb == 512 || tcb == 1024 ? tcb : kTC);
-    const int nch = std::max(1, (max_t + tc - 1) / tc);
-    const int pk = max_t <= 0x3FFF ? 1 : 0;   // 4-byte partials while train indices fit 14 bits
+    MatchRoute r;
+    r.tc = small ? kTCSmall : (tcb == 512 || tcb == 1024 ? tcb : kTC);
+    r.nch = std::max(1, (max_t + r.tc - 1) / r.tc);
+    // batches: whole pairs per XCD (ORBHIP_MATCH_XCD=0: the plain round-robin order)
+    r.xrun = !small && match_xcd_on() && npairs >= 8 ? qblocks * r.nch : 0;
+    r.pk = max_t <= 0x3FFF ? 1 : 0;   // 4-byte partials while train indices fit 14 bits
+    return r;
+}
+
+static void run_match(const MatchView& v, int npairs, int max_q, int max_t, int th_low, float ratio,
+                      int check_orientation, int32_t* match, int32_t* best, int32_t* second, int32_t* nmatch,
+                      uint2* part, hipStream_t st, StageTimer* timer = nullptr, int* sync = nullptr) {
+    if (npairs <= 0) return;
+    const MatchRoute r = match_route(npairs, max_q, max_t, sync != nullptr);
+    if (r.tc == 0) {
+        if (timer) timer->begin(5, st);
+        ORBHIP_LAUNCH(k_match_fused, dim3((unsigned)std::max(1, (max_q + kFQ - 1) / kFQ), npairs), dim3(1024),
+                           0, st, v, th_low, ratio, check_orientation, match, best, second, nmatch, sync);
+        if (timer) timer->end(5, st);
+        return;
+    }
+    const int qblocks = (max_q + 63) / 64;
     if (timer) timer->begin(5, st);
     if (qblocks > 0 && max_t > 0) {
-        if (small)
-            ORBHIP_LAUNCH(k_match_top2<kTCSmall>, dim3(qblocks, nch, npairs), dim3(256), 0, st, v, part, nch,
-                               max_q, 0, pk);
-        else if (tc == 1024)   // batches: whole pairs per XCD (ORBHIP_MATCH_XCD=0: the plain round-robin order)
-            ORBHIP_LAUNCH(k_match_top2<1024>, dim3(qblocks, nch, npairs), dim3(256), 0, st, v, part, nch, max_q,
-                          match_xcd_on() && npairs >= 8 ? qblocks * nch : 0, pk);
-        else if (tc == 512)
-            ORBHIP_LAUNCH(k_match_top2<512>, dim3(qblocks, nch, npairs), dim3(256), 0, st, v, part, nch, max_q,
-                          match_xcd_on() && npairs >= 8 ? qblocks * nch : 0, pk);
+        const dim3 grid(qblocks, r.nch, npairs);
+        if (r.tc == kTCSmall)
+            ORBHIP_LAUNCH(k_match_top2<kTCSmall>, grid, dim3(256), 0, st, v, part, r.nch, max_q, r.xrun, r.pk);
+        else if (r.tc == 1024)
+            ORBHIP_LAUNCH(k_match_top2<1024>, grid, dim3(256), 0, st, v, part, r.nch, max_q, r.xrun, r.pk);
+        else if (r.tc == 512)
+            ORBHIP_LAUNCH(k_match_top2<512>, grid, dim3(256), 0, st, v, part, r.nch, max_q, r.xrun, r.pk);
         else
-            ORBHIP_LAUNCH(k_match_top2<kTC>, dim3(qblocks, nch, npairs), dim3(256), 0, st, v, part, nch, max_q,
-                          match_xcd_on() && npairs >= 8 ? qblocks * nch : 0, pk);
+            ORBHIP_LAUNCH(k_match_top2<kTC>, grid, dim3(256), 0, st, v, part, r.nch, max_q, r.xrun, r.pk);
     }
     if (timer) { timer->end(5, st); timer->begin(6, st); }
-    ORBHIP_LAUNCH(k_match_finish, dim3(npairs), dim3(1024), 0, st, v, part, nch, max_q, tc, th_low, ratio,
-                       check_orientation, match, best, second, nmatch, pk);
+    ORBHIP_LAUNCH(k_match_finish, dim3(npairs), dim3(1024), 0, st, v, part, r.nch, max_q, r.tc, th_low, ratio,
+                       check_orientation, match, best, second, nmatch, r.pk);
     if (timer) timer->end(6, st);
 }
 

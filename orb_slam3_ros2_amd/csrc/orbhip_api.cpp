@@ -1559,6 +1559,16 @@ int orbhip_test_nd_stages(const double* A, const double* b, double* x, int np, c
     return nd_test(A, b, x, np, bi, bj, nblk, K, reps, ms, K_used, stage_ms, seg_out);
 }
 
+// host only (no device): the matcher's dispatch decision (match_route, the function run_match
+// follows) for a call shape. out4 = {trains per chunk (0 = k_match_fused), chunks per pair,
+// xcd_runs run length, 4-byte partials}
+int orbhip_test_match_route(int npairs, int max_q, int max_t, int fused_allowed, int32_t* out4) {
+    if (!out4 || npairs <= 0 || max_q < 0 || max_t < 0) return ORBHIP_ERR_ARG;
+    const MatchRoute r = match_route(npairs, max_q, max_t, fused_allowed != 0);
+    out4[0] = r.tc; out4[1] = r.nch; out4[2] = r.xrun; out4[3] = r.pk;
+    return ORBHIP_OK;
+}
+
 int orbhip_test_sincosf(const float* x, float* cs, float* sn, int64_t n) {
     if (!x || !cs || !sn || n <= 0) return ORBHIP_ERR_ARG;
     float *dx = nullptr, *dc = nullptr, *ds = nullptr;

@@ -133,6 +133,12 @@ void launch_desc(const ExtractPlan* dP, const ExtractPlan& hP, const FrameBufs& 
 // matcher's counters, reset by each launch); null = the two-kernel path
 constexpr int kMatchSyncInts = 64 * 4;
 size_t match_part_entries(int npairs, int max_q, int max_t);
+// The matcher's dispatch decision for a call of `npairs` pairs with at most max_q queries and
+// max_t trains each (host only; reads ORBHIP_MATCH_UNFUSED / _TC / _XCD per call). tc == 0:
+// k_match_fused (nch, xrun, pk unused, 0); else k_match_top2<tc> + k_match_finish with nch chunks
+// per pair, the xcd_runs run length xrun (0 = dispatch order) and pk = 4-byte partials.
+struct MatchRoute { int tc, nch, xrun, pk; };
+MatchRoute match_route(int npairs, int max_q, int max_t, bool fused_allowed);
 void launch_match_pairs(const orbhip_kp* kps, const uint8_t* desc, const int32_t* n, int npairs, int cap,
                         int th_low, float ratio, int check_orientation, int32_t* match, int32_t* best,
                         int32_t* second, int32_t* nmatch, void* part, hipStream_t st, StageTimer* timer,

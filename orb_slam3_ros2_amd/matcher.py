@@ -57,6 +57,20 @@ class ORBmatcher:
                                               ptr(match), ptr(best), ptr(second), ptr(nmatch), st),
               "orbhip_match_pairs_device")
 
+    def match_frames_device(self, q_kps, q_desc, nq, t_kps, t_desc, nt, match, best, second, nmatch, th_low=None,
+                            stream=None):
+        """Device tensors of two frames in separate allocations: kps (cap, 6) float32, desc (cap, 32)
+        uint8, nq / nt int32 device scalars; match / best / second (cap,) int32, nmatch (1,) int32."""
+        cap = q_desc.shape[0]
+        if t_desc.shape[0] != cap:
+            raise ValueError("match_frames_device: query and train capacities differ")
+        th = self.TH_LOW if th_low is None else int(th_low)
+        st = torch_stream(stream)
+        check(lib().orbhip_match_frames_device(self.ctx.handle, ptr(q_kps), ptr(q_desc), ptr(nq), ptr(t_kps),
+                                               ptr(t_desc), ptr(nt), cap, th, ctypes.c_float(self.mfNNratio),
+                                               int(self.mbCheckOrientation), ptr(match), ptr(best), ptr(second),
+                                               ptr(nmatch), st), "orbhip_match_frames_device")
+
     def SearchByBoW(self, kf_desc, kf_angle, kf_node, kf_weight, kf_valid, f_desc, f_angle, f_node, f_weight,
                     th_low: int | None = None):
         """U:src/ORBmatcher.cc::SearchByBoW(KeyFrame*, Frame&, vpMapPointMatches) on the GPU.

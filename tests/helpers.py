@@ -1,6 +1,7 @@
 """Shared test helpers: compare product keypoints/descriptors with the oracle's; the numerics of
 the dense-solver tests (SPD test matrices, a long-double reference solve, the backward error);
-the BA result comparison against the oracle."""
+the BA result comparison against the oracle; the brute-force matcher's route hook and data sets
+with matches planted by construction."""
 import numpy as np
 
 from orb_slam3_ros2_amd._lib import KP_DTYPE
@@ -148,3 +149,113 @@ def diff_report(gk, gd, ok, od, max_lines=10) -> str:
         if any(gk[f][i] != ok[f][i] for f in KP_DTYPE.names):
             lines.append(f"  [{i}] gpu={gk[i]} oracle={ok[i]}")
     return "\n".join(lines)
+
+
+# ---- the brute-force matcher: its dispatch route and data sets with matches by construction ----
+
+def match_route(npairs: int, max_q: int, max_t: int, fused_allowed: bool = True) -> dict:
+    """The matcher's dispatch decision for a call shape (the function run_match itself follows),
+    under the current ORBHIP_MATCH_* switches. kernel: "fused" or "tc64" / "tc256" / "tc512" /
+    "tc1024" (k_match_top2<N> + k_match_finish); nch chunks per pair; xrun the xcd_runs run length
+    (0 = dispatch order); pk 1 = 4-byte partials."""
+    import ctypes
+    from orb_slam3_ros2_amd._lib import lib
+    out = (ctypes.c_int32 * 4)()
+    assert lib().orbhip_test_match_route(npairs, max_q, max_t, int(fused_allowed), out) == 0
+    return {"kernel": "fused" if out[0] == 0 else f"tc{out[0]}", "nch": out[1], "xrun": out[2], "pk": out[3]}
+
+
+class PlantedSet:
+    """q (nq, 32) / qa (nq,), t (nt, 32) / ta (nt,); per query: train (the train it was planted
+    from, -1 = random query), bin (its rotation bin), flips (its distance to that train)."""
+
+    def __init__(self, q, qa, t, ta, train, bin_, flips):
+        self.q, self.qa, self.t, self.ta, self.train, self.bin, self.flips = q, qa, t, ta, train, bin_, flips
+
+    @property
+    def planted(self):
+        return self.train >= 0
+
+
+def _flip_masks(rng, n: int):
+    """rank[i, bit]: the position of `bit` in query i's own random bit order; flipping the bits of
+    rank < k gives distance exactly k, and the same k always picks the same bits."""
+    perm = np.argsort(rng.random((n, 256)), axis=1)
+    rank = np.empty((n, 256), np.int64)
+    rank[np.arange(n)[:, None], perm] = np.arange(256)[None, :]
+    return rank
+
+
+def _mask_bytes(rank_row, k):
+    return np.packbits(rank_row < k, axis=-1, bitorder="little")
+
+
+def planted_match_set(nq: int, nt: int, hist=None, flips=(0, 40), seed=0, plants=(), trains=None) -> PlantedSet:
+    """Random descriptors never match (best ~ 100), so the matches are built in.
+
+    Trains: random 32-byte descriptors, angles integer degrees in [0, 360) (or `trains` = (t, ta),
+    copied). For every bin b of `hist` = {bin: count}, `count` queries (random positions) copy a
+    train (distinct trains while nt allows) and flip k bits, k uniform in `flips` (inclusive); their
+    angle is train_angle + rot (- 360 from 360 on), rot = 30 b for b in 0..11 and 350 for b = 12, so
+    every angle and every difference is an exact float and the query lands in bin b. `plants` =
+    (query, train index, k) fix distances exactly: the first plant of a query derives the query
+    from that train (bin 0); a further plant of the same query overwrites its train with the query
+    flipped in k bits (the same k picks the same bits: two plants with equal k make two equal
+    trains). Planted queries and trains of `plants` are kept apart from those of `hist`. Every
+    other query is random."""
+    rng = np.random.default_rng(seed)
+    if trains is None:
+        t = rng.integers(0, 256, (nt, 32), dtype=np.uint8)
+        ta = rng.integers(0, 360, nt).astype(np.float32)
+    else:
+        t, ta = np.array(trains[0], np.uint8).reshape(nt, 32), np.array(trains[1], np.float32).reshape(nt)
+    q = rng.integers(0, 256, (nq, 32), dtype=np.uint8)
+    qa = rng.integers(0, 360, nq).astype(np.float32)
+    train = np.full(nq, -1, np.int64); bin_ = np.full(nq, -1, np.int64); nflip = np.full(nq, -1, np.int64)
+    rank = _flip_masks(rng, nq)
+    used_q, used_t = set(), set()
+    for (qi, ti, k) in plants:
+        assert 0 <= qi < nq and 0 <= ti < nt and 0 <= k <= 256 and ti not in used_t
+        used_t.add(ti)
+        if qi not in used_q:
+            used_q.add(qi)
+            q[qi] = t[ti] ^ _mask_bytes(rank[qi], k)
+            qa[qi] = ta[ti]
+            train[qi], bin_[qi], nflip[qi] = ti, 0, k
+        else:
+            t[ti] = q[qi] ^ _mask_bytes(rank[qi], k)
+            ta[ti] = qa[qi]
+            if (k, ti) < (nflip[qi], train[qi]):
+                train[qi], nflip[qi] = ti, k
+    hist = dict(hist or {})
+    total = sum(hist.values())
+    assert all(0 <= b <= 12 for b in hist) and total <= nq - len(used_q) and (total == 0 or nt > len(used_t))
+    if total:
+        free_q = np.array([i for i in range(nq) if i not in used_q])
+        free_t = np.array([i for i in range(nt) if i not in used_t])
+        qs = rng.permutation(free_q)[:total]
+        ts = rng.permutation(free_t)[:total] if total <= len(free_t) else rng.choice(free_t, total)
+        ks = rng.integers(flips[0], flips[1] + 1, total)
+        bins = np.concatenate([np.full(c, b) for b, c in sorted(hist.items())])
+        rot = np.where(bins == 12, 350, 30 * bins).astype(np.float32)
+        q[qs] = t[ts] ^ _mask_bytes(rank[qs], ks[:, None])
+        a = ta[ts] + rot
+        qa[qs] = np.where(a >= 360, a - 360, a).astype(np.float32)
+        train[qs], bin_[qs], nflip[qs] = ts, bins, ks
+    return PlantedSet(q, qa, t, ta, train, bin_, nflip)
+
+
+# histogram {bin: count} -> (bins ComputeThreeMaxima keeps, matches kept)
+MATCH_HISTOGRAMS = [
+    ({3: 40, 7: 40, 9: 40, 11: 40}, (3, 7, 9), 120),      # four equal bins: the lower indices win
+    ({0: 100, 5: 10, 8: 9}, (0, 5), 110),                 # 10 < 0.1f * 100 is false, 9 is below
+    ({0: 99, 5: 10, 8: 9}, (0, 5), 109),
+    ({0: 101, 5: 10, 8: 10}, (0,), 101),                  # 10 < 10.1: the second AND the third go
+    ({2: 100, 6: 9, 7: 9}, (2,), 100),
+    ({4: 100, 1: 10, 12: 10, 6: 10}, (4, 1, 6), 120),     # three tied runners-up: bin 12 is the one dropped
+    ({12: 7}, (12,), 7),                                  # rot 350 -> the last bin that can fill
+    ({0: 1}, (0,), 1),
+    ({}, (), 0),
+    ({1: 5, 2: 6, 3: 7, 4: 8}, (4, 3, 2), 21),
+]
+MATCH_HIST_IDS = ["-".join(f"{b}x{c}" for b, c in h.items()) or "empty" for h, _, _ in MATCH_HISTOGRAMS]

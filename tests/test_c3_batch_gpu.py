@@ -58,9 +58,10 @@ def test_c3_batch_vs_oracle(c3, oracle):
         ok[f] = (k6, od)
     for p in range(B - 1):
         (k1, d1), (k2, d2) = ok[p], ok[p + 1]
-        on, om, _, _ = oracle.match_bf(d1, k1[:, 3].astype(np.float32), d2, k2[:, 3].astype(np.float32), 50, 0.9,
-                                       True)
+        on, om, ob, os_ = oracle.match_bf(d1, k1[:, 3].astype(np.float32), d2, k2[:, 3].astype(np.float32), 50, 0.9,
+                                          True)
         assert nm[p] == on and np.array_equal(mm[0, p, :n[p]], om), p
+        assert np.array_equal(mm[1, p, :n[p]], ob) and np.array_equal(mm[2, p, :n[p]], os_), p
         assert on > 200
 
 
