@@ -198,7 +198,8 @@ int orbhip_frontend_context(orbhip_frontend* fe, int j, orbhip_ctx** out);
 /* ---- diagnostics: live kernel timing ----------------------------------------------
  * orbhip_profile_stage selects ONE stage whose launches are bracketed by hipEvents on the
  * stream they run on (0 off, 1 pyramid resize, 2 FAST cells, 3 octree, 4 orientation +
- * descriptor, 5 Hamming top-2, 6 rotation filter). orbhip_profile_collect synchronises and
+ * descriptor, 5 Hamming top-2, 6 rotation filter, 7 SearchForTriangulation: the ordering pre-pass
+ * and the search of one call form one pair). orbhip_profile_collect synchronises and
  * returns the summed duration (ms) and the number of bracketed launches, then resets. The one-launch
  * pyramid (k_pyr_cone) and the octree also time themselves on the device (first workgroup start to
  * last workgroup end, s_memrealtime: the span rocprofv3's kernel trace reports); their stages
@@ -441,6 +442,44 @@ int orbhip_search_bow(orbhip_ctx* ctx, const uint8_t* kf_desc, const float* kf_a
                       const double* kf_weight, const uint8_t* kf_valid, int nkf, const uint8_t* f_desc,
                       const float* f_angle, const int32_t* f_node, const double* f_weight, int nf,
                       float ratio, int check_orientation, int th_low, int32_t* match);
+
+/* ---- new map points: SearchForTriangulation -------------------------
+ * U:src/ORBmatcher.cc::SearchForTriangulation(pKF1, pKF2, vMatchedPairs, bOnlyStereo = false,
+ * bCoarse = false), as U:src/LocalMapping.cc::CreateNewMapPoints calls it (ORBmatcher(0.6, false))
+ * once per covisible neighbour: monocular, one pinhole camera per keyframe, mvKeysUn. KF1 is
+ * matched against B neighbours in one call. Per shared FeatureVector node, every KF1 feature
+ * without a MapPoint takes the KF2 feature without a MapPoint of least descriptor distance
+ * (<= TH_LOW = 50; of equal distances the highest index) among those that are not within
+ * 10 * sqrt(mvScaleFactors[octave2]) px of the epipole and lie within 3.84 * mvLevelSigma2[octave2]
+ * of the epipolar line x1^T F12. No ratio test; several KF1 features may share one KF2 feature
+ * (vbMatched2 is never set upstream). With check_orientation the rotation histogram
+ * (HISTO_LENGTH 30, ComputeThreeMaxima) drops matches outside the main bins. DESIGN.md fixes the
+ * fp32 operation order of the geometry and of every gate. */
+typedef struct {
+    int32_t n;                 /* <= 2048 */
+    const orbhip_kp* kps;      /* mvKeysUn */
+    const uint8_t* desc;       /* n x 32 */
+    const int32_t* node;       /* orbhip_bow_transform node ids (levelsup 4), -1 = none */
+    const double* weight;      /* > 0: in the FeatureVector */
+    const uint8_t* has_mp;     /* GetMapPoint(i) != NULL */
+    float fx, fy, cx, cy;
+    float pose_q[4], pose_t[3];/* Tcw, (x, y, z, w) as orbhip_frame */
+} orbhip_tri_keyframe;
+
+/* host only, no context: the per-pair geometry the kernel consumes. F12 row-major
+ * (K1^-T [t12]x R12 K2^-1 with closed-form K^-1), ep = KF1's camera centre in image 2. Only the
+ * intrinsics and poses of the two keyframes are read. */
+int orbhip_triangulation_geometry(const orbhip_tri_keyframe* kf1, const orbhip_tri_keyframe* kf2,
+                                  float F12[9], float ep[2]);
+
+/* KF1 against B neighbours in one call. match12: B x kf1->n (idx2 or -1), nmatches: B.
+ * Returns the sum of nmatches. n > 2048 on either side or B > 64: ORBHIP_ERR_UNSUPPORTED; a
+ * keypoint octave outside [0, n_levels): ORBHIP_ERR_ARG. One upload, one launch pair (KF1's
+ * FeatureVector ordered once, then one work-group per neighbour), one read-back. */
+int orbhip_search_for_triangulation(orbhip_ctx* ctx, const orbhip_tri_keyframe* kf1,
+                                    const orbhip_tri_keyframe* nbrs, int B,
+                                    const float* scale_factors, const float* level_sigma2, int n_levels,
+                                    int check_orientation, int32_t* match12, int32_t* nmatches);
 
 /* ---- multi-GPU BundleAdjustment (SURVEY.md §8e, C5 GlobalBundleAdjustment) --------
  * One process per GPU. Landmarks (with their edges) are partitioned across ranks; every rank

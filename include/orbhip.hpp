@@ -148,6 +148,27 @@ public:
         return rc;
     }
 
+    // U:src/ORBmatcher.cc::SearchForTriangulation(pKF1, pKF2, vMatchedPairs, false, false) of pKF1
+    // against every neighbour in one call (LocalMapping::CreateNewMapPoints).
+    // vMatches12[b][i] = neighbour b's feature matched to pKF1's feature i, or -1 (vMatchedPairs of
+    // pair b = the (i, vMatches12[b][i]) with a match, in i order). Returns the matches per neighbour.
+    std::vector<int> SearchForTriangulation(orbhip_ctx* ctx, const orbhip_tri_keyframe& kf1,
+                                            const std::vector<orbhip_tri_keyframe>& neighbours,
+                                            const std::vector<float>& mvScaleFactors,
+                                            const std::vector<float>& mvLevelSigma2,
+                                            std::vector<std::vector<int>>& vMatches12) const {
+        const int B = (int)neighbours.size(), n1 = kf1.n;
+        std::vector<int32_t> flat((size_t)B * (size_t)std::max(n1, 0), -1), nm(B, 0);
+        const int rc = orbhip_search_for_triangulation(ctx, &kf1, neighbours.data(), B, mvScaleFactors.data(),
+                                                       mvLevelSigma2.data(),
+                                                       (int)std::min(mvScaleFactors.size(), mvLevelSigma2.size()),
+                                                       mbCheckOrientation ? 1 : 0, flat.data(), nm.data());
+        check(rc, "orbhip_search_for_triangulation");
+        vMatches12.assign(B, std::vector<int>());
+        for (int b = 0; b < B; b++) vMatches12[b].assign(flat.begin() + (size_t)b * n1, flat.begin() + (size_t)(b + 1) * n1);
+        return std::vector<int>(nm.begin(), nm.end());
+    }
+
     float mfNNratio;
     bool mbCheckOrientation;
 };

@@ -92,6 +92,13 @@ class InitFrameC(ctypes.Structure):
                 ("max_x", ctypes.c_float), ("min_y", ctypes.c_float), ("max_y", ctypes.c_float)]
 
 
+class TriKeyFrameC(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_int32), ("kps", ctypes.c_void_p), ("desc", ctypes.c_void_p), ("node", ctypes.c_void_p),
+                ("weight", ctypes.c_void_p), ("has_mp", ctypes.c_void_p), ("fx", ctypes.c_float),
+                ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
+                ("pose_q", ctypes.c_float * 4), ("pose_t", ctypes.c_float * 3)]
+
+
 class KfdbQueryC(ctypes.Structure):
     _fields_ = [("query_id", ctypes.c_int64), ("words", ctypes.c_void_p), ("values", ctypes.c_void_p),
                 ("n", ctypes.c_int32), ("covis", ctypes.c_void_p), ("kf_map", ctypes.c_void_p),
@@ -115,6 +122,7 @@ EXPORTED = ["orbhip_abi_version", "orbhip_create", "orbhip_destroy", "orbhip_lev
             "orbhip_bow_transform", "orbhip_bow_transform_device", "orbhip_search_bow",
             "orbhip_pose_optimization", "orbhip_pose_optimization_batch", "orbhip_search_by_projection_last",
             "orbhip_search_local_points", "orbhip_search_for_initialization",
+            "orbhip_triangulation_geometry", "orbhip_search_for_triangulation",
             "orbhip_kfdb_create", "orbhip_kfdb_destroy", "orbhip_kfdb_add", "orbhip_kfdb_erase",
             "orbhip_kfdb_detect_relocalization", "orbhip_kfdb_detect_nbest",
             "orbhip_frontend_create", "orbhip_frontend_destroy", "orbhip_frontend_push", "orbhip_frontend_view",
@@ -179,6 +187,9 @@ def lib():
                                              i32, f32, vp, vp, vp]
     L.orbhip_search_for_initialization.argtypes = [vp, ctypes.POINTER(InitFrameC), ctypes.POINTER(InitFrameC), vp,
                                                    i32, f32, i32, vp]
+    L.orbhip_triangulation_geometry.argtypes = [ctypes.POINTER(TriKeyFrameC), ctypes.POINTER(TriKeyFrameC), vp, vp]
+    L.orbhip_search_for_triangulation.argtypes = [vp, ctypes.POINTER(TriKeyFrameC), ctypes.POINTER(TriKeyFrameC), i32,
+                                                  vp, vp, i32, i32, vp, vp]
     L.orbhip_kfdb_create.argtypes = [vp, i32, ctypes.POINTER(vp)]
     L.orbhip_kfdb_destroy.argtypes = [vp]
     L.orbhip_kfdb_add.argtypes = [vp, i32, vp, vp, i32]

@@ -68,7 +68,20 @@ struct DevBuf {
     }
 };
 
-constexpr int kConeHiStart = 2;        // batches: k_resize for levels 1..2, one cone launch for the rest
+struct PinBuf {   // pinned host staging, grown on demand
+    uint8_t* p = nullptr;
+    size_t n = 0;
+    ~PinBuf() { if (p) (void)hipHostFree(p); }
+    hipError_t ensure(size_t bytes) {
+        if (bytes <= n && p) return hipSuccess;
+        if (p) { (void)hipHostFree(p); p = nullptr; n = 0; }
+        hipError_t e = hipHostMalloc((void**)&p, std::max<size_t>(bytes, 1), hipHostMallocDefault);
+        if (e == hipSuccess) n = bytes;
+        return e;
+    }
+};
+
+constexpr int kConeHiStart = 2;       // batches: k_resize for levels 1..2, one cone launch for the rest
 // threads per batch-cone tile: ORBHIP_CONE_HI_THREADS (256 / 512 / 1024), else 256
 static int cone_hi_threads() {
     static const int t = std::getenv("ORBHIP_CONE_HI_THREADS") ? std::atoi(std::getenv("ORBHIP_CONE_HI_THREADS")) : 256;
@@ -157,6 +170,8 @@ struct orbhip_ctx {
     DevBuf<int> d_msync;        // one-launch matcher counters (zeroed once, reset by every launch)
     DevBuf<double> d_bw;        // bag-of-words weights (host transform)
     DevBuf<uint8_t> d_bow_stage;   // SearchByBoW host-call staging
+    DevBuf<uint8_t> d_tri_stage;   // SearchForTriangulation: the call's device block
+    PinBuf h_tri_stage;            // its pinned image (upload) and the read-back
     DevBuf<LevelKp> d_lvl_kp;
     DevBuf<orbhip_kp> d_kps;
     DevBuf<uint8_t> d_desc;
@@ -1119,7 +1134,7 @@ int orbhip_launch_graphs(orbhip_ctx* c) {
 }
 
 int orbhip_profile_stage(orbhip_ctx* c, int stage) {
-    if (!c || stage < 0 || stage > 6) return ORBHIP_ERR_ARG;
+    if (!c || stage < 0 || stage > 7) return ORBHIP_ERR_ARG;
     HIPOK(hipSetDevice(c->device));
     StageTimer& t = c->timer;
     if (!t.created) {
@@ -1517,6 +1532,106 @@ int orbhip_search_bow(orbhip_ctx* c, const uint8_t* kf_desc, const float* kf_ang
     HIPOK(hipMemcpyAsync(&nm, d_nm, 4, hipMemcpyDeviceToHost, st));
     HIPOK(hipStreamSynchronize(st));
     return nm;
+}
+
+// ---- SearchForTriangulation: KF1 against B neighbours ----
+int orbhip_triangulation_geometry(const orbhip_tri_keyframe* kf1, const orbhip_tri_keyframe* kf2, float F12[9],
+                                  float ep[2]) {
+    if (!kf1 || !kf2 || !F12 || !ep) return ORBHIP_ERR_ARG;
+    tri_geometry(*kf1, *kf2, F12, ep);
+    return ORBHIP_OK;
+}
+
+static int tri_check_side(const orbhip_tri_keyframe& k, int n_levels) {
+    if (k.n < 0) return ORBHIP_ERR_ARG;
+    if (k.n > kTriMax) return ORBHIP_ERR_UNSUPPORTED;
+    if (k.n == 0) return ORBHIP_OK;
+    if (!k.kps || !k.desc || !k.node || !k.weight || !k.has_mp) return ORBHIP_ERR_ARG;
+    for (int i = 0; i < k.n; i++)
+        if (k.kps[i].octave < 0 || k.kps[i].octave >= n_levels) return ORBHIP_ERR_ARG;
+    return ORBHIP_OK;
+}
+
+int orbhip_search_for_triangulation(orbhip_ctx* c, const orbhip_tri_keyframe* kf1, const orbhip_tri_keyframe* nbrs,
+                                    int B, const float* scale_factors, const float* level_sigma2, int n_levels,
+                                    int check_orientation, int32_t* match12, int32_t* nmatches) {
+    if (!c || !kf1 || B < 0) return ORBHIP_ERR_ARG;
+    if (B == 0) return 0;
+    if (B > kTriMaxPairs) return ORBHIP_ERR_UNSUPPORTED;
+    if (!nbrs || !nmatches || !scale_factors || !level_sigma2 || n_levels <= 0) return ORBHIP_ERR_ARG;
+    int rc = tri_check_side(*kf1, n_levels);
+    for (int b = 0; b < B && rc == ORBHIP_OK; b++) rc = tri_check_side(nbrs[b], n_levels);
+    if (rc != ORBHIP_OK) return rc;
+    const int n1 = kf1->n;
+    for (int b = 0; b < B; b++) nmatches[b] = 0;
+    if (n1 == 0) return 0;
+    if (!match12) return ORBHIP_ERR_ARG;
+    HIPOK(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    // one block, the same layout on the host (pinned) and the device:
+    // [sides (1 + B) | geometry B | scale factors | sigma2 | per keyframe: kps desc node weight has_mp]
+    // then device only [KF1 keys | m1 | match12 B x n1 | nmatches B]; the last two are read back
+    size_t off = 0;
+    auto take = [&](size_t bytes) { off = (off + 15) & ~size_t(15); const size_t o = off; off += bytes; return o; };
+    const size_t o_sides = take((size_t)(1 + B) * sizeof(TriSide));
+    const size_t o_geom = take((size_t)B * sizeof(TriGeom));
+    const size_t o_sf = take((size_t)n_levels * 4), o_s2 = take((size_t)n_levels * 4);
+    struct SideOff { size_t kps, desc, node, weight, mp; };
+    std::vector<SideOff> so(1 + B);
+    for (int s = 0; s <= B; s++) {
+        const size_t n = (size_t)(s ? nbrs[s - 1].n : n1);
+        so[s] = {take(n * sizeof(orbhip_kp)), take(n * 32), take(n * 4), take(n * 8), take(n)};
+    }
+    const size_t up_bytes = take(0);
+    const size_t o_keys = take((size_t)kTriMax * 8), o_m1 = take(4);
+    const size_t o_match = take((size_t)B * n1 * 4);
+    const size_t back_bytes = (size_t)B * n1 * 4 + (size_t)B * 4;   // nmatches directly behind match12
+    off = o_match + back_bytes;
+    const size_t dev_bytes = take(0);
+    HIPOK(c->d_tri_stage.ensure(dev_bytes));
+    HIPOK(c->h_tri_stage.ensure(up_bytes + back_bytes + 16));
+    uint8_t* const d = c->d_tri_stage.p;
+    uint8_t* const h = c->h_tri_stage.p;
+    TriSide* sides = (TriSide*)(h + o_sides);
+    TriGeom* geom = (TriGeom*)(h + o_geom);
+    for (int s = 0; s <= B; s++) {
+        const orbhip_tri_keyframe& k = s ? nbrs[s - 1] : *kf1;
+        const size_t n = (size_t)k.n;
+        sides[s] = {(const orbhip_kp*)(d + so[s].kps), d + so[s].desc, (const int32_t*)(d + so[s].node),
+                    (const double*)(d + so[s].weight), d + so[s].mp, k.n, 0};
+        if (n) {
+            std::memcpy(h + so[s].kps, k.kps, n * sizeof(orbhip_kp));
+            std::memcpy(h + so[s].desc, k.desc, n * 32);
+            std::memcpy(h + so[s].node, k.node, n * 4);
+            std::memcpy(h + so[s].weight, k.weight, n * 8);
+            std::memcpy(h + so[s].mp, k.has_mp, n);
+        }
+        if (s) {
+            geom[s - 1].pad = 0.f;
+            tri_geometry(*kf1, k, geom[s - 1].F, geom[s - 1].ep);
+        }
+    }
+    std::memcpy(h + o_sf, scale_factors, (size_t)n_levels * 4);
+    std::memcpy(h + o_s2, level_sigma2, (size_t)n_levels * 4);
+    HIPOK(hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
+    (void)hipGetLastError();
+    {
+        const StageScope scope(c->timer);
+        c->timer.begin(7, st);
+        launch_tri_search((const TriSide*)(d + o_sides), (const TriGeom*)(d + o_geom), n1, B, (const float*)(d + o_sf),
+                          (const float*)(d + o_s2), (unsigned long long*)(d + o_keys), (int32_t*)(d + o_m1),
+                          check_orientation, (int32_t*)(d + o_match), (int32_t*)(d + o_match + (size_t)B * n1 * 4), st);
+        c->timer.end(7, st);
+    }
+    HIPOK(hipGetLastError());
+    uint8_t* const hb = h + ((up_bytes + 15) & ~size_t(15));
+    HIPOK(hipMemcpyAsync(hb, d + o_match, back_bytes, hipMemcpyDeviceToHost, st));
+    HIPOK(hipStreamSynchronize(st));
+    std::memcpy(match12, hb, (size_t)B * n1 * 4);
+    std::memcpy(nmatches, hb + (size_t)B * n1 * 4, (size_t)B * 4);
+    int total = 0;
+    for (int b = 0; b < B; b++) total += nmatches[b];
+    return total;
 }
 
 // ---- test hooks (not part of the reference surface) ----

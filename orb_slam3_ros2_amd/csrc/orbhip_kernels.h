@@ -179,6 +179,25 @@ bool search_bow_set_lds_limit();
 void launch_search_bow(const BowSide& K, const BowSide& F, float ratio, int check_orientation, int th_low,
                        int32_t* match, int32_t* nmatch, hipStream_t st);
 
+// ---- SearchForTriangulation (triangulation_kernels.hip) ----
+constexpr int kTriMax = 2048;     // features per keyframe (LDS-resident keys, 16-bit indices)
+constexpr int kTriMaxPairs = 64;  // neighbours per call
+struct TriSide {                  // one keyframe in the call's staging block (device pointers)
+    const orbhip_kp* kps;
+    const uint8_t* desc;          // n x 32
+    const int32_t* node;
+    const double* weight;
+    const uint8_t* has_mp;
+    int n, pad;
+};
+struct TriGeom { float F[9]; float ep[2]; float pad; };   // F12 row-major, epipole in image 2
+// host, fp32 in a fixed operation order: the geometry k_tri_search consumes
+void tri_geometry(const orbhip_tri_keyframe& k1, const orbhip_tri_keyframe& k2, float* F, float* ep);
+// sides[0] = KF1, sides[1 + b] = neighbour b; keys1: kTriMax entries, m1: 1 (both written by the pre-pass)
+void launch_tri_search(const TriSide* sides, const TriGeom* geom, int n1, int B, const float* scale_factors,
+                       const float* level_sigma2, unsigned long long* keys1, int32_t* m1, int check_orientation,
+                       int32_t* match12, int32_t* nmatches, hipStream_t st);
+
 // ---- ingest ----
 void launch_bgr2gray(const uint8_t* src, int B, int w, int h, int sstride, int64_t sfstride, uint8_t* dst, int dstride,
                      int64_t dfstride, hipStream_t st);

@@ -13,7 +13,8 @@ import ctypes
 
 import numpy as np
 
-from ._lib import (KP_DTYPE, FrameC, InitFrameC, LocalPointsC, ProjLastC, torch_stream, Context, check, lib, ptr)
+from ._lib import (KP_DTYPE, FrameC, InitFrameC, LocalPointsC, ProjLastC, TriKeyFrameC, torch_stream, Context, check,
+                   lib, ptr)
 
 
 class ORBmatcher:
@@ -162,6 +163,90 @@ class ORBmatcher:
                                                    int(far_points), float(th_far), ptr(in_view), ptr(level),
                                                    ptr(match)), "orbhip_search_local_points")
         return n, match, in_view, level
+
+    # ---- new map points (LocalMapping::CreateNewMapPoints) ----
+    def SearchForTriangulation(self, kf1: "TriKeyFrame", neighbours, scale_factors, level_sigma2):
+        """U:src/ORBmatcher.cc::SearchForTriangulation(pKF1, pKF2, vMatchedPairs, false, false) of
+        kf1 against every keyframe of `neighbours` (at most 64) in one call, with this matcher's
+        mbCheckOrientation (CreateNewMapPoints uses ORBmatcher(0.6, false); there is no ratio test).
+        Returns (nmatches[B], match12[B, n1]) with match12[b, i] = the feature of neighbour b
+        matched to kf1's feature i, or -1."""
+        nb = list(neighbours)
+        B, n1 = len(nb), kf1.n
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        s2 = np.ascontiguousarray(level_sigma2, np.float32)
+        if sf.shape[0] != s2.shape[0]:
+            raise ValueError("SearchForTriangulation: scale_factors and level_sigma2 differ in length")
+        nm = np.zeros(B, np.int32)
+        m = np.full((B, n1), -1, np.int32)
+        if B == 0:
+            return nm, m
+        arr = (TriKeyFrameC * B)(*[k.to_c() for k in nb])
+        c1 = kf1.to_c()
+        check(lib().orbhip_search_for_triangulation(self.ctx.handle, ctypes.byref(c1), arr, B, ptr(sf), ptr(s2),
+                                                    sf.shape[0], int(self.mbCheckOrientation), ptr(m), ptr(nm)),
+              "orbhip_search_for_triangulation")
+        return nm, m
+
+
+class TriKeyFrame:
+    """A KeyFrame as SearchForTriangulation reads it: mvKeysUn (orbhip_kp records), descriptors, the
+    FeatureVector as per-feature (node, weight) from ORBVocabulary.transform_features (levelsup 4;
+    weight > 0 and node >= 0: in the vector), has_mp[i] = GetMapPoint(i) is set, the pinhole
+    intrinsics and Tcw."""
+
+    def __init__(self, kps, desc, node, weight, has_mp, pose_q, pose_t, fx, fy, cx, cy):
+        self.kps = np.ascontiguousarray(kps, KP_DTYPE)
+        self.n = self.kps.shape[0]
+        self.desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        self.node = np.ascontiguousarray(node, np.int32)
+        self.weight = np.ascontiguousarray(weight, np.float64)
+        self.has_mp = np.ascontiguousarray(has_mp, np.uint8)
+        for a in (self.desc, self.node, self.weight, self.has_mp):
+            if a.shape[0] != self.n:
+                raise ValueError("TriKeyFrame: per-feature arrays differ in length")
+        self.pose_q = np.array(pose_q, np.float32).reshape(4)
+        self.pose_t = np.array(pose_t, np.float32).reshape(3)
+        self.fx, self.fy, self.cx, self.cy = float(fx), float(fy), float(cx), float(cy)
+        self._c = None
+
+    def to_c(self) -> TriKeyFrameC:
+        """The C view (it points into this object's arrays: keep the object alive while it is used).
+        The pointer fields are cached while the five per-feature arrays are the same objects (a
+        neighbour list is passed again for every new keyframe); the pose and the intrinsics are
+        re-filled on every call, so they may change in place or be reassigned."""
+        hit = self._c
+        if hit is None or not (hit[0][0] is self.kps and hit[0][1] is self.desc and hit[0][2] is self.node
+                               and hit[0][3] is self.weight and hit[0][4] is self.has_mp):
+            self.kps = np.ascontiguousarray(self.kps, KP_DTYPE)
+            self.n = self.kps.shape[0]
+            self.desc = np.ascontiguousarray(self.desc, np.uint8).reshape(-1, 32)
+            self.node = np.ascontiguousarray(self.node, np.int32)
+            self.weight = np.ascontiguousarray(self.weight, np.float64)
+            self.has_mp = np.ascontiguousarray(self.has_mp, np.uint8)
+            arrs = (self.kps, self.desc, self.node, self.weight, self.has_mp)
+            if any(a.shape[0] != self.n for a in arrs):
+                raise ValueError("TriKeyFrame: per-feature arrays differ in length")
+            c = TriKeyFrameC()
+            c.n = self.n
+            c.kps, c.desc, c.node, c.weight, c.has_mp = (ptr(a) for a in arrs)
+            self._c = hit = (arrs, c)
+        c = hit[1]
+        c.fx, c.fy, c.cx, c.cy = self.fx, self.fy, self.cx, self.cy
+        # (through float32 first: the C fields hold exactly what the arrays hold)
+        c.pose_q[:] = np.asarray(self.pose_q, np.float32).reshape(4).tolist()
+        c.pose_t[:] = np.asarray(self.pose_t, np.float32).reshape(3).tolist()
+        return c
+
+    def geometry(self, other: "TriKeyFrame"):
+        """(F12 (3, 3), ep (2,)) of the pair (self = KF1, other = KF2), as the kernel consumes them
+        (orbhip_triangulation_geometry: host only, fp32)."""
+        F = np.zeros(9, np.float32)
+        ep = np.zeros(2, np.float32)
+        a, b = self.to_c(), other.to_c()
+        check(lib().orbhip_triangulation_geometry(ctypes.byref(a), ctypes.byref(b), ptr(F), ptr(ep)),
+              "orbhip_triangulation_geometry")
+        return F.reshape(3, 3), ep
 
 
 class ProjFrame:

@@ -417,3 +417,196 @@ def banded_pose_system(n_pose, w, cyclic, seed, n_land=None):
     bi = np.array([b[0] for b in sorted(blocks)], np.int32)
     bj = np.array([b[1] for b in sorted(blocks)], np.int32)
     return A, rng.normal(size=n), bi, bj
+
+
+# ---------------------------------------------------------------------------
+# SearchForTriangulation scenes (LocalMapping::CreateNewMapPoints)
+# ---------------------------------------------------------------------------
+def orb_scale_tables(n_levels=8, scale_factor=1.2):
+    """(mvScaleFactors, mvLevelSigma2) as the ORBextractor ctor fills them (float32)."""
+    sf = np.ones(n_levels, np.float32)
+    for i in range(1, n_levels):
+        sf[i] = np.float32(np.float64(sf[i - 1]) * np.float64(np.float32(scale_factor)))
+    return sf, (sf * sf).astype(np.float32)
+
+
+def quat_to_rot64(q):
+    """The rotation a float32 quaternion (x, y, z, w) stands for, in float64."""
+    x, y, z, w = (float(v) for v in q)
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+
+def pinhole_project(q, t, cam, P):
+    """World points P (m, 3) through Tcw = (q, t) and the pinhole cam: (uv (m, 2), depth (m,)), float64."""
+    Xc = P @ quat_to_rot64(q).T + np.asarray(t, np.float64)
+    z = Xc[:, 2]
+    uv = np.stack([cam["fx"] * Xc[:, 0] / z + cam["cx"], cam["fy"] * Xc[:, 1] / z + cam["cy"]], 1)
+    return uv, z
+
+
+def synthetic_triangulation_scene(n=300, B=3, seed=0, n_nodes=12, n2=None, mp_frac=1.0 / 3, n_levels=8,
+                                  scale_factor=1.2, cam=None):
+    """A keyframe with n features and B covisible neighbours that see common 3-D points, for
+    SearchForTriangulation. Neighbour b moves sideways (b % 3 == 0), forward along the optical axis
+    (b % 3 == 1: its epipole lies inside the image) or diagonally (b % 3 == 2), each with a small
+    rotation. KF1's features are the noise-free projections of points 2-8 m away; a neighbour sees
+    90 % of them (the "twins") with pixel noise of half a level sigma (15 % displaced by 2.5-8 sigma:
+    epipolar outliers), 0-30 flipped descriptor bits, the keyframe's in-plane rotation (12 % random:
+    the orientation filter), node ids from an alphabet of n_nodes (7 % moved to another node), some
+    weights 0 and nodes -1; mp_frac of KF1's features carry MapPoints (their twins mostly too), plus
+    random distractors. Planted: on every forward neighbour, twins within 6 px of the epipole (the
+    epipole exclusion); exact copies of twins (equal distances: the later index wins); KF1 features
+    duplicated next to themselves (two KF1 features share one target). Each neighbour is shuffled.
+    n2: features per neighbour (an int, or one per neighbour): twins are dropped / distractors added
+    to reach it. Returns a dict: kf1, neighbours (TriKeyFrame), scale_factors, level_sigma2, twin[b]
+    (n,) = the neighbour feature that is KF1 feature i's twin or -1, epi[b] = KF1 features planted at
+    neighbour b's epipole."""
+    from ._lib import KP_DTYPE
+    from .matcher import TriKeyFrame
+    rng = np.random.Generator(np.random.PCG64(seed))
+    cam = dict(D435I if cam is None else cam)
+    W, H = cam["w"], cam["h"]
+    sf, s2 = orb_scale_tables(n_levels, scale_factor)
+    alphabet = np.sort(rng.choice(np.arange(1000, 1_000_000), n_nodes, replace=False)).astype(np.int32)
+    R1 = _rodrigues(rng.normal(size=3) * 0.05)
+    t1 = rng.normal(size=3) * 0.1
+    q1 = _mat_to_quat(R1).astype(np.float32)
+    t1 = t1.astype(np.float32)
+    R1 = quat_to_rot64(q1)
+    # neighbour poses, relative to KF1's camera frame: X2 = Rrel (X1 - c)
+    poses, rels = [], []
+    for b in range(B):
+        kind = b % 3
+        c = (np.array([0.35, 0.02, 0.0]), np.array([0.01, -0.01, 0.45]), np.array([-0.25, 0.15, 0.05]))[kind].copy()
+        if b >= 3:
+            c *= rng.uniform(0.6, 1.5)
+            c[:2] += rng.normal(size=2) * (0.005 if kind == 1 else 0.05)
+        Rrel = _rodrigues(rng.normal(size=3) * 0.03)
+        q2 = _mat_to_quat(Rrel @ R1).astype(np.float32)
+        t2 = (Rrel @ (t1.astype(np.float64) - c)).astype(np.float32)
+        poses.append((q2, t2))
+        rels.append((Rrel, c))
+    fwd = [b for b in range(B) if b % 3 == 1]
+    n_epi = min(8, n // 20) if fwd else 0
+    n_dup = n // 40
+    if n_epi * len(fwd) + n_dup > n // 2:      # a small keyframe against many neighbours: no plants
+        n_epi = n_dup = 0
+    n_pts = n - n_epi * len(fwd) - n_dup
+    # 3-D points in KF1's camera frame
+    u = rng.uniform(20, W - 20, n_pts); v = rng.uniform(20, H - 20, n_pts); z = rng.uniform(2.0, 8.0, n_pts)
+    X1 = [np.stack([(u - cam["cx"]) / cam["fx"] * z, (v - cam["cy"]) / cam["fy"] * z, z], 1)]
+    epi_of = np.full(n, -1, np.int64)   # KF1 feature -> the neighbour whose epipole it was planted at
+    pos = n_pts
+    for b in fwd:
+        Rrel, c = rels[b]
+        e2 = Rrel @ (-c)                                           # KF1's centre in KF2's frame
+        ep = np.array([cam["fx"] * e2[0] / e2[2] + cam["cx"], cam["fy"] * e2[1] / e2[2] + cam["cy"]])
+        ang = rng.uniform(0, 2 * np.pi, n_epi); rad = rng.uniform(0.5, 6.0, n_epi); d = rng.uniform(3.0, 8.0, n_epi)
+        px = ep[0] + rad * np.cos(ang); py = ep[1] + rad * np.sin(ang)
+        X2 = np.stack([(px - cam["cx"]) / cam["fx"] * d, (py - cam["cy"]) / cam["fy"] * d, d], 1)
+        X1.append(X2 @ Rrel + c)                                   # X1 = Rrel^T X2 + c
+        epi_of[pos:pos + n_epi] = b
+        pos += n_epi
+    X1 = np.concatenate(X1)
+    Pw = (X1 - t1.astype(np.float64)) @ R1                         # Xw = R1^T (X1 - t1)
+    n_real = X1.shape[0]
+    # KF1 features: one per point, then duplicates of unclaimed features next to themselves
+    k1 = np.zeros(n, KP_DTYPE)
+    uv1, _ = pinhole_project(q1, t1, cam, Pw)
+    d1 = rng.integers(0, 256, (n, 32), dtype=np.uint8)
+    node1 = alphabet[rng.integers(0, n_nodes, n)]
+    w1 = rng.uniform(0.1, 1.0, n)
+    mp1 = (rng.random(n) < mp_frac).astype(np.uint8)
+    k1["x"][:n_real] = uv1[:, 0].astype(np.float32); k1["y"][:n_real] = uv1[:, 1].astype(np.float32)
+    k1["octave"] = np.minimum(rng.integers(0, n_levels, n), rng.integers(0, n_levels, n))
+    k1["angle"] = rng.integers(0, 360, n).astype(np.float32)
+    k1["size"] = 31.0
+    k1["response"] = rng.uniform(20, 80, n).astype(np.float32)
+    planted = epi_of >= 0
+    if mp_frac < 1.0:
+        mp1[planted] = 0
+    src_of = np.arange(n)                                          # the point feature a duplicate copies
+    for j in range(n_real, n):
+        i = int(rng.integers(0, n_pts))
+        src_of[j] = i
+        if mp_frac < 1.0:
+            mp1[i] = mp1[j] = 0
+        k1["x"][j] = np.float32(k1["x"][i] + rng.uniform(-0.3, 0.3)); k1["y"][j] = np.float32(k1["y"][i] + rng.uniform(-0.3, 0.3))
+        k1["angle"][j] = k1["angle"][i]
+        d1[j] = _flip_bits(rng, d1[i], int(rng.integers(1, 7)))
+        node1[j] = node1[i]
+    bad = rng.random(n)
+    free = ~planted & (src_of == np.arange(n)) & ~np.isin(np.arange(n), src_of[n_real:])
+    w1[free & (bad < 0.03)] = 0.0
+    node1[free & (bad > 0.98)] = -1
+    kf1 = TriKeyFrame(k1, d1, node1, w1, mp1, q1, t1, cam["fx"], cam["fy"], cam["cx"], cam["cy"])
+    n2 = [n2] * B if n2 is None or np.isscalar(n2) else list(n2)
+    neighbours, twins = [], []
+    for b in range(B):
+        q2, t2 = poses[b]
+        uv2, z2 = pinhole_project(q2, t2, cam, Pw)
+        rot_b = 7.0 + 11.0 * (b % 7)
+        rows = []                                                  # (kp fields, desc, node, weight, mp, twin of)
+        def feat(x, y, octave, angle, desc, node, weight, mp, of):
+            r = np.zeros(1, KP_DTYPE)[0]
+            a = np.float32(angle % 360.0)
+            r["x"], r["y"], r["octave"], r["angle"] = np.float32(x), np.float32(y), octave, (a if a < 360 else 0.0)
+            r["size"], r["response"] = 31.0, 50.0
+            rows.append((r, desc, node, weight, mp, of))
+        tie_left = max(3, n // 60)
+        for i in range(n_real):
+            at_epi = epi_of[i] == b
+            inside = z2[i] > 0.1 and 0 <= uv2[i, 0] < W and 0 <= uv2[i, 1] < H
+            if not inside or (not at_epi and rng.random() > 0.9):
+                continue
+            octave = int(min(rng.integers(0, n_levels), rng.integers(0, n_levels)))
+            sig = float(sf[octave])
+            if at_epi:
+                octave, sig = int(rng.integers(0, 3)), 0.0
+                dx, dy = rng.normal(size=2) * 0.2
+            elif rng.random() < 0.15:
+                a = rng.uniform(0, 2 * np.pi); r_ = rng.uniform(2.5, 8.0) * sig
+                dx, dy = r_ * np.cos(a), r_ * np.sin(a)
+            else:
+                dx, dy = rng.normal(size=2) * 0.5 * sig
+            angle = k1["angle"][i] - rot_b + rng.normal() * 2.0 if (at_epi or rng.random() > 0.12) else rng.uniform(0, 360)
+            node = node1[i]
+            if not at_epi and rng.random() < 0.07:
+                node = alphabet[rng.integers(0, n_nodes)]
+            weight = 0.0 if (not at_epi and rng.random() < 0.03) else rng.uniform(0.1, 1.0)
+            if not at_epi and rng.random() < 0.02:
+                node = -1
+            mp = 0 if at_epi else int(rng.random() < (0.85 if mp1[i] else 0.05))
+            desc = _flip_bits(rng, d1[i], int(rng.integers(0, 11 if at_epi else 31)))
+            feat(uv2[i, 0] + dx, uv2[i, 1] + dy, octave, angle, desc, node, weight, mp, i)
+            if tie_left and not at_epi and not mp and not mp1[i] and node == node1[i] and weight > 0 and w1[i] > 0 \
+                    and node >= 0 and abs(dx) + abs(dy) < sig:
+                tie_left -= 1                                      # an exact copy: equal distance, the later index wins
+                feat(uv2[i, 0] + dx, uv2[i, 1] + dy, octave, angle, desc.copy(), node, weight, 0, -1)
+        target = n2[b]
+        n_dis = int(0.2 * n) if target is None else max(target - len(rows), 0)
+        if target is not None and len(rows) > target:
+            keep = np.sort(rng.permutation(len(rows))[:target])
+            rows = [rows[k] for k in keep]
+        for _ in range(n_dis):
+            feat(rng.uniform(0, W), rng.uniform(0, H), int(rng.integers(0, n_levels)), rng.uniform(0, 360),
+                 rng.integers(0, 256, 32, dtype=np.uint8), alphabet[rng.integers(0, n_nodes)], rng.uniform(0.1, 1.0),
+                 int(rng.random() < 0.1), -1)
+        perm = rng.permutation(len(rows))
+        rows = [rows[k] for k in perm]
+        m = len(rows)
+        k2 = np.array([r[0] for r in rows], KP_DTYPE) if m else np.zeros(0, KP_DTYPE)
+        d2 = np.stack([r[1] for r in rows]).astype(np.uint8) if m else np.zeros((0, 32), np.uint8)
+        twin = np.full(n, -1, np.int64)
+        for j, r in enumerate(rows):
+            if r[5] >= 0:
+                twin[r[5]] = j
+        neighbours.append(TriKeyFrame(k2, d2, np.array([r[2] for r in rows], np.int32),
+                                      np.array([r[3] for r in rows], np.float64),
+                                      np.array([r[4] for r in rows], np.uint8), q2, t2, cam["fx"], cam["fy"],
+                                      cam["cx"], cam["cy"]))
+        twins.append(twin)
+    return dict(kf1=kf1, neighbours=neighbours, scale_factors=sf, level_sigma2=s2, twin=twins,
+                epi=[np.nonzero(epi_of == b)[0] for b in range(B)], cam=cam)

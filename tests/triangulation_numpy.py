@@ -1,0 +1,209 @@
+"""Test infrastructure: the restatement of U:src/ORBmatcher.cc::SearchForTriangulation(pKF1, pKF2,
+vMatchedPairs, bOnlyStereo=false, bCoarse=false) (monocular, one pinhole camera per keyframe) that
+DESIGN.md writes down, in explicit np.float32 scalar operations: every product, sum, quotient and
+comparison is one IEEE operation in the order the library performs it (no `@`, no dot: BLAS may
+fuse), so the library's fp32 results can be compared bit for bit. Not used by the product.
+
+Keyframes are objects with the attributes of orb_slam3_ros2_amd.matcher.TriKeyFrame."""
+import numpy as np
+
+f32 = np.float32
+TH_LOW = 50
+HISTO_LENGTH = 30
+_POP = np.array([bin(i).count("1") for i in range(256)], np.int64)
+
+
+def _rot(q):
+    """Eigen's Quaternion::toRotationMatrix in fp32 (row-major list of 9)."""
+    x, y, z, w = (f32(v) for v in q)
+    two = f32(2)
+    tx, ty, tz = two * x, two * y, two * z
+    twx, twy, twz = tx * w, ty * w, tz * w
+    txx, txy, txz = tx * x, ty * x, tz * x
+    tyy, tyz, tzz = ty * y, tz * y, tz * z
+    one = f32(1)
+    return [one - (tyy + tzz), txy - twz, txz + twy,
+            txy + twz, one - (txx + tzz), tyz - twx,
+            txz - twy, tyz + twx, one - (txx + tyy)]
+
+
+def geometry(kf1, kf2):
+    """(F12 (3, 3) float32, ep (2,) float32): F12 = K1^-T [t12]x R12 K2^-1 with the closed-form K^-1
+    and KF1's camera centre projected into image 2."""
+    with np.errstate(all="ignore"):
+        R1, R2 = _rot(kf1.pose_q), _rot(kf2.pose_q)
+        t1 = [f32(v) for v in kf1.pose_t]
+        t2 = [f32(v) for v in kf2.pose_t]
+        R12 = [None] * 9
+        for i in range(3):
+            for j in range(3):
+                R12[3 * i + j] = (R1[3 * i] * R2[3 * j] + R1[3 * i + 1] * R2[3 * j + 1]) + R1[3 * i + 2] * R2[3 * j + 2]
+        t12 = [t1[i] - ((R12[3 * i] * t2[0] + R12[3 * i + 1] * t2[1]) + R12[3 * i + 2] * t2[2]) for i in range(3)]
+        Cw = [-((R1[i] * t1[0] + R1[3 + i] * t1[1]) + R1[6 + i] * t1[2]) for i in range(3)]
+        C2 = [((R2[3 * i] * Cw[0] + R2[3 * i + 1] * Cw[1]) + R2[3 * i + 2] * Cw[2]) + t2[i] for i in range(3)]
+        fx1, fy1, cx1, cy1 = f32(kf1.fx), f32(kf1.fy), f32(kf1.cx), f32(kf1.cy)
+        fx2, fy2, cx2, cy2 = f32(kf2.fx), f32(kf2.fy), f32(kf2.cx), f32(kf2.cy)
+        ep = np.array([(fx2 * C2[0]) / C2[2] + cx2, (fy2 * C2[1]) / C2[2] + cy2], f32)
+        E = [None] * 9
+        for j in range(3):
+            E[j] = t12[1] * R12[6 + j] - t12[2] * R12[3 + j]
+            E[3 + j] = t12[2] * R12[j] - t12[0] * R12[6 + j]
+            E[6 + j] = t12[0] * R12[3 + j] - t12[1] * R12[j]
+        one = f32(1)
+        ifx1, ify1, mcx1, mcy1 = one / fx1, one / fy1, (-cx1) / fx1, (-cy1) / fy1
+        ifx2, ify2, mcx2, mcy2 = one / fx2, one / fy2, (-cx2) / fx2, (-cy2) / fy2
+        G = [None] * 9
+        for j in range(3):
+            G[j] = ifx1 * E[j]
+            G[3 + j] = ify1 * E[3 + j]
+            G[6 + j] = (mcx1 * E[j] + mcy1 * E[3 + j]) + E[6 + j]
+        F = [None] * 9
+        for i in range(3):
+            F[3 * i] = G[3 * i] * ifx2
+            F[3 * i + 1] = G[3 * i + 1] * ify2
+            F[3 * i + 2] = (G[3 * i] * mcx2 + G[3 * i + 1] * mcy2) + G[3 * i + 2]
+        return np.array(F, f32).reshape(3, 3), ep
+
+
+def roundf(v) -> int:
+    """C roundf: halves away from zero (np.round rounds them to even)."""
+    v = float(v)
+    return int(np.floor(v + 0.5)) if v >= 0 else -int(np.floor(-v + 0.5))
+
+
+def three_maxima(hist):
+    """ORBmatcher::ComputeThreeMaxima over bin counts."""
+    max1 = max2 = max3 = 0
+    ind1 = ind2 = ind3 = -1
+    for i, s in enumerate(hist):
+        if s > max1:
+            max3, max2, max1 = max2, max1, s
+            ind3, ind2, ind1 = ind2, ind1, i
+        elif s > max2:
+            max3, max2 = max2, s
+            ind3, ind2 = ind2, i
+        elif s > max3:
+            max3, ind3 = s, i
+    if f32(max2) < f32(0.1) * f32(max1):
+        ind2 = ind3 = -1
+    elif f32(max3) < f32(0.1) * f32(max1):
+        ind3 = -1
+    return ind1, ind2, ind3
+
+
+def _feature_vector(kf):
+    """node -> ascending feature indices (weight > 0 and node >= 0 only), as Frame::ComputeBoW."""
+    fv = {}
+    for i in range(kf.n):
+        if kf.node[i] >= 0 and kf.weight[i] > 0:
+            fv.setdefault(int(kf.node[i]), []).append(i)
+    return fv
+
+
+def search_pair(kf1, kf2, scale_factors, level_sigma2, check_orientation, F12=None, ep=None):
+    """One (KF1, KF2) pair. Returns (nmatches, match12 (n1,) int32, counters). counters: `epipole`
+    / `epiline` candidates that passed the distance gates and were rejected by the epipole
+    exclusion / the epipolar-line gate (den == 0 included), `ties` accepts at a distance equal to
+    the running best (the later index replaces the earlier), `shared` KF2 features matched by more
+    than one KF1 feature (before the orientation filter), `pruned` matches the filter removed."""
+    if F12 is None or ep is None:
+        F12, ep = geometry(kf1, kf2)
+    F = np.asarray(F12, f32).reshape(3, 3)
+    ex, ey = f32(ep[0]), f32(ep[1])
+    sf = np.asarray(scale_factors, f32)
+    s2 = np.asarray(level_sigma2, f32)
+    n1 = kf1.n
+    match = np.full(n1, -1, np.int32)
+    cnt = dict(epipole=0, epiline=0, ties=0, shared=0, pruned=0)
+    fv1, fv2 = _feature_vector(kf1), _feature_vector(kf2)
+    d2all = np.asarray(kf2.desc, np.uint8).reshape(-1, 32)
+    factor = f32(1.0) / f32(HISTO_LENGTH)
+    rot_hist = [[] for _ in range(HISTO_LENGTH)]
+    with np.errstate(all="ignore"):
+        for node in sorted(set(fv1) & set(fv2)):
+            cand = np.array(fv2[node], np.int64)
+            for idx1 in fv1[node]:
+                if kf1.has_mp[idx1]:
+                    continue
+                dists = _POP[np.bitwise_xor(d2all[cand], np.asarray(kf1.desc[idx1], np.uint8).reshape(1, 32))].sum(1)
+                x1, y1 = f32(kf1.kps["x"][idx1]), f32(kf1.kps["y"][idx1])
+                a = (x1 * F[0, 0] + y1 * F[1, 0]) + F[2, 0]
+                b = (x1 * F[0, 1] + y1 * F[1, 1]) + F[2, 1]
+                c = (x1 * F[0, 2] + y1 * F[1, 2]) + F[2, 2]
+                den = a * a + b * b
+                best_dist, best_idx2 = TH_LOW, -1
+                for k, idx2 in enumerate(cand):
+                    idx2 = int(idx2)
+                    if kf2.has_mp[idx2]:
+                        continue
+                    dist = int(dists[k])
+                    if dist > TH_LOW or dist > best_dist:
+                        continue
+                    x2, y2 = f32(kf2.kps["x"][idx2]), f32(kf2.kps["y"][idx2])
+                    o2 = int(kf2.kps["octave"][idx2])
+                    dex, dey = ex - x2, ey - y2
+                    if dex * dex + dey * dey < f32(100) * sf[o2]:
+                        cnt["epipole"] += 1
+                        continue
+                    num = (a * x2 + b * y2) + c
+                    if den == f32(0):
+                        cnt["epiline"] += 1
+                        continue
+                    dsqr = (num * num) / den
+                    if not (np.float64(dsqr) < np.float64(3.84) * np.float64(s2[o2])):
+                        cnt["epiline"] += 1
+                        continue
+                    if best_idx2 >= 0 and dist == best_dist:
+                        cnt["ties"] += 1
+                    best_idx2, best_dist = idx2, dist
+                if best_idx2 >= 0:
+                    match[idx1] = best_idx2
+                    if check_orientation:
+                        rot = f32(kf1.kps["angle"][idx1]) - f32(kf2.kps["angle"][best_idx2])
+                        if rot < 0:
+                            rot = rot + f32(360)
+                        bin_ = roundf(rot * factor)
+                        if bin_ == HISTO_LENGTH:
+                            bin_ = 0
+                        assert 0 <= bin_ < HISTO_LENGTH
+                        rot_hist[bin_].append(idx1)
+    targets = match[match >= 0]
+    cnt["shared"] = int((np.bincount(targets, minlength=1) > 1).sum()) if targets.size else 0
+    if check_orientation:
+        keep = three_maxima([len(h) for h in rot_hist])
+        for i in range(HISTO_LENGTH):
+            if i not in keep:
+                for idx1 in rot_hist[i]:
+                    match[idx1] = -1
+                    cnt["pruned"] += 1
+    return int((match >= 0).sum()), match, cnt
+
+
+def search_for_triangulation(kf1, neighbours, scale_factors, level_sigma2, check_orientation, geoms=None):
+    """kf1 against every neighbour. geoms: per neighbour (F12, ep), e.g. the library's own
+    (TriKeyFrame.geometry); None = geometry() above. Returns (nmatches (B,), match12 (B, n1),
+    counters summed over the pairs, per-pair counters)."""
+    nm, rows, per = [], [], []
+    total = dict(epipole=0, epiline=0, ties=0, shared=0, pruned=0)
+    for b, kf2 in enumerate(neighbours):
+        F, ep = geoms[b] if geoms is not None else (None, None)
+        n, m, c = search_pair(kf1, kf2, scale_factors, level_sigma2, check_orientation, F, ep)
+        nm.append(n); rows.append(m); per.append(c)
+        for k in total:
+            total[k] += c[k]
+    m12 = np.stack(rows) if rows else np.zeros((0, kf1.n), np.int32)
+    return np.array(nm, np.int32), m12, total, per
+
+
+# ---- the parity scene set (tests/test_triangulation.py asserts its Conditions on the CPU,
+# tests/test_triangulation_gpu.py runs the library on it) ----
+PARITY_SCENES = [dict(n=300, B=3, seed=s) for s in (0, 1, 2)]
+_scene_cache = {}
+
+
+def parity_scene(k: int):
+    """Scene k of the set (built once per process; treat it as read-only)."""
+    if k not in _scene_cache:
+        from orb_slam3_ros2_amd.synthetic import synthetic_triangulation_scene
+        _scene_cache[k] = synthetic_triangulation_scene(**PARITY_SCENES[k])
+    return _scene_cache[k]
