@@ -199,7 +199,8 @@ int orbhip_frontend_context(orbhip_frontend* fe, int j, orbhip_ctx** out);
  * orbhip_profile_stage selects ONE stage whose launches are bracketed by hipEvents on the
  * stream they run on (0 off, 1 pyramid resize, 2 FAST cells, 3 octree, 4 orientation +
  * descriptor, 5 Hamming top-2, 6 rotation filter, 7 SearchForTriangulation: the ordering pre-pass
- * and the search of one call form one pair). orbhip_profile_collect synchronises and
+ * and the search of one call form one pair, 8 Fuse: the grid build and the search of one call form
+ * one pair). orbhip_profile_collect synchronises and
  * returns the summed duration (ms) and the number of bracketed launches, then resets. The one-launch
  * pyramid (k_pyr_cone) and the octree also time themselves on the device (first workgroup start to
  * last workgroup end, s_memrealtime: the span rocprofv3's kernel trace reports); their stages
@@ -480,6 +481,38 @@ int orbhip_search_for_triangulation(orbhip_ctx* ctx, const orbhip_tri_keyframe* 
                                     const orbhip_tri_keyframe* nbrs, int B,
                                     const float* scale_factors, const float* level_sigma2, int n_levels,
                                     int check_orientation, int32_t* match12, int32_t* nmatches);
+
+/* ---- map point fusion: Fuse ------------------------------------------
+ * U:src/ORBmatcher.cc::Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, const float th,
+ * bRight = false), as U:src/LocalMapping.cc::SearchInNeighbors calls it: monocular, one pinhole
+ * camera, mvKeysUn, no stereo coordinate. B keyframes are searched for the same list of MapPoints in
+ * one call. Per (keyframe b, MapPoint m) not skipped: the point is projected with Tcw (quaternion
+ * form), must lie in front of the camera, inside the image (IsInImage: the maximum is strict),
+ * within [0.8 mfMinDistance, 1.2 mfMaxDistance] of the camera centre and within 60 degrees of its
+ * normal; PredictScale gives the level, th * mvScaleFactors[level] the window of
+ * KeyFrame::GetFeaturesInArea; a candidate keypoint needs octave in [level - 1, level] and a squared
+ * reprojection error e2 with e2 * inv_level_sigma2[octave] <= 5.99; of the candidates the one of
+ * least descriptor distance wins (the first in the reference's walk order among equals) and is
+ * accepted at distance <= TH_LOW = 50. No pair reads state another pair writes: the call sees every
+ * MapPoint as it is at call time, and the adapter applies Replace / AddObservation / AddMapPoint in
+ * upstream order. DESIGN.md fixes the fp32 operation order of every gate.
+ *
+ * kfs[b]: mvKeysUn, descriptors, image bounds, scale tables, intrinsics, Tcw; claimed is ignored
+ * (the adapter looks pKF->GetMapPoint(best_idx) up itself). All keyframes of a call share n_levels,
+ * scale_factors (by value) and log_scale_factor, else ORBHIP_ERR_ARG. mps->skip[m] = !pMP ||
+ * pMP->isBad(); pair_skip[b * n + m] = pMP->IsInKeyFrame(kf b) (NULL: none).
+ * Outputs, B x mps->n: best_idx = the keypoint of keyframe b the point fuses into, or -1;
+ * best_dist (optional) = the least distance over the gated candidates, 256 without one, reported
+ * even above 50; level (optional) = nPredictedLevel, -1 when the point was skipped or rejected before
+ * PredictScale. nfused[b] = accepted points of keyframe b; returns their sum. B = 0 or n = 0: 0.
+ * B > 64, mps->n > 65536, a keyframe of more than 65535 keypoints or n_levels > 256:
+ * ORBHIP_ERR_UNSUPPORTED; a keypoint octave outside [0, n_levels): ORBHIP_ERR_ARG. One upload, two
+ * launches (the keyframes' grids, the search), one read-back. */
+int orbhip_fuse(orbhip_ctx* ctx, const orbhip_frame* kfs, int B, const orbhip_local_points* mps,
+                const uint8_t* pair_skip /* B x mps->n or NULL: IsInKeyFrame(kf b) */,
+                const float* inv_level_sigma2 /* n_levels */, float th,
+                int32_t* best_idx /* B x n */, int32_t* best_dist /* B x n or NULL */,
+                int32_t* level /* B x n or NULL */, int32_t* nfused /* B */);
 
 /* ---- multi-GPU BundleAdjustment (SURVEY.md §8e, C5 GlobalBundleAdjustment) --------
  * One process per GPU. Landmarks (with their edges) are partitioned across ranks; every rank

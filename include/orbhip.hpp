@@ -169,6 +169,38 @@ public:
         return std::vector<int>(nm.begin(), nm.end());
     }
 
+    // U:src/ORBmatcher.cc::Fuse(pKF, vpMapPoints, th) of every keyframe against the same MapPoints in
+    // one call (LocalMapping::SearchInNeighbors). vbPairSkip: empty, or B x n with
+    // pMP->IsInKeyFrame(keyframe b). vBestIdx[b][m] = the keypoint of keyframe b MapPoint m fuses into,
+    // or -1; the adapter applies Replace / AddObservation / AddMapPoint in upstream order. vBestDist /
+    // vLevel (optional) receive the winning distance and nPredictedLevel. Returns the fused points per
+    // keyframe.
+    std::vector<int> Fuse(orbhip_ctx* ctx, const std::vector<orbhip_frame>& keyframes,
+                          const orbhip_local_points& vpMapPoints, const std::vector<uint8_t>& vbPairSkip,
+                          const std::vector<float>& mvInvLevelSigma2, float th,
+                          std::vector<std::vector<int>>& vBestIdx, std::vector<std::vector<int>>* vBestDist = nullptr,
+                          std::vector<std::vector<int>>* vLevel = nullptr) const {
+        const int B = (int)keyframes.size();
+        const size_t n = (size_t)std::max(vpMapPoints.n, 0);
+        if (!vbPairSkip.empty() && vbPairSkip.size() != (size_t)B * n) throw Error(ORBHIP_ERR_ARG, "Fuse: vbPairSkip");
+        for (const orbhip_frame& f : keyframes)
+            if ((size_t)std::max(f.n_levels, 0) > mvInvLevelSigma2.size()) throw Error(ORBHIP_ERR_ARG, "Fuse: mvInvLevelSigma2");
+        std::vector<int32_t> idx((size_t)B * n, -1), dist(vBestDist ? (size_t)B * n : 0), lvl(vLevel ? (size_t)B * n : 0);
+        std::vector<int32_t> nf(B, 0);
+        const int rc = orbhip_fuse(ctx, keyframes.data(), B, &vpMapPoints, vbPairSkip.empty() ? nullptr : vbPairSkip.data(),
+                                   mvInvLevelSigma2.data(), th, idx.data(), vBestDist ? dist.data() : nullptr,
+                                   vLevel ? lvl.data() : nullptr, nf.data());
+        check(rc, "orbhip_fuse");
+        auto rows = [&](const std::vector<int32_t>& flat, std::vector<std::vector<int>>& out) {
+            out.assign(B, std::vector<int>());
+            for (int b = 0; b < B; b++) out[b].assign(flat.begin() + (size_t)b * n, flat.begin() + (size_t)(b + 1) * n);
+        };
+        rows(idx, vBestIdx);
+        if (vBestDist) rows(dist, *vBestDist);
+        if (vLevel) rows(lvl, *vLevel);
+        return std::vector<int>(nf.begin(), nf.end());
+    }
+
     float mfNNratio;
     bool mbCheckOrientation;
 };

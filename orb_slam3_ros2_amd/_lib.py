@@ -122,7 +122,7 @@ EXPORTED = ["orbhip_abi_version", "orbhip_create", "orbhip_destroy", "orbhip_lev
             "orbhip_bow_transform", "orbhip_bow_transform_device", "orbhip_search_bow",
             "orbhip_pose_optimization", "orbhip_pose_optimization_batch", "orbhip_search_by_projection_last",
             "orbhip_search_local_points", "orbhip_search_for_initialization",
-            "orbhip_triangulation_geometry", "orbhip_search_for_triangulation",
+            "orbhip_triangulation_geometry", "orbhip_search_for_triangulation", "orbhip_fuse",
             "orbhip_kfdb_create", "orbhip_kfdb_destroy", "orbhip_kfdb_add", "orbhip_kfdb_erase",
             "orbhip_kfdb_detect_relocalization", "orbhip_kfdb_detect_nbest",
             "orbhip_frontend_create", "orbhip_frontend_destroy", "orbhip_frontend_push", "orbhip_frontend_view",
@@ -190,6 +190,8 @@ def lib():
     L.orbhip_triangulation_geometry.argtypes = [ctypes.POINTER(TriKeyFrameC), ctypes.POINTER(TriKeyFrameC), vp, vp]
     L.orbhip_search_for_triangulation.argtypes = [vp, ctypes.POINTER(TriKeyFrameC), ctypes.POINTER(TriKeyFrameC), i32,
                                                   vp, vp, i32, i32, vp, vp]
+    L.orbhip_fuse.argtypes = [vp, ctypes.POINTER(FrameC), i32, ctypes.POINTER(LocalPointsC), vp, vp, f32, vp, vp, vp,
+                              vp]
     L.orbhip_kfdb_create.argtypes = [vp, i32, ctypes.POINTER(vp)]
     L.orbhip_kfdb_destroy.argtypes = [vp]
     L.orbhip_kfdb_add.argtypes = [vp, i32, vp, vp, i32]

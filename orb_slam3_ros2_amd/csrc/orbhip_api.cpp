@@ -172,6 +172,8 @@ struct orbhip_ctx {
     DevBuf<uint8_t> d_bow_stage;   // SearchByBoW host-call staging
     DevBuf<uint8_t> d_tri_stage;   // SearchForTriangulation: the call's device block
     PinBuf h_tri_stage;            // its pinned image (upload) and the read-back
+    DevBuf<uint8_t> d_fuse_stage;  // Fuse: the call's device block
+    PinBuf h_fuse_stage;           // its pinned image (upload) and the read-back
     DevBuf<LevelKp> d_lvl_kp;
     DevBuf<orbhip_kp> d_kps;
     DevBuf<uint8_t> d_desc;
@@ -1134,7 +1136,7 @@ int orbhip_launch_graphs(orbhip_ctx* c) {
 }
 
 int orbhip_profile_stage(orbhip_ctx* c, int stage) {
-    if (!c || stage < 0 || stage > 7) return ORBHIP_ERR_ARG;
+    if (!c || stage < 0 || stage > 8) return ORBHIP_ERR_ARG;
     HIPOK(hipSetDevice(c->device));
     StageTimer& t = c->timer;
     if (!t.created) {
@@ -1631,6 +1633,109 @@ int orbhip_search_for_triangulation(orbhip_ctx* c, const orbhip_tri_keyframe* kf
     std::memcpy(nmatches, hb + (size_t)B * n1 * 4, (size_t)B * 4);
     int total = 0;
     for (int b = 0; b < B; b++) total += nmatches[b];
+    return total;
+}
+
+// ---- Fuse: B keyframes against one list of MapPoints ----
+int orbhip_fuse(orbhip_ctx* c, const orbhip_frame* kfs, int B, const orbhip_local_points* mps,
+                const uint8_t* pair_skip, const float* inv_level_sigma2, float th, int32_t* best_idx,
+                int32_t* best_dist, int32_t* level, int32_t* nfused) {
+    if (!c || B < 0 || !mps || mps->n < 0) return ORBHIP_ERR_ARG;
+    if (B == 0) return 0;
+    if (B > kFuseMaxKf || mps->n > kFuseMaxPoints) return ORBHIP_ERR_UNSUPPORTED;
+    if (!kfs || !nfused) return ORBHIP_ERR_ARG;
+    const int n = mps->n, L = kfs[0].n_levels;
+    if (L <= 0 || !kfs[0].scale_factors || !inv_level_sigma2) return ORBHIP_ERR_ARG;
+    if (L > kFuseMaxLevels) return ORBHIP_ERR_UNSUPPORTED;
+    size_t nk_total = 0;
+    for (int b = 0; b < B; b++) {
+        const orbhip_frame& f = kfs[b];
+        if (f.n < 0) return ORBHIP_ERR_ARG;
+        if (f.n > 65535) return ORBHIP_ERR_UNSUPPORTED;
+        if (f.n && (!f.kps || !f.desc)) return ORBHIP_ERR_ARG;
+        // one scale pyramid per call
+        if (f.n_levels != L || !f.scale_factors || f.log_scale_factor != kfs[0].log_scale_factor) return ORBHIP_ERR_ARG;
+        if (std::memcmp(f.scale_factors, kfs[0].scale_factors, (size_t)L * 4) != 0) return ORBHIP_ERR_ARG;
+        for (int i = 0; i < f.n; i++)
+            if (f.kps[i].octave < 0 || f.kps[i].octave >= L) return ORBHIP_ERR_ARG;
+        nk_total += (size_t)f.n;
+    }
+    for (int b = 0; b < B; b++) nfused[b] = 0;
+    if (n == 0) return 0;
+    if (!best_idx || !mps->points || !mps->normals || !mps->min_dist || !mps->max_dist || !mps->desc)
+        return ORBHIP_ERR_ARG;
+    HIPOK(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    // one block, the same layout on the host (pinned) and the device:
+    // [keyframes B | scale factors | inv sigma2 | points normals min max desc skip | pair_skip B x n |
+    //  keypoints | keyframe descriptors], then device only [cell_start B x 3073 | records |
+    //  nfused B | best_idx B x n | best_dist B x n | level B x n]; the last four are read back
+    size_t off = 0;
+    auto take = [&](size_t bytes) { off = (off + 15) & ~size_t(15); const size_t o = off; off += bytes; return o; };
+    const size_t bn = (size_t)B * (size_t)n;
+    const size_t o_kf = take((size_t)B * sizeof(FuseKf));
+    const size_t o_sf = take((size_t)L * 4), o_s2 = take((size_t)L * 4);
+    const size_t o_pts = take((size_t)n * 12), o_nrm = take((size_t)n * 12), o_min = take((size_t)n * 4);
+    const size_t o_max = take((size_t)n * 4), o_desc = take((size_t)n * 32), o_skip = take((size_t)n);
+    const size_t o_pskip = take(pair_skip ? bn : 0);
+    const size_t o_kps = take(nk_total * sizeof(orbhip_kp)), o_kdesc = take(nk_total * 32);
+    const size_t up_bytes = take(0);
+    const size_t o_cs = take((size_t)B * (kFuseCells + 1) * 4), o_rec = take(nk_total * sizeof(FuseRec));
+    const size_t o_back = take(0);
+    const size_t nf_bytes = ((size_t)B * 4 + 15) & ~size_t(15);   // best_idx starts 16-byte aligned behind nfused
+    const size_t n_out = level ? 3 : (best_dist ? 2 : 1);         // arrays read back: a prefix of idx, dist, level
+    const size_t back_bytes = nf_bytes + n_out * bn * 4;
+    off = o_back + nf_bytes + 3 * bn * 4;
+    const size_t dev_bytes = take(0);
+    HIPOK(c->d_fuse_stage.ensure(dev_bytes));
+    HIPOK(c->h_fuse_stage.ensure(up_bytes + back_bytes + 16));
+    uint8_t* const d = c->d_fuse_stage.p;
+    uint8_t* const h = c->h_fuse_stage.p;
+    FuseKf* hk = (FuseKf*)(h + o_kf);
+    size_t base = 0;
+    for (int b = 0; b < B; b++) {
+        const orbhip_frame& f = kfs[b];
+        fuse_kf_params(f, (int)base, &hk[b]);
+        if (f.n) {
+            std::memcpy(h + o_kps + base * sizeof(orbhip_kp), f.kps, (size_t)f.n * sizeof(orbhip_kp));
+            std::memcpy(h + o_kdesc + base * 32, f.desc, (size_t)f.n * 32);
+        }
+        base += (size_t)f.n;
+    }
+    std::memcpy(h + o_sf, kfs[0].scale_factors, (size_t)L * 4);
+    std::memcpy(h + o_s2, inv_level_sigma2, (size_t)L * 4);
+    std::memcpy(h + o_pts, mps->points, (size_t)n * 12);
+    std::memcpy(h + o_nrm, mps->normals, (size_t)n * 12);
+    std::memcpy(h + o_min, mps->min_dist, (size_t)n * 4);
+    std::memcpy(h + o_max, mps->max_dist, (size_t)n * 4);
+    std::memcpy(h + o_desc, mps->desc, (size_t)n * 32);
+    if (mps->skip) std::memcpy(h + o_skip, mps->skip, (size_t)n);
+    else std::memset(h + o_skip, 0, (size_t)n);
+    if (pair_skip) std::memcpy(h + o_pskip, pair_skip, bn);
+    HIPOK(hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
+    (void)hipGetLastError();
+    int32_t* const d_nf = (int32_t*)(d + o_back);
+    int32_t* const d_idx = (int32_t*)(d + o_back + nf_bytes);
+    {
+        const StageScope scope(c->timer);
+        c->timer.begin(8, st);
+        const FusePoints mp{n, (const float*)(d + o_pts), (const float*)(d + o_nrm), (const float*)(d + o_min),
+                            (const float*)(d + o_max), d + o_desc, d + o_skip};
+        launch_fuse((const FuseKf*)(d + o_kf), B, mp, pair_skip ? d + o_pskip : nullptr, (const float*)(d + o_sf),
+                    (const float*)(d + o_s2), L, kfs[0].log_scale_factor, th, (const orbhip_kp*)(d + o_kps), d + o_kdesc,
+                    (int32_t*)(d + o_cs), (FuseRec*)(d + o_rec), d_idx, d_idx + bn, d_idx + 2 * bn, d_nf, st);
+        c->timer.end(8, st);
+    }
+    HIPOK(hipGetLastError());
+    uint8_t* const hb = h + ((up_bytes + 15) & ~size_t(15));
+    HIPOK(hipMemcpyAsync(hb, d + o_back, back_bytes, hipMemcpyDeviceToHost, st));
+    HIPOK(hipStreamSynchronize(st));
+    std::memcpy(nfused, hb, (size_t)B * 4);
+    std::memcpy(best_idx, hb + nf_bytes, bn * 4);
+    if (best_dist) std::memcpy(best_dist, hb + nf_bytes + bn * 4, bn * 4);
+    if (level) std::memcpy(level, hb + nf_bytes + 2 * bn * 4, bn * 4);
+    int total = 0;
+    for (int b = 0; b < B; b++) total += nfused[b];
     return total;
 }
 

@@ -198,6 +198,31 @@ void launch_tri_search(const TriSide* sides, const TriGeom* geom, int n1, int B,
                        const float* level_sigma2, unsigned long long* keys1, int32_t* m1, int check_orientation,
                        int32_t* match12, int32_t* nmatches, hipStream_t st);
 
+// ---- Fuse (fuse_kernels.hip) ----
+constexpr int kFuseCols = 64, kFuseRows = 48, kFuseCells = kFuseCols * kFuseRows;   // the frame grid
+constexpr int kFuseMaxKf = 64;         // keyframes per call
+constexpr int kFuseMaxPoints = 65536;  // MapPoints per call
+constexpr int kFuseMaxLevels = 256;    // the octave shares a word with the cell
+struct FuseKf {                        // one keyframe of the call
+    int n, base;                       // its keypoints are entries [base, base + n) of the call's arrays
+    float minx, maxx, miny, maxy, invw, invh;
+    float q[4], t[3], Ow[3], fx, fy, cx, cy;
+};
+struct FuseRec { float x, y; int cell_oct, idx; };   // a keypoint in cell order: cell << 8 | octave, its index
+struct FusePoints {                    // the MapPoints (device pointers; skip is never null here)
+    int n;
+    const float *pts, *nrm, *mind, *maxd;
+    const uint8_t *desc, *skip;
+};
+// host, fp32 in a fixed operation order: grid scales and mOw
+void fuse_kf_params(const orbhip_frame& f, int base, FuseKf* k);
+// cell_start: B x 3073, recs: one per keypoint of the call (both written by k_fuse_grid);
+// best_idx / best_dist / level: B x n, nfused: B (zeroed by k_fuse_grid)
+void launch_fuse(const FuseKf* kfs, int B, const FusePoints& mp, const uint8_t* pair_skip, const float* scale_factors,
+                 const float* inv_level_sigma2, int n_levels, float log_sf, float th, const orbhip_kp* kps,
+                 const uint8_t* kf_desc, int32_t* cell_start, FuseRec* recs, int32_t* best_idx, int32_t* best_dist,
+                 int32_t* level, int32_t* nfused, hipStream_t st);
+
 // ---- ingest ----
 void launch_bgr2gray(const uint8_t* src, int B, int w, int h, int sstride, int64_t sfstride, uint8_t* dst, int dstride,
                      int64_t dfstride, hipStream_t st);

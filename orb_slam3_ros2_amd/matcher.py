@@ -188,6 +188,44 @@ class ORBmatcher:
               "orbhip_search_for_triangulation")
         return nm, m
 
+    # ---- map point fusion (LocalMapping::SearchInNeighbors) ----
+    def Fuse(self, kfs, points, normals, min_dist, max_dist, mp_desc, inv_level_sigma2, th: float = 3.0,
+             skip=None, pair_skip=None):
+        """U:src/ORBmatcher.cc::Fuse(pKF, vpMapPoints, th) of every keyframe of `kfs` (a list of
+        ProjFrame, at most 64, one scale pyramid) against the same MapPoints in one call.
+        skip[m] = !pMP || isBad(), pair_skip[b, m] = pMP->IsInKeyFrame(kfs[b]). Every point is seen as
+        it is at call time; the caller applies Replace / AddObservation / AddMapPoint in upstream
+        order (INTEGRATION.md). Returns (nfused[B], best_idx[B, n], best_dist[B, n], level[B, n]):
+        best_idx = the keypoint of kfs[b] the point fuses into or -1, best_dist = the least distance
+        over the gated candidates (256: none), level = nPredictedLevel (-1: rejected before it)."""
+        kfs = list(kfs)
+        B = len(kfs)
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n = pts.shape[0]
+        nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        mn = np.ascontiguousarray(min_dist, np.float32)
+        mx = np.ascontiguousarray(max_dist, np.float32)
+        d = np.ascontiguousarray(mp_desc, np.uint8).reshape(-1, 32)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+        ps = None if pair_skip is None else np.ascontiguousarray(pair_skip, np.uint8).reshape(B, n)
+        s2 = np.ascontiguousarray(inv_level_sigma2, np.float32)
+        for a in (nrm, mn, mx, d) + (() if sk is None else (sk,)):
+            if a.shape[0] != n:
+                raise ValueError("Fuse: per-point arrays differ in length")
+        nf = np.zeros(B, np.int32)
+        idx = np.full((B, n), -1, np.int32)
+        dist = np.full((B, n), 256, np.int32)
+        lvl = np.full((B, n), -1, np.int32)
+        if B == 0:
+            return nf, idx, dist, lvl
+        if any(s2.shape[0] < len(k.scale_factors) for k in kfs):
+            raise ValueError("Fuse: inv_level_sigma2 shorter than the keyframes' scale tables")
+        arr = (FrameC * B)(*[k.to_c() for k in kfs])
+        lc = LocalPointsC(n, ptr(pts), ptr(nrm), ptr(mn), ptr(mx), ptr(d), ptr(sk))
+        check(lib().orbhip_fuse(self.ctx.handle, arr, B, ctypes.byref(lc), ptr(ps), ptr(s2), float(th), ptr(idx),
+                                ptr(dist), ptr(lvl), ptr(nf)), "orbhip_fuse")
+        return nf, idx, dist, lvl
+
 
 class TriKeyFrame:
     """A KeyFrame as SearchForTriangulation reads it: mvKeysUn (orbhip_kp records), descriptors, the

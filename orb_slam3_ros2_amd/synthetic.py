@@ -610,3 +610,177 @@ def synthetic_triangulation_scene(n=300, B=3, seed=0, n_nodes=12, n2=None, mp_fr
         twins.append(twin)
     return dict(kf1=kf1, neighbours=neighbours, scale_factors=sf, level_sigma2=s2, twin=twins,
                 epi=[np.nonzero(epi_of == b)[0] for b in range(B)], cam=cam)
+
+
+# ---------------------------------------------------------------------------
+# Fuse scenes (LocalMapping::SearchInNeighbors)
+# ---------------------------------------------------------------------------
+FUSE_KINDS = ("plain", "th_low", "chi2", "level", "twin_same", "twin_cell", "none", "behind", "outside", "far",
+              "near", "angle")
+
+
+def fuse_level_margin(kfs, points, max_dist):
+    """min over the keyframes of |x - nearest integer|, x = log(max_dist / dist3D) / log_scale_factor
+    in float64 from the float32 inputs, per MapPoint: how far PredictScale's ceil is from a step."""
+    P = np.asarray(points, np.float64)
+    out = np.full(P.shape[0], np.inf)
+    for k in kfs:
+        R = quat_to_rot64(k.pose_q)
+        Ow = -R.T @ np.asarray(k.pose_t, np.float64)
+        d = np.linalg.norm(P - Ow, axis=1)
+        with np.errstate(all="ignore"):
+            x = np.log(np.asarray(max_dist, np.float64) / d) / float(k.log_scale_factor)
+        out = np.minimum(out, np.abs(x - np.rint(x)))
+    return out
+
+
+def synthetic_fuse_scene(n_kp=300, n_mp=300, B=3, seed=0, n_levels=8, scale_factor=1.2, th=3.0, cam=None,
+                         radius=4.5, arc=0.7):
+    """B keyframes on an arc of `arc` radians, `radius` m from one cloud of n_mp MapPoints they all
+    look at, for ORBmatcher.Fuse. n_kp: keypoints per keyframe (an int, or one per keyframe). Every
+    point has a kind (FUSE_KINDS, returned as `kind`) that says what each keyframe that sees it gets:
+      plain      one keypoint within 1.5 level sigma of the projection, octave = the predicted level or
+                 one below, 0-40 descriptor bits flipped
+      th_low     as plain with 49 / 50 / 51 / 52 flipped bits (both sides of TH_LOW)
+      chi2       one keypoint 2.44 or 2.455 level sigma away (5.99 = 2.4474^2: inside / outside)
+      level      an exact copy of the descriptor at octave level - 2 or level + 1 (outside the gate),
+                 and mostly a proper keypoint with 20 flipped bits
+      twin_same  a plain keypoint and an equal copy 0.25 px beside it (usually the same cell)
+      twin_cell  two equal copies 3.2 level sigma apart in x (levels >= 5: usually different cells)
+      none       no keypoint
+      behind / outside / far / near / angle   the point lies behind the cameras / outside the images /
+                 beyond 1.2 mfMaxDistance / below 0.8 mfMinDistance / is seen at more than 60 degrees
+    The distance ranges put the predicted levels across 0 .. n_levels - 1. A point whose
+    log(max_dist / dist3D) / log_scale_factor comes within 2e-3 of an integer for some keyframe gets
+    its distance range scaled by 1.01 until none does (fuse_level_margin), so a last-bit difference
+    between two logf implementations cannot move a level. Keypoints are shuffled; a keyframe with
+    fewer planted keypoints than n_kp is filled with random ones, one with more drops the excess.
+    Returns a dict: kfs (ProjFrame), points, normals, min_dist, max_dist, mp_desc, skip, pair_skip,
+    scale_factors, inv_level_sigma2, th, kind, nudged (how many points had their range scaled)."""
+    from ._lib import KP_DTYPE
+    from .matcher import ProjFrame
+    rng = np.random.Generator(np.random.PCG64(seed))
+    cam = dict(D435I if cam is None else cam)
+    W, H = cam["w"], cam["h"]
+    sf, s2 = orb_scale_tables(n_levels, scale_factor)
+    inv_s2 = (np.float32(1.0) / s2).astype(np.float32)
+    n_kps = [int(n_kp)] * B if np.isscalar(n_kp) else [int(v) for v in n_kp]
+    assert len(n_kps) == B
+    # the keyframes
+    thetas = np.linspace(-arc / 2, arc / 2, B) if B > 1 else np.zeros(1)
+    poses, centres = [], []
+    for b in range(B):
+        c = radius * np.array([np.sin(thetas[b]), 0.1 * np.sin(3 * thetas[b]), -np.cos(thetas[b])])
+        R = _rodrigues(rng.normal(size=3) * 0.02) @ _look_at(c)
+        q = _mat_to_quat(R).astype(np.float32)
+        t = (-(quat_to_rot64(q) @ c)).astype(np.float32)
+        poses.append((q, t))
+        centres.append(-quat_to_rot64(q).T @ t.astype(np.float64))
+    mid = np.mean(centres, axis=0) if B else np.array([0.0, 0.0, -radius])
+    # the points
+    kind = rng.choice(len(FUSE_KINDS), n_mp, p=[0.44, 0.07, 0.07, 0.06, 0.06, 0.06, 0.06, 0.03, 0.04, 0.04, 0.03,
+                                               0.04])
+    K = {name: i for i, name in enumerate(FUSE_KINDS)}
+    P = np.stack([rng.uniform(-1.8, 1.8, n_mp), rng.uniform(-1.3, 1.3, n_mp), rng.uniform(-0.6, 0.6, n_mp)], 1)
+    P[kind == K["behind"]] = mid * rng.uniform(1.3, 2.0, (int((kind == K["behind"]).sum()), 1)) + \
+        rng.normal(size=(int((kind == K["behind"]).sum()), 3)) * 0.3
+    side = kind == K["outside"]
+    P[side, 0] = rng.choice([-1.0, 1.0], int(side.sum())) * rng.uniform(5.0, 8.0, int(side.sum()))
+    P = P.astype(np.float32)
+    P64 = P.astype(np.float64)
+    PO = P64 - mid
+    d_ref = np.linalg.norm(PO, axis=1)
+    normals = PO / d_ref[:, None] + rng.normal(size=(n_mp, 3)) * 0.03
+    ang = kind == K["angle"]
+    if ang.any():   # tilt by 70-85 degrees about an axis perpendicular to the viewing ray
+        for m in np.nonzero(ang)[0]:
+            axis = np.cross(PO[m], rng.normal(size=3))
+            axis /= np.linalg.norm(axis)
+            normals[m] = _rodrigues(axis * np.deg2rad(rng.uniform(70, 85))) @ (PO[m] / d_ref[m])
+    normals /= np.linalg.norm(normals, axis=1)[:, None]
+    target = rng.integers(0, n_levels, n_mp)
+    twin_cell = kind == K["twin_cell"]
+    target[twin_cell] = rng.integers(min(5, n_levels - 1), n_levels, int(twin_cell.sum()))
+    max_dist = d_ref * np.float64(scale_factor) ** (target - 0.5)
+    max_dist[kind == K["far"]] = d_ref[kind == K["far"]] * rng.uniform(0.5, 0.75, int((kind == K["far"]).sum()))
+    near = kind == K["near"]
+    max_dist[near] = d_ref[near] * rng.uniform(1.4, 1.8, int(near.sum())) * np.float64(scale_factor) ** (n_levels - 1)
+    max_dist = max_dist.astype(np.float32)
+    probe = [ProjFrame(np.zeros(0, KP_DTYPE), np.zeros((0, 32), np.uint8), q, t, cam["fx"], cam["fy"], cam["cx"],
+                       cam["cy"], W, H, scale_factor, n_levels) for q, t in poses]
+    nudged = np.zeros(n_mp, bool)
+    for _ in range(200):
+        close = fuse_level_margin(probe, P, max_dist) <= 2e-3
+        if not close.any():
+            break
+        nudged |= close
+        max_dist[close] = (max_dist[close] * np.float32(1.01)).astype(np.float32)
+    else:
+        raise RuntimeError("synthetic_fuse_scene: the level margin could not be reached")
+    min_dist = (max_dist.astype(np.float64) / np.float64(scale_factor) ** (n_levels - 1)).astype(np.float32)
+    mp_desc = rng.integers(0, 256, (n_mp, 32), dtype=np.uint8)
+    log_sf = float(probe[0].log_scale_factor) if B else float(np.log(np.float32(scale_factor)))
+    # the keypoints of every keyframe
+    kfs = []
+    for b in range(B):
+        q, t = poses[b]
+        uv, z = pinhole_project(q, t, cam, P64)
+        dist = np.linalg.norm(P64 - centres[b], axis=1)
+        with np.errstate(all="ignore"):
+            lvl = np.clip(np.ceil(np.log(max_dist.astype(np.float64) / dist) / log_sf), 0, n_levels - 1).astype(int)
+        seen = (z > 0.1) & (uv[:, 0] > 8) & (uv[:, 0] < W - 8) & (uv[:, 1] > 8) & (uv[:, 1] < H - 8)
+        rows = []   # (x, y, octave, descriptor)
+
+        def plant(m, rho, octave, desc, direction=None):
+            a = rng.uniform(0, 2 * np.pi) if direction is None else direction
+            e = rho * float(sf[octave])
+            rows.append((uv[m, 0] + e * np.cos(a), uv[m, 1] + e * np.sin(a), octave, desc))
+
+        for m in np.nonzero(seen)[0]:
+            L = int(lvl[m])
+            below = L - 1 if (L > 0 and rng.random() < 0.3) else L
+            kd = FUSE_KINDS[kind[m]]
+            if kd == "plain":
+                plant(m, rng.uniform(0, 1.5), below, _flip_bits(rng, mp_desc[m], int(rng.integers(0, 41))))
+            elif kd == "th_low":
+                plant(m, rng.uniform(0, 1.5), below, _flip_bits(rng, mp_desc[m], int(rng.choice([49, 50, 51, 52]))))
+            elif kd == "chi2":
+                plant(m, float(rng.choice([2.44, 2.455])), L, _flip_bits(rng, mp_desc[m], 10))
+            elif kd == "level":
+                wrong = L - 2 if L >= 2 else L + 1
+                if 0 <= wrong < n_levels:
+                    plant(m, rng.uniform(0, 0.3), wrong, mp_desc[m].copy())
+                if rng.random() < 0.6:
+                    plant(m, rng.uniform(0, 1.5), below, _flip_bits(rng, mp_desc[m], 20))
+            elif kd == "twin_same" or (kd == "twin_cell" and L < 5):
+                d = _flip_bits(rng, mp_desc[m], int(rng.integers(0, 31)))
+                plant(m, rng.uniform(0, 1.0), below, d)
+                x, y, o, _ = rows[-1]
+                rows.append((x + 0.25, y, o, d.copy()))
+            elif kd == "twin_cell":
+                d = _flip_bits(rng, mp_desc[m], int(rng.integers(0, 31)))
+                plant(m, 1.6, L, d, direction=0.0)
+                plant(m, 1.6, L, d.copy(), direction=np.pi)
+        nb = n_kps[b]
+        order = rng.permutation(len(rows))[:nb]
+        kps = np.zeros(nb, KP_DTYPE)
+        desc = rng.integers(0, 256, (nb, 32), dtype=np.uint8)
+        kps["x"] = rng.uniform(0, W, nb).astype(np.float32)
+        kps["y"] = rng.uniform(0, H, nb).astype(np.float32)
+        kps["octave"] = rng.integers(0, n_levels, nb)
+        for slot, r in enumerate(order):
+            x, y, o, d = rows[r]
+            kps["x"][slot], kps["y"][slot], kps["octave"][slot] = np.float32(x), np.float32(y), o
+            desc[slot] = d
+        shuffle = rng.permutation(nb)
+        kps, desc = kps[shuffle], desc[shuffle]
+        kps["angle"] = rng.uniform(0, 360, nb).astype(np.float32)
+        kps["size"] = (31.0 * sf[kps["octave"]]).astype(np.float32)
+        kps["response"] = rng.uniform(20, 80, nb).astype(np.float32)
+        kfs.append(ProjFrame(kps, desc, q, t, cam["fx"], cam["fy"], cam["cx"], cam["cy"], W, H, scale_factor,
+                             n_levels))
+    skip = (rng.random(n_mp) < 0.03).astype(np.uint8)
+    pair_skip = (rng.random((B, n_mp)) < 0.03).astype(np.uint8)
+    return dict(kfs=kfs, points=P, normals=normals.astype(np.float32), min_dist=min_dist, max_dist=max_dist,
+                mp_desc=mp_desc, skip=skip, pair_skip=pair_skip, scale_factors=sf, inv_level_sigma2=inv_s2,
+                th=float(th), kind=np.array(FUSE_KINDS)[kind], nudged=int(nudged.sum()))
