@@ -363,7 +363,7 @@ typedef struct {
     const int32_t* words;
     const double* values;
     int32_t n;
-    const int32_t* covis;       /* max_kf x 10 */
+    const int32_t* covis;       /* max_kf x 10, entries < max_kf (else ORBHIP_ERR_ARG); < 0 ends a row */
     const int32_t* kf_map;      /* max_kf or NULL (one map) */
     int32_t query_map;
     const uint8_t* kf_flags;    /* max_kf or NULL */

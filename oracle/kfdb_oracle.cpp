@@ -93,6 +93,18 @@ void orc_kfdb_erase(void* h, int kf) {
     k.active = false;
 }
 
+// the persistent members of every slot: mode 0 mnRelocQuery / mnRelocWords / mRelocScore,
+// mode 1 mnPlaceRecognitionQuery / Words / Score
+void orc_kfdb_members(void* h, int mode, long long* query, int32_t* words, float* score) {
+    DB* d = (DB*)h;
+    for (size_t i = 0; i < d->kf.size(); i++) {
+        const KF& k = d->kf[i];
+        query[i] = mode ? k.pr_query : k.reloc_query;
+        words[i] = mode ? k.pr_words : k.reloc_words;
+        score[i] = mode ? k.pr_score : k.reloc_score;
+    }
+}
+
 // covis: n_slots x 10 (GetBestCovisibilityKeyFrames(10), -1 padded); kf_map: map id per slot.
 int orc_kfdb_detect_relocalization(void* h, long long qid, const int32_t* words, const double* values, int n,
                                    const int32_t* covis, const int32_t* kf_map, int query_map, int32_t* out) {

@@ -79,6 +79,8 @@ def lib():
                                                      _i32p]
         L.orc_kfdb_detect_nbest.argtypes = [vp, ctypes.c_longlong, _i32p, _f64p, c_int, _i32p, vp, vp, c_int, vp,
                                             c_int, _i32p, _i32p, _i32p, _i32p]
+        L.orc_kfdb_members.argtypes = [vp, c_int, np.ctypeslib.ndpointer(dtype=np.int64, flags="C_CONTIGUOUS"), _i32p,
+                                       _f32p]
         L.orc_bgr2gray.argtypes = [_u8p, c_int, c_int, c_int, _u8p, c_int]
         L.orc_glibc_sincosf_range.argtypes = [ctypes.c_uint32, ctypes.c_uint32, _f32p, _f32p]
         _lib = L
@@ -339,6 +341,12 @@ class KeyFrameDatabase:
         lib().orc_kfdb_detect_nbest(self._h, int(query_id), w, v, w.shape[0], cv, _vp(con), _vp(km), int(query_map),
                                     _vp(fl), int(n), lo, nl, me, nm)
         return lo[: nl[0]].copy(), me[: nm[0]].copy()
+
+    def _members(self, mode):
+        """The persistent per-slot members of mode 0 (reloc) or 1 (place recognition) -> (query, words, score)."""
+        qy = np.zeros(self.max_kf, np.int64); wd = np.zeros(self.max_kf, np.int32); sc = np.zeros(self.max_kf, np.float32)
+        lib().orc_kfdb_members(self._h, int(mode), qy, wd, sc)
+        return qy, wd, sc
 
     def __del__(self):
         try:

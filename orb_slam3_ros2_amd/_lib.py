@@ -218,6 +218,8 @@ def lib():
     L.orbhip_test_cholesky_dag.argtypes = [vp, vp, vp, i32, i32, i32, ctypes.POINTER(f32), vp]
     # host only: the matcher's dispatch decision for a call shape (tests assert the route they mean to reach)
     L.orbhip_test_match_route.argtypes = [i32, i32, i32, i32, vp]
+    # the persistent KeyFrame members of a KeyFrameDatabase, per slot (tests compare them with the oracle's)
+    L.orbhip_test_kfdb_members.argtypes = [vp, i32, vp, vp, vp]
     _lib = L
     return L
 

@@ -430,6 +430,10 @@ static int run_query(KfDb* d, int mode, const orbhip_kfdb_query* q, const uint8_
     for (int i = 1; i < q->n; i++)
         if (q->words[i] <= q->words[i - 1]) return ORBHIP_ERR_ARG;
     const size_t ns = (size_t)d->n_slots;
+    // k_kfdb_select indexes the members by covis entries (a negative one ends its row)
+    int covis_bad = 0;
+    for (size_t i = 0; i < ns * kCovis; i++) covis_bad |= q->covis[i] >= d->n_slots;
+    if (covis_bad) return ORBHIP_ERR_ARG;
     if (q->n) {
         KDOK(hipMemcpyAsync(d->qw, q->words, (size_t)q->n * 4, hipMemcpyHostToDevice, d->st));
         KDOK(hipMemcpyAsync(d->qv, q->values, (size_t)q->n * 8, hipMemcpyHostToDevice, d->st));
@@ -481,6 +485,17 @@ int kfdb_detect_nbest(KfDb* d, const orbhip_kfdb_query* q, const uint8_t* connec
     for (int i = 0; i < cnt[0]; i++) loop_out[i] = o[i];
     for (int i = 0; i < cnt[1]; i++) merge_out[i] = o[ncand + i];
     return cnt[0] + cnt[1];
+}
+
+int kfdb_members(KfDb* d, int mode, long long* query, int32_t* words, float* score) {
+    if (!d || (mode != 0 && mode != 1) || !query || !words || !score) return ORBHIP_ERR_ARG;
+    const size_t ns = (size_t)d->n_slots;
+    KDOK(hipStreamSynchronize(d->st));
+    KDOK(hipMemcpyAsync(query, mode ? d->pq : d->rq, ns * 8, hipMemcpyDeviceToHost, d->st));
+    KDOK(hipMemcpyAsync(words, mode ? d->pw : d->rw, ns * 4, hipMemcpyDeviceToHost, d->st));
+    KDOK(hipMemcpyAsync(score, mode ? d->ps : d->rs, ns * 4, hipMemcpyDeviceToHost, d->st));
+    KDOK(hipStreamSynchronize(d->st));
+    return ORBHIP_OK;
 }
 
 }  // namespace orbhip

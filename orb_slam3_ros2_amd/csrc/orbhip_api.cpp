@@ -1789,6 +1789,14 @@ int orbhip_test_match_route(int npairs, int max_q, int max_t, int fused_allowed,
     return ORBHIP_OK;
 }
 
+// the persistent KeyFrame members of a KeyFrameDatabase (mode 0: mnRelocQuery / mnRelocWords /
+// mRelocScore, mode 1: the mnPlaceRecognition* ones), max_kf entries each, after a stream sync
+int orbhip_test_kfdb_members(orbhip_kfdb* db, int mode, int64_t* query, int32_t* words, float* score) {
+    if (!db) return ORBHIP_ERR_ARG;
+    HIPOK(hipSetDevice(db->device));
+    return kfdb_members(db->d, mode, (long long*)query, words, score);
+}
+
 int orbhip_test_sincosf(const float* x, float* cs, float* sn, int64_t n) {
     if (!x || !cs || !sn || n <= 0) return ORBHIP_ERR_ARG;
     float *dx = nullptr, *dc = nullptr, *ds = nullptr;

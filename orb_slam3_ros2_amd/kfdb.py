@@ -1,7 +1,11 @@
 """KeyFrameDatabase mirror (U:src/KeyFrameDatabase.cc) over liborbhip.so: add / erase with a
 KeyFrame's BowVector, DetectRelocalizationCandidates and DetectNBestCandidates on the device.
 KeyFrames are slots 0..max_kf-1 (the adapter's KeyFrame index); BowVectors are (words ascending,
-values) pairs as ORBVocabulary.transform returns them."""
+values) pairs as ORBVocabulary.transform returns them.
+
+Every query of a mode carries its own query_id (Frame / KeyFrame mnId), as upstream's do. Repeating
+a query_id in the same mode is outside that contract: upstream (and the oracle) then keeps counting
+on top of the common-word counts of the first query, the device counts afresh."""
 from __future__ import annotations
 
 import ctypes
@@ -60,6 +64,13 @@ class KeyFrameDatabase:
         check(lib().orbhip_kfdb_detect_nbest(self._h, ctypes.byref(q), ptr(con), int(n), ptr(lo), ctypes.byref(nl),
                                              ptr(me), ctypes.byref(nm)), "orbhip_kfdb_detect_nbest")
         return lo[:nl.value].copy(), me[:nm.value].copy()
+
+    def _members(self, mode: int):
+        """Test hook: the persistent per-slot members of mode 0 (mnRelocQuery, mnRelocWords,
+        mRelocScore) or 1 (mnPlaceRecognitionQuery / Words / Score) -> (query, words, score)."""
+        qy = np.zeros(self.max_kf, np.int64); wd = np.zeros(self.max_kf, np.int32); sc = np.zeros(self.max_kf, np.float32)
+        check(lib().orbhip_test_kfdb_members(self._h, int(mode), ptr(qy), ptr(wd), ptr(sc)), "orbhip_test_kfdb_members")
+        return qy, wd, sc
 
     def close(self):
         if self._h:
