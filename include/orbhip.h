@@ -199,8 +199,9 @@ int orbhip_frontend_context(orbhip_frontend* fe, int j, orbhip_ctx** out);
  * orbhip_profile_stage selects ONE stage whose launches are bracketed by hipEvents on the
  * stream they run on (0 off, 1 pyramid resize, 2 FAST cells, 3 octree, 4 orientation +
  * descriptor, 5 Hamming top-2, 6 rotation filter, 7 SearchForTriangulation: the ordering pre-pass
- * and the search of one call form one pair, 8 Fuse: the grid build and the search of one call form
- * one pair). orbhip_profile_collect synchronises and
+ * and the search of one call form one pair, 8 Fuse and Fuse with a Sim3: the grid build and the
+ * search of one call form one pair, 9 SearchByProjection with a Sim3: the grid build, the search and
+ * the resolve of one call form one pair). orbhip_profile_collect synchronises and
  * returns the summed duration (ms) and the number of bracketed launches, then resets. The one-launch
  * pyramid (k_pyr_cone) and the octree also time themselves on the device (first workgroup start to
  * last workgroup end, s_memrealtime: the span rocprofv3's kernel trace reports); their stages
@@ -513,6 +514,42 @@ int orbhip_fuse(orbhip_ctx* ctx, const orbhip_frame* kfs, int B, const orbhip_lo
                 const float* inv_level_sigma2 /* n_levels */, float th,
                 int32_t* best_idx /* B x n */, int32_t* best_dist /* B x n or NULL */,
                 int32_t* level /* B x n or NULL */, int32_t* nfused /* B */);
+
+/* ---- LoopClosing: Fuse and SearchByProjection with a Sim3 ------------------------------
+ * U:src/ORBmatcher.cc::Fuse(KeyFrame* pKF, Sophus::Sim3f& Scw, const vector<MapPoint*>& vpPoints,
+ * float th, vector<MapPoint*>& vpReplacePoint) (LoopClosing::SearchAndFuse, th = 4) and
+ * ::SearchByProjection(KeyFrame* pKF, Sophus::Sim3<float>& Scw, const vector<MapPoint*>& vpPoints,
+ * vector<MapPoint*>& vpMatched, int th, float ratioHamming) (DetectCommonRegionsFromBoW,
+ * DetectAndReffineSim3FromLastKF, FindMatchesByProjection; also the overload with vpPointsKFs /
+ * vpMatchedKF, which computes the same). Both decompose Scw first: the adapter passes
+ * Tcw = (Scw.rotationMatrix(), Scw.translation() / Scw.scale()) in pose_q / pose_t and the library
+ * never sees the scale. Per (keyframe, point) the gates are those of orbhip_fuse up to
+ * the window of GetFeaturesInArea and the octave in [level - 1, level]; there is NO chi-square gate.
+ *
+ * orbhip_fuse_sim3: arguments, outputs, envelope and errors of orbhip_fuse without inv_level_sigma2;
+ * it computes what orbhip_fuse computes with an all-zero inv_level_sigma2. mps->skip[m] = isBad(),
+ * pair_skip[b * n + m] = pKF_b->GetMapPoints().count(pMP). The adapter fills vpReplacePoint[m] from
+ * pKF->GetMapPoint(best_idx) or calls AddObservation / AddMapPoint, in upstream order.
+ *
+ * orbhip_search_by_projection_sim3: one keyframe. kf->claimed[k] = vpMatched[k] != NULL at call time
+ * (NULL: none); mps->skip[m] = isBad() || pMP is in vpMatched at call time (spAlreadyFound). The
+ * sequential greedy pass of upstream, exactly: for m ascending, of the gated candidates whose
+ * keypoint is claimed neither at call time nor by an earlier point of this call, the one of least
+ * descriptor distance (the first in the reference's walk order among equals); if (float)distance <=
+ * 50.0f * ratio_hamming the point claims it. match[m] = that keypoint or -1 (the adapter sets
+ * vpMatched[match[m]] = pMP, or vpMatchedKF[match[m]] = vpPointsKFs[m]); match_dist (optional) = its
+ * distance, 256 when -1; level (optional) as orbhip_fuse. Returns nmatches; n = 0: 0.
+ * ratio_hamming not positive and finite: ORBHIP_ERR_ARG. mps->n > 65536, more than 65535 keypoints or
+ * n_levels > 256: ORBHIP_ERR_UNSUPPORTED; a keypoint octave outside [0, n_levels): ORBHIP_ERR_ARG. One
+ * upload, three launches (the grid, the candidate lists, the greedy pass as a fixed point in one
+ * work-group), one read-back. */
+int orbhip_fuse_sim3(orbhip_ctx* ctx, const orbhip_frame* kfs, int B, const orbhip_local_points* mps,
+                     const uint8_t* pair_skip /* B x mps->n or NULL */, float th,
+                     int32_t* best_idx /* B x n */, int32_t* best_dist /* B x n or NULL */,
+                     int32_t* level /* B x n or NULL */, int32_t* nfused /* B */);
+int orbhip_search_by_projection_sim3(orbhip_ctx* ctx, const orbhip_frame* kf, const orbhip_local_points* mps,
+                                     float th, float ratio_hamming, int32_t* match /* n */,
+                                     int32_t* match_dist /* n or NULL */, int32_t* level /* n or NULL */);
 
 /* ---- multi-GPU BundleAdjustment (SURVEY.md §8e, C5 GlobalBundleAdjustment) --------
  * One process per GPU. Landmarks (with their edges) are partitioned across ranks; every rank

@@ -201,6 +201,53 @@ public:
         return std::vector<int>(nf.begin(), nf.end());
     }
 
+    // U:src/ORBmatcher.cc::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) of every keyframe against the
+    // same MapPoints in one call (LoopClosing::SearchAndFuse). Each orbhip_frame
+    // carries Tcw = (Scw.rotationMatrix(), Scw.translation() / Scw.scale()). vbPairSkip: empty, or
+    // B x n with pKF_b->GetMapPoints().count(pMP). Outputs as Fuse; the adapter fills vpReplacePoint
+    // from pKF->GetMapPoint(vBestIdx[b][m]) or calls AddObservation / AddMapPoint.
+    std::vector<int> FuseSim3(orbhip_ctx* ctx, const std::vector<orbhip_frame>& keyframes,
+                              const orbhip_local_points& vpPoints, const std::vector<uint8_t>& vbPairSkip, float th,
+                              std::vector<std::vector<int>>& vBestIdx, std::vector<std::vector<int>>* vBestDist = nullptr,
+                              std::vector<std::vector<int>>* vLevel = nullptr) const {
+        const int B = (int)keyframes.size();
+        const size_t n = (size_t)std::max(vpPoints.n, 0);
+        if (!vbPairSkip.empty() && vbPairSkip.size() != (size_t)B * n) throw Error(ORBHIP_ERR_ARG, "FuseSim3: vbPairSkip");
+        std::vector<int32_t> idx((size_t)B * n, -1), dist(vBestDist ? (size_t)B * n : 0), lvl(vLevel ? (size_t)B * n : 0);
+        std::vector<int32_t> nf(B, 0);
+        const int rc = orbhip_fuse_sim3(ctx, keyframes.data(), B, &vpPoints, vbPairSkip.empty() ? nullptr : vbPairSkip.data(),
+                                        th, idx.data(), vBestDist ? dist.data() : nullptr, vLevel ? lvl.data() : nullptr,
+                                        nf.data());
+        check(rc, "orbhip_fuse_sim3");
+        auto rows = [&](const std::vector<int32_t>& flat, std::vector<std::vector<int>>& out) {
+            out.assign(B, std::vector<int>());
+            for (int b = 0; b < B; b++) out[b].assign(flat.begin() + (size_t)b * n, flat.begin() + (size_t)(b + 1) * n);
+        };
+        rows(idx, vBestIdx);
+        if (vBestDist) rows(dist, *vBestDist);
+        if (vLevel) rows(lvl, *vLevel);
+        return std::vector<int>(nf.begin(), nf.end());
+    }
+
+    // U:src/ORBmatcher.cc::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming) (and the
+    // overload with vpPointsKFs / vpMatchedKF), the sequential greedy pass exactly. keyframe carries
+    // Tcw = (R, t / s) and claimed[k] = vpMatched[k] != NULL; vpPoints.skip[m] = isBad() or the point
+    // is in vpMatched already. vnMatch[m] = the keypoint point m claims, or -1 (the adapter sets
+    // vpMatched[vnMatch[m]] = vpPoints[m]). Returns nmatches.
+    int SearchByProjectionSim3(orbhip_ctx* ctx, const orbhip_frame& keyframe, const orbhip_local_points& vpPoints, int th,
+                               float ratioHamming, std::vector<int>& vnMatch, std::vector<int>* vnDist = nullptr,
+                               std::vector<int>* vnLevel = nullptr) const {
+        const size_t n = (size_t)std::max(vpPoints.n, 0);
+        std::vector<int32_t> m(n, -1), dist(vnDist ? n : 0), lvl(vnLevel ? n : 0);
+        const int rc = orbhip_search_by_projection_sim3(ctx, &keyframe, &vpPoints, (float)th, ratioHamming, m.data(),
+                                                        vnDist ? dist.data() : nullptr, vnLevel ? lvl.data() : nullptr);
+        check(rc, "orbhip_search_by_projection_sim3");
+        vnMatch.assign(m.begin(), m.end());
+        if (vnDist) vnDist->assign(dist.begin(), dist.end());
+        if (vnLevel) vnLevel->assign(lvl.begin(), lvl.end());
+        return rc;
+    }
+
     float mfNNratio;
     bool mbCheckOrientation;
 };

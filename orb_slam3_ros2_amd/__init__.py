@@ -15,6 +15,7 @@ Host-side mirror of the reference's hot-path interfaces over th
   ORBmatcher.SearchByProjectionLastFrame / SearchLocalPoints(...)           U:src/ORBmatcher.cc
   ORBmatcher.SearchForTriangulation(kf1, neighbours, ...)                   U:src/ORBmatcher.cc
   ORBmatcher.Fuse(kfs, points, ...)                                         U:src/ORBmatcher.cc
+  ORBmatcher.FuseSim3 / SearchByProjectionSim3(...)   (LoopClosing)         U:src/ORBmatcher.cc
   KeyFrameDatabase(max_kf).DetectRelocalizationCandidates / DetectNBestCandidates
                                                                             U:src/KeyFrameDatabase.cc
   FrameStream(w, h, frames_in_flight).push(frame)   Frame ctor -> ExtractORB + match to the last

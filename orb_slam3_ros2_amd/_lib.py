@@ -123,6 +123,7 @@ EXPORTED = ["orbhip_abi_version", "orbhip_create", "orbhip_destroy", "orbhip_lev
             "orbhip_pose_optimization", "orbhip_pose_optimization_batch", "orbhip_search_by_projection_last",
             "orbhip_search_local_points", "orbhip_search_for_initialization",
             "orbhip_triangulation_geometry", "orbhip_search_for_triangulation", "orbhip_fuse",
+            "orbhip_fuse_sim3", "orbhip_search_by_projection_sim3",
             "orbhip_kfdb_create", "orbhip_kfdb_destroy", "orbhip_kfdb_add", "orbhip_kfdb_erase",
             "orbhip_kfdb_detect_relocalization", "orbhip_kfdb_detect_nbest",
             "orbhip_frontend_create", "orbhip_frontend_destroy", "orbhip_frontend_push", "orbhip_frontend_view",
@@ -192,6 +193,9 @@ def lib():
                                                   vp, vp, i32, i32, vp, vp]
     L.orbhip_fuse.argtypes = [vp, ctypes.POINTER(FrameC), i32, ctypes.POINTER(LocalPointsC), vp, vp, f32, vp, vp, vp,
                               vp]
+    L.orbhip_fuse_sim3.argtypes = [vp, ctypes.POINTER(FrameC), i32, ctypes.POINTER(LocalPointsC), vp, f32, vp, vp, vp, vp]
+    L.orbhip_search_by_projection_sim3.argtypes = [vp, ctypes.POINTER(FrameC), ctypes.POINTER(LocalPointsC), f32, f32,
+                                                   vp, vp, vp]
     L.orbhip_kfdb_create.argtypes = [vp, i32, ctypes.POINTER(vp)]
     L.orbhip_kfdb_destroy.argtypes = [vp]
     L.orbhip_kfdb_add.argtypes = [vp, i32, vp, vp, i32]
@@ -220,6 +224,8 @@ def lib():
     L.orbhip_test_match_route.argtypes = [i32, i32, i32, i32, vp]
     # the persistent KeyFrame members of a KeyFrameDatabase, per slot (tests compare them with the oracle's)
     L.orbhip_test_kfdb_members.argtypes = [vp, i32, vp, vp, vp]
+    # the stored list capacity of the Sim3 projection search (tests build a chain deeper than it)
+    L.orbhip_test_sim3_list_cap.argtypes = []
     _lib = L
     return L
 

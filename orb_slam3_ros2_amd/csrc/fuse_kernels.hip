@@ -16,7 +16,17 @@
 //                     No pair reads what another pair writes (no `taken`, no stealing, no rotation
 //                     histogram), so there is no resolve phase. nfused[b]: one LDS atomic per wave,
 //                     one global atomic per work-group.
-// LDS: k_fuse_grid 12 KiB histogram + 12 KiB cursors + scan scratch; k_fuse_search 4 bytes.
+//                     k_fuse_search<S, false> is the rule of Fuse with a Sim3 (LoopClosing::SearchAndFuse):
+//                     the same walk without the chi-square gate.
+// and LoopClosing's SearchByProjection with a Sim3, one keyframe, upstream's sequential greedy pass
+// (DESIGN.md "Sim3 functions of LoopClosing"):
+//   k_sim3_search     the walk again, four lanes per point, also testing `claimed` and the distance
+//                     threshold; per point the 8 smallest keys (sorted, in registers), their total
+//                     count and the window go to global memory
+//   k_sim3_resolve    ONE 1024-thread work-group turns the lists into the sequential result as a fixed
+//                     point over an owner table in global memory; a list longer than 8 is continued by
+//                     walking the window again; rounds <= (points with a list) + 1
+// LDS: k_fuse_grid 12 KiB histogram + 12 KiB cursors + scan scratch; k_fuse_search 4 bytes; k_sim3_resolve 12 bytes.
 #include <hip/hip_runtime.h>
 
 #include "orbhip_device.h"
@@ -122,9 +132,63 @@ constexpr int kFuseThreads = 256;
 // 20.9 / 18.1 us
 constexpr int kFuseSplit = 4;
 
+// Steps 1-8 of the rule for one (keyframe, point) that is not skipped: false at a gate. lvl is set
+// from step 6 on (-1 before it), so a pair rejected by GetFeaturesInArea's early returns keeps it.
+struct FuseWin { float u, v, r; int lvl, x0, x1, y0, y1; };
+__device__ __forceinline__ bool fuse_gates(const FuseKf& f, const FusePoints& mp, int m,
+                                           const float* __restrict__ scale_factors, int n_levels, float log_sf,
+                                           float th, FuseWin& w) {
+    w.lvl = -1;
+    const float P[3] = {mp.pts[3 * m], mp.pts[3 * m + 1], mp.pts[3 * m + 2]};
+    // 1. Sophus SE3f * p
+    float Pc[3];
+    fuse_qrot_dev(f.q, P, Pc);
+    Pc[0] += f.t[0]; Pc[1] += f.t[1]; Pc[2] += f.t[2];
+    if (Pc[2] < 0.0f) return false;
+    // 2., 3. Pinhole::project, KeyFrame::IsInImage (the maximum is strict)
+    const float u = (f.fx * Pc[0]) / Pc[2] + f.cx, v = (f.fy * Pc[1]) / Pc[2] + f.cy;
+    if (!(u >= f.minx && u < f.maxx && v >= f.miny && v < f.maxy)) return false;
+    // 4. distance range
+    const float PO[3] = {P[0] - f.Ow[0], P[1] - f.Ow[1], P[2] - f.Ow[2]};
+    const float dist3D = sqrtf((PO[0] * PO[0] + PO[1] * PO[1]) + PO[2] * PO[2]);
+    const float maxd = mp.maxd[m];
+    if (dist3D < 0.8f * mp.mind[m] || dist3D > 1.2f * maxd) return false;
+    // 5. viewing angle
+    const float* Pn = mp.nrm + 3 * m;
+    if ((PO[0] * Pn[0] + PO[1] * Pn[1]) + PO[2] * Pn[2] < 0.5f * dist3D) return false;
+    // 6. MapPoint::PredictScale (clamped before the conversion: the same for every finite value)
+    const float fl = ceilf(logf(maxd / dist3D) / log_sf);
+    const int lvl = !(fl > 0.0f) ? 0 : (fl >= (float)n_levels ? n_levels - 1 : (int)fl);
+    w.lvl = lvl;
+    // 7. radius
+    const float r = th * scale_factors[lvl];
+    w.u = u; w.v = v; w.r = r;
+    // 8. KeyFrame::GetFeaturesInArea: the cell rectangle with its early returns
+    w.x0 = max(0, (int)floorf((u - f.minx - r) * f.invw));
+    if (w.x0 >= kFuseCols) return false;
+    w.x1 = min(kFuseCols - 1, (int)ceilf((u - f.minx + r) * f.invw));
+    if (w.x1 < 0) return false;
+    w.y0 = max(0, (int)floorf((v - f.miny - r) * f.invh));
+    if (w.y0 >= kFuseRows) return false;
+    w.y1 = min(kFuseRows - 1, (int)ceilf((v - f.miny + r) * f.invh));
+    if (w.y1 < 0) return false;
+    return true;
+}
+
+__device__ __forceinline__ unsigned fuse_hamming(const uint4& da, const uint4& db, const uint8_t* __restrict__ d) {
+    const uint4* d2 = (const uint4*)d;
+    const uint4 ea = d2[0], eb = d2[1];
+    return __popc(da.x ^ ea.x) + __popc(da.y ^ ea.y) + __popc(da.z ^ ea.z) + __popc(da.w ^ ea.w) +
+           __popc(db.x ^ eb.x) + __popc(db.y ^ eb.y) + __popc(db.z ^ eb.z) + __popc(db.w ^ eb.w);
+}
+__device__ __forceinline__ unsigned long long fuse_key(unsigned dist, const FuseRec& k) {
+    return ((unsigned long long)dist << 32) | ((unsigned long long)(k.cell_oct >> 8) << 16) | (unsigned)k.idx;
+}
+
 // S neighbouring lanes share a point: each computes the gates of steps 1-7 (the same values, so the
-// same exits), they take the candidates of a column span in turns and merge their minima
-template <int S>
+// same exits), they take the candidates of a column span in turns and merge their minima.
+// CHI2 = false: the rule of Fuse with a Sim3, which has no chi-square gate (inv_level_sigma2 unread)
+template <int S, bool CHI2>
 __global__ __launch_bounds__(kFuseThreads) void k_fuse_search(const FuseKf* __restrict__ kfs, FusePoints mp,
                                                               const uint8_t* __restrict__ pair_skip,
                                                               const float* __restrict__ scale_factors,
@@ -149,46 +213,20 @@ __global__ __launch_bounds__(kFuseThreads) void k_fuse_search(const FuseKf* __re
         if (m >= mp.n) break;
         if (mp.skip[m]) break;
         if (pair_skip && pair_skip[(int64_t)b * mp.n + m]) break;
-        const float P[3] = {mp.pts[3 * m], mp.pts[3 * m + 1], mp.pts[3 * m + 2]};
-        // 1. Sophus SE3f * p
-        float Pc[3];
-        fuse_qrot_dev(f.q, P, Pc);
-        Pc[0] += f.t[0]; Pc[1] += f.t[1]; Pc[2] += f.t[2];
-        if (Pc[2] < 0.0f) break;
-        // 2., 3. Pinhole::project, KeyFrame::IsInImage (the maximum is strict)
-        const float u = (f.fx * Pc[0]) / Pc[2] + f.cx, v = (f.fy * Pc[1]) / Pc[2] + f.cy;
-        if (!(u >= f.minx && u < f.maxx && v >= f.miny && v < f.maxy)) break;
-        // 4. distance range
-        const float PO[3] = {P[0] - f.Ow[0], P[1] - f.Ow[1], P[2] - f.Ow[2]};
-        const float dist3D = sqrtf((PO[0] * PO[0] + PO[1] * PO[1]) + PO[2] * PO[2]);
-        const float maxd = mp.maxd[m];
-        if (dist3D < 0.8f * mp.mind[m] || dist3D > 1.2f * maxd) break;
-        // 5. viewing angle
-        const float* Pn = mp.nrm + 3 * m;
-        if ((PO[0] * Pn[0] + PO[1] * Pn[1]) + PO[2] * Pn[2] < 0.5f * dist3D) break;
-        // 6. MapPoint::PredictScale (clamped before the conversion: the same for every finite value)
-        const float fl = ceilf(logf(maxd / dist3D) / log_sf);
-        const int lvl = !(fl > 0.0f) ? 0 : (fl >= (float)n_levels ? n_levels - 1 : (int)fl);
-        outLvl = lvl;
-        // 7. radius
-        const float r = th * scale_factors[lvl];
-        // 8. KeyFrame::GetFeaturesInArea: the cell rectangle with its early returns
-        const int x0 = max(0, (int)floorf((u - f.minx - r) * f.invw));
-        if (x0 >= kFuseCols) break;
-        const int x1 = min(kFuseCols - 1, (int)ceilf((u - f.minx + r) * f.invw));
-        if (x1 < 0) break;
-        const int y0 = max(0, (int)floorf((v - f.miny - r) * f.invh));
-        if (y0 >= kFuseRows) break;
-        const int y1 = min(kFuseRows - 1, (int)ceilf((v - f.miny + r) * f.invh));
-        if (y1 < 0) break;
+        FuseWin w;
+        const bool in = fuse_gates(f, mp, m, scale_factors, n_levels, log_sf, th, w);
+        outLvl = w.lvl;
+        if (!in) break;
+        const float u = w.u, v = w.v, r = w.r;
+        const int lvl = w.lvl;
         const uint4* dm = (const uint4*)(mp.desc + (int64_t)m * 32);
         const uint4 da = dm[0], db = dm[1];
         const int32_t* cs = cell_start + (int64_t)b * (kFuseCells + 1);
         const FuseRec* rc = recs + f.base;
         const uint8_t* kd = kf_desc + (int64_t)f.base * 32;
-        for (int ix = x0; ix <= x1; ix++) {
+        for (int ix = w.x0; ix <= w.x1; ix++) {
             // the cells (ix, y0..y1) are neighbours in the cell-ordered array: one span per column
-            const int j0 = cs[ix * kFuseRows + y0], j1 = cs[ix * kFuseRows + y1 + 1];
+            const int j0 = cs[ix * kFuseRows + w.y0], j1 = cs[ix * kFuseRows + w.y1 + 1];
             for (int j = j0 + sub; j < j1; j += S) {
                 const FuseRec k = rc[j];
                 const float dx = k.x - u, dy = k.y - v;
@@ -196,16 +234,12 @@ __global__ __launch_bounds__(kFuseThreads) void k_fuse_search(const FuseKf* __re
                 // 9. level gate, chi-square gate, then the descriptor
                 const int octave = k.cell_oct & 0xFF;
                 if (octave < lvl - 1 || octave > lvl) continue;
-                const float ex = u - k.x, ey = v - k.y;
-                const float e2 = ex * ex + ey * ey;
-                if ((double)(e2 * inv_level_sigma2[octave]) > 5.99) continue;
-                const uint4* d2 = (const uint4*)(kd + (int64_t)k.idx * 32);
-                const uint4 ea = d2[0], eb = d2[1];
-                const unsigned dist = __popc(da.x ^ ea.x) + __popc(da.y ^ ea.y) + __popc(da.z ^ ea.z) +
-                                      __popc(da.w ^ ea.w) + __popc(db.x ^ eb.x) + __popc(db.y ^ eb.y) +
-                                      __popc(db.z ^ eb.z) + __popc(db.w ^ eb.w);
-                const unsigned long long key =
-                    ((unsigned long long)dist << 32) | ((unsigned long long)(k.cell_oct >> 8) << 16) | (unsigned)k.idx;
+                if (CHI2) {
+                    const float ex = u - k.x, ey = v - k.y;
+                    const float e2 = ex * ex + ey * ey;
+                    if ((double)(e2 * inv_level_sigma2[octave]) > 5.99) continue;
+                }
+                const unsigned long long key = fuse_key(fuse_hamming(da, db, kd + (int64_t)k.idx * 32), k);
                 best = key < best ? key : best;
             }
         }
@@ -232,15 +266,234 @@ __global__ __launch_bounds__(kFuseThreads) void k_fuse_search(const FuseKf* __re
     if (threadIdx.x == 0 && s_count) atomicAdd(&nfused[b], s_count);
 }
 
+// ---- SearchByProjection with a Sim3: the lists, then the greedy pass over them ----
+constexpr unsigned long long kSim3None = ~0ull;
+
+// A candidate of the sequential pass that can ever be claimed: inside the window, octave in
+// [lvl - 1, lvl], not claimed at call time, dist < 256 and (float)dist <= thr. kSim3None otherwise.
+__device__ __forceinline__ unsigned long long sim3_candidate(const FuseRec& k, float u, float v, float r, int lvl,
+                                                             const uint8_t* __restrict__ claimed, const uint4& da,
+                                                             const uint4& db, const uint8_t* __restrict__ kd, float thr) {
+    const float dx = k.x - u, dy = k.y - v;
+    if (!(fabsf(dx) < r && fabsf(dy) < r)) return kSim3None;
+    if (claimed[k.idx]) return kSim3None;
+    const int octave = k.cell_oct & 0xFF;
+    if (octave < lvl - 1 || octave > lvl) return kSim3None;
+    const unsigned dist = fuse_hamming(da, db, kd + (int64_t)k.idx * 32);
+    if (!(dist < 256u && (float)dist <= thr)) return kSim3None;
+    return fuse_key(dist, k);
+}
+
+// The walk of k_fuse_search for one keyframe, without the chi-square gate and with the two tests of
+// sim3_candidate. Each of the S lanes of a point keeps the kSim3ListCap smallest keys it met, sorted,
+// in registers (an unrolled insertion: static indices only); the lanes' lists are merged into the
+// point's list[m] (ascending, kSim3None behind the end), count[m] is the number of candidates met.
+// level[m] and win[m] are written for every point; match / match_dist are k_sim3_resolve's.
+template <int S>
+__global__ __launch_bounds__(kFuseThreads) void k_sim3_search(const FuseKf* __restrict__ kfs, FusePoints mp,
+                                                              const uint8_t* __restrict__ claimed,
+                                                              const float* __restrict__ scale_factors, int n_levels,
+                                                              float log_sf, float th, float thr,
+                                                              const int32_t* __restrict__ cell_start,
+                                                              const FuseRec* __restrict__ recs,
+                                                              const uint8_t* __restrict__ kf_desc, Sim3Work wk,
+                                                              int32_t* __restrict__ level) {
+    static_assert(S >= 1 && S <= 64 && (S & (S - 1)) == 0, "the lanes of a point lie in one wave");
+    constexpr int K = kSim3ListCap;
+    const int m = (blockIdx.x * kFuseThreads + threadIdx.x) / S, sub = threadIdx.x % S;
+    const FuseKf f = kfs[0];
+    unsigned long long a[K];
+#pragma unroll
+    for (int i = 0; i < K; i++) a[i] = kSim3None;
+    int cnt = 0;
+    FuseWin w;
+    w.lvl = -1; w.u = w.v = w.r = 0.0f; w.x0 = w.x1 = w.y0 = w.y1 = 0;
+    bool in = false;
+    if (m < mp.n && !mp.skip[m]) in = fuse_gates(f, mp, m, scale_factors, n_levels, log_sf, th, w);
+    if (in) {
+        const uint4* dm = (const uint4*)(mp.desc + (int64_t)m * 32);
+        const uint4 da = dm[0], db = dm[1];
+        for (int ix = w.x0; ix <= w.x1; ix++) {
+            const int j0 = cell_start[ix * kFuseRows + w.y0], j1 = cell_start[ix * kFuseRows + w.y1 + 1];
+            for (int j = j0 + sub; j < j1; j += S) {
+                unsigned long long key = sim3_candidate(recs[j], w.u, w.v, w.r, w.lvl, claimed, da, db, kf_desc, thr);
+                if (key == kSim3None) continue;
+                cnt++;
+                if (key < a[K - 1]) {
+#pragma unroll
+                    for (int i = 0; i < K; i++) {
+                        const unsigned long long lo = key < a[i] ? key : a[i];
+                        key = key < a[i] ? a[i] : key;
+                        a[i] = lo;
+                    }
+                }
+            }
+        }
+    }
+    // merge: K times the least head of the S lanes; keys are distinct (the index is in them), so one
+    // lane pops. Lanes of points past n or rejected hold empty lists and take part all the same.
+#pragma unroll
+    for (int s = 1; s < S; s <<= 1) cnt += __shfl_xor(cnt, s);
+    unsigned long long out[K];
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        unsigned long long mn = a[0];
+#pragma unroll
+        for (int s = 1; s < S; s <<= 1) {
+            const unsigned long long o = __shfl_xor(mn, s);
+            mn = o < mn ? o : mn;
+        }
+        out[j] = mn;
+        if (a[0] == mn && mn != kSim3None) {
+#pragma unroll
+            for (int i = 0; i + 1 < K; i++) a[i] = a[i + 1];
+            a[K - 1] = kSim3None;
+        }
+    }
+    if (m < mp.n && sub == 0) {
+        level[m] = w.lvl;
+        wk.win[m] = Sim3Win{w.u, w.v, w.r, in ? w.lvl : -1, w.x0 | (w.x1 << 8) | (w.y0 << 16) | (w.y1 << 24)};
+        wk.count[m] = cnt;
+#pragma unroll
+        for (int j = 0; j < K; j++) wk.list[(int64_t)m * K + j] = out[j];
+    }
+}
+
+// The owner table lives in global memory (65535 keypoints do not fit LDS as words) and is read and
+// written by one work-group only: atomics at agent scope, so no access is served from a stale L1 line.
+__device__ __forceinline__ int sim3_owner(const int32_t* owner, int idx) {
+    return __hip_atomic_load(owner + idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The first entry of L[m] whose keypoint no earlier point holds (owner >= m): from the stored keys,
+// and, when all of them are held and the list is longer than what is stored, from a walk of the
+// window for the least key above the last stored one.
+__device__ unsigned long long sim3_eval(int m, const FusePoints& mp, const uint8_t* __restrict__ claimed,
+                                        float thr, const int32_t* __restrict__ cell_start,
+                                        const FuseRec* __restrict__ recs, const uint8_t* __restrict__ kf_desc,
+                                        const Sim3Work& wk) {
+    constexpr int K = kSim3ListCap;
+    const int cnt = wk.count[m];
+    const unsigned long long* l = wk.list + (int64_t)m * K;
+    unsigned long long last = 0;
+    for (int j = 0; j < K && j < cnt; j++) {
+        last = l[j];
+        if (sim3_owner(wk.owner, (int)(last & 0xFFFF)) >= m) return last;
+    }
+    if (cnt <= K) return kSim3None;
+    const Sim3Win w = wk.win[m];
+    const int x0 = w.rect & 0xFF, x1 = (w.rect >> 8) & 0xFF, y0 = (w.rect >> 16) & 0xFF, y1 = (w.rect >> 24) & 0xFF;
+    const uint4* dm = (const uint4*)(mp.desc + (int64_t)m * 32);
+    const uint4 da = dm[0], db = dm[1];
+    unsigned long long best = kSim3None;
+    for (int ix = x0; ix <= x1; ix++) {
+        const int j0 = cell_start[ix * kFuseRows + y0], j1 = cell_start[ix * kFuseRows + y1 + 1];
+        for (int j = j0; j < j1; j++) {
+            const unsigned long long key = sim3_candidate(recs[j], w.u, w.v, w.r, w.lvl, claimed, da, db, kf_desc, thr);
+            if (key == kSim3None || key <= last || key >= best) continue;
+            if (sim3_owner(wk.owner, (int)(key & 0xFFFF)) >= m) best = key;
+        }
+    }
+    return best;
+}
+
+constexpr int kSim3ResolveThreads = 1024;
+constexpr int kSim3NoOwner = 0x7FFFFFFF;
+
+// The sequential pass as a fixed point, in ONE work-group (no work-group waits for another):
+//   pick_{r+1}[m] = the first e of L[m] with min{m' : pick_r[m'] = e.idx} >= m
+// from pick_0 = nothing. After round k the k lowest points with a list hold their final keypoint (a
+// point's choice depends on the picks of lower points only), so the first round that changes nothing
+// is the sequential result and it comes within (points with a list) + 1 rounds: the loop's bound.
+// owner[idx] = the lowest point whose pick is idx, rebuilt between rounds (only the entries the old
+// picks set are cleared).
+__global__ __launch_bounds__(kSim3ResolveThreads) void k_sim3_resolve(FusePoints mp,
+                                                                       const uint8_t* __restrict__ claimed, float thr,
+                                                                       int nk, const int32_t* __restrict__ cell_start,
+                                                                       const FuseRec* __restrict__ recs,
+                                                                       const uint8_t* __restrict__ kf_desc, Sim3Work wk,
+                                                                       int32_t* __restrict__ match,
+                                                                       int32_t* __restrict__ match_dist,
+                                                                       int32_t* __restrict__ nmatches) {
+    __shared__ int s_active, s_changed, s_matched;
+    const int tid = threadIdx.x, n = mp.n;
+    if (tid == 0) { s_active = 0; s_changed = 0; s_matched = 0; }
+    __syncthreads();
+    for (int i = tid; i < nk; i += kSim3ResolveThreads)
+        __hip_atomic_store(wk.owner + i, kSim3NoOwner, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    int mine = 0;
+    for (int m = tid; m < n; m += kSim3ResolveThreads) {
+        wk.pick[m] = kSim3None;
+        mine += wk.count[m] > 0;
+    }
+    if (mine) atomicAdd(&s_active, mine);
+    __syncthreads();
+    const int rounds = s_active + 1;
+    for (int r = 0; r < rounds; r++) {
+        bool diff = false;
+        for (int m = tid; m < n; m += kSim3ResolveThreads) {
+            if (wk.count[m] == 0) continue;
+            const unsigned long long p = sim3_eval(m, mp, claimed, thr, cell_start, recs, kf_desc, wk);
+            wk.pick_new[m] = p;
+            diff |= p != wk.pick[m];
+        }
+        if (diff) s_changed = 1;
+        __syncthreads();
+        const bool changed = s_changed != 0;     // the same value in every thread: the exit is uniform
+        if (!changed) break;
+        for (int m = tid; m < n; m += kSim3ResolveThreads) {
+            const unsigned long long p = wk.pick[m];
+            if (p != kSim3None)
+                __hip_atomic_store(wk.owner + (int)(p & 0xFFFF), kSim3NoOwner, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        __syncthreads();
+        if (tid == 0) s_changed = 0;
+        for (int m = tid; m < n; m += kSim3ResolveThreads) {
+            if (wk.count[m] == 0) continue;
+            const unsigned long long p = wk.pick_new[m];
+            wk.pick[m] = p;
+            if (p != kSim3None) atomicMin(wk.owner + (int)(p & 0xFFFF), m);
+        }
+        __syncthreads();
+    }
+    int got = 0;
+    for (int m = tid; m < n; m += kSim3ResolveThreads) {
+        const unsigned long long p = wk.pick[m];
+        match[m] = p == kSim3None ? -1 : (int)(p & 0xFFFF);
+        match_dist[m] = p == kSim3None ? 256 : (int)(p >> 32);
+        got += p != kSim3None;
+    }
+    if (got) atomicAdd(&s_matched, got);
+    __syncthreads();
+    if (tid == 0) nmatches[0] = s_matched;
+}
+
+void launch_sim3_search(const FuseKf* kf, const FusePoints& mp, const uint8_t* claimed, const float* scale_factors,
+                        int n_levels, float log_sf, float th, float thr, const orbhip_kp* kps, const uint8_t* kf_desc,
+                        int nk, int32_t* cell_start, FuseRec* recs, const Sim3Work& w, int32_t* match,
+                        int32_t* match_dist, int32_t* level, int32_t* nmatches, hipStream_t st) {
+    ORBHIP_LAUNCH(k_fuse_grid, dim3(1), dim3(kFuseGridThreads), 0, st, kf, kps, cell_start, recs, nmatches);
+    const unsigned tiles = (unsigned)(((int64_t)mp.n * kFuseSplit + kFuseThreads - 1) / kFuseThreads);
+    ORBHIP_LAUNCH(k_sim3_search<kFuseSplit>, dim3(tiles), dim3(kFuseThreads), 0, st, kf, mp, claimed, scale_factors,
+                  n_levels, log_sf, th, thr, (const int32_t*)cell_start, (const FuseRec*)recs, kf_desc, w, level);
+    ORBHIP_LAUNCH(k_sim3_resolve, dim3(1), dim3(kSim3ResolveThreads), 0, st, mp, claimed, thr, nk,
+                  (const int32_t*)cell_start, (const FuseRec*)recs, kf_desc, w, match, match_dist, nmatches);
+}
+
 void launch_fuse(const FuseKf* kfs, int B, const FusePoints& mp, const uint8_t* pair_skip, const float* scale_factors,
                  const float* inv_level_sigma2, int n_levels, float log_sf, float th, const orbhip_kp* kps,
                  const uint8_t* kf_desc, int32_t* cell_start, FuseRec* recs, int32_t* best_idx, int32_t* best_dist,
                  int32_t* level, int32_t* nfused, hipStream_t st) {
     ORBHIP_LAUNCH(k_fuse_grid, dim3((unsigned)B), dim3(kFuseGridThreads), 0, st, kfs, kps, cell_start, recs, nfused);
     const unsigned tiles = (unsigned)(((int64_t)mp.n * kFuseSplit + kFuseThreads - 1) / kFuseThreads);
-    ORBHIP_LAUNCH(k_fuse_search<kFuseSplit>, dim3(tiles, (unsigned)B), dim3(kFuseThreads), 0, st, kfs, mp, pair_skip,
-                  scale_factors, inv_level_sigma2, n_levels, log_sf, th, (const int32_t*)cell_start,
-                  (const FuseRec*)recs, kf_desc, best_idx, best_dist, level, nfused);
+    if (inv_level_sigma2)
+        ORBHIP_LAUNCH((k_fuse_search<kFuseSplit, true>), dim3(tiles, (unsigned)B), dim3(kFuseThreads), 0, st, kfs, mp,
+                      pair_skip, scale_factors, inv_level_sigma2, n_levels, log_sf, th, (const int32_t*)cell_start,
+                      (const FuseRec*)recs, kf_desc, best_idx, best_dist, level, nfused);
+    else
+        ORBHIP_LAUNCH((k_fuse_search<kFuseSplit, false>), dim3(tiles, (unsigned)B), dim3(kFuseThreads), 0, st, kfs, mp,
+                      pair_skip, scale_factors, inv_level_sigma2, n_levels, log_sf, th, (const int32_t*)cell_start,
+                      (const FuseRec*)recs, kf_desc, best_idx, best_dist, level, nfused);
 }
 
 }  // namespace orbhip

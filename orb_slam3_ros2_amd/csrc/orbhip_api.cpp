@@ -1136,7 +1136,7 @@ int orbhip_launch_graphs(orbhip_ctx* c) {
 }
 
 int orbhip_profile_stage(orbhip_ctx* c, int stage) {
-    if (!c || stage < 0 || stage > 8) return ORBHIP_ERR_ARG;
+    if (!c || stage < 0 || stage > 9) return ORBHIP_ERR_ARG;
     HIPOK(hipSetDevice(c->device));
     StageTimer& t = c->timer;
     if (!t.created) {
@@ -1637,17 +1637,13 @@ int orbhip_search_for_triangulation(orbhip_ctx* c, const orbhip_tri_keyframe* kf
 }
 
 // ---- Fuse: B keyframes against one list of MapPoints ----
-int orbhip_fuse(orbhip_ctx* c, const orbhip_frame* kfs, int B, const orbhip_local_points* mps,
-                const uint8_t* pair_skip, const float* inv_level_sigma2, float th, int32_t* best_idx,
-                int32_t* best_dist, int32_t* level, int32_t* nfused) {
-    if (!c || B < 0 || !mps || mps->n < 0) return ORBHIP_ERR_ARG;
-    if (B == 0) return 0;
-    if (B > kFuseMaxKf || mps->n > kFuseMaxPoints) return ORBHIP_ERR_UNSUPPORTED;
-    if (!kfs || !nfused) return ORBHIP_ERR_ARG;
-    const int n = mps->n, L = kfs[0].n_levels;
-    if (L <= 0 || !kfs[0].scale_factors || !inv_level_sigma2) return ORBHIP_ERR_ARG;
+// The envelope and argument checks Fuse and the Sim3 searches share: the keyframes of a call have one
+// scale pyramid, at most 65535 keypoints each and octaves inside it. nk_total: their keypoints.
+static int fuse_check_keyframes(const orbhip_frame* kfs, int B, size_t* nk_total) {
+    const int L = kfs[0].n_levels;
+    if (L <= 0 || !kfs[0].scale_factors) return ORBHIP_ERR_ARG;
     if (L > kFuseMaxLevels) return ORBHIP_ERR_UNSUPPORTED;
-    size_t nk_total = 0;
+    *nk_total = 0;
     for (int b = 0; b < B; b++) {
         const orbhip_frame& f = kfs[b];
         if (f.n < 0) return ORBHIP_ERR_ARG;
@@ -1658,8 +1654,23 @@ int orbhip_fuse(orbhip_ctx* c, const orbhip_frame* kfs, int B, const orbhip_loca
         if (std::memcmp(f.scale_factors, kfs[0].scale_factors, (size_t)L * 4) != 0) return ORBHIP_ERR_ARG;
         for (int i = 0; i < f.n; i++)
             if (f.kps[i].octave < 0 || f.kps[i].octave >= L) return ORBHIP_ERR_ARG;
-        nk_total += (size_t)f.n;
+        *nk_total += (size_t)f.n;
     }
+    return ORBHIP_OK;
+}
+
+// chi2 = false: Fuse with a Sim3 (no chi-square gate, inv_level_sigma2 unused)
+static int fuse_call(orbhip_ctx* c, const orbhip_frame* kfs, int B, const orbhip_local_points* mps,
+                     const uint8_t* pair_skip, bool chi2, const float* inv_level_sigma2, float th, int32_t* best_idx,
+                     int32_t* best_dist, int32_t* level, int32_t* nfused) {
+    if (!c || B < 0 || !mps || mps->n < 0) return ORBHIP_ERR_ARG;
+    if (B == 0) return 0;
+    if (B > kFuseMaxKf || mps->n > kFuseMaxPoints) return ORBHIP_ERR_UNSUPPORTED;
+    if (!kfs || !nfused) return ORBHIP_ERR_ARG;
+    const int n = mps->n, L = kfs[0].n_levels;
+    if (chi2 && !inv_level_sigma2) return ORBHIP_ERR_ARG;
+    size_t nk_total = 0;
+    if (const int rc = fuse_check_keyframes(kfs, B, &nk_total)) return rc;
     for (int b = 0; b < B; b++) nfused[b] = 0;
     if (n == 0) return 0;
     if (!best_idx || !mps->points || !mps->normals || !mps->min_dist || !mps->max_dist || !mps->desc)
@@ -1674,7 +1685,7 @@ int orbhip_fuse(orbhip_ctx* c, const orbhip_frame* kfs, int B, const orbhip_loca
     auto take = [&](size_t bytes) { off = (off + 15) & ~size_t(15); const size_t o = off; off += bytes; return o; };
     const size_t bn = (size_t)B * (size_t)n;
     const size_t o_kf = take((size_t)B * sizeof(FuseKf));
-    const size_t o_sf = take((size_t)L * 4), o_s2 = take((size_t)L * 4);
+    const size_t o_sf = take((size_t)L * 4), o_s2 = take(chi2 ? (size_t)L * 4 : 0);
     const size_t o_pts = take((size_t)n * 12), o_nrm = take((size_t)n * 12), o_min = take((size_t)n * 4);
     const size_t o_max = take((size_t)n * 4), o_desc = take((size_t)n * 32), o_skip = take((size_t)n);
     const size_t o_pskip = take(pair_skip ? bn : 0);
@@ -1703,7 +1714,7 @@ int orbhip_fuse(orbhip_ctx* c, const orbhip_frame* kfs, int B, const orbhip_loca
         base += (size_t)f.n;
     }
     std::memcpy(h + o_sf, kfs[0].scale_factors, (size_t)L * 4);
-    std::memcpy(h + o_s2, inv_level_sigma2, (size_t)L * 4);
+    if (chi2) std::memcpy(h + o_s2, inv_level_sigma2, (size_t)L * 4);
     std::memcpy(h + o_pts, mps->points, (size_t)n * 12);
     std::memcpy(h + o_nrm, mps->normals, (size_t)n * 12);
     std::memcpy(h + o_min, mps->min_dist, (size_t)n * 4);
@@ -1722,7 +1733,8 @@ int orbhip_fuse(orbhip_ctx* c, const orbhip_frame* kfs, int B, const orbhip_loca
         const FusePoints mp{n, (const float*)(d + o_pts), (const float*)(d + o_nrm), (const float*)(d + o_min),
                             (const float*)(d + o_max), d + o_desc, d + o_skip};
         launch_fuse((const FuseKf*)(d + o_kf), B, mp, pair_skip ? d + o_pskip : nullptr, (const float*)(d + o_sf),
-                    (const float*)(d + o_s2), L, kfs[0].log_scale_factor, th, (const orbhip_kp*)(d + o_kps), d + o_kdesc,
+                    chi2 ? (const float*)(d + o_s2) : nullptr, L, kfs[0].log_scale_factor, th,
+                    (const orbhip_kp*)(d + o_kps), d + o_kdesc,
                     (int32_t*)(d + o_cs), (FuseRec*)(d + o_rec), d_idx, d_idx + bn, d_idx + 2 * bn, d_nf, st);
         c->timer.end(8, st);
     }
@@ -1738,6 +1750,104 @@ int orbhip_fuse(orbhip_ctx* c, const orbhip_frame* kfs, int B, const orbhip_loca
     for (int b = 0; b < B; b++) total += nfused[b];
     return total;
 }
+
+int orbhip_fuse(orbhip_ctx* c, const orbhip_frame* kfs, int B, const orbhip_local_points* mps,
+                const uint8_t* pair_skip, const float* inv_level_sigma2, float th, int32_t* best_idx,
+                int32_t* best_dist, int32_t* level, int32_t* nfused) {
+    return fuse_call(c, kfs, B, mps, pair_skip, true, inv_level_sigma2, th, best_idx, best_dist, level, nfused);
+}
+
+// ---- LoopClosing: Fuse and SearchByProjection with a Sim3 (the pose arrives as Tcw = (R, t / s)) ----
+int orbhip_fuse_sim3(orbhip_ctx* c, const orbhip_frame* kfs, int B, const orbhip_local_points* mps,
+                     const uint8_t* pair_skip, float th, int32_t* best_idx, int32_t* best_dist, int32_t* level,
+                     int32_t* nfused) {
+    return fuse_call(c, kfs, B, mps, pair_skip, false, nullptr, th, best_idx, best_dist, level, nfused);
+}
+
+int orbhip_search_by_projection_sim3(orbhip_ctx* c, const orbhip_frame* kf, const orbhip_local_points* mps, float th,
+                                     float ratio_hamming, int32_t* match, int32_t* match_dist, int32_t* level) {
+    if (!c || !kf || !mps || mps->n < 0) return ORBHIP_ERR_ARG;
+    if (!(ratio_hamming > 0.0f) || !std::isfinite(ratio_hamming)) return ORBHIP_ERR_ARG;
+    if (mps->n > kFuseMaxPoints) return ORBHIP_ERR_UNSUPPORTED;
+    size_t nk = 0;
+    if (const int rc = fuse_check_keyframes(kf, 1, &nk)) return rc;
+    const int n = mps->n, L = kf->n_levels;
+    if (n == 0) return 0;
+    if (!match || !mps->points || !mps->normals || !mps->min_dist || !mps->max_dist || !mps->desc) return ORBHIP_ERR_ARG;
+    const float thr = 50.0f * ratio_hamming;
+    HIPOK(hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    // one block, the same layout on the host (pinned) and the device:
+    // [keyframe | scale factors | points normals min max desc skip | claimed | keypoints | descriptors],
+    // then device only [cell_start 3073 | records | windows n | lists n x 8 | counts n | picks 2 x n |
+    //  owners | nmatches | match n | match_dist n | level n]; the last four are read back
+    size_t off = 0;
+    auto take = [&](size_t bytes) { off = (off + 15) & ~size_t(15); const size_t o = off; off += bytes; return o; };
+    const size_t o_kf = take(sizeof(FuseKf)), o_sf = take((size_t)L * 4);
+    const size_t o_pts = take((size_t)n * 12), o_nrm = take((size_t)n * 12), o_min = take((size_t)n * 4);
+    const size_t o_max = take((size_t)n * 4), o_desc = take((size_t)n * 32), o_skip = take((size_t)n);
+    const size_t o_claimed = take(nk), o_kps = take(nk * sizeof(orbhip_kp)), o_kdesc = take(nk * 32);
+    const size_t up_bytes = take(0);
+    const size_t o_cs = take((size_t)(kFuseCells + 1) * 4), o_rec = take(nk * sizeof(FuseRec));
+    const size_t o_win = take((size_t)n * sizeof(Sim3Win)), o_list = take((size_t)n * kSim3ListCap * 8);
+    const size_t o_cnt = take((size_t)n * 4), o_pick = take((size_t)n * 8), o_pnew = take((size_t)n * 8);
+    const size_t o_own = take(nk * 4);
+    const size_t o_back = take(0);
+    const size_t n_out = level ? 3 : (match_dist ? 2 : 1);   // arrays read back: a prefix of match, dist, level
+    const size_t back_bytes = 16 + n_out * (size_t)n * 4;     // match starts 16-byte aligned behind nmatches
+    off = o_back + 16 + 3 * (size_t)n * 4;
+    const size_t dev_bytes = take(0);
+    HIPOK(c->d_fuse_stage.ensure(dev_bytes));
+    HIPOK(c->h_fuse_stage.ensure(up_bytes + back_bytes + 16));
+    uint8_t* const d = c->d_fuse_stage.p;
+    uint8_t* const h = c->h_fuse_stage.p;
+    fuse_kf_params(*kf, 0, (FuseKf*)(h + o_kf));
+    std::memcpy(h + o_sf, kf->scale_factors, (size_t)L * 4);
+    std::memcpy(h + o_pts, mps->points, (size_t)n * 12);
+    std::memcpy(h + o_nrm, mps->normals, (size_t)n * 12);
+    std::memcpy(h + o_min, mps->min_dist, (size_t)n * 4);
+    std::memcpy(h + o_max, mps->max_dist, (size_t)n * 4);
+    std::memcpy(h + o_desc, mps->desc, (size_t)n * 32);
+    if (mps->skip) std::memcpy(h + o_skip, mps->skip, (size_t)n);
+    else std::memset(h + o_skip, 0, (size_t)n);
+    if (nk) {
+        if (kf->claimed) std::memcpy(h + o_claimed, kf->claimed, nk);
+        else std::memset(h + o_claimed, 0, nk);
+        std::memcpy(h + o_kps, kf->kps, nk * sizeof(orbhip_kp));
+        std::memcpy(h + o_kdesc, kf->desc, nk * 32);
+    }
+    HIPOK(hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
+    (void)hipGetLastError();
+    int32_t* const d_nm = (int32_t*)(d + o_back);
+    int32_t* const d_match = (int32_t*)(d + o_back + 16);
+    {
+        const StageScope scope(c->timer);
+        c->timer.begin(9, st);
+        const FusePoints mp{n, (const float*)(d + o_pts), (const float*)(d + o_nrm), (const float*)(d + o_min),
+                            (const float*)(d + o_max), d + o_desc, d + o_skip};
+        const Sim3Work w{(Sim3Win*)(d + o_win), (unsigned long long*)(d + o_list), (int32_t*)(d + o_cnt),
+                         (unsigned long long*)(d + o_pick), (unsigned long long*)(d + o_pnew), (int32_t*)(d + o_own)};
+        launch_sim3_search((const FuseKf*)(d + o_kf), mp, d + o_claimed, (const float*)(d + o_sf), L,
+                           kf->log_scale_factor, th, thr, (const orbhip_kp*)(d + o_kps), d + o_kdesc, (int)nk,
+                           (int32_t*)(d + o_cs), (FuseRec*)(d + o_rec), w, d_match, d_match + n, d_match + 2 * (size_t)n,
+                           d_nm, st);
+        c->timer.end(9, st);
+    }
+    HIPOK(hipGetLastError());
+    uint8_t* const hb = h + ((up_bytes + 15) & ~size_t(15));
+    HIPOK(hipMemcpyAsync(hb, d + o_back, back_bytes, hipMemcpyDeviceToHost, st));
+    HIPOK(hipStreamSynchronize(st));
+    std::memcpy(match, hb + 16, (size_t)n * 4);
+    if (match_dist) std::memcpy(match_dist, hb + 16 + (size_t)n * 4, (size_t)n * 4);
+    if (level) std::memcpy(level, hb + 16 + 2 * (size_t)n * 4, (size_t)n * 4);
+    int32_t nm;
+    std::memcpy(&nm, hb, 4);
+    return nm;
+}
+
+// the stored list capacity of the Sim3 projection search; the resolve has no round cap other than
+// (points with a list) + 1 (tests assert that their chain is deeper than the capacity)
+int orbhip_test_sim3_list_cap(void) { return kSim3ListCap; }
 
 // ---- test hooks (not part of the reference surface) ----
 int orbhip_test_cholesky(const double* A, const double* b, double* x, int n, unsigned long long* phases5,

@@ -217,11 +217,33 @@ struct FusePoints {                    // the MapPoints (device pointers; skip i
 // host, fp32 in a fixed operation order: grid scales and mOw
 void fuse_kf_params(const orbhip_frame& f, int base, FuseKf* k);
 // cell_start: B x 3073, recs: one per keypoint of the call (both written by k_fuse_grid);
-// best_idx / best_dist / level: B x n, nfused: B (zeroed by k_fuse_grid)
+// best_idx / best_dist / level: B x n, nfused: B (zeroed by k_fuse_grid).
+// inv_level_sigma2 == nullptr: the rule without the chi-square gate (Fuse with a Sim3)
 void launch_fuse(const FuseKf* kfs, int B, const FusePoints& mp, const uint8_t* pair_skip, const float* scale_factors,
                  const float* inv_level_sigma2, int n_levels, float log_sf, float th, const orbhip_kp* kps,
                  const uint8_t* kf_desc, int32_t* cell_start, FuseRec* recs, int32_t* best_idx, int32_t* best_dist,
                  int32_t* level, int32_t* nfused, hipStream_t st);
+
+// ---- SearchByProjection with a Sim3 (fuse_kernels.hip) ----
+constexpr int kSim3ListCap = 8;        // smallest keys k_sim3_search stores per point
+struct Sim3Win {                       // what k_sim3_resolve needs to walk a point's window again
+    float u, v, r;
+    int lvl;                           // -1: the point never reached the walk
+    int rect;                          // x0 | x1 << 8 | y0 << 16 | y1 << 24
+};
+struct Sim3Work {                      // device scratch of one call (n points, nk keypoints)
+    Sim3Win* win;                      // n
+    unsigned long long* list;          // n x kSim3ListCap, ascending, ~0 = empty
+    int32_t* count;                    // n: the full length of the list
+    unsigned long long *pick, *pick_new;   // n each
+    int32_t* owner;                    // nk
+};
+// match / match_dist / level: n, nmatches: 1. cell_start: 3073 + recs: nk (written by k_fuse_grid,
+// which also zeroes nmatches)
+void launch_sim3_search(const FuseKf* kf, const FusePoints& mp, const uint8_t* claimed, const float* scale_factors,
+                        int n_levels, float log_sf, float th, float thr, const orbhip_kp* kps, const uint8_t* kf_desc,
+                        int nk, int32_t* cell_start, FuseRec* recs, const Sim3Work& w, int32_t* match,
+                        int32_t* match_dist, int32_t* level, int32_t* nmatches, hipStream_t st);
 
 // ---- ingest ----
 void launch_bgr2gray(const uint8_t* src, int B, int w, int h, int sstride, int64_t sfstride, uint8_t* dst, int dstride,

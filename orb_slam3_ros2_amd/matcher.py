@@ -226,6 +226,61 @@ class ORBmatcher:
                                 ptr(dist), ptr(lvl), ptr(nf)), "orbhip_fuse")
         return nf, idx, dist, lvl
 
+    # ---- loop closing (LoopClosing::SearchAndFuse, DetectCommonRegionsFromBoW, ...) ----
+    @staticmethod
+    def _points_c(what, points, normals, min_dist, max_dist, mp_desc, skip):
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        n = pts.shape[0]
+        nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        mn = np.ascontiguousarray(min_dist, np.float32)
+        mx = np.ascontiguousarray(max_dist, np.float32)
+        d = np.ascontiguousarray(mp_desc, np.uint8).reshape(-1, 32)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8)
+        for a in (nrm, mn, mx, d) + (() if sk is None else (sk,)):
+            if a.shape[0] != n:
+                raise ValueError(f"{what}: per-point arrays differ in length")
+        # (the arrays are returned with the view: it points into them)
+        return n, LocalPointsC(n, ptr(pts), ptr(nrm), ptr(mn), ptr(mx), ptr(d), ptr(sk)), (pts, nrm, mn, mx, d, sk)
+
+    def FuseSim3(self, kfs, points, normals, min_dist, max_dist, mp_desc, th: float = 4.0, skip=None,
+                 pair_skip=None):
+        """U:src/ORBmatcher.cc::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) of every keyframe of `kfs`
+        against the same MapPoints in one call (LoopClosing::SearchAndFuse, th = 4). Each ProjFrame
+        carries Tcw = (Scw.rotationMatrix(), Scw.translation() / Scw.scale()). The rule of Fuse
+        without the chi-square gate; skip[m] = isBad(), pair_skip[b, m] = the keyframe already holds
+        the point. Returns (nfused[B], best_idx[B, n], best_dist[B, n], level[B, n]) as Fuse."""
+        kfs = list(kfs)
+        B = len(kfs)
+        n, lc, keep = self._points_c("FuseSim3", points, normals, min_dist, max_dist, mp_desc, skip)
+        ps = None if pair_skip is None else np.ascontiguousarray(pair_skip, np.uint8).reshape(B, n)
+        nf = np.zeros(B, np.int32)
+        idx = np.full((B, n), -1, np.int32)
+        dist = np.full((B, n), 256, np.int32)
+        lvl = np.full((B, n), -1, np.int32)
+        if B == 0:
+            return nf, idx, dist, lvl
+        arr = (FrameC * B)(*[k.to_c() for k in kfs])
+        check(lib().orbhip_fuse_sim3(self.ctx.handle, arr, B, ctypes.byref(lc), ptr(ps), float(th), ptr(idx),
+                                     ptr(dist), ptr(lvl), ptr(nf)), "orbhip_fuse_sim3")
+        return nf, idx, dist, lvl
+
+    def SearchByProjectionSim3(self, kf: "ProjFrame", points, normals, min_dist, max_dist, mp_desc, th: float,
+                               ratioHamming: float = 1.0, skip=None):
+        """U:src/ORBmatcher.cc::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th, ratioHamming)
+        (and the overload with vpPointsKFs / vpMatchedKF) with upstream's sequential greedy semantics.
+        kf carries Tcw = (R, t / s) of Scw and claimed[k] = vpMatched[k] is set at call time;
+        skip[m] = isBad() or the point is in vpMatched already. Returns (nmatches, match[n] = the
+        keypoint the point claims or -1, match_dist[n] = its distance or 256, level[n])."""
+        n, lc, keep = self._points_c("SearchByProjectionSim3", points, normals, min_dist, max_dist, mp_desc, skip)
+        match = np.full(n, -1, np.int32)
+        dist = np.full(n, 256, np.int32)
+        lvl = np.full(n, -1, np.int32)
+        fc = kf.to_c()
+        nm = check(lib().orbhip_search_by_projection_sim3(self.ctx.handle, ctypes.byref(fc), ctypes.byref(lc), float(th),
+                                                          float(ratioHamming), ptr(match), ptr(dist), ptr(lvl)),
+                   "orbhip_search_by_projection_sim3")
+        return nm, match, dist, lvl
+
 
 class TriKeyFrame:
     """A KeyFrame as SearchForTriangulation reads it: mvKeysUn (orbhip_kp records), descriptors, the

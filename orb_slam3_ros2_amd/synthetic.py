@@ -784,3 +784,35 @@ def synthetic_fuse_scene(n_kp=300, n_mp=300, B=3, seed=0, n_levels=8, scale_fact
     return dict(kfs=kfs, points=P, normals=normals.astype(np.float32), min_dist=min_dist, max_dist=max_dist,
                 mp_desc=mp_desc, skip=skip, pair_skip=pair_skip, scale_factors=sf, inv_level_sigma2=inv_s2,
                 th=float(th), kind=np.array(FUSE_KINDS)[kind], nudged=int(nudged.sum()))
+
+
+# ---------------------------------------------------------------------------
+# Sim3 scenes (LoopClosing: SearchByProjection with a Sim3)
+# ---------------------------------------------------------------------------
+def synthetic_sim3_scene(n_kp=300, n_mp=400, seed=0, th=3.0, ratio=1.5, n_claimed=20, **fuse_args):
+    """One keyframe and n_mp MapPoints for ORBmatcher.SearchByProjectionSim3: the one-keyframe
+    synthetic_fuse_scene of the first ceil(3 n_mp / 4) points, and behind them a copy of every third
+    of those points (position, normal, range and descriptor), so that a copy competes with its
+    original for the same keypoints and, coming later in the list, loses its first choice.
+    n_claimed keypoints (fewer when the keyframe has fewer) are claimed at call time (vpMatched set).
+    The keyframe's pose stands for Tcw = (R, t / s) of the Sim3 the adapter decomposed. Returns a
+    dict: kf (ProjFrame with claimed), points, normals, min_dist, max_dist, mp_desc, skip, th, ratio,
+    kind, copy_of (-1 for an original)."""
+    from .matcher import ProjFrame
+    base = (3 * n_mp + 3) // 4
+    s = synthetic_fuse_scene(n_kp, base, 1, seed, th=th, **fuse_args)
+    src = 3 * np.arange(n_mp - base)
+    assert src.size == 0 or src[-1] < base
+    rng = np.random.Generator(np.random.PCG64(1000 + seed))
+    k0 = s["kfs"][0]
+    nk = k0.kps.shape[0]
+    claimed = np.zeros(nk, np.uint8)
+    claimed[rng.choice(nk, min(n_claimed, nk), replace=False)] = 1
+    kf = ProjFrame(k0.kps, k0.desc, k0.pose_q, k0.pose_t, k0.fx, k0.fy, k0.cx, k0.cy, *k0.bounds[1::2],
+                   claimed=claimed)
+    kf.scale_factors, kf.log_scale_factor = k0.scale_factors, k0.log_scale_factor
+    out = {k: np.concatenate([s[k], s[k][src]]) for k in ("points", "normals", "min_dist", "max_dist", "mp_desc",
+                                                          "skip", "kind")}
+    out.update(kf=kf, th=float(th), ratio=float(ratio), scale_factors=s["scale_factors"],
+               inv_level_sigma2=s["inv_level_sigma2"], copy_of=np.concatenate([np.full(base, -1), src]))
+    return out
