@@ -1,11 +1,13 @@
 """Bag of words: DBoW2 transform + BowVector / FeatureVector and
 ORBmatcher::SearchByBoW. CPU: known-answer tests of the oracle restatement on hand-built
 vocabularies, the ORBvoc.txt text round trip. GPU: bit-exact word / node / weight per descriptor
-and identical SearchByBoW matches vs the oracle. Parity unpinned by the reference (DBoW2 and
+and identical SearchByBoW matches vs the oracle (the happy paths; tests/test_bow_gpu.py sweeps the
+edges, and the last part of this file checks its scenes on the CPU first). Parity unpinned by the reference (DBoW2 and
 ORBvoc.txt are absent): the vocabularies are synthetic (orb_slam3_ros2_amd.vocabulary)."""
 import numpy as np
 import pytest
 
+import bow_numpy as B
 from orb_slam3_ros2_amd.vocabulary import Vocabulary, bow_vector, feature_vector
 
 
@@ -146,3 +148,122 @@ def test_gpu_search_bow_matches_oracle(oracle, ratio, ori, levelsup):
                                  np.where(fwt > 0, fn, -1), ratio=ratio, check_orientation=ori)
     assert n == on2 and np.array_equal(m, om2)
     assert n > 50
+
+
+# ------------------------------------------- the scenes of tests/test_bow_gpu.py, on the CPU
+# Before the device is compared with the oracle on a scene, the oracle and an independent plain
+# restatement (tests/bow_numpy.py) must agree on it, and the scene must reach what it is there for.
+def _oracle_search(oracle, sc, ratio, ori, th_low=50):
+    gk, gf = B.gated(sc)
+    return oracle.search_bow(sc["kd"], sc["ka"], gk, sc["kv"], sc["fd"], sc["fa"], gf, ratio=ratio,
+                             check_orientation=ori, th_low=th_low)
+
+
+def _numpy_search(sc, ratio, ori, th_low=50):
+    gk, gf = B.gated(sc)
+    st = {}
+    n, m = B.search_bow_numpy(sc["kd"], sc["ka"], gk, sc["kv"], sc["fd"], sc["fa"], gf, ratio, ori, th_low, stats=st)
+    return n, m, st
+
+
+@pytest.mark.parametrize("name", list(B.SCENES))
+def test_scene_oracle_equals_restatement_and_is_not_trivial(oracle, name):
+    sc = B.scene(name)
+    gk, gf = B.gated(sc)
+    pos = B.position_in_node(gf)
+    for ratio, ori in B.SEARCH_PARAMS:
+        n, m = _oracle_search(oracle, sc, ratio, ori)
+        rn, rm, st = _numpy_search(sc, ratio, ori)
+        assert n == rn and np.array_equal(m, rm)
+        assert n == int((m >= 0).sum()) and n > 0.25 * min(len(gk), len(gf))
+        # both sides carry zero-weight features, invalid KF features and one-sided nodes
+        assert (sc["kw"] == 0).any() and (sc["fw"] == 0).any() and (sc["kv"] == 0).any() and sc["kv"].any()
+        assert set(gk[gk >= 0]) - set(gf[gf >= 0]) and set(gf[gf >= 0]) - set(gk[gk >= 0])
+        # a KF feature within th_low that only the ratio rule rejects, with best == second
+        assert st["ratio_ties"] >= 1
+        if name in B.CROWDED:
+            # more than two 64-lane chunks in one node, and a match found past the first chunk
+            assert np.bincount(gf[gf >= 0]).max() > 128
+            assert pos[m >= 0].max() >= 64
+    if name in B.ROTATION_BINS:
+        # the rotation filter drops matches, and keeps exactly the bins the mixture is built for
+        n0, m0 = _oracle_search(oracle, sc, 0.9, False)
+        n1, m1 = _oracle_search(oracle, sc, 0.9, True)
+        assert n1 < n0 and np.array_equal(m1[m1 >= 0], m0[m1 >= 0])
+        bins = [B.rotation_bin(sc["ka"][m0[f]], sc["fa"][f]) for f in np.nonzero(m0 >= 0)[0]]
+        keep = [k for k in B.three_maxima(np.bincount(bins, minlength=30)) if k >= 0]
+        assert len(keep) == B.ROTATION_BINS[name]
+        assert n1 == sum(b in keep for b in bins)
+
+
+def test_scene_th_low_30(oracle):
+    sc = B.scene("flip45")
+    n, m = _oracle_search(oracle, sc, 0.9, True, th_low=30)
+    rn, rm, st = _numpy_search(sc, 0.9, True, th_low=30)
+    assert n == rn and np.array_equal(m, rm)
+    assert 0 < n < _oracle_search(oracle, sc, 0.9, True)[0]      # the tighter bound rejects matches
+
+
+@pytest.mark.parametrize("name", B.DEGENERATE)
+def test_degenerate_scenes_give_no_match(oracle, name):
+    sc = B.degenerate(name)
+    for ratio, ori in B.SEARCH_PARAMS:
+        n, m = _oracle_search(oracle, sc, ratio, ori)
+        rn, rm, _ = _numpy_search(sc, ratio, ori)
+        assert n == rn == 0 and (m == -1).all() and (rm == -1).all()
+
+
+@pytest.mark.parametrize("seed", [1, 2])
+def test_ragged_vocabulary_oracle_equals_numpy_descent(oracle, seed):
+    v = B.ragged_vocabulary(5, 5, seed)
+    first, nch, children, word = v.csr()
+    dep = B.depths(v)
+    assert (v.parent[1:] < np.arange(1, v.n_nodes)).all() and dep.max() == v.L
+    assert (nch == 1).any() and 1 < nch.max() <= v.k
+    assert ((v.is_leaf > 0) & (dep < v.L)).any()                         # leaves above depth L
+    assert ((v.is_leaf > 0) & (v.weight == 0)).any() and (v.weight[v.is_leaf == 0] == 0).all()
+    twins = [i for i in range(2, v.n_nodes)
+             if v.parent[i] == v.parent[i - 1] and np.array_equal(v.desc[i], v.desc[i - 1])]
+    assert twins                                                         # identical siblings
+    f = B.transform_feats(v, 257, seed)
+    for levelsup in (0, v.L - 1, v.L, v.L + 2):
+        ow, on, ov = oracle.bow_transform(v, f, levelsup)
+        rw, rn, rv = B.bow_transform_numpy(v, f, levelsup)
+        assert np.array_equal(ow, rw) and np.array_equal(on, rn) and np.array_equal(ov, rv)
+        if levelsup >= v.L:
+            assert (on == 0).all()                                       # the root
+    ow, on, ov = oracle.bow_transform(v, f, 0)
+    early = dep[np.nonzero(v.is_leaf)[0][ow]] < v.L
+    assert early.any() and (on[early] == 0).all() and (on[~early] > 0).all()   # level L never reached: node 0
+    assert (ov == 0).any()
+    path_nodes = oracle.bow_transform(v, f, v.L - 1)[1]                  # the level-1 node of each path
+    assert set(np.nonzero(nch == 1)[0]) & set(path_nodes)                # a single-child node is descended
+    assert not set(twins) & set(np.nonzero(v.is_leaf)[0][ow])            # the first of two equal siblings wins
+
+
+@pytest.mark.parametrize("levelsup,n_nodes", [(5, 10), (6, 1)])
+def test_vocabulary_scene_oracle_equals_restatement(oracle, levelsup, n_nodes):
+    sc = _vocabulary_scene(oracle.bow_transform, levelsup)
+    assert len(set(sc["kn"]) | set(sc["fn"])) == n_nodes
+    for ratio, ori in B.SEARCH_PARAMS:
+        n, m = _oracle_search(oracle, sc, ratio, ori)
+        rn, rm, _ = _numpy_search(sc, ratio, ori)
+        assert n == rn and np.array_equal(m, rm) and n > 100
+
+
+_SYNTH = {}
+
+
+def _synthetic_10_6():
+    if not _SYNTH:
+        _SYNTH["v"] = Vocabulary.synthetic(10, 6, seed=11)
+    return _SYNTH["v"]
+
+
+def _vocabulary_scene(transform, levelsup):
+    """A 600 x 600 scene whose nodes and weights come from `transform(vocabulary, desc, levelsup)`."""
+    sc = dict(B.bow_scene(600, 600, [0], seed=600))
+    v = _synthetic_10_6()
+    _, sc["kn"], sc["kw"] = transform(v, sc["kd"], levelsup)
+    _, sc["fn"], sc["fw"] = transform(v, sc["fd"], levelsup)
+    return sc

@@ -4,6 +4,11 @@ and the device path (one wavefront per frame) against the oracle on the GPU.
 Parity unpinned by the reference (no fixtures upstream); the oracle is pinned by definitional
 KATs: exact observations converge to the ground-truth pose, injected gross mismatches are the
 outliers, fewer than 3 correspondences leave the pose untouched and return 0.
+
+The edge sweep (second half): every problem it runs on the device is first shown, on the CPU, to
+have oracle flags that do not depend on the edge order; then the register-cache boundary, frames
+whose edges all become outliers, quaternion normalisation, points behind the camera, the default
+wave width, the large-batch transfer path, workspace regrowth and the argument check.
 """
 import numpy as np
 import pytest
@@ -85,3 +90,291 @@ def test_pose_optimization_batch_and_edge_cases(oracle, monkeypatch, waves):
     for p, r in zip(probs, rs):
         _check(r, oracle.pose_optimization(p))
     assert rs[0].n_inliers == 0 and rs[2].n_inliers == 0
+
+
+# ------------------------------------------------- the cases of the edge sweep (CPU and GPU)
+# Every problem the GPU sweep below runs, by name. The device sums the edges in another order than
+# the oracle, so the bit-exact flag comparison is only honest for problems whose oracle flags do not
+# depend on the edge order: test_oracle_sweep_cases_are_order_stable asserts that for each one
+# (a seed that fails is replaced by another seed; no comparison is loosened, no edge left out).
+_BOUNDARY_N = [127, 128, 129, 1023, 1024, 1025]     # EC * NT: 128 edges (1 wave), 1024 (4 waves)
+# seed 300 + n, but for 129 and 1025 the first seed from there at which the one edge past the
+# register cache ends as an outlier: inactive edges then fall on both sides of the cache
+_BOUNDARY_SEED = {n: 300 + n for n in _BOUNDARY_N} | {129: 440, 1025: 1326}
+_ALL_OUTLIER_N = [10, 64, 300]
+_SMALL_B, _LARGE_B, _LARGE_N = 520, 64, 800
+_EDGE_BYTES = 24                                    # PoseEdgeIn: X[3], u, v, info as float
+
+
+def _behind_camera_problem(n=200, seed=61, frac=0.05):
+    """5 % of the map points mirrored behind the camera (finite, z in [-6, -2] m in the true camera
+    frame and still < 0 from the perturbed initial pose)."""
+    prob, gt = synthetic_pose_problem(n=n, outlier_frac=0.1, seed=seed)
+    rng = np.random.Generator(np.random.PCG64(seed + 1))
+    behind = np.sort(rng.choice(n, size=int(round(n * frac)), replace=False))
+    Xc = prob.points.astype(np.float64) @ gt["R"].T + gt["t"]
+    Xc[behind, 2] = -Xc[behind, 2]
+    prob.points = ((Xc - gt["t"]) @ gt["R"]).astype(np.float32)
+    return prob, behind
+
+
+_CASES = {}
+
+
+def _case(name):
+    """The named PoseProblem; all of them are built once per process and never modified."""
+    if not _CASES:
+        for n in _BOUNDARY_N:
+            _CASES[f"boundary{n}"] = synthetic_pose_problem(n=n, outlier_frac=0.2, seed=_BOUNDARY_SEED[n])[0]
+        for n in _ALL_OUTLIER_N:
+            _CASES[f"alloutlier{n}"] = synthetic_pose_problem(n=n, outlier_frac=1.0, seed=1000)[0]
+        _CASES["quat"] = synthetic_pose_problem(n=150, outlier_frac=0.1, seed=51)[0]
+        _CASES["behind"] = _behind_camera_problem()[0]
+        for i in range(_SMALL_B):
+            _CASES[f"small{i}"] = synthetic_pose_problem(n=3 + i % 20, outlier_frac=0.2, seed=2000 + i)[0]
+        for i in range(_LARGE_B):
+            _CASES[f"large{i}"] = synthetic_pose_problem(n=_LARGE_N, outlier_frac=0.05 * (i % 7), seed=4000 + i)[0]
+        for i, n in enumerate([10, 63, 150]):
+            _CASES[f"regrow{i}"] = synthetic_pose_problem(n=n, outlier_frac=0.2, seed=500 + i)[0]
+    return _CASES[name]
+
+
+_ORACLE = {}
+
+
+def _ref(oracle, name):
+    """The oracle's result for a named case, computed once and left unchanged."""
+    if name not in _ORACLE:
+        _ORACLE[name] = oracle.pose_optimization(_case(name))
+    return _ORACLE[name]
+
+
+def _case_names():
+    _case("quat")
+    return list(_CASES)
+
+
+def _permuted(prob, perm):
+    from orb_slam3_ros2_amd.optimizer import PoseProblem
+    return PoseProblem(prob.pose_q, prob.pose_t, prob.points[perm], prob.uv[perm], prob.octave[perm],
+                       prob.inv_sigma2, prob.fx, prob.fy, prob.cx, prob.cy)
+
+
+def _order_stability(oracle, name, n_perm=8):
+    """(flags stable, lm_trials stable) of the oracle under n_perm random edge permutations."""
+    prob, ref = _case(name), _ref(oracle, name)
+    rng = np.random.Generator(np.random.PCG64(77))
+    flags, trials = True, True
+    for _ in range(n_perm):
+        perm = rng.permutation(prob.points.shape[0])
+        r = oracle.pose_optimization(_permuted(prob, perm))
+        out = np.empty_like(r["outlier"])
+        out[perm] = r["outlier"]
+        flags &= bool(np.array_equal(out, ref["outlier"])) and r["n_inliers"] == ref["n_inliers"]
+        trials &= r["lm_trials"] == ref["lm_trials"]
+    return flags, trials
+
+
+# the cases whose lm_trials the GPU sweep compares with the oracle: the CPU test asserts that the
+# oracle's count is the same under every permutation for exactly these
+_TRIALS_STABLE = [f"alloutlier{n}" for n in _ALL_OUTLIER_N]
+
+
+def test_oracle_sweep_cases_are_order_stable(oracle):
+    unstable = [nm for nm in _case_names() if not _order_stability(oracle, nm)[0]]
+    assert unstable == []
+    for nm in _TRIALS_STABLE:
+        assert _order_stability(oracle, nm)[1], nm
+
+
+def test_oracle_sweep_cases_are_not_trivial(oracle):
+    # the register-cache boundary cases have inactive edges on both sides of the cache (EC * NT)
+    for n, cache in [(129, 128), (1025, 1024)]:
+        out = _ref(oracle, f"boundary{n}")["outlier"]
+        assert out[:cache].any() and not out[:cache].all() and out[cache:].all()
+    # a round that marks every edge an outlier: the rounds after it have no active edge and
+    # optimize() does nothing, so the pose that comes back is the (normalised) initial pose, bit for bit
+    for n in _ALL_OUTLIER_N:
+        r, p = _ref(oracle, f"alloutlier{n}"), _case(f"alloutlier{n}")
+        assert r["n_inliers"] == 0 and r["outlier"].all() and r["lm_trials"] >= 10
+        q = p.pose_q.astype(np.float64)
+        q = q / np.linalg.norm(q) * (1.0 if q[3] >= 0 else -1.0)
+        assert np.array_equal(r["pose_q"], q.astype(np.float32)) and np.array_equal(r["pose_t"], p.pose_t)
+    # a negated, scaled quaternion is the same rotation: same flags and pose
+    p = _case("quat")
+    from orb_slam3_ros2_amd.optimizer import PoseProblem
+    r2 = oracle.pose_optimization(PoseProblem(**{**p.__dict__, "pose_q": p.pose_q * np.float32(-2.5)}))
+    r = _ref(oracle, "quat")
+    assert np.array_equal(r2["outlier"], r["outlier"]) and np.array_equal(r2["pose_q"], r["pose_q"])
+    assert np.array_equal(r2["pose_t"], r["pose_t"])
+    # the mirrored points are behind the camera at the initial and at the final pose, and outliers
+    prob, behind = _behind_camera_problem()
+    r = _ref(oracle, "behind")
+    assert len(behind) == 10
+    for q, t in [(prob.pose_q, prob.pose_t), (r["pose_q"], r["pose_t"])]:
+        z = (prob.points[behind].astype(np.float64) @ _quat_to_mat(q).T + t)[:, 2]
+        assert np.isfinite(z).all() and (z < -1.0).all()
+    assert r["outlier"][behind].all() and 0 < r["n_inliers"] < 200
+    # the large batch is past the packed-input threshold of the DMA transfer path
+    assert _EDGE_BYTES * _LARGE_B * _LARGE_N > 2 ** 20
+
+
+def _quat_to_mat(q):
+    x, y, z, w = (np.asarray(q, np.float64) / np.linalg.norm(q)).tolist()
+    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+
+
+# --------------------------------------------------------------------------- GPU edge sweep
+def _batch(opt, names):
+    return opt.PoseOptimization_batch([_case(nm) for nm in names])
+
+
+def _check_names(oracle, names, results, trials=()):
+    for nm, g in zip(names, results):
+        _check(g, _ref(oracle, nm))
+        if nm in trials:
+            assert g.lm_trials == _ref(oracle, nm)["lm_trials"], nm
+
+
+def _same_bits(a, b):
+    return (np.array_equal(a.pose_q, b.pose_q) and np.array_equal(a.pose_t, b.pose_t)
+            and np.array_equal(a.outlier, b.outlier) and a.n_inliers == b.n_inliers and a.lm_trials == b.lm_trials)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("waves", ["1", "4"])
+@pytest.mark.parametrize("n", _BOUNDARY_N)
+def test_pose_register_cache_boundary(oracle, monkeypatch, waves, n):
+    """n - 1, n, n + 1 around the edges a thread keeps in registers (128 at 1 wave, 1024 at 4),
+    with outliers (inactive edges after round 0) inside and past the cached part."""
+    monkeypatch.setenv("ORBHIP_POSE_WAVES", waves)
+    from orb_slam3_ros2_amd import Optimizer
+    _check(Optimizer().PoseOptimization(_case(f"boundary{n}")), _ref(oracle, f"boundary{n}"))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("waves", ["1", "4", None])
+@pytest.mark.parametrize("n", _ALL_OUTLIER_N)
+def test_pose_all_outlier_frame_keeps_initial_pose(oracle, monkeypatch, waves, n):
+    """Round 0 marks every edge an outlier: the later rounds have no active edge, optimize() does
+    nothing, and the frame comes back with its normalised initial pose and 0 inliers."""
+    if waves is None:
+        monkeypatch.delenv("ORBHIP_POSE_WAVES", raising=False)
+    else:
+        monkeypatch.setenv("ORBHIP_POSE_WAVES", waves)
+    from orb_slam3_ros2_amd import Optimizer
+    nm = f"alloutlier{n}"
+    p, o = _case(nm), _ref(oracle, nm)
+    g = Optimizer().PoseOptimization(p)
+    _check(g, o)
+    assert g.n_inliers == 0 and g.outlier.all()
+    assert np.array_equal(g.pose_q, o["pose_q"]) and np.array_equal(g.pose_t, p.pose_t)
+    assert nm in _TRIALS_STABLE and g.lm_trials == o["lm_trials"]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("waves", ["1", "4"])
+def test_pose_scaled_negated_quaternion(oracle, monkeypatch, waves):
+    monkeypatch.setenv("ORBHIP_POSE_WAVES", waves)
+    from orb_slam3_ros2_amd import Optimizer
+    from orb_slam3_ros2_amd.optimizer import PoseProblem
+    opt = Optimizer()
+    p = _case("quat")
+    p2 = PoseProblem(**{**p.__dict__, "pose_q": p.pose_q * np.float32(-2.5)})
+    g, g2 = opt.PoseOptimization(p), opt.PoseOptimization(p2)
+    _check(g2, oracle.pose_optimization(p2))
+    _check(g2, _ref(oracle, "quat"))
+    # the same rotation: the same flags and float pose (-2.5 q rounds in float, so the normalised
+    # quaternions differ in their last double bits and the trial counts may)
+    assert np.array_equal(g.pose_q, g2.pose_q) and np.array_equal(g.pose_t, g2.pose_t)
+    assert np.array_equal(g.outlier, g2.outlier) and g.n_inliers == g2.n_inliers
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("waves", ["1", "4"])
+def test_pose_points_behind_the_camera(oracle, monkeypatch, waves):
+    monkeypatch.setenv("ORBHIP_POSE_WAVES", waves)
+    from orb_slam3_ros2_amd import Optimizer
+    g = Optimizer().PoseOptimization(_case("behind"))
+    _check(g, _ref(oracle, "behind"))
+    assert g.outlier[_behind_camera_problem()[1]].all()
+
+
+@pytest.mark.gpu
+def test_pose_default_width_many_small_frames(oracle, monkeypatch):
+    """No ORBHIP_POSE_WAVES: B > 512 takes one wave per frame, 4 frames per work-group. B = 520 fills
+    its 130 work-groups; B = 517 of the same frames leaves one frame in the last work-group."""
+    monkeypatch.delenv("ORBHIP_POSE_WAVES", raising=False)
+    from orb_slam3_ros2_amd import Optimizer
+    opt = Optimizer()
+    names = [f"small{i}" for i in range(_SMALL_B)]
+    _check_names(oracle, names, _batch(opt, names))
+    _check_names(oracle, names[:517], _batch(opt, names[:517]))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B", [1, 2, 3, 5])
+def test_pose_one_wave_part_filled_group(oracle, monkeypatch, B):
+    monkeypatch.setenv("ORBHIP_POSE_WAVES", "1")
+    from orb_slam3_ros2_amd import Optimizer
+    names = [f"small{i}" for i in range(7, 7 + B)]
+    _check_names(oracle, names, _batch(Optimizer(), names))
+
+
+@pytest.mark.gpu
+def test_pose_large_batch_transfer_path(oracle, monkeypatch):
+    """Packed input over 1 MiB: DMA upload, device-resident outputs, one download of [out | outlier]."""
+    monkeypatch.delenv("ORBHIP_POSE_WAVES", raising=False)
+    from orb_slam3_ros2_amd import Optimizer
+    names = [f"large{i}" for i in range(_LARGE_B)]
+    E = sum(_case(nm).points.shape[0] for nm in names)
+    assert _EDGE_BYTES * E > 2 ** 20
+    _check_names(oracle, names, _batch(Optimizer(), names))
+
+
+@pytest.mark.gpu
+def test_pose_workspace_regrowth(oracle, monkeypatch):
+    """One Optimizer: a small batch, the large one (the workspace grows), the small batch again."""
+    monkeypatch.delenv("ORBHIP_POSE_WAVES", raising=False)
+    from orb_slam3_ros2_amd import Optimizer
+    opt = Optimizer()
+    small = [f"regrow{i}" for i in range(3)]
+    large = [f"large{i}" for i in range(_LARGE_B)]
+    first = _batch(opt, small)
+    _check_names(oracle, small, first)
+    _check_names(oracle, large, _batch(opt, large))
+    third = _batch(opt, small)
+    _check_names(oracle, small, third)
+    assert all(_same_bits(a, b) for a, b in zip(first, third))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("octave", [-1, 8])
+def test_pose_octave_out_of_range_is_an_argument_error(octave):
+    """ORBHIP_ERR_ARG before anything runs: no result of the batch is written."""
+    import ctypes
+    from orb_slam3_ros2_amd import Optimizer
+    from orb_slam3_ros2_amd._lib import OrbHipError, PoseProblemC, PoseResultC, check, lib, ptr
+    opt = Optimizer()
+    good, bad = _case("regrow0").normalized(), _case("regrow1").normalized()
+    assert octave == -1 or octave == len(bad.inv_sigma2)
+    bad.octave = bad.octave.copy()
+    bad.octave[17] = octave
+    ps = [good, bad]
+    outl = [np.full(p.points.shape[0], 0xCC, np.uint8) for p in ps]
+    cprobs = (PoseProblemC * 2)(*[p.to_c() for p in ps])
+    cres = (PoseResultC * 2)()
+    for r, o in zip(cres, outl):
+        r.pose_q[:] = [9.0] * 4
+        r.pose_t[:] = [9.0] * 3
+        r.outlier, r.n_inliers, r.lm_trials = ptr(o), -77, -77
+    with pytest.raises(OrbHipError) as ei:
+        check(lib().orbhip_pose_optimization_batch(opt.ctx.handle, cprobs, 2, cres), "orbhip_pose_optimization_batch")
+    assert ei.value.code == -1 and "ORBHIP_ERR_ARG" in str(ei.value)
+    for r, o in zip(cres, outl):
+        assert list(r.pose_q) == [9.0] * 4 and list(r.pose_t) == [9.0] * 3
+        assert (r.n_inliers, r.lm_trials) == (-77, -77) and (o == 0xCC).all()
+    with pytest.raises(OrbHipError):
+        opt.PoseOptimization(bad)
