@@ -15,14 +15,10 @@
 
 #include "orbhip_device.h"
 #include "dev_attr.h"
+#include "geom.h"
 #include "orbhip_kernels.h"
 
 namespace orbhip {
-
-__device__ __forceinline__ int ham2(uint4 a, uint4 b, uint4 c, uint4 d) {
-    return __popc(a.x ^ c.x) + __popc(a.y ^ c.y) + __popc(a.z ^ c.z) + __popc(a.w ^ c.w) + __popc(b.x ^ d.x) +
-           __popc(b.y ^ d.y) + __popc(b.z ^ d.z) + __popc(b.w ^ d.w);
-}
 
 __global__ __launch_bounds__(256) void k_bow_transform(VocabView V, const uint8_t* __restrict__ desc,
                                                        const int32_t* __restrict__ n_arr, int n_fixed, int cap,
@@ -41,10 +37,10 @@ __global__ __launch_bounds__(256) void k_bow_transform(VocabView V, const uint8_
         const int* ch = V.children + V.first_child[fid];
         const int nc = V.n_child[fid];
         int best = ch[0];
-        int bd = ham2(qa, qb, V.desc[2 * best], V.desc[2 * best + 1]);
+        int bd = hamming256(qa, qb, V.desc[2 * best], V.desc[2 * best + 1]);
         for (int c = 1; c < nc; c++) {
             const int id = ch[c];
-            const int d = ham2(qa, qb, V.desc[2 * id], V.desc[2 * id + 1]);
+            const int d = hamming256(qa, qb, V.desc[2 * id], V.desc[2 * id + 1]);
             if (d < bd) { bd = d; best = id; }
         }
         fid = best;
@@ -159,7 +155,7 @@ __global__ __launch_bounds__(1024) void k_search_bow(BowSide K, BowSide F, float
                 if (c < fbnd && !S.taken[c]) {
                     const int fidx = (int)(S.fb[c] & 0xFFFF);
                     const uint4* fd = (const uint4*)(F.desc + (int64_t)fidx * 32);
-                    d = ham2(ka, kb2, fd[0], fd[1]);
+                    d = hamming256(ka, kb2, fd[0], fd[1]);
                 }
                 // chunk best by (distance, position) and the chunk's multiset second
                 int key = (d << 20) | (c < fbnd ? (c - fa) : 0xFFFFF);

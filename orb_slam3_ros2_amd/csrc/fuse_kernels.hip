@@ -29,58 +29,62 @@
 // LDS: k_fuse_grid 12 KiB histogram + 12 KiB cursors + scan scratch; k_fuse_search 4 bytes; k_sim3_resolve 12 bytes.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
+
+#include "geom.h"
 #include "orbhip_device.h"
 #include "orbhip_kernels.h"
+#include "stage.h"
+
+#define HIPOK(x) ORBHIP_HIPOK(" fuse", x)
 
 namespace orbhip {
 
-// ---- host: per-keyframe constants (all fp32, every operation in the order written; no FMA) ----
-static void fuse_qrot(const float q[4], const float v[3], float o[3]) {   // Eigen _transformVector
-    float uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]};
-    uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
-    const float c[3] = {q[1] * uv[2] - q[2] * uv[1], q[2] * uv[0] - q[0] * uv[2], q[0] * uv[1] - q[1] * uv[0]};
-    o[0] = v[0] + q[3] * uv[0] + c[0];
-    o[1] = v[1] + q[3] * uv[1] + c[1];
-    o[2] = v[2] + q[3] * uv[2] + c[2];
-}
+constexpr int kFuseMaxKf = 64;         // keyframes per call
+constexpr int kFuseMaxPoints = 65536;  // MapPoints per call
+constexpr int kFuseMaxLevels = 256;    // the octave shares a word with the cell
+struct FuseKf {                        // one keyframe of the call
+    int n, base;                       // its keypoints are entries [base, base + n) of the call's arrays
+    float minx, maxx, miny, maxy, invw, invh;
+    float q[4], t[3], Ow[3], fx, fy, cx, cy;
+};
+struct FuseRec { float x, y; int cell_oct, idx; };   // a keypoint in cell order: cell << 8 | octave, its index
+struct Sim3Win {                       // what k_sim3_resolve needs to walk a point's window again
+    float u, v, r;
+    int lvl;                           // -1: the point never reached the walk
+    int rect;                          // x0 | x1 << 8 | y0 << 16 | y1 << 24
+};
+struct Sim3Work {                      // device scratch of one call (n points, nk keypoints)
+    Sim3Win* win;                      // n
+    unsigned long long* list;          // n x kSim3ListCap, ascending, ~0 = empty
+    int32_t* count;                    // n: the full length of the list
+    unsigned long long *pick, *pick_new;   // n each
+    int32_t* owner;                    // nk
+};
 
-void fuse_kf_params(const orbhip_frame& f, int base, FuseKf* k) {
+// ---- host: per-keyframe constants (all fp32, every operation in the order written; no FMA):
+// grid scales and mOw ----
+static void fuse_kf_params(const orbhip_frame& f, int base, FuseKf* k) {
     k->n = f.n;
     k->base = base;
     k->minx = f.min_x; k->maxx = f.max_x; k->miny = f.min_y; k->maxy = f.max_y;
-    k->invw = (float)kFuseCols / (f.max_x - f.min_x);
-    k->invh = (float)kFuseRows / (f.max_y - f.min_y);
+    k->invw = (float)kGridCols / (f.max_x - f.min_x);
+    k->invh = (float)kGridRows / (f.max_y - f.min_y);
     for (int i = 0; i < 4; i++) k->q[i] = f.pose_q[i];
     for (int i = 0; i < 3; i++) k->t[i] = f.pose_t[i];
     const float qc[4] = {-f.pose_q[0], -f.pose_q[1], -f.pose_q[2], f.pose_q[3]};
     const float mt[3] = {f.pose_t[0] * -1.0f, f.pose_t[1] * -1.0f, f.pose_t[2] * -1.0f};
-    fuse_qrot(qc, mt, k->Ow);
+    quat_rotate(qc, mt, k->Ow);
     k->fx = f.fx; k->fy = f.fy; k->cx = f.cx; k->cy = f.cy;
 }
 
 // ---- device ----
-__device__ __forceinline__ void fuse_qrot_dev(const float q[4], const float v[3], float o[3]) {
-    float uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]};
-    uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
-    const float c[3] = {q[1] * uv[2] - q[2] * uv[1], q[2] * uv[0] - q[0] * uv[2], q[0] * uv[1] - q[1] * uv[0]};
-    o[0] = v[0] + q[3] * uv[0] + c[0];
-    o[1] = v[1] + q[3] * uv[1] + c[1];
-    o[2] = v[2] + q[3] * uv[2] + c[2];
-}
-
-// PosInGrid: cell = px * 48 + py, -1 outside the grid (as k_proj_cells)
-__device__ __forceinline__ int fuse_cell(const FuseKf& f, float x, float y) {
-    const int px = (int)roundf((x - f.minx) * f.invw);
-    const int py = (int)roundf((y - f.miny) * f.invh);
-    return (px < 0 || px >= kFuseCols || py < 0 || py >= kFuseRows) ? -1 : px * kFuseRows + py;
-}
-
 constexpr int kFuseGridThreads = 1024;
-constexpr int kFuseBinsPerThread = kFuseCells / kFuseGridThreads;
-static_assert(kFuseBinsPerThread * kFuseGridThreads == kFuseCells, "k_fuse_grid scans 3 bins per thread");
+constexpr int kFuseBinsPerThread = kGridCells / kFuseGridThreads;
+static_assert(kFuseBinsPerThread * kFuseGridThreads == kGridCells, "k_fuse_grid scans 3 bins per thread");
 struct FuseGridLds {
-    int hist[kFuseCells];     // keypoints per cell
-    int cursor[kFuseCells];   // next free slot of a cell while scattering
+    int hist[kGridCells];     // keypoints per cell
+    int cursor[kGridCells];   // next free slot of a cell while scattering
     int scan[kFuseGridThreads / 64 + 1];
 };
 
@@ -93,11 +97,11 @@ __global__ __launch_bounds__(kFuseGridThreads) void k_fuse_grid(const FuseKf* __
     const int tid = threadIdx.x, b = blockIdx.x;
     const FuseKf f = kfs[b];
     const orbhip_kp* kp = kps + f.base;
-    for (int c = tid; c < kFuseCells; c += kFuseGridThreads) L.hist[c] = 0;
+    for (int c = tid; c < kGridCells; c += kFuseGridThreads) L.hist[c] = 0;
     if (tid == 0) nfused[b] = 0;
     __syncthreads();
     for (int i = tid; i < f.n; i += kFuseGridThreads) {
-        const int c = fuse_cell(f, kp[i].x, kp[i].y);
+        const int c = grid_cell(f.minx, f.miny, f.invw, f.invh, kp[i].x, kp[i].y);
         if (c >= 0) atomicAdd(&L.hist[c], 1);
     }
     __syncthreads();
@@ -106,7 +110,7 @@ __global__ __launch_bounds__(kFuseGridThreads) void k_fuse_grid(const FuseKf* __
     for (int k = 0; k < kFuseBinsPerThread; k++) { h[k] = L.hist[tid * kFuseBinsPerThread + k]; sum += h[k]; }
     int total;
     int pos = block_excl_scan(sum, L.scan, &total);
-    int32_t* cs = cell_start + (int64_t)b * (kFuseCells + 1);
+    int32_t* cs = cell_start + (int64_t)b * (kGridCells + 1);
 #pragma unroll
     for (int k = 0; k < kFuseBinsPerThread; k++) {
         const int c = tid * kFuseBinsPerThread + k;
@@ -114,14 +118,14 @@ __global__ __launch_bounds__(kFuseGridThreads) void k_fuse_grid(const FuseKf* __
         cs[c] = pos;
         pos += h[k];
     }
-    if (tid == 0) cs[kFuseCells] = total;
+    if (tid == 0) cs[kGridCells] = total;
     __syncthreads();
     // the slot inside a cell is the order in which the LDS counter is reached: any order serves,
     // k_fuse_search's key minimum does not depend on it
     FuseRec* out = recs + f.base;
     for (int i = tid; i < f.n; i += kFuseGridThreads) {
         const orbhip_kp k = kp[i];
-        const int c = fuse_cell(f, k.x, k.y);
+        const int c = grid_cell(f.minx, f.miny, f.invw, f.invh, k.x, k.y);
         if (c >= 0) out[atomicAdd(&L.cursor[c], 1)] = FuseRec{k.x, k.y, (c << 8) | k.octave, i};
     }
 }
@@ -135,14 +139,14 @@ constexpr int kFuseSplit = 4;
 // Steps 1-8 of the rule for one (keyframe, point) that is not skipped: false at a gate. lvl is set
 // from step 6 on (-1 before it), so a pair rejected by GetFeaturesInArea's early returns keeps it.
 struct FuseWin { float u, v, r; int lvl, x0, x1, y0, y1; };
-__device__ __forceinline__ bool fuse_gates(const FuseKf& f, const FusePoints& mp, int m,
+__device__ __forceinline__ bool fuse_gates(const FuseKf& f, const DevPoints& mp, int m,
                                            const float* __restrict__ scale_factors, int n_levels, float log_sf,
                                            float th, FuseWin& w) {
     w.lvl = -1;
     const float P[3] = {mp.pts[3 * m], mp.pts[3 * m + 1], mp.pts[3 * m + 2]};
     // 1. Sophus SE3f * p
     float Pc[3];
-    fuse_qrot_dev(f.q, P, Pc);
+    quat_rotate(f.q, P, Pc);
     Pc[0] += f.t[0]; Pc[1] += f.t[1]; Pc[2] += f.t[2];
     if (Pc[2] < 0.0f) return false;
     // 2., 3. Pinhole::project, KeyFrame::IsInImage (the maximum is strict)
@@ -165,21 +169,19 @@ __device__ __forceinline__ bool fuse_gates(const FuseKf& f, const FusePoints& mp
     w.u = u; w.v = v; w.r = r;
     // 8. KeyFrame::GetFeaturesInArea: the cell rectangle with its early returns
     w.x0 = max(0, (int)floorf((u - f.minx - r) * f.invw));
-    if (w.x0 >= kFuseCols) return false;
-    w.x1 = min(kFuseCols - 1, (int)ceilf((u - f.minx + r) * f.invw));
+    if (w.x0 >= kGridCols) return false;
+    w.x1 = min(kGridCols - 1, (int)ceilf((u - f.minx + r) * f.invw));
     if (w.x1 < 0) return false;
     w.y0 = max(0, (int)floorf((v - f.miny - r) * f.invh));
-    if (w.y0 >= kFuseRows) return false;
-    w.y1 = min(kFuseRows - 1, (int)ceilf((v - f.miny + r) * f.invh));
+    if (w.y0 >= kGridRows) return false;
+    w.y1 = min(kGridRows - 1, (int)ceilf((v - f.miny + r) * f.invh));
     if (w.y1 < 0) return false;
     return true;
 }
 
 __device__ __forceinline__ unsigned fuse_hamming(const uint4& da, const uint4& db, const uint8_t* __restrict__ d) {
     const uint4* d2 = (const uint4*)d;
-    const uint4 ea = d2[0], eb = d2[1];
-    return __popc(da.x ^ ea.x) + __popc(da.y ^ ea.y) + __popc(da.z ^ ea.z) + __popc(da.w ^ ea.w) +
-           __popc(db.x ^ eb.x) + __popc(db.y ^ eb.y) + __popc(db.z ^ eb.z) + __popc(db.w ^ eb.w);
+    return hamming256(da, db, d2[0], d2[1]);
 }
 __device__ __forceinline__ unsigned long long fuse_key(unsigned dist, const FuseRec& k) {
     return ((unsigned long long)dist << 32) | ((unsigned long long)(k.cell_oct >> 8) << 16) | (unsigned)k.idx;
@@ -189,7 +191,7 @@ __device__ __forceinline__ unsigned long long fuse_key(unsigned dist, const Fuse
 // same exits), they take the candidates of a column span in turns and merge their minima.
 // CHI2 = false: the rule of Fuse with a Sim3, which has no chi-square gate (inv_level_sigma2 unread)
 template <int S, bool CHI2>
-__global__ __launch_bounds__(kFuseThreads) void k_fuse_search(const FuseKf* __restrict__ kfs, FusePoints mp,
+__global__ __launch_bounds__(kFuseThreads) void k_fuse_search(const FuseKf* __restrict__ kfs, DevPoints mp,
                                                               const uint8_t* __restrict__ pair_skip,
                                                               const float* __restrict__ scale_factors,
                                                               const float* __restrict__ inv_level_sigma2,
@@ -221,12 +223,12 @@ __global__ __launch_bounds__(kFuseThreads) void k_fuse_search(const FuseKf* __re
         const int lvl = w.lvl;
         const uint4* dm = (const uint4*)(mp.desc + (int64_t)m * 32);
         const uint4 da = dm[0], db = dm[1];
-        const int32_t* cs = cell_start + (int64_t)b * (kFuseCells + 1);
+        const int32_t* cs = cell_start + (int64_t)b * (kGridCells + 1);
         const FuseRec* rc = recs + f.base;
         const uint8_t* kd = kf_desc + (int64_t)f.base * 32;
         for (int ix = w.x0; ix <= w.x1; ix++) {
             // the cells (ix, y0..y1) are neighbours in the cell-ordered array: one span per column
-            const int j0 = cs[ix * kFuseRows + w.y0], j1 = cs[ix * kFuseRows + w.y1 + 1];
+            const int j0 = cs[ix * kGridRows + w.y0], j1 = cs[ix * kGridRows + w.y1 + 1];
             for (int j = j0 + sub; j < j1; j += S) {
                 const FuseRec k = rc[j];
                 const float dx = k.x - u, dy = k.y - v;
@@ -290,7 +292,7 @@ __device__ __forceinline__ unsigned long long sim3_candidate(const FuseRec& k, f
 // point's list[m] (ascending, kSim3None behind the end), count[m] is the number of candidates met.
 // level[m] and win[m] are written for every point; match / match_dist are k_sim3_resolve's.
 template <int S>
-__global__ __launch_bounds__(kFuseThreads) void k_sim3_search(const FuseKf* __restrict__ kfs, FusePoints mp,
+__global__ __launch_bounds__(kFuseThreads) void k_sim3_search(const FuseKf* __restrict__ kfs, DevPoints mp,
                                                               const uint8_t* __restrict__ claimed,
                                                               const float* __restrict__ scale_factors, int n_levels,
                                                               float log_sf, float th, float thr,
@@ -314,7 +316,7 @@ __global__ __launch_bounds__(kFuseThreads) void k_sim3_search(const FuseKf* __re
         const uint4* dm = (const uint4*)(mp.desc + (int64_t)m * 32);
         const uint4 da = dm[0], db = dm[1];
         for (int ix = w.x0; ix <= w.x1; ix++) {
-            const int j0 = cell_start[ix * kFuseRows + w.y0], j1 = cell_start[ix * kFuseRows + w.y1 + 1];
+            const int j0 = cell_start[ix * kGridRows + w.y0], j1 = cell_start[ix * kGridRows + w.y1 + 1];
             for (int j = j0 + sub; j < j1; j += S) {
                 unsigned long long key = sim3_candidate(recs[j], w.u, w.v, w.r, w.lvl, claimed, da, db, kf_desc, thr);
                 if (key == kSim3None) continue;
@@ -368,7 +370,7 @@ __device__ __forceinline__ int sim3_owner(const int32_t* owner, int idx) {
 // The first entry of L[m] whose keypoint no earlier point holds (owner >= m): from the stored keys,
 // and, when all of them are held and the list is longer than what is stored, from a walk of the
 // window for the least key above the last stored one.
-__device__ unsigned long long sim3_eval(int m, const FusePoints& mp, const uint8_t* __restrict__ claimed,
+__device__ unsigned long long sim3_eval(int m, const DevPoints& mp, const uint8_t* __restrict__ claimed,
                                         float thr, const int32_t* __restrict__ cell_start,
                                         const FuseRec* __restrict__ recs, const uint8_t* __restrict__ kf_desc,
                                         const Sim3Work& wk) {
@@ -387,7 +389,7 @@ __device__ unsigned long long sim3_eval(int m, const FusePoints& mp, const uint8
     const uint4 da = dm[0], db = dm[1];
     unsigned long long best = kSim3None;
     for (int ix = x0; ix <= x1; ix++) {
-        const int j0 = cell_start[ix * kFuseRows + y0], j1 = cell_start[ix * kFuseRows + y1 + 1];
+        const int j0 = cell_start[ix * kGridRows + y0], j1 = cell_start[ix * kGridRows + y1 + 1];
         for (int j = j0; j < j1; j++) {
             const unsigned long long key = sim3_candidate(recs[j], w.u, w.v, w.r, w.lvl, claimed, da, db, kf_desc, thr);
             if (key == kSim3None || key <= last || key >= best) continue;
@@ -407,7 +409,7 @@ constexpr int kSim3NoOwner = 0x7FFFFFFF;
 // is the sequential result and it comes within (points with a list) + 1 rounds: the loop's bound.
 // owner[idx] = the lowest point whose pick is idx, rebuilt between rounds (only the entries the old
 // picks set are cleared).
-__global__ __launch_bounds__(kSim3ResolveThreads) void k_sim3_resolve(FusePoints mp,
+__global__ __launch_bounds__(kSim3ResolveThreads) void k_sim3_resolve(DevPoints mp,
                                                                        const uint8_t* __restrict__ claimed, float thr,
                                                                        int nk, const int32_t* __restrict__ cell_start,
                                                                        const FuseRec* __restrict__ recs,
@@ -468,10 +470,14 @@ __global__ __launch_bounds__(kSim3ResolveThreads) void k_sim3_resolve(FusePoints
     if (tid == 0) nmatches[0] = s_matched;
 }
 
-void launch_sim3_search(const FuseKf* kf, const FusePoints& mp, const uint8_t* claimed, const float* scale_factors,
-                        int n_levels, float log_sf, float th, float thr, const orbhip_kp* kps, const uint8_t* kf_desc,
-                        int nk, int32_t* cell_start, FuseRec* recs, const Sim3Work& w, int32_t* match,
-                        int32_t* match_dist, int32_t* level, int32_t* nmatches, hipStream_t st) {
+// ---- host ----
+// match / match_dist / level: n, nmatches: 1. cell_start: 3073 + recs: nk (written by k_fuse_grid,
+// which also zeroes nmatches)
+static void launch_sim3_search(const FuseKf* kf, const DevPoints& mp, const uint8_t* claimed,
+                               const float* scale_factors, int n_levels, float log_sf, float th, float thr,
+                               const orbhip_kp* kps, const uint8_t* kf_desc, int nk, int32_t* cell_start,
+                               FuseRec* recs, const Sim3Work& w, int32_t* match, int32_t* match_dist, int32_t* level,
+                               int32_t* nmatches, hipStream_t st) {
     ORBHIP_LAUNCH(k_fuse_grid, dim3(1), dim3(kFuseGridThreads), 0, st, kf, kps, cell_start, recs, nmatches);
     const unsigned tiles = (unsigned)(((int64_t)mp.n * kFuseSplit + kFuseThreads - 1) / kFuseThreads);
     ORBHIP_LAUNCH(k_sim3_search<kFuseSplit>, dim3(tiles), dim3(kFuseThreads), 0, st, kf, mp, claimed, scale_factors,
@@ -480,10 +486,13 @@ void launch_sim3_search(const FuseKf* kf, const FusePoints& mp, const uint8_t* c
                   (const int32_t*)cell_start, (const FuseRec*)recs, kf_desc, w, match, match_dist, nmatches);
 }
 
-void launch_fuse(const FuseKf* kfs, int B, const FusePoints& mp, const uint8_t* pair_skip, const float* scale_factors,
-                 const float* inv_level_sigma2, int n_levels, float log_sf, float th, const orbhip_kp* kps,
-                 const uint8_t* kf_desc, int32_t* cell_start, FuseRec* recs, int32_t* best_idx, int32_t* best_dist,
-                 int32_t* level, int32_t* nfused, hipStream_t st) {
+// cell_start: B x 3073, recs: one per keypoint of the call (both written by k_fuse_grid);
+// best_idx / best_dist / level: B x n, nfused: B (zeroed by k_fuse_grid).
+// inv_level_sigma2 == nullptr: the rule without the chi-square gate (Fuse with a Sim3)
+static void launch_fuse(const FuseKf* kfs, int B, const DevPoints& mp, const uint8_t* pair_skip,
+                        const float* scale_factors, const float* inv_level_sigma2, int n_levels, float log_sf,
+                        float th, const orbhip_kp* kps, const uint8_t* kf_desc, int32_t* cell_start, FuseRec* recs,
+                        int32_t* best_idx, int32_t* best_dist, int32_t* level, int32_t* nfused, hipStream_t st) {
     ORBHIP_LAUNCH(k_fuse_grid, dim3((unsigned)B), dim3(kFuseGridThreads), 0, st, kfs, kps, cell_start, recs, nfused);
     const unsigned tiles = (unsigned)(((int64_t)mp.n * kFuseSplit + kFuseThreads - 1) / kFuseThreads);
     if (inv_level_sigma2)
@@ -494,6 +503,164 @@ void launch_fuse(const FuseKf* kfs, int B, const FusePoints& mp, const uint8_t* 
         ORBHIP_LAUNCH((k_fuse_search<kFuseSplit, false>), dim3(tiles, (unsigned)B), dim3(kFuseThreads), 0, st, kfs, mp,
                       pair_skip, scale_factors, inv_level_sigma2, n_levels, log_sf, th, (const int32_t*)cell_start,
                       (const FuseRec*)recs, kf_desc, best_idx, best_dist, level, nfused);
+}
+
+// The envelope and argument checks Fuse and the Sim3 searches share: the keyframes of a call have one
+// scale pyramid, at most 65535 keypoints each and octaves inside it. nk_total: their keypoints.
+static int fuse_check_keyframes(const orbhip_frame* kfs, int B, size_t* nk_total) {
+    const int L = kfs[0].n_levels;
+    if (L <= 0 || !kfs[0].scale_factors) return ORBHIP_ERR_ARG;
+    if (L > kFuseMaxLevels) return ORBHIP_ERR_UNSUPPORTED;
+    *nk_total = 0;
+    for (int b = 0; b < B; b++) {
+        const orbhip_frame& f = kfs[b];
+        if (f.n < 0) return ORBHIP_ERR_ARG;
+        if (f.n > 65535) return ORBHIP_ERR_UNSUPPORTED;
+        if (f.n && (!f.kps || !f.desc)) return ORBHIP_ERR_ARG;
+        // one scale pyramid per call
+        if (f.n_levels != L || !f.scale_factors || f.log_scale_factor != kfs[0].log_scale_factor) return ORBHIP_ERR_ARG;
+        if (std::memcmp(f.scale_factors, kfs[0].scale_factors, (size_t)L * 4) != 0) return ORBHIP_ERR_ARG;
+        for (int i = 0; i < f.n; i++)
+            if (f.kps[i].octave < 0 || f.kps[i].octave >= L) return ORBHIP_ERR_ARG;
+        *nk_total += (size_t)f.n;
+    }
+    return ORBHIP_OK;
+}
+
+int fuse_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_frame* kfs, int B,
+                const orbhip_local_points* mps, const uint8_t* pair_skip, bool chi2, const float* inv_level_sigma2,
+                float th, int32_t* best_idx, int32_t* best_dist, int32_t* level, int32_t* nfused) {
+    if (B < 0 || !mps || mps->n < 0) return ORBHIP_ERR_ARG;
+    if (B == 0) return 0;
+    if (B > kFuseMaxKf || mps->n > kFuseMaxPoints) return ORBHIP_ERR_UNSUPPORTED;
+    if (!kfs || !nfused) return ORBHIP_ERR_ARG;
+    const int n = mps->n, L = kfs[0].n_levels;
+    if (chi2 && !inv_level_sigma2) return ORBHIP_ERR_ARG;
+    size_t nk_total = 0;
+    if (const int rc = fuse_check_keyframes(kfs, B, &nk_total)) return rc;
+    for (int b = 0; b < B; b++) nfused[b] = 0;
+    if (n == 0) return 0;
+    if (!best_idx || !mps->points || !mps->normals || !mps->min_dist || !mps->max_dist || !mps->desc)
+        return ORBHIP_ERR_ARG;
+    // one block, the same layout on the host (pinned) and the device:
+    // [keyframes B | scale factors | inv sigma2 | points normals min max desc skip | pair_skip B x n |
+    //  keypoints | keyframe descriptors], then device only [cell_start B x 3073 | records |
+    //  nfused B, best_idx B x n, best_dist B x n, level B x n]; the last segment is read back
+    StageLayout lay(16);
+    const size_t bn = (size_t)B * (size_t)n;
+    const size_t o_kf = lay.take((size_t)B * sizeof(FuseKf));
+    const size_t o_sf = lay.take((size_t)L * 4), o_s2 = lay.take(chi2 ? (size_t)L * 4 : 0);
+    const PointsLayout o_mp(lay, (size_t)n);
+    const size_t o_pskip = lay.take(pair_skip ? bn : 0);
+    const size_t o_kps = lay.take(nk_total * sizeof(orbhip_kp)), o_kdesc = lay.take(nk_total * 32);
+    const size_t up_bytes = lay.total();
+    const size_t o_cs = lay.take((size_t)B * (kGridCells + 1) * 4), o_rec = lay.take(nk_total * sizeof(FuseRec));
+    const size_t nf_bytes = ((size_t)B * 4 + 15) & ~size_t(15);   // best_idx starts 16-byte aligned behind nfused
+    const size_t n_out = level ? 3 : (best_dist ? 2 : 1);         // arrays read back: a prefix of idx, dist, level
+    const size_t back_bytes = nf_bytes + n_out * bn * 4;
+    const size_t o_back = lay.take(nf_bytes + 3 * bn * 4);
+    HIPOK(S.ensure(lay.total(), up_bytes + back_bytes + 16));
+    uint8_t* const d = S.d;
+    uint8_t* const h = S.h;
+    FuseKf* hk = (FuseKf*)(h + o_kf);
+    size_t base = 0;
+    for (int b = 0; b < B; b++) {
+        const orbhip_frame& f = kfs[b];
+        fuse_kf_params(f, (int)base, &hk[b]);
+        put_keyframe(S, o_kps, o_kdesc, base, f.kps, f.desc, (size_t)f.n);
+        base += (size_t)f.n;
+    }
+    S.put(o_sf, kfs[0].scale_factors, (size_t)L * 4);
+    if (chi2) S.put(o_s2, inv_level_sigma2, (size_t)L * 4);
+    const DevPoints mp = o_mp.put(S, *mps, true);   // the kernels read skip unconditionally
+    if (pair_skip) S.put(o_pskip, pair_skip, bn);
+    HIPOK(hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
+    (void)hipGetLastError();
+    int32_t* const d_nf = (int32_t*)(d + o_back);
+    int32_t* const d_idx = (int32_t*)(d + o_back + nf_bytes);
+    {
+        const StageScope scope(timer);
+        timer.begin(8, st);
+        launch_fuse((const FuseKf*)(d + o_kf), B, mp, pair_skip ? d + o_pskip : nullptr, (const float*)(d + o_sf),
+                    chi2 ? (const float*)(d + o_s2) : nullptr, L, kfs[0].log_scale_factor, th,
+                    (const orbhip_kp*)(d + o_kps), d + o_kdesc,
+                    (int32_t*)(d + o_cs), (FuseRec*)(d + o_rec), d_idx, d_idx + bn, d_idx + 2 * bn, d_nf, st);
+        timer.end(8, st);
+    }
+    HIPOK(hipGetLastError());
+    uint8_t* const hb = h + up_bytes;   // the read-back lies behind the upload in the pinned image
+    HIPOK(hipMemcpyAsync(hb, d + o_back, back_bytes, hipMemcpyDeviceToHost, st));
+    HIPOK(hipStreamSynchronize(st));
+    std::memcpy(nfused, hb, (size_t)B * 4);
+    std::memcpy(best_idx, hb + nf_bytes, bn * 4);
+    if (best_dist) std::memcpy(best_dist, hb + nf_bytes + bn * 4, bn * 4);
+    if (level) std::memcpy(level, hb + nf_bytes + 2 * bn * 4, bn * 4);
+    int total = 0;
+    for (int b = 0; b < B; b++) total += nfused[b];
+    return total;
+}
+
+int sim3_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_frame* kf,
+                const orbhip_local_points* mps, float th, float ratio_hamming, int32_t* match, int32_t* match_dist,
+                int32_t* level) {
+    if (!kf || !mps || mps->n < 0) return ORBHIP_ERR_ARG;
+    if (!(ratio_hamming > 0.0f) || !std::isfinite(ratio_hamming)) return ORBHIP_ERR_ARG;
+    if (mps->n > kFuseMaxPoints) return ORBHIP_ERR_UNSUPPORTED;
+    size_t nk = 0;
+    if (const int rc = fuse_check_keyframes(kf, 1, &nk)) return rc;
+    const int n = mps->n, L = kf->n_levels;
+    if (n == 0) return 0;
+    if (!match || !mps->points || !mps->normals || !mps->min_dist || !mps->max_dist || !mps->desc) return ORBHIP_ERR_ARG;
+    const float thr = 50.0f * ratio_hamming;
+    // one block, the same layout on the host (pinned) and the device:
+    // [keyframe | scale factors | points normals min max desc skip | claimed | keypoints | descriptors],
+    // then device only [cell_start 3073 | records | windows n | lists n x 8 | counts n | picks 2 x n |
+    //  owners | nmatches, match n, match_dist n, level n]; the last segment is read back
+    StageLayout lay(16);
+    const size_t o_kf = lay.take(sizeof(FuseKf)), o_sf = lay.take((size_t)L * 4);
+    const PointsLayout o_mp(lay, (size_t)n);
+    const size_t o_claimed = lay.take(nk), o_kps = lay.take(nk * sizeof(orbhip_kp)), o_kdesc = lay.take(nk * 32);
+    const size_t up_bytes = lay.total();
+    const size_t o_cs = lay.take((size_t)(kGridCells + 1) * 4), o_rec = lay.take(nk * sizeof(FuseRec));
+    const size_t o_win = lay.take((size_t)n * sizeof(Sim3Win)), o_list = lay.take((size_t)n * kSim3ListCap * 8);
+    const size_t o_cnt = lay.take((size_t)n * 4), o_pick = lay.take((size_t)n * 8), o_pnew = lay.take((size_t)n * 8);
+    const size_t o_own = lay.take(nk * 4);
+    const size_t n_out = level ? 3 : (match_dist ? 2 : 1);   // arrays read back: a prefix of match, dist, level
+    const size_t back_bytes = 16 + n_out * (size_t)n * 4;     // match starts 16-byte aligned behind nmatches
+    const size_t o_back = lay.take(16 + 3 * (size_t)n * 4);
+    HIPOK(S.ensure(lay.total(), up_bytes + back_bytes + 16));
+    uint8_t* const d = S.d;
+    uint8_t* const h = S.h;
+    fuse_kf_params(*kf, 0, (FuseKf*)(h + o_kf));
+    S.put(o_sf, kf->scale_factors, (size_t)L * 4);
+    const DevPoints mp = o_mp.put(S, *mps, true);   // the kernels read skip unconditionally
+    S.put_or_zero(o_claimed, kf->claimed, nk);
+    put_keyframe(S, o_kps, o_kdesc, 0, kf->kps, kf->desc, nk);
+    HIPOK(hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
+    (void)hipGetLastError();
+    int32_t* const d_nm = (int32_t*)(d + o_back);
+    int32_t* const d_match = (int32_t*)(d + o_back + 16);
+    {
+        const StageScope scope(timer);
+        timer.begin(9, st);
+        const Sim3Work w{(Sim3Win*)(d + o_win), (unsigned long long*)(d + o_list), (int32_t*)(d + o_cnt),
+                         (unsigned long long*)(d + o_pick), (unsigned long long*)(d + o_pnew), (int32_t*)(d + o_own)};
+        launch_sim3_search((const FuseKf*)(d + o_kf), mp, d + o_claimed, (const float*)(d + o_sf), L,
+                           kf->log_scale_factor, th, thr, (const orbhip_kp*)(d + o_kps), d + o_kdesc, (int)nk,
+                           (int32_t*)(d + o_cs), (FuseRec*)(d + o_rec), w, d_match, d_match + n, d_match + 2 * (size_t)n,
+                           d_nm, st);
+        timer.end(9, st);
+    }
+    HIPOK(hipGetLastError());
+    uint8_t* const hb = h + up_bytes;   // the read-back lies behind the upload in the pinned image
+    HIPOK(hipMemcpyAsync(hb, d + o_back, back_bytes, hipMemcpyDeviceToHost, st));
+    HIPOK(hipStreamSynchronize(st));
+    std::memcpy(match, hb + 16, (size_t)n * 4);
+    if (match_dist) std::memcpy(match_dist, hb + 16 + (size_t)n * 4, (size_t)n * 4);
+    if (level) std::memcpy(level, hb + 16 + 2 * (size_t)n * 4, (size_t)n * 4);
+    int32_t nm;
+    std::memcpy(&nm, hb, 4);
+    return nm;
 }
 
 }  // namespace orbhip

@@ -16,6 +16,7 @@
 #include <algorithm>
 #include <cstdlib>
 
+#include "geom.h"
 #include "orbhip_device.h"
 #include "orbhip_kernels.h"
 
@@ -97,8 +98,7 @@ __global__ __launch_bounds__(256) void k_match_top2(MatchView v, uint2* __restri
     const int w0 = wid * (TC / 4), w1 = min(tn, w0 + TC / 4);
     for (int t = w0; t < w1; t++) {
         const uint4 x = tile[2 * t], y = tile[2 * t + 1];
-        const int d = __popc(x.x ^ qa.x) + __popc(x.y ^ qa.y) + __popc(x.z ^ qa.z) + __popc(x.w ^ qa.w) +
-                      __popc(y.x ^ qb.x) + __popc(y.y ^ qb.y) + __popc(y.z ^ qb.z) + __popc(y.w ^ qb.w);
+        const int d = hamming256(x, y, qa, qb);
         if (d < b) { s = b; b = d; bi = t0 + t; }
         else if (d < s) s = d;
     }
@@ -348,8 +348,7 @@ __global__ __launch_bounds__(1024) void k_match_fused(MatchView v, int th_low, f
         __syncthreads();
         for (int t = slice; t < tn; t += 64) {
             const uint4 x = tile[2 * t], y = tile[2 * t + 1];
-            const int d = __popc(x.x ^ qa.x) + __popc(x.y ^ qa.y) + __popc(x.z ^ qa.z) + __popc(x.w ^ qa.w) +
-                          __popc(y.x ^ qb.x) + __popc(y.y ^ qb.y) + __popc(y.z ^ qb.z) + __popc(y.w ^ qb.w);
+            const int d = hamming256(x, y, qa, qb);
             if (d < b) { s = b; b = d; bi = c0 + t; }
             else if (d < s) s = d;
         }

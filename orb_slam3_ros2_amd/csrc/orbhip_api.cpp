@@ -34,18 +34,11 @@
 #include "orbhip_kernels.h"
 #include "orbhip_plan.h"
 #include "graph_cache.h"
+#include "stage.h"
 
 using namespace orbhip;
 
-#define HIPOK(x)                                                                                   \
-    do {                                                                                           \
-        hipError_t e_ = (x);                                                                       \
-        if (e_ != hipSuccess) {                                                                    \
-            std::fprintf(stderr, "orbhip: %s failed: %s (%s:%d)\n", #x, hipGetErrorString(e_),     \
-                         __FILE__, __LINE__);                                                      \
-            return ORBHIP_ERR_DEVICE;                                                              \
-        }                                                                                          \
-    } while (0)
+#define HIPOK(x) ORBHIP_HIPOK("", x)
 
 namespace {
 
@@ -64,19 +57,6 @@ struct DevBuf {
         if (p) { (void)hipFree(p); p = nullptr; n = 0; }
         hipError_t e = hipMalloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T));
         if (e == hipSuccess) n = count;
-        return e;
-    }
-};
-
-struct PinBuf {   // pinned host staging, grown on demand
-    uint8_t* p = nullptr;
-    size_t n = 0;
-    ~PinBuf() { if (p) (void)hipHostFree(p); }
-    hipError_t ensure(size_t bytes) {
-        if (bytes <= n && p) return hipSuccess;
-        if (p) { (void)hipHostFree(p); p = nullptr; n = 0; }
-        hipError_t e = hipHostMalloc((void**)&p, std::max<size_t>(bytes, 1), hipHostMallocDefault);
-        if (e == hipSuccess) n = bytes;
         return e;
     }
 };
@@ -170,10 +150,8 @@ struct orbhip_ctx {
     DevBuf<int> d_msync;        // one-launch matcher counters (zeroed once, reset by every launch)
     DevBuf<double> d_bw;        // bag-of-words weights (host transform)
     DevBuf<uint8_t> d_bow_stage;   // SearchByBoW host-call staging
-    DevBuf<uint8_t> d_tri_stage;   // SearchForTriangulation: the call's device block
-    PinBuf h_tri_stage;            // its pinned image (upload) and the read-back
-    DevBuf<uint8_t> d_fuse_stage;  // Fuse: the call's device block
-    PinBuf h_fuse_stage;           // its pinned image (upload) and the read-back
+    StageBlock tri_stage{false};    // SearchForTriangulation's block (stage.h)
+    StageBlock fuse_stage{false};   // Fuse's, Fuse with a Sim3's and the Sim3 projection search's
     DevBuf<LevelKp> d_lvl_kp;
     DevBuf<orbhip_kp> d_kps;
     DevBuf<uint8_t> d_desc;
@@ -1544,305 +1522,40 @@ int orbhip_triangulation_geometry(const orbhip_tri_keyframe* kf1, const orbhip_t
     return ORBHIP_OK;
 }
 
-static int tri_check_side(const orbhip_tri_keyframe& k, int n_levels) {
-    if (k.n < 0) return ORBHIP_ERR_ARG;
-    if (k.n > kTriMax) return ORBHIP_ERR_UNSUPPORTED;
-    if (k.n == 0) return ORBHIP_OK;
-    if (!k.kps || !k.desc || !k.node || !k.weight || !k.has_mp) return ORBHIP_ERR_ARG;
-    for (int i = 0; i < k.n; i++)
-        if (k.kps[i].octave < 0 || k.kps[i].octave >= n_levels) return ORBHIP_ERR_ARG;
-    return ORBHIP_OK;
-}
-
 int orbhip_search_for_triangulation(orbhip_ctx* c, const orbhip_tri_keyframe* kf1, const orbhip_tri_keyframe* nbrs,
                                     int B, const float* scale_factors, const float* level_sigma2, int n_levels,
                                     int check_orientation, int32_t* match12, int32_t* nmatches) {
-    if (!c || !kf1 || B < 0) return ORBHIP_ERR_ARG;
-    if (B == 0) return 0;
-    if (B > kTriMaxPairs) return ORBHIP_ERR_UNSUPPORTED;
-    if (!nbrs || !nmatches || !scale_factors || !level_sigma2 || n_levels <= 0) return ORBHIP_ERR_ARG;
-    int rc = tri_check_side(*kf1, n_levels);
-    for (int b = 0; b < B && rc == ORBHIP_OK; b++) rc = tri_check_side(nbrs[b], n_levels);
-    if (rc != ORBHIP_OK) return rc;
-    const int n1 = kf1->n;
-    for (int b = 0; b < B; b++) nmatches[b] = 0;
-    if (n1 == 0) return 0;
-    if (!match12) return ORBHIP_ERR_ARG;
+    if (!c) return ORBHIP_ERR_ARG;
     HIPOK(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    // one block, the same layout on the host (pinned) and the device:
-    // [sides (1 + B) | geometry B | scale factors | sigma2 | per keyframe: kps desc node weight has_mp]
-    // then device only [KF1 keys | m1 | match12 B x n1 | nmatches B]; the last two are read back
-    size_t off = 0;
-    auto take = [&](size_t bytes) { off = (off + 15) & ~size_t(15); const size_t o = off; off += bytes; return o; };
-    const size_t o_sides = take((size_t)(1 + B) * sizeof(TriSide));
-    const size_t o_geom = take((size_t)B * sizeof(TriGeom));
-    const size_t o_sf = take((size_t)n_levels * 4), o_s2 = take((size_t)n_levels * 4);
-    struct SideOff { size_t kps, desc, node, weight, mp; };
-    std::vector<SideOff> so(1 + B);
-    for (int s = 0; s <= B; s++) {
-        const size_t n = (size_t)(s ? nbrs[s - 1].n : n1);
-        so[s] = {take(n * sizeof(orbhip_kp)), take(n * 32), take(n * 4), take(n * 8), take(n)};
-    }
-    const size_t up_bytes = take(0);
-    const size_t o_keys = take((size_t)kTriMax * 8), o_m1 = take(4);
-    const size_t o_match = take((size_t)B * n1 * 4);
-    const size_t back_bytes = (size_t)B * n1 * 4 + (size_t)B * 4;   // nmatches directly behind match12
-    off = o_match + back_bytes;
-    const size_t dev_bytes = take(0);
-    HIPOK(c->d_tri_stage.ensure(dev_bytes));
-    HIPOK(c->h_tri_stage.ensure(up_bytes + back_bytes + 16));
-    uint8_t* const d = c->d_tri_stage.p;
-    uint8_t* const h = c->h_tri_stage.p;
-    TriSide* sides = (TriSide*)(h + o_sides);
-    TriGeom* geom = (TriGeom*)(h + o_geom);
-    for (int s = 0; s <= B; s++) {
-        const orbhip_tri_keyframe& k = s ? nbrs[s - 1] : *kf1;
-        const size_t n = (size_t)k.n;
-        sides[s] = {(const orbhip_kp*)(d + so[s].kps), d + so[s].desc, (const int32_t*)(d + so[s].node),
-                    (const double*)(d + so[s].weight), d + so[s].mp, k.n, 0};
-        if (n) {
-            std::memcpy(h + so[s].kps, k.kps, n * sizeof(orbhip_kp));
-            std::memcpy(h + so[s].desc, k.desc, n * 32);
-            std::memcpy(h + so[s].node, k.node, n * 4);
-            std::memcpy(h + so[s].weight, k.weight, n * 8);
-            std::memcpy(h + so[s].mp, k.has_mp, n);
-        }
-        if (s) {
-            geom[s - 1].pad = 0.f;
-            tri_geometry(*kf1, k, geom[s - 1].F, geom[s - 1].ep);
-        }
-    }
-    std::memcpy(h + o_sf, scale_factors, (size_t)n_levels * 4);
-    std::memcpy(h + o_s2, level_sigma2, (size_t)n_levels * 4);
-    HIPOK(hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
-    (void)hipGetLastError();
-    {
-        const StageScope scope(c->timer);
-        c->timer.begin(7, st);
-        launch_tri_search((const TriSide*)(d + o_sides), (const TriGeom*)(d + o_geom), n1, B, (const float*)(d + o_sf),
-                          (const float*)(d + o_s2), (unsigned long long*)(d + o_keys), (int32_t*)(d + o_m1),
-                          check_orientation, (int32_t*)(d + o_match), (int32_t*)(d + o_match + (size_t)B * n1 * 4), st);
-        c->timer.end(7, st);
-    }
-    HIPOK(hipGetLastError());
-    uint8_t* const hb = h + ((up_bytes + 15) & ~size_t(15));
-    HIPOK(hipMemcpyAsync(hb, d + o_match, back_bytes, hipMemcpyDeviceToHost, st));
-    HIPOK(hipStreamSynchronize(st));
-    std::memcpy(match12, hb, (size_t)B * n1 * 4);
-    std::memcpy(nmatches, hb + (size_t)B * n1 * 4, (size_t)B * 4);
-    int total = 0;
-    for (int b = 0; b < B; b++) total += nmatches[b];
-    return total;
+    return tri_search(c->tri_stage, c->timer, c->stream, kf1, nbrs, B, scale_factors, level_sigma2, n_levels,
+                      check_orientation, match12, nmatches);
 }
 
 // ---- Fuse: B keyframes against one list of MapPoints ----
-// The envelope and argument checks Fuse and the Sim3 searches share: the keyframes of a call have one
-// scale pyramid, at most 65535 keypoints each and octaves inside it. nk_total: their keypoints.
-static int fuse_check_keyframes(const orbhip_frame* kfs, int B, size_t* nk_total) {
-    const int L = kfs[0].n_levels;
-    if (L <= 0 || !kfs[0].scale_factors) return ORBHIP_ERR_ARG;
-    if (L > kFuseMaxLevels) return ORBHIP_ERR_UNSUPPORTED;
-    *nk_total = 0;
-    for (int b = 0; b < B; b++) {
-        const orbhip_frame& f = kfs[b];
-        if (f.n < 0) return ORBHIP_ERR_ARG;
-        if (f.n > 65535) return ORBHIP_ERR_UNSUPPORTED;
-        if (f.n && (!f.kps || !f.desc)) return ORBHIP_ERR_ARG;
-        // one scale pyramid per call
-        if (f.n_levels != L || !f.scale_factors || f.log_scale_factor != kfs[0].log_scale_factor) return ORBHIP_ERR_ARG;
-        if (std::memcmp(f.scale_factors, kfs[0].scale_factors, (size_t)L * 4) != 0) return ORBHIP_ERR_ARG;
-        for (int i = 0; i < f.n; i++)
-            if (f.kps[i].octave < 0 || f.kps[i].octave >= L) return ORBHIP_ERR_ARG;
-        *nk_total += (size_t)f.n;
-    }
-    return ORBHIP_OK;
-}
-
-// chi2 = false: Fuse with a Sim3 (no chi-square gate, inv_level_sigma2 unused)
-static int fuse_call(orbhip_ctx* c, const orbhip_frame* kfs, int B, const orbhip_local_points* mps,
-                     const uint8_t* pair_skip, bool chi2, const float* inv_level_sigma2, float th, int32_t* best_idx,
-                     int32_t* best_dist, int32_t* level, int32_t* nfused) {
-    if (!c || B < 0 || !mps || mps->n < 0) return ORBHIP_ERR_ARG;
-    if (B == 0) return 0;
-    if (B > kFuseMaxKf || mps->n > kFuseMaxPoints) return ORBHIP_ERR_UNSUPPORTED;
-    if (!kfs || !nfused) return ORBHIP_ERR_ARG;
-    const int n = mps->n, L = kfs[0].n_levels;
-    if (chi2 && !inv_level_sigma2) return ORBHIP_ERR_ARG;
-    size_t nk_total = 0;
-    if (const int rc = fuse_check_keyframes(kfs, B, &nk_total)) return rc;
-    for (int b = 0; b < B; b++) nfused[b] = 0;
-    if (n == 0) return 0;
-    if (!best_idx || !mps->points || !mps->normals || !mps->min_dist || !mps->max_dist || !mps->desc)
-        return ORBHIP_ERR_ARG;
-    HIPOK(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    // one block, the same layout on the host (pinned) and the device:
-    // [keyframes B | scale factors | inv sigma2 | points normals min max desc skip | pair_skip B x n |
-    //  keypoints | keyframe descriptors], then device only [cell_start B x 3073 | records |
-    //  nfused B | best_idx B x n | best_dist B x n | level B x n]; the last four are read back
-    size_t off = 0;
-    auto take = [&](size_t bytes) { off = (off + 15) & ~size_t(15); const size_t o = off; off += bytes; return o; };
-    const size_t bn = (size_t)B * (size_t)n;
-    const size_t o_kf = take((size_t)B * sizeof(FuseKf));
-    const size_t o_sf = take((size_t)L * 4), o_s2 = take(chi2 ? (size_t)L * 4 : 0);
-    const size_t o_pts = take((size_t)n * 12), o_nrm = take((size_t)n * 12), o_min = take((size_t)n * 4);
-    const size_t o_max = take((size_t)n * 4), o_desc = take((size_t)n * 32), o_skip = take((size_t)n);
-    const size_t o_pskip = take(pair_skip ? bn : 0);
-    const size_t o_kps = take(nk_total * sizeof(orbhip_kp)), o_kdesc = take(nk_total * 32);
-    const size_t up_bytes = take(0);
-    const size_t o_cs = take((size_t)B * (kFuseCells + 1) * 4), o_rec = take(nk_total * sizeof(FuseRec));
-    const size_t o_back = take(0);
-    const size_t nf_bytes = ((size_t)B * 4 + 15) & ~size_t(15);   // best_idx starts 16-byte aligned behind nfused
-    const size_t n_out = level ? 3 : (best_dist ? 2 : 1);         // arrays read back: a prefix of idx, dist, level
-    const size_t back_bytes = nf_bytes + n_out * bn * 4;
-    off = o_back + nf_bytes + 3 * bn * 4;
-    const size_t dev_bytes = take(0);
-    HIPOK(c->d_fuse_stage.ensure(dev_bytes));
-    HIPOK(c->h_fuse_stage.ensure(up_bytes + back_bytes + 16));
-    uint8_t* const d = c->d_fuse_stage.p;
-    uint8_t* const h = c->h_fuse_stage.p;
-    FuseKf* hk = (FuseKf*)(h + o_kf);
-    size_t base = 0;
-    for (int b = 0; b < B; b++) {
-        const orbhip_frame& f = kfs[b];
-        fuse_kf_params(f, (int)base, &hk[b]);
-        if (f.n) {
-            std::memcpy(h + o_kps + base * sizeof(orbhip_kp), f.kps, (size_t)f.n * sizeof(orbhip_kp));
-            std::memcpy(h + o_kdesc + base * 32, f.desc, (size_t)f.n * 32);
-        }
-        base += (size_t)f.n;
-    }
-    std::memcpy(h + o_sf, kfs[0].scale_factors, (size_t)L * 4);
-    if (chi2) std::memcpy(h + o_s2, inv_level_sigma2, (size_t)L * 4);
-    std::memcpy(h + o_pts, mps->points, (size_t)n * 12);
-    std::memcpy(h + o_nrm, mps->normals, (size_t)n * 12);
-    std::memcpy(h + o_min, mps->min_dist, (size_t)n * 4);
-    std::memcpy(h + o_max, mps->max_dist, (size_t)n * 4);
-    std::memcpy(h + o_desc, mps->desc, (size_t)n * 32);
-    if (mps->skip) std::memcpy(h + o_skip, mps->skip, (size_t)n);
-    else std::memset(h + o_skip, 0, (size_t)n);
-    if (pair_skip) std::memcpy(h + o_pskip, pair_skip, bn);
-    HIPOK(hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
-    (void)hipGetLastError();
-    int32_t* const d_nf = (int32_t*)(d + o_back);
-    int32_t* const d_idx = (int32_t*)(d + o_back + nf_bytes);
-    {
-        const StageScope scope(c->timer);
-        c->timer.begin(8, st);
-        const FusePoints mp{n, (const float*)(d + o_pts), (const float*)(d + o_nrm), (const float*)(d + o_min),
-                            (const float*)(d + o_max), d + o_desc, d + o_skip};
-        launch_fuse((const FuseKf*)(d + o_kf), B, mp, pair_skip ? d + o_pskip : nullptr, (const float*)(d + o_sf),
-                    chi2 ? (const float*)(d + o_s2) : nullptr, L, kfs[0].log_scale_factor, th,
-                    (const orbhip_kp*)(d + o_kps), d + o_kdesc,
-                    (int32_t*)(d + o_cs), (FuseRec*)(d + o_rec), d_idx, d_idx + bn, d_idx + 2 * bn, d_nf, st);
-        c->timer.end(8, st);
-    }
-    HIPOK(hipGetLastError());
-    uint8_t* const hb = h + ((up_bytes + 15) & ~size_t(15));
-    HIPOK(hipMemcpyAsync(hb, d + o_back, back_bytes, hipMemcpyDeviceToHost, st));
-    HIPOK(hipStreamSynchronize(st));
-    std::memcpy(nfused, hb, (size_t)B * 4);
-    std::memcpy(best_idx, hb + nf_bytes, bn * 4);
-    if (best_dist) std::memcpy(best_dist, hb + nf_bytes + bn * 4, bn * 4);
-    if (level) std::memcpy(level, hb + nf_bytes + 2 * bn * 4, bn * 4);
-    int total = 0;
-    for (int b = 0; b < B; b++) total += nfused[b];
-    return total;
-}
-
 int orbhip_fuse(orbhip_ctx* c, const orbhip_frame* kfs, int B, const orbhip_local_points* mps,
                 const uint8_t* pair_skip, const float* inv_level_sigma2, float th, int32_t* best_idx,
                 int32_t* best_dist, int32_t* level, int32_t* nfused) {
-    return fuse_call(c, kfs, B, mps, pair_skip, true, inv_level_sigma2, th, best_idx, best_dist, level, nfused);
+    if (!c) return ORBHIP_ERR_ARG;
+    HIPOK(hipSetDevice(c->device));
+    return fuse_search(c->fuse_stage, c->timer, c->stream, kfs, B, mps, pair_skip, true, inv_level_sigma2, th,
+                       best_idx, best_dist, level, nfused);
 }
 
 // ---- LoopClosing: Fuse and SearchByProjection with a Sim3 (the pose arrives as Tcw = (R, t / s)) ----
 int orbhip_fuse_sim3(orbhip_ctx* c, const orbhip_frame* kfs, int B, const orbhip_local_points* mps,
                      const uint8_t* pair_skip, float th, int32_t* best_idx, int32_t* best_dist, int32_t* level,
                      int32_t* nfused) {
-    return fuse_call(c, kfs, B, mps, pair_skip, false, nullptr, th, best_idx, best_dist, level, nfused);
+    if (!c) return ORBHIP_ERR_ARG;
+    HIPOK(hipSetDevice(c->device));
+    return fuse_search(c->fuse_stage, c->timer, c->stream, kfs, B, mps, pair_skip, false, nullptr, th, best_idx,
+                       best_dist, level, nfused);
 }
 
 int orbhip_search_by_projection_sim3(orbhip_ctx* c, const orbhip_frame* kf, const orbhip_local_points* mps, float th,
                                      float ratio_hamming, int32_t* match, int32_t* match_dist, int32_t* level) {
-    if (!c || !kf || !mps || mps->n < 0) return ORBHIP_ERR_ARG;
-    if (!(ratio_hamming > 0.0f) || !std::isfinite(ratio_hamming)) return ORBHIP_ERR_ARG;
-    if (mps->n > kFuseMaxPoints) return ORBHIP_ERR_UNSUPPORTED;
-    size_t nk = 0;
-    if (const int rc = fuse_check_keyframes(kf, 1, &nk)) return rc;
-    const int n = mps->n, L = kf->n_levels;
-    if (n == 0) return 0;
-    if (!match || !mps->points || !mps->normals || !mps->min_dist || !mps->max_dist || !mps->desc) return ORBHIP_ERR_ARG;
-    const float thr = 50.0f * ratio_hamming;
+    if (!c) return ORBHIP_ERR_ARG;
     HIPOK(hipSetDevice(c->device));
-    hipStream_t st = c->stream;
-    // one block, the same layout on the host (pinned) and the device:
-    // [keyframe | scale factors | points normals min max desc skip | claimed | keypoints | descriptors],
-    // then device only [cell_start 3073 | records | windows n | lists n x 8 | counts n | picks 2 x n |
-    //  owners | nmatches | match n | match_dist n | level n]; the last four are read back
-    size_t off = 0;
-    auto take = [&](size_t bytes) { off = (off + 15) & ~size_t(15); const size_t o = off; off += bytes; return o; };
-    const size_t o_kf = take(sizeof(FuseKf)), o_sf = take((size_t)L * 4);
-    const size_t o_pts = take((size_t)n * 12), o_nrm = take((size_t)n * 12), o_min = take((size_t)n * 4);
-    const size_t o_max = take((size_t)n * 4), o_desc = take((size_t)n * 32), o_skip = take((size_t)n);
-    const size_t o_claimed = take(nk), o_kps = take(nk * sizeof(orbhip_kp)), o_kdesc = take(nk * 32);
-    const size_t up_bytes = take(0);
-    const size_t o_cs = take((size_t)(kFuseCells + 1) * 4), o_rec = take(nk * sizeof(FuseRec));
-    const size_t o_win = take((size_t)n * sizeof(Sim3Win)), o_list = take((size_t)n * kSim3ListCap * 8);
-    const size_t o_cnt = take((size_t)n * 4), o_pick = take((size_t)n * 8), o_pnew = take((size_t)n * 8);
-    const size_t o_own = take(nk * 4);
-    const size_t o_back = take(0);
-    const size_t n_out = level ? 3 : (match_dist ? 2 : 1);   // arrays read back: a prefix of match, dist, level
-    const size_t back_bytes = 16 + n_out * (size_t)n * 4;     // match starts 16-byte aligned behind nmatches
-    off = o_back + 16 + 3 * (size_t)n * 4;
-    const size_t dev_bytes = take(0);
-    HIPOK(c->d_fuse_stage.ensure(dev_bytes));
-    HIPOK(c->h_fuse_stage.ensure(up_bytes + back_bytes + 16));
-    uint8_t* const d = c->d_fuse_stage.p;
-    uint8_t* const h = c->h_fuse_stage.p;
-    fuse_kf_params(*kf, 0, (FuseKf*)(h + o_kf));
-    std::memcpy(h + o_sf, kf->scale_factors, (size_t)L * 4);
-    std::memcpy(h + o_pts, mps->points, (size_t)n * 12);
-    std::memcpy(h + o_nrm, mps->normals, (size_t)n * 12);
-    std::memcpy(h + o_min, mps->min_dist, (size_t)n * 4);
-    std::memcpy(h + o_max, mps->max_dist, (size_t)n * 4);
-    std::memcpy(h + o_desc, mps->desc, (size_t)n * 32);
-    if (mps->skip) std::memcpy(h + o_skip, mps->skip, (size_t)n);
-    else std::memset(h + o_skip, 0, (size_t)n);
-    if (nk) {
-        if (kf->claimed) std::memcpy(h + o_claimed, kf->claimed, nk);
-        else std::memset(h + o_claimed, 0, nk);
-        std::memcpy(h + o_kps, kf->kps, nk * sizeof(orbhip_kp));
-        std::memcpy(h + o_kdesc, kf->desc, nk * 32);
-    }
-    HIPOK(hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
-    (void)hipGetLastError();
-    int32_t* const d_nm = (int32_t*)(d + o_back);
-    int32_t* const d_match = (int32_t*)(d + o_back + 16);
-    {
-        const StageScope scope(c->timer);
-        c->timer.begin(9, st);
-        const FusePoints mp{n, (const float*)(d + o_pts), (const float*)(d + o_nrm), (const float*)(d + o_min),
-                            (const float*)(d + o_max), d + o_desc, d + o_skip};
-        const Sim3Work w{(Sim3Win*)(d + o_win), (unsigned long long*)(d + o_list), (int32_t*)(d + o_cnt),
-                         (unsigned long long*)(d + o_pick), (unsigned long long*)(d + o_pnew), (int32_t*)(d + o_own)};
-        launch_sim3_search((const FuseKf*)(d + o_kf), mp, d + o_claimed, (const float*)(d + o_sf), L,
-                           kf->log_scale_factor, th, thr, (const orbhip_kp*)(d + o_kps), d + o_kdesc, (int)nk,
-                           (int32_t*)(d + o_cs), (FuseRec*)(d + o_rec), w, d_match, d_match + n, d_match + 2 * (size_t)n,
-                           d_nm, st);
-        c->timer.end(9, st);
-    }
-    HIPOK(hipGetLastError());
-    uint8_t* const hb = h + ((up_bytes + 15) & ~size_t(15));
-    HIPOK(hipMemcpyAsync(hb, d + o_back, back_bytes, hipMemcpyDeviceToHost, st));
-    HIPOK(hipStreamSynchronize(st));
-    std::memcpy(match, hb + 16, (size_t)n * 4);
-    if (match_dist) std::memcpy(match_dist, hb + 16 + (size_t)n * 4, (size_t)n * 4);
-    if (level) std::memcpy(level, hb + 16 + 2 * (size_t)n * 4, (size_t)n * 4);
-    int32_t nm;
-    std::memcpy(&nm, hb, 4);
-    return nm;
+    return sim3_search(c->fuse_stage, c->timer, c->stream, kf, mps, th, ratio_hamming, match, match_dist, level);
 }
 
 // the stored list capacity of the Sim3 projection search; the resolve has no round cap other than

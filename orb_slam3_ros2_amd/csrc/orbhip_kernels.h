@@ -179,71 +179,24 @@ bool search_bow_set_lds_limit();
 void launch_search_bow(const BowSide& K, const BowSide& F, float ratio, int check_orientation, int th_low,
                        int32_t* match, int32_t* nmatch, hipStream_t st);
 
-// ---- SearchForTriangulation (triangulation_kernels.hip) ----
-constexpr int kTriMax = 2048;     // features per keyframe (LDS-resident keys, 16-bit indices)
-constexpr int kTriMaxPairs = 64;  // neighbours per call
-struct TriSide {                  // one keyframe in the call's staging block (device pointers)
-    const orbhip_kp* kps;
-    const uint8_t* desc;          // n x 32
-    const int32_t* node;
-    const double* weight;
-    const uint8_t* has_mp;
-    int n, pad;
-};
-struct TriGeom { float F[9]; float ep[2]; float pad; };   // F12 row-major, epipole in image 2
+// ---- host calls that stage one block (stage.h), next to their kernels ----
+struct StageBlock;
+// SearchForTriangulation (triangulation_kernels.hip); stage 7 of the timer
 // host, fp32 in a fixed operation order: the geometry k_tri_search consumes
 void tri_geometry(const orbhip_tri_keyframe& k1, const orbhip_tri_keyframe& k2, float* F, float* ep);
-// sides[0] = KF1, sides[1 + b] = neighbour b; keys1: kTriMax entries, m1: 1 (both written by the pre-pass)
-void launch_tri_search(const TriSide* sides, const TriGeom* geom, int n1, int B, const float* scale_factors,
-                       const float* level_sigma2, unsigned long long* keys1, int32_t* m1, int check_orientation,
-                       int32_t* match12, int32_t* nmatches, hipStream_t st);
-
-// ---- Fuse (fuse_kernels.hip) ----
-constexpr int kFuseCols = 64, kFuseRows = 48, kFuseCells = kFuseCols * kFuseRows;   // the frame grid
-constexpr int kFuseMaxKf = 64;         // keyframes per call
-constexpr int kFuseMaxPoints = 65536;  // MapPoints per call
-constexpr int kFuseMaxLevels = 256;    // the octave shares a word with the cell
-struct FuseKf {                        // one keyframe of the call
-    int n, base;                       // its keypoints are entries [base, base + n) of the call's arrays
-    float minx, maxx, miny, maxy, invw, invh;
-    float q[4], t[3], Ow[3], fx, fy, cx, cy;
-};
-struct FuseRec { float x, y; int cell_oct, idx; };   // a keypoint in cell order: cell << 8 | octave, its index
-struct FusePoints {                    // the MapPoints (device pointers; skip is never null here)
-    int n;
-    const float *pts, *nrm, *mind, *maxd;
-    const uint8_t *desc, *skip;
-};
-// host, fp32 in a fixed operation order: grid scales and mOw
-void fuse_kf_params(const orbhip_frame& f, int base, FuseKf* k);
-// cell_start: B x 3073, recs: one per keypoint of the call (both written by k_fuse_grid);
-// best_idx / best_dist / level: B x n, nfused: B (zeroed by k_fuse_grid).
-// inv_level_sigma2 == nullptr: the rule without the chi-square gate (Fuse with a Sim3)
-void launch_fuse(const FuseKf* kfs, int B, const FusePoints& mp, const uint8_t* pair_skip, const float* scale_factors,
-                 const float* inv_level_sigma2, int n_levels, float log_sf, float th, const orbhip_kp* kps,
-                 const uint8_t* kf_desc, int32_t* cell_start, FuseRec* recs, int32_t* best_idx, int32_t* best_dist,
-                 int32_t* level, int32_t* nfused, hipStream_t st);
-
-// ---- SearchByProjection with a Sim3 (fuse_kernels.hip) ----
+int tri_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_tri_keyframe* kf1,
+               const orbhip_tri_keyframe* nbrs, int B, const float* scale_factors, const float* level_sigma2,
+               int n_levels, int check_orientation, int32_t* match12, int32_t* nmatches);
+// Fuse (fuse_kernels.hip); stage 8. chi2 = false: Fuse with a Sim3 (no chi-square gate,
+// inv_level_sigma2 unused)
+int fuse_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_frame* kfs, int B,
+                const orbhip_local_points* mps, const uint8_t* pair_skip, bool chi2, const float* inv_level_sigma2,
+                float th, int32_t* best_idx, int32_t* best_dist, int32_t* level, int32_t* nfused);
+// SearchByProjection with a Sim3 (fuse_kernels.hip); stage 9
 constexpr int kSim3ListCap = 8;        // smallest keys k_sim3_search stores per point
-struct Sim3Win {                       // what k_sim3_resolve needs to walk a point's window again
-    float u, v, r;
-    int lvl;                           // -1: the point never reached the walk
-    int rect;                          // x0 | x1 << 8 | y0 << 16 | y1 << 24
-};
-struct Sim3Work {                      // device scratch of one call (n points, nk keypoints)
-    Sim3Win* win;                      // n
-    unsigned long long* list;          // n x kSim3ListCap, ascending, ~0 = empty
-    int32_t* count;                    // n: the full length of the list
-    unsigned long long *pick, *pick_new;   // n each
-    int32_t* owner;                    // nk
-};
-// match / match_dist / level: n, nmatches: 1. cell_start: 3073 + recs: nk (written by k_fuse_grid,
-// which also zeroes nmatches)
-void launch_sim3_search(const FuseKf* kf, const FusePoints& mp, const uint8_t* claimed, const float* scale_factors,
-                        int n_levels, float log_sf, float th, float thr, const orbhip_kp* kps, const uint8_t* kf_desc,
-                        int nk, int32_t* cell_start, FuseRec* recs, const Sim3Work& w, int32_t* match,
-                        int32_t* match_dist, int32_t* level, int32_t* nmatches, hipStream_t st);
+int sim3_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_frame* kf,
+                const orbhip_local_points* mps, float th, float ratio_hamming, int32_t* match, int32_t* match_dist,
+                int32_t* level);
 
 // ---- ingest ----
 void launch_bgr2gray(const uint8_t* src, int B, int w, int h, int sstride, int64_t sfstride, uint8_t* dst, int dstride,

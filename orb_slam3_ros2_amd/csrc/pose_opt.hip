@@ -25,8 +25,10 @@
 #include "../../include/orbhip.h"
 #include "ba_se3.h"
 #include "pose_opt.h"
-#include "proj.h"
+#include "stage.h"
 #include "wave_f64.h"
+
+#define HIPOK(x) ORBHIP_HIPOK(" pose", x)
 
 namespace orbhip {
 
@@ -359,28 +361,11 @@ __global__ __launch_bounds__(256) void k_pose_opt(const PoseHdr* __restrict__ hd
 // host
 // ---------------------------------------------------------------------------
 struct PoseWorkspace {
-    void* d = nullptr;
-    size_t dcap = 0;
-    void* h = nullptr;
-    void* hd = nullptr;   // device alias of h
-    size_t hcap = 0;
-    ~PoseWorkspace() {
-        if (d) (void)hipFree(d);
-        if (h) (void)hipHostFree(h);
-    }
+    StageBlock s{true};
 };
 
 PoseWorkspace* pose_ws_create() { return new PoseWorkspace(); }
 void pose_ws_destroy(PoseWorkspace* w) { delete w; }
-
-#define PSOK(x)                                                                                    \
-    do {                                                                                           \
-        hipError_t e_ = (x);                                                                       \
-        if (e_ != hipSuccess) {                                                                    \
-            std::fprintf(stderr, "orbhip pose: %s: %s\n", #x, hipGetErrorString(e_));              \
-            return ORBHIP_ERR_DEVICE;                                                              \
-        }                                                                                          \
-    } while (0)
 
 int pose_opt_batch(PoseWorkspace* ws, const orbhip_pose_problem* probs, int B, orbhip_pose_result* res,
                    hipStream_t st) {
@@ -395,27 +380,14 @@ int pose_opt_batch(PoseWorkspace* ws, const orbhip_pose_problem* probs, int B, o
         E += p.n;
     }
     // packed: [hdr B][edges E] (one upload) [out B][outlier E] (one download) [chi2 E][level E]
-    auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-    const size_t o_hdr = 0, o_edge = al(sizeof(PoseHdr) * B), o_out = o_edge + al(sizeof(PoseEdgeIn) * E);
-    const size_t o_ol = o_out + al(sizeof(PoseOut) * B), o_c2 = o_ol + al(E);
-    const size_t o_lv = o_c2 + al(sizeof(double) * E), total = o_lv + al(E);
-    if (ws->dcap < total) {
-        if (ws->d) (void)hipFree(ws->d);
-        ws->d = nullptr;
-        ws->dcap = 0;
-        PSOK(hipMalloc(&ws->d, total));
-        ws->dcap = total;
-    }
-    if (ws->hcap < total) {
-        if (ws->h) (void)hipHostFree(ws->h);
-        ws->h = nullptr;
-        ws->hcap = 0;
-        PSOK(hipHostMalloc(&ws->h, total + total / 4, hipHostMallocDefault));
-        ws->hcap = total + total / 4;
-        PSOK(hipHostGetDevicePointer(&ws->hd, ws->h, 0));
-    }
-    char* H = (char*)ws->h;
-    char* D = (char*)ws->d;
+    StageLayout lay(256);
+    const size_t o_hdr = lay.take(sizeof(PoseHdr) * B), o_edge = lay.take(sizeof(PoseEdgeIn) * E);
+    const size_t o_out = lay.take(sizeof(PoseOut) * B), o_ol = lay.take(E), o_c2 = lay.take(sizeof(double) * E);
+    const size_t o_lv = lay.take(E), total = lay.total();
+    HIPOK(ws->s.ensure(total, total));
+    char* H = (char*)ws->s.h;
+    char* D = (char*)ws->s.d;
+    char* HD = (char*)ws->s.hd;
     PoseHdr* hh = (PoseHdr*)(H + o_hdr);
     PoseEdgeIn* he = (PoseEdgeIn*)(H + o_edge);
     const float deltaMono = (float)std::sqrt(5.991);
@@ -443,8 +415,8 @@ int pose_opt_batch(PoseWorkspace* ws, const orbhip_pose_problem* probs, int B, o
     // pinned block (no DMA-engine copies); large batches: DMA both ways
     const size_t in_bytes = o_edge + sizeof(PoseEdgeIn) * E;
     const bool small = in_bytes <= ((size_t)1 << 20);
-    if (small) PSOK(upload_inputs(ws->hd, D, H, in_bytes, st));
-    else PSOK(hipMemcpyAsync(D, H, in_bytes, hipMemcpyHostToDevice, st));
+    if (small) HIPOK(upload_inputs(HD, D, H, in_bytes, st));
+    else HIPOK(hipMemcpyAsync(D, H, in_bytes, hipMemcpyHostToDevice, st));
     // W = 4 wavefronts per frame while that still fills the chip's SIMDs twice over, else one
     int W = B <= 512 ? 4 : 1;
     if (const char* s = std::getenv("ORBHIP_POSE_WAVES")) W = std::atoi(s) == 1 ? 1 : 4;
@@ -453,16 +425,16 @@ int pose_opt_batch(PoseWorkspace* ws, const orbhip_pose_problem* probs, int B, o
     uint8_t* dlv = (uint8_t*)(D + o_lv);
     uint8_t* dol = (uint8_t*)(D + o_ol);
     double* dc2 = (double*)(D + o_c2);
-    PoseOut* dout = (PoseOut*)((small ? (char*)ws->hd : D) + o_out);
-    uint8_t* olc = small ? (uint8_t*)ws->hd + o_ol : nullptr;
+    PoseOut* dout = (PoseOut*)((small ? HD : D) + o_out);
+    uint8_t* olc = small ? (uint8_t*)HD + o_ol : nullptr;
     if (W == 4)
         hipLaunchKernelGGL(k_pose_opt<4>, dim3((unsigned)B), dim3(256), 0, st, dh, de, dlv, dol, dc2, dout, olc, B);
     else
         hipLaunchKernelGGL(k_pose_opt<1>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, dh, de, dlv, dol, dc2,
                            dout, olc, B);
-    PSOK(hipGetLastError());
-    if (!small) PSOK(hipMemcpyAsync(H + o_out, D + o_out, o_ol - o_out + E, hipMemcpyDeviceToHost, st));
-    PSOK(hipStreamSynchronize(st));
+    HIPOK(hipGetLastError());
+    if (!small) HIPOK(hipMemcpyAsync(H + o_out, D + o_out, o_ol - o_out + E, hipMemcpyDeviceToHost, st));
+    HIPOK(hipStreamSynchronize(st));
     const PoseOut* ho = (const PoseOut*)(H + o_out);
     const uint8_t* hol = (const uint8_t*)(H + o_ol);
     for (int b = 0; b < B; b++) {

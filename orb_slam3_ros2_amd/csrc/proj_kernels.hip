@@ -29,9 +29,13 @@
 
 #include "../../include/orbhip.h"
 #include "dev_attr.h"
+#include "geom.h"
 #include "orbhip_device.h"
 #include "orbhip_kernels.h"
 #include "proj.h"
+#include "stage.h"
+
+#define HIPOK(x) ORBHIP_HIPOK(" proj", x)
 
 namespace orbhip {
 
@@ -39,7 +43,7 @@ ORBHIP_TRACE_UNIT(proj)   // kernel id 7: k_proj_lists (phases 1-3), its resolvi
 
 namespace {
 
-constexpr int kGridCols = 64, kGridRows = 48, kThHigh = 100, kHisto = 30;
+constexpr int kThHigh = 100, kHisto = 30;
 
 struct ProjFrame {     // the current Frame
     int n;
@@ -52,23 +56,10 @@ struct Query {         // one projected MapPoint: GetFeaturesInArea(u, v, r, min
     int minL, maxL, valid;
 };
 
-// Eigen QuaternionBase::_transformVector, float
-__device__ __forceinline__ void qrotf(const float q[4], const float v[3], float o[3]) {
-    float uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]};
-    uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
-    const float c[3] = {q[1] * uv[2] - q[2] * uv[1], q[2] * uv[0] - q[0] * uv[2], q[0] * uv[1] - q[1] * uv[0]};
-    o[0] = v[0] + q[3] * uv[0] + c[0];
-    o[1] = v[1] + q[3] * uv[1] + c[1];
-    o[2] = v[2] + q[3] * uv[2] + c[2];
-}
-
-// PosInGrid: cell = px * 48 + py, -1 outside the grid
 __global__ void k_proj_cells(ProjFrame f, const orbhip_kp* __restrict__ kps, int* __restrict__ cell) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= f.n) return;
-    const int px = (int)roundf((kps[k].x - f.minx) * f.invw);
-    const int py = (int)roundf((kps[k].y - f.miny) * f.invh);
-    cell[k] = (px < 0 || px >= kGridCols || py < 0 || py >= kGridRows) ? -1 : px * kGridRows + py;
+    cell[k] = grid_cell(f.minx, f.miny, f.invw, f.invh, kps[k].x, kps[k].y);
 }
 
 // SearchByProjection(CurrentFrame, LastFrame, th, bMono): window th * scale[lastOctave], levels
@@ -83,7 +74,7 @@ __device__ __forceinline__ Query prep_last(const ProjFrame& f, const PrepLast& a
     Query Q{0, 0, 0, 0, 0, 0};
     const float P[3] = {a.pts[3 * i], a.pts[3 * i + 1], a.pts[3 * i + 2]};
     float Xc[3];
-    qrotf(f.q, P, Xc);
+    quat_rotate(f.q, P, Xc);
     Xc[0] += f.t[0]; Xc[1] += f.t[1]; Xc[2] += f.t[2];
     const float invzc = (float)(1.0 / (double)Xc[2]);
     if (!(invzc < 0)) {
@@ -217,8 +208,7 @@ __global__ __launch_bounds__(256) void k_proj_round(ProjFrame f, int nq, int mod
                 if ((claimed && claimed[k]) || owner[k] < i) continue;
                 const uint4* kd4 = (const uint4*)(kdesc + 32 * (size_t)k);
                 const uint4 ka = kd4[0], kb = kd4[1];
-                const int d = __popc(qa.x ^ ka.x) + __popc(qa.y ^ ka.y) + __popc(qa.z ^ ka.z) + __popc(qa.w ^ ka.w) +
-                              __popc(qb.x ^ kb.x) + __popc(qb.y ^ kb.y) + __popc(qb.z ^ kb.z) + __popc(qb.w ^ kb.w);
+                const int d = hamming256(qa, qb, ka, kb);
                 if (d == 256) continue;   // never best (dist < 256) nor second (dist < bestDist2 <= 256)
                 top2_add(t, d, (c << 16) | k, kp.octave);
             }
@@ -415,9 +405,7 @@ __global__ __launch_bounds__(1024) void k_proj_lists(ProjFrame f, int nq, PrepLa
         for (int u = 0; u < 2; u++) {
             const int k = k0 + u * nt;
             if (k >= n) break;
-            const int px = (int)roundf((kp[u].x - f.minx) * f.invw);
-            const int py = (int)roundf((kp[u].y - f.miny) * f.invh);
-            const int c = (px < 0 || px >= kGridCols || py < 0 || py >= kGridRows) ? 0xFFFF : px * kGridRows + py;
+            const int c = grid_cell(f.minx, f.miny, f.invw, f.invh, kp[u].x, kp[u].y, 0xFFFF);
             kl[k] = uint4{__float_as_uint(kp[u].x), __float_as_uint(kp[u].y), ((uint32_t)c << 16) | (cl[u] << 8) |
                           (uint32_t)(kp[u].octave & 0xFF), 0u};
             kc[k] = (uint16_t)c;
@@ -507,9 +495,7 @@ __global__ __launch_bounds__(1024) void k_proj_lists(ProjFrame f, int nq, PrepLa
             if (kk[u] < 0) continue;
             const int k = kk[u];
             const uint32_t z = kl[k].z, oct = z & 0xFF, key = ((z >> 16) << 16) | (uint32_t)k;
-            const int d = __popc(qa.x ^ ka[u].x) + __popc(qa.y ^ ka[u].y) + __popc(qa.z ^ ka[u].z) +
-                          __popc(qa.w ^ ka[u].w) + __popc(qb.x ^ kb[u].x) + __popc(qb.y ^ kb[u].y) +
-                          __popc(qb.z ^ kb[u].z) + __popc(qb.w ^ kb[u].w);
+            const int d = hamming256(qa, qb, ka[u], kb[u]);
             st_ag(out + lane + 64 * u, ((uint64_t)d << 32) | (uint64_t)((key << 4) | (oct & 15u)));
             if (d != 256) top2_add(t, d, (int)key, (int)(oct & 15u));
         }
@@ -739,7 +725,6 @@ __global__ __launch_bounds__(1024) void k_proj_resolve(int n, int nq, float nnra
 // distance is the second element of the multiset, so the chain is exact. The bin of the pair
 // (the rotHist push) rides in the low bits, so the chain never touches the keypoints.
 // ---------------------------------------------------------------------------
-constexpr int kInitCells = kGridCols * kGridRows;   // 3072
 constexpr int kThLow = 50;
 constexpr int kInitK = 16;   // smallest list entries per query handed to the chain
 constexpr int kInitR = 4;    // ring of 4-query blocks in flight in the chain
@@ -763,47 +748,41 @@ struct InitGeom {
     int list_cap;    // entries per query list (>= number of ranked F2 keypoints, multiple of 64)
 };
 
-__device__ __forceinline__ int init_cell(const InitGeom& g, float x, float y) {   // PosInGrid
-    const int px = (int)roundf((x - g.minx) * g.invw);
-    const int py = (int)roundf((y - g.miny) * g.invh);
-    return (px < 0 || px >= kGridCols || py < 0 || py >= kGridRows) ? -1 : px * kGridRows + py;
-}
-
 // counts[0] = queries (F1 octave 0), counts[1] = ranked F2 keypoints, counts[2] = nmatches
 __global__ __launch_bounds__(1024) void k_init_prep(InitGeom g, const orbhip_kp* __restrict__ kps1,
                                                     const orbhip_kp* __restrict__ kps2, int* __restrict__ slot,
                                                     int* __restrict__ qlist, int* __restrict__ counts,
                                                     int* __restrict__ cnt3, int* __restrict__ flags, int nflags) {
-    __shared__ int cnt[kInitCells], start[kInitCells], scratch[20], tot;
+    __shared__ int cnt[kGridCells], start[kGridCells], scratch[20], tot;
     const int tid = threadIdx.x, nt = blockDim.x;
-    for (int c = tid; c < kInitCells; c += nt) cnt[c] = 0;
+    for (int c = tid; c < kGridCells; c += nt) cnt[c] = 0;
     __syncthreads();
     for (int k = tid; k < g.n2; k += nt) {
         const orbhip_kp kp = kps2[k];
-        const int c = kp.octave == 0 ? init_cell(g, kp.x, kp.y) : -1;
+        const int c = kp.octave == 0 ? grid_cell(g.minx, g.miny, g.invw, g.invh, kp.x, kp.y) : -1;
         if (c >= 0) atomicAdd(&cnt[c], 1);
     }
     __syncthreads();
     // exclusive scan of the 3072 cell counts (3 per thread, in order)
     {
         int v[3], s = 0;
-        for (int j = 0; j < 3; j++) { const int c = tid * 3 + j; v[j] = c < kInitCells ? cnt[c] : 0; s += v[j]; }
+        for (int j = 0; j < 3; j++) { const int c = tid * 3 + j; v[j] = c < kGridCells ? cnt[c] : 0; s += v[j]; }
         int total;
         int base = block_excl_scan(s, scratch, &total);
-        for (int j = 0; j < 3; j++) { const int c = tid * 3 + j; if (c < kInitCells) start[c] = base; base += v[j]; }
+        for (int j = 0; j < 3; j++) { const int c = tid * 3 + j; if (c < kGridCells) start[c] = base; base += v[j]; }
         if (tid == 0) tot = total;
     }
     __syncthreads();
-    for (int c = tid; c < kInitCells; c += nt) cnt[c] = 0;
+    for (int c = tid; c < kGridCells; c += nt) cnt[c] = 0;
     __syncthreads();
     for (int k = tid; k < g.n2; k += nt) {
         const orbhip_kp kp = kps2[k];
-        const int c = kp.octave == 0 ? init_cell(g, kp.x, kp.y) : -1;
+        const int c = kp.octave == 0 ? grid_cell(g.minx, g.miny, g.invw, g.invh, kp.x, kp.y) : -1;
         if (c >= 0) slot[start[c] + atomicAdd(&cnt[c], 1)] = k;
     }
     __syncthreads();
     // index order inside each cell (cells hold a handful of keypoints)
-    for (int c = tid; c < kInitCells; c += nt) {
+    for (int c = tid; c < kGridCells; c += nt) {
         int* a = slot + start[c];
         const int m = cnt[c];
         for (int i = 1; i < m; i++) {
@@ -863,15 +842,13 @@ __global__ __launch_bounds__(256) void k_init_cands(InitGeom g, const orbhip_kp*
             if (rk < nr) {
                 const int k = slot[rk];
                 const orbhip_kp kp = kps2[k];
-                const int c = init_cell(g, kp.x, kp.y);
+                const int c = grid_cell(g.minx, g.miny, g.invw, g.invh, kp.x, kp.y);
                 const int px = c / kGridRows, py = c - px * kGridRows;
                 if (px >= nMinCellX && px <= nMaxCellX && py >= nMinCellY && py <= nMaxCellY &&
                     fabsf(kp.x - x) < r && fabsf(kp.y - y) < r) {
                     const uint4* kd4 = (const uint4*)(desc2 + 32 * (size_t)k);
                     const uint4 ka = kd4[0], kb = kd4[1];
-                    const int d = __popc(qa.x ^ ka.x) + __popc(qa.y ^ ka.y) + __popc(qa.z ^ ka.z) +
-                                  __popc(qa.w ^ ka.w) + __popc(qb.x ^ kb.x) + __popc(qb.y ^ kb.y) +
-                                  __popc(qb.z ^ kb.z) + __popc(qb.w ^ kb.w);
+                    const int d = hamming256(qa, qb, ka, kb);
                     float rot = a1 - kp.angle;
                     if (rot < 0.0) rot += 360.0f;
                     int bin = (int)roundf(rot * factor);
@@ -1249,39 +1226,18 @@ __global__ __launch_bounds__(1024) void k_init_finish(InitGeom g, int check_orie
 // host
 // ---------------------------------------------------------------------------
 struct ProjWorkspace {
-    void* d = nullptr;
-    size_t dcap = 0;
-    void* h = nullptr;
-    void* hd = nullptr;   // h as the device addresses it (kernels write results there: no download)
+    StageBlock s{true};      // the two-launch form writes its results straight into the pinned image
     int* arrive = nullptr;   // the one-launch search's arrival counter (0 between launches)
-    size_t hcap = 0;
     int ahead = 4;   // rounds launched per host sync (adapts to the last search)
     int init_ahead = 6;   // the same for SearchForInitialization's rounds
     ~ProjWorkspace() {
         if (arrive) (void)hipFree(arrive);
-        if (d) (void)hipFree(d);
-        if (h) (void)hipHostFree(h);
     }
 };
 ProjWorkspace* proj_ws_create() { return new ProjWorkspace(); }
 void proj_ws_destroy(ProjWorkspace* w) { delete w; }
 
-#define PJOK(x)                                                                                    \
-    do {                                                                                           \
-        hipError_t e_ = (x);                                                                       \
-        if (e_ != hipSuccess) {                                                                    \
-            std::fprintf(stderr, "orbhip proj: %s: %s\n", #x, hipGetErrorString(e_));              \
-            return ORBHIP_ERR_DEVICE;                                                              \
-        }                                                                                          \
-    } while (0)
-
 namespace {
-
-// staging layout helper: consecutive 256-byte aligned segments
-struct Layout {
-    size_t off = 0;
-    size_t add(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~size_t(255); return o; }
-};
 
 ProjFrame make_frame(const orbhip_frame* F) {
     ProjFrame f{};
@@ -1294,70 +1250,20 @@ ProjFrame make_frame(const orbhip_frame* F) {
     f.fx = F->fx; f.fy = F->fy; f.cx = F->cx; f.cy = F->cy;
     // mRcw = q.toRotationMatrix(); mOw = conj(q)._transformVector(-t) (Sophus SE3f::inverse)
     const float* q = f.q;
-    const float tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];
-    const float twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
-    const float txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
-    const float tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
-    f.R[0] = 1 - (tyy + tzz); f.R[1] = txy - twz; f.R[2] = txz + twy;
-    f.R[3] = txy + twz; f.R[4] = 1 - (txx + tzz); f.R[5] = tyz - twx;
-    f.R[6] = txz - twy; f.R[7] = tyz + twx; f.R[8] = 1 - (txx + tyy);
+    quat_to_matrix(q, f.R);
     const float qc[4] = {-q[0], -q[1], -q[2], q[3]};
     const float v[3] = {f.t[0] * -1.0f, f.t[1] * -1.0f, f.t[2] * -1.0f};
-    float uv[3] = {qc[1] * v[2] - qc[2] * v[1], qc[2] * v[0] - qc[0] * v[2], qc[0] * v[1] - qc[1] * v[0]};
-    uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
-    const float c[3] = {qc[1] * uv[2] - qc[2] * uv[1], qc[2] * uv[0] - qc[0] * uv[2], qc[0] * uv[1] - qc[1] * uv[0]};
-    f.Ow[0] = v[0] + qc[3] * uv[0] + c[0];
-    f.Ow[1] = v[1] + qc[3] * uv[1] + c[1];
-    f.Ow[2] = v[2] + qc[3] * uv[2] + c[2];
+    quat_rotate(qc, v, f.Ow);
     return f;
 }
 
-// The staged inputs to device memory by the shader: every lane reads two 16-byte pieces of the
-// pinned staging block over the bus (~140 KB per search: a few us) instead of a DMA-engine copy,
-// whose start-up and ~15 GB/s rate cost ~12 us per call (rocprofv3 memory-copy trace, r03).
-// ORBHIP_PROJ_DMA=1 restores hipMemcpyAsync (A/B, read per call). Also the pose solver's upload.
-__global__ __launch_bounds__(256) void k_upload(const uint4* __restrict__ src, uint4* __restrict__ dst, int n16) {
-    const int i = blockIdx.x * 512 + threadIdx.x;
-    uint4 a{}, b{};
-    if (i < n16) a = src[i];
-    if (i + 256 < n16) b = src[i + 256];
-    if (i < n16) dst[i] = a;
-    if (i + 256 < n16) dst[i + 256] = b;
-}
-}  // namespace
-
-hipError_t upload_inputs(const void* hd, void* d, const void* h, size_t bytes, hipStream_t st) {
-    const char* e = std::getenv("ORBHIP_PROJ_DMA");
-    if (e && e[0] == '1') return hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st);
-    const int n16 = (int)((bytes + 15) / 16);   // bytes: a multiple of 256 (Layout)
-    if (n16 == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_upload, dim3((unsigned)((n16 + 511) / 512)), dim3(256), 0, st, (const uint4*)hd, (uint4*)d,
-                       n16);
-    return hipGetLastError();
-}
-
-namespace {
-
+// the block of `total` bytes on both sides, and the arrival counter
 int ensure(ProjWorkspace* ws, size_t total) {
     if (!ws->arrive) {
-        PJOK(hipMalloc((void**)&ws->arrive, sizeof(int)));
-        PJOK(hipMemset(ws->arrive, 0, sizeof(int)));
+        HIPOK(hipMalloc((void**)&ws->arrive, sizeof(int)));
+        HIPOK(hipMemset(ws->arrive, 0, sizeof(int)));
     }
-    if (ws->dcap < total) {
-        if (ws->d) (void)hipFree(ws->d);
-        ws->d = nullptr;
-        ws->dcap = 0;
-        PJOK(hipMalloc(&ws->d, total));
-        ws->dcap = total;
-    }
-    if (ws->hcap < total) {
-        if (ws->h) (void)hipHostFree(ws->h);
-        ws->h = nullptr;
-        ws->hcap = 0;
-        PJOK(hipHostMalloc(&ws->h, total + total / 4, hipHostMallocDefault));
-        ws->hcap = total + total / 4;
-        PJOK(hipHostGetDevicePointer(&ws->hd, ws->h, 0));
-    }
+    HIPOK(ws->s.ensure(total, total));
     return ORBHIP_OK;
 }
 
@@ -1373,8 +1279,8 @@ int run_rounds(ProjWorkspace* ws, const ProjFrame& f, int nq, int mode, float nn
     const int cap = nq + 2;   // a fixed point is reached within nq + 1 rounds
     int* chg = (int*)(D + o_chg);
     const int* hchg = (const int*)(H + o_chg);
-    PJOK(hipMemsetAsync(D + o_own, 0x7F, 3 * sizeof(int) * (size_t)std::max(f.n, 1), st));   // > any query
-    PJOK(hipMemsetAsync(chg, 0, sizeof(int) * (size_t)cap, st));
+    HIPOK(hipMemsetAsync(D + o_own, 0x7F, 3 * sizeof(int) * (size_t)std::max(f.n, 1), st));   // > any query
+    HIPOK(hipMemsetAsync(chg, 0, sizeof(int) * (size_t)cap, st));
     int r = 0;
     for (;;) {
         const int R = std::min(ws->ahead, cap - r);
@@ -1383,10 +1289,10 @@ int run_rounds(ProjWorkspace* ws, const ProjFrame& f, int nq, int mode, float nn
                                (const Query*)(D + o_q), (const orbhip_kp*)(D + o_kps), (const uint8_t*)(D + o_kd),
                                (const int*)(D + o_cell), claimed, (int*)(D + o_own), (const uint8_t*)(D + o_qd),
                                (int*)(D + o_pick), chg);
-        PJOK(hipGetLastError());
+        HIPOK(hipGetLastError());
         if (int rc = tail()) return rc;
-        PJOK(hipMemcpyAsync(H + o_chg + sizeof(int) * r, chg + r, sizeof(int) * R, hipMemcpyDeviceToHost, st));
-        PJOK(hipStreamSynchronize(st));
+        HIPOK(hipMemcpyAsync(H + o_chg + sizeof(int) * r, chg + r, sizeof(int) * R, hipMemcpyDeviceToHost, st));
+        HIPOK(hipStreamSynchronize(st));
         for (int j = 0; j < R; j++)
             if (hchg[r + j] == 0) {
                 const int rounds = r + j + 1;
@@ -1398,10 +1304,6 @@ int run_rounds(ProjWorkspace* ws, const ProjFrame& f, int nq, int mode, float nn
         ws->ahead = std::min(16, 2 * ws->ahead);
     }
 }
-
-}  // namespace
-
-namespace {
 
 // the two-launch form applies: every octave fits the list entry's 4 bits, the owner tables fit LDS
 constexpr size_t kResolveLds = 150 * 1024;   // k_proj_resolve's dynamic LDS
@@ -1462,31 +1364,34 @@ int proj_search_last(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_proj
     if (nq == 0) return 0;
     const bool onepass = onepass_ok(F, nq);
     const int cap = proj_cap();
-    if (onepass) PJOK(proj_lds_attr());
+    if (onepass) HIPOK(proj_lds_attr());
     const OutBlock ob(nq);
-    Layout lay;
-    const size_t o_kps = lay.add(sizeof(orbhip_kp) * n), o_kd = lay.add(32 * (size_t)n), o_cl = lay.add(n);
-    const size_t o_scale = lay.add(sizeof(float) * F->n_levels);
-    const size_t o_pts = lay.add(12 * (size_t)nq), o_qd = lay.add(32 * (size_t)nq), o_oct = lay.add(4 * (size_t)nq);
-    const size_t o_ang = lay.add(4 * (size_t)nq), o_in_end = lay.off;
-    const size_t o_cell = lay.add(4 * (size_t)n), o_own = lay.add(12 * (size_t)std::max(n, 1));
-    const size_t o_q = lay.add(sizeof(Query) * nq), o_chg = lay.add(4 * ((size_t)nq + 2));
-    const size_t o_pick = lay.add(4 * (size_t)nq), o_out = lay.add(ob.bytes);
-    const size_t o_list = onepass ? lay.add(8 * (size_t)nq * cap) : 0, o_lcnt = lay.add(4 * (size_t)nq);
-    const size_t o_pick0 = lay.add(4 * (size_t)nq);
-    if (int rc = ensure(ws, lay.off)) return rc;
-    char* H = (char*)ws->h;
-    char* HD = (char*)ws->hd;   // the two-launch form writes its results straight into H
-    char* D = (char*)ws->d;
-    std::memcpy(H + o_kps, F->kps, sizeof(orbhip_kp) * n);
-    std::memcpy(H + o_kd, F->desc, 32 * (size_t)n);
-    if (F->claimed) std::memcpy(H + o_cl, F->claimed, n);
-    std::memcpy(H + o_scale, F->scale_factors, sizeof(float) * F->n_levels);
-    std::memcpy(H + o_pts, L->points, 12 * (size_t)nq);
-    std::memcpy(H + o_qd, L->desc, 32 * (size_t)nq);
-    std::memcpy(H + o_oct, L->octave, 4 * (size_t)nq);
-    std::memcpy(H + o_ang, L->angle, 4 * (size_t)nq);
-    PJOK(upload_inputs(ws->hd, D, H, o_in_end, st));
+    // uploaded: [keypoints | descriptors | claimed | scale factors | points | point descriptors |
+    //  octaves | angles], then device only [cells | owners x 3 | queries | changed flags | picks |
+    //  outputs (OutBlock) | lists | list counts | first picks]
+    StageLayout lay(256);
+    const size_t o_kps = lay.take(sizeof(orbhip_kp) * n), o_kd = lay.take(32 * (size_t)n), o_cl = lay.take(n);
+    const size_t o_scale = lay.take(sizeof(float) * F->n_levels);
+    const size_t o_pts = lay.take(12 * (size_t)nq), o_qd = lay.take(32 * (size_t)nq), o_oct = lay.take(4 * (size_t)nq);
+    const size_t o_ang = lay.take(4 * (size_t)nq), o_in_end = lay.total();
+    const size_t o_cell = lay.take(4 * (size_t)n), o_own = lay.take(12 * (size_t)std::max(n, 1));
+    const size_t o_q = lay.take(sizeof(Query) * nq), o_chg = lay.take(4 * ((size_t)nq + 2));
+    const size_t o_pick = lay.take(4 * (size_t)nq), o_out = lay.take(ob.bytes);
+    const size_t o_list = onepass ? lay.take(8 * (size_t)nq * cap) : 0, o_lcnt = lay.take(4 * (size_t)nq);
+    const size_t o_pick0 = lay.take(4 * (size_t)nq);
+    if (int rc = ensure(ws, lay.total())) return rc;
+    StageBlock& S = ws->s;
+    char* H = (char*)S.h;
+    char* HD = (char*)S.hd;   // the two-launch form writes its results straight into H
+    char* D = (char*)S.d;
+    put_keyframe(S, o_kps, o_kd, 0, F->kps, F->desc, n);
+    if (F->claimed) S.put(o_cl, F->claimed, n);
+    S.put(o_scale, F->scale_factors, sizeof(float) * F->n_levels);
+    S.put(o_pts, L->points, 12 * (size_t)nq);
+    S.put(o_qd, L->desc, 32 * (size_t)nq);
+    S.put(o_oct, L->octave, 4 * (size_t)nq);
+    S.put(o_ang, L->angle, 4 * (size_t)nq);
+    HIPOK(upload_inputs(S.hd, D, H, o_in_end, st));
     const ProjFrame f = make_frame(F);
     const PrepLast pl{(const float*)(D + o_pts), (const int*)(D + o_oct), (const float*)(D + o_scale), th};
     const uint8_t* dcl = F->claimed ? (const uint8_t*)(D + o_cl) : nullptr;
@@ -1504,15 +1409,15 @@ int proj_search_last(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_proj
             hipLaunchKernelGGL(k_proj_resolve<0>, dim3(1), dim3(1024), kResolveLds, st, n, nq, 0.f, check_orientation,
                                cap, ra.ent_cap, ra.qangle, (const orbhip_kp*)(D + o_kps), (const uint64_t*)(D + o_list),
                                (const int*)(D + o_lcnt), (const int*)(D + o_pick0), ra.match, ra.res);
-        PJOK(hipGetLastError());
-        PJOK(hipStreamSynchronize(st));
+        HIPOK(hipGetLastError());
+        HIPOK(hipStreamSynchronize(st));
         if (hres[1] == 0) {
             std::memcpy(match, H + o_out + ob.match, 4 * (size_t)nq);
             if (rounds_out) *rounds_out = hres[2];
             return hres[0];
         }
     }
-    PJOK(hipMemsetAsync(D + o_pick, 0xFF, 4 * (size_t)nq, st));   // -1: the first round always "changes"
+    HIPOK(hipMemsetAsync(D + o_pick, 0xFF, 4 * (size_t)nq, st));   // -1: the first round always "changes"
     if (n) hipLaunchKernelGGL(k_proj_cells, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, f,
                               (const orbhip_kp*)(D + o_kps), (int*)(D + o_cell));
     hipLaunchKernelGGL(k_proj_prep_last, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, f, nq, pl,
@@ -1521,7 +1426,7 @@ int proj_search_last(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_proj
         hipLaunchKernelGGL(k_proj_finish, dim3(1), dim3(1024), 0, st, nq, check_orientation,
                            (const float*)(D + o_ang), (const orbhip_kp*)(D + o_kps), (const int*)(D + o_pick),
                            (int*)(D + o_out + ob.match), (int*)(D + o_out + ob.res));
-        PJOK(hipMemcpyAsync(H + o_out, D + o_out, ob.bytes, hipMemcpyDeviceToHost, st));
+        HIPOK(hipMemcpyAsync(H + o_out, D + o_out, ob.bytes, hipMemcpyDeviceToHost, st));
         return 0;
     };
     const int rounds = run_rounds(ws, f, nq, 0, 0.f, D, o_q, o_kps, o_kd, o_cell, dcl, o_own, o_qd, o_pick, o_chg, H,
@@ -1543,37 +1448,33 @@ int proj_search_local(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_loc
     if (nq == 0) return 0;
     const bool onepass = onepass_ok(F, nq);
     const int cap = proj_cap();
-    if (onepass) PJOK(proj_lds_attr());
+    if (onepass) HIPOK(proj_lds_attr());
     const OutBlock ob(nq);
-    Layout lay;
-    const size_t o_kps = lay.add(sizeof(orbhip_kp) * n), o_kd = lay.add(32 * (size_t)n), o_cl = lay.add(n);
-    const size_t o_scale = lay.add(sizeof(float) * F->n_levels);
-    const size_t o_pts = lay.add(12 * (size_t)nq), o_nrm = lay.add(12 * (size_t)nq), o_mind = lay.add(4 * (size_t)nq);
-    const size_t o_maxd = lay.add(4 * (size_t)nq), o_qd = lay.add(32 * (size_t)nq), o_skip = lay.add(nq);
-    const size_t o_in_end = lay.off;
-    const size_t o_cell = lay.add(4 * (size_t)n), o_own = lay.add(12 * (size_t)std::max(n, 1));
-    const size_t o_q = lay.add(sizeof(Query) * nq), o_chg = lay.add(4 * ((size_t)nq + 2));
-    const size_t o_pick = lay.add(4 * (size_t)nq), o_out = lay.add(ob.bytes);
-    const size_t o_list = onepass ? lay.add(8 * (size_t)nq * cap) : 0, o_lcnt = lay.add(4 * (size_t)nq);
-    const size_t o_pick0 = lay.add(4 * (size_t)nq);
-    if (int rc = ensure(ws, lay.off)) return rc;
-    char* H = (char*)ws->h;
-    char* HD = (char*)ws->hd;   // the two-launch form writes its results straight into H
-    char* D = (char*)ws->d;
-    std::memcpy(H + o_kps, F->kps, sizeof(orbhip_kp) * n);
-    std::memcpy(H + o_kd, F->desc, 32 * (size_t)n);
-    if (F->claimed) std::memcpy(H + o_cl, F->claimed, n);
-    std::memcpy(H + o_scale, F->scale_factors, sizeof(float) * F->n_levels);
-    std::memcpy(H + o_pts, M->points, 12 * (size_t)nq);
-    std::memcpy(H + o_nrm, M->normals, 12 * (size_t)nq);
-    std::memcpy(H + o_mind, M->min_dist, 4 * (size_t)nq);
-    std::memcpy(H + o_maxd, M->max_dist, 4 * (size_t)nq);
-    std::memcpy(H + o_qd, M->desc, 32 * (size_t)nq);
-    if (M->skip) std::memcpy(H + o_skip, M->skip, nq);
-    PJOK(upload_inputs(ws->hd, D, H, o_in_end, st));
+    // uploaded: [keypoints | descriptors | claimed | scale factors | points normals min max desc skip],
+    // then device only as proj_search_last
+    StageLayout lay(256);
+    const size_t o_kps = lay.take(sizeof(orbhip_kp) * n), o_kd = lay.take(32 * (size_t)n), o_cl = lay.take(n);
+    const size_t o_scale = lay.take(sizeof(float) * F->n_levels);
+    const PointsLayout o_mp(lay, (size_t)nq);
+    const size_t o_qd = o_mp.desc;
+    const size_t o_in_end = lay.total();
+    const size_t o_cell = lay.take(4 * (size_t)n), o_own = lay.take(12 * (size_t)std::max(n, 1));
+    const size_t o_q = lay.take(sizeof(Query) * nq), o_chg = lay.take(4 * ((size_t)nq + 2));
+    const size_t o_pick = lay.take(4 * (size_t)nq), o_out = lay.take(ob.bytes);
+    const size_t o_list = onepass ? lay.take(8 * (size_t)nq * cap) : 0, o_lcnt = lay.take(4 * (size_t)nq);
+    const size_t o_pick0 = lay.take(4 * (size_t)nq);
+    if (int rc = ensure(ws, lay.total())) return rc;
+    StageBlock& S = ws->s;
+    char* H = (char*)S.h;
+    char* HD = (char*)S.hd;   // the two-launch form writes its results straight into H
+    char* D = (char*)S.d;
+    put_keyframe(S, o_kps, o_kd, 0, F->kps, F->desc, n);
+    if (F->claimed) S.put(o_cl, F->claimed, n);
+    S.put(o_scale, F->scale_factors, sizeof(float) * F->n_levels);
+    const DevPoints mp = o_mp.put(S, *M, false);   // no skip array: a null pointer
+    HIPOK(upload_inputs(S.hd, D, H, o_in_end, st));
     const ProjFrame f = make_frame(F);
-    const PrepLocal pc{(const float*)(D + o_pts), (const float*)(D + o_nrm), (const float*)(D + o_mind),
-                       (const float*)(D + o_maxd), M->skip ? (const uint8_t*)(D + o_skip) : nullptr,
+    const PrepLocal pc{mp.pts, mp.nrm, mp.mind, mp.maxd, mp.skip,
                        (const float*)(D + o_scale), F->n_levels, F->log_scale_factor, view_cos_limit, th, far_points,
                        th_far};
     const uint8_t* dcl = F->claimed ? (const uint8_t*)(D + o_cl) : nullptr;
@@ -1599,15 +1500,15 @@ int proj_search_local(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_loc
                                ra.ent_cap, (const float*)nullptr, (const orbhip_kp*)(D + o_kps),
                                (const uint64_t*)(D + o_list), (const int*)(D + o_lcnt), (const int*)(D + o_pick0),
                                ra.match, ra.res);
-        PJOK(hipGetLastError());
-        PJOK(hipStreamSynchronize(st));
+        HIPOK(hipGetLastError());
+        HIPOK(hipStreamSynchronize(st));
         if (hres[1] == 0) {
             outputs();
             if (rounds_out) *rounds_out = hres[2];
             return hres[0];
         }
     }
-    PJOK(hipMemsetAsync(D + o_pick, 0xFF, 4 * (size_t)nq, st));
+    HIPOK(hipMemsetAsync(D + o_pick, 0xFF, 4 * (size_t)nq, st));
     if (n) hipLaunchKernelGGL(k_proj_cells, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, f,
                               (const orbhip_kp*)(D + o_kps), (int*)(D + o_cell));
     hipLaunchKernelGGL(k_proj_prep_local, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, f, nq, pc,
@@ -1616,7 +1517,7 @@ int proj_search_local(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_loc
         hipLaunchKernelGGL(k_proj_finish, dim3(1), dim3(1024), 0, st, nq, 0, (const float*)nullptr,
                            (const orbhip_kp*)(D + o_kps), (const int*)(D + o_pick), (int*)(D + o_out + ob.match),
                            (int*)(D + o_out + ob.res));
-        PJOK(hipMemcpyAsync(H + o_out, D + o_out, ob.bytes, hipMemcpyDeviceToHost, st));
+        HIPOK(hipMemcpyAsync(H + o_out, D + o_out, ob.bytes, hipMemcpyDeviceToHost, st));
         return 0;
     };
     const int rounds = run_rounds(ws, f, nq, 1, nnratio, D, o_q, o_kps, o_kd, o_cell, dcl, o_own, o_qd, o_pick, o_chg,
@@ -1651,33 +1552,32 @@ int init_search(ProjWorkspace* ws, const orbhip_init_frame* F1, const orbhip_ini
     // the kernel's static LDS (histogram) comes on top of the dynamic 150 KiB envelope
     static LdsAttrOnce attr;   // per device, thread-safe (dev_attr.h)
     static const void* const fs[] = {(const void*)k_init_greedy, (const void*)k_init_finish};
-    PJOK(attr.ensure(fs, 2, 152 * 1024));
-    Layout lay;
-    const size_t o_k1 = lay.add(sizeof(orbhip_kp) * n1), o_d1 = lay.add(32 * (size_t)n1);
-    const size_t o_k2 = lay.add(sizeof(orbhip_kp) * std::max(n2, 1)), o_d2 = lay.add(32 * (size_t)std::max(n2, 1));
-    const size_t o_prev = lay.add(8 * (size_t)n1), o_in_end = lay.off;
-    const size_t o_match = lay.add(4 * (size_t)n1), o_cnt = lay.add(16), o_out_end = lay.off;
-    const size_t o_slot = lay.add(4 * (size_t)std::max(n2, 1)), o_ql = lay.add(4 * (size_t)n1);
-    const size_t o_len = lay.add(4 * ((size_t)n1 + 1)), o_list = lay.add(4 * (size_t)std::max(nq0, 1) * list_cap);
-    const size_t o_topk = lay.add(4 * (size_t)kInitK * (((size_t)std::max(nq0, 1) + 3) & ~size_t(3)));
-    const size_t o_need = lay.add(4 * (size_t)std::max(nq0, 1));
+    HIPOK(attr.ensure(fs, 2, 152 * 1024));
+    // uploaded: [F1 keypoints | F1 descriptors | F2 keypoints | F2 descriptors | prev_matched], read
+    // back: [matches | counts], then device only: the slots, lists and claim tables of the rounds
+    StageLayout lay(256);
+    const size_t o_k1 = lay.take(sizeof(orbhip_kp) * n1), o_d1 = lay.take(32 * (size_t)n1);
+    const size_t o_k2 = lay.take(sizeof(orbhip_kp) * std::max(n2, 1)), o_d2 = lay.take(32 * (size_t)std::max(n2, 1));
+    const size_t o_prev = lay.take(8 * (size_t)n1), o_in_end = lay.total();
+    const size_t o_match = lay.take(4 * (size_t)n1), o_cnt = lay.take(16), o_out_end = lay.total();
+    const size_t o_slot = lay.take(4 * (size_t)std::max(n2, 1)), o_ql = lay.take(4 * (size_t)n1);
+    const size_t o_len = lay.take(4 * ((size_t)n1 + 1)), o_list = lay.take(4 * (size_t)std::max(nq0, 1) * list_cap);
+    const size_t o_topk = lay.take(4 * (size_t)kInitK * (((size_t)std::max(nq0, 1) + 3) & ~size_t(3)));
+    const size_t o_need = lay.take(4 * (size_t)std::max(nq0, 1));
     const int cap = std::min(kInitMaxRounds, nq0 + 2);
-    const size_t o_cnt3 = lay.add(4 * 3 * (size_t)std::max(nr0, 1));
-    const size_t o_ent3 = lay.add(4 * 3 * (size_t)std::max(nr0, 1) * kInitC);
-    const size_t o_pick = lay.add(4 * (size_t)std::max(nq0, 1));
-    const size_t o_pout = lay.add(8 * (size_t)n1);
-    const size_t o_flags = lay.add(4 * ((size_t)cap + 1));
-    if (int rc = ensure(ws, lay.off)) return rc;
-    char* H = (char*)ws->h;
-    char* D = (char*)ws->d;
-    std::memcpy(H + o_k1, F1->kps, sizeof(orbhip_kp) * n1);
-    std::memcpy(H + o_d1, F1->desc, 32 * (size_t)n1);
-    if (n2) {
-        std::memcpy(H + o_k2, F2->kps, sizeof(orbhip_kp) * n2);
-        std::memcpy(H + o_d2, F2->desc, 32 * (size_t)n2);
-    }
-    std::memcpy(H + o_prev, prev_matched, 8 * (size_t)n1);
-    PJOK(upload_inputs(ws->hd, D, H, o_in_end, st));
+    const size_t o_cnt3 = lay.take(4 * 3 * (size_t)std::max(nr0, 1));
+    const size_t o_ent3 = lay.take(4 * 3 * (size_t)std::max(nr0, 1) * kInitC);
+    const size_t o_pick = lay.take(4 * (size_t)std::max(nq0, 1));
+    const size_t o_pout = lay.take(8 * (size_t)n1);
+    const size_t o_flags = lay.take(4 * ((size_t)cap + 1));
+    if (int rc = ensure(ws, lay.total())) return rc;
+    StageBlock& S = ws->s;
+    char* H = (char*)S.h;
+    char* D = (char*)S.d;
+    put_keyframe(S, o_k1, o_d1, 0, F1->kps, F1->desc, n1);
+    put_keyframe(S, o_k2, o_d2, 0, F2->kps, F2->desc, n2);
+    S.put(o_prev, prev_matched, 8 * (size_t)n1);
+    HIPOK(upload_inputs(S.hd, D, H, o_in_end, st));
     InitGeom g{};
     g.n1 = n1; g.n2 = n2;
     g.minx = F2->min_x; g.maxx = F2->max_x; g.miny = F2->min_y; g.maxy = F2->max_y;
@@ -1695,7 +1595,7 @@ int init_search(ProjWorkspace* ws, const orbhip_init_frame* F1, const orbhip_ini
                        (const uint8_t*)(D + o_d1), dk2, (const uint8_t*)(D + o_d2), (const float*)(D + o_prev),
                        (const int*)(D + o_slot), (const int*)(D + o_ql), (const int*)counts, (uint32_t*)(D + o_list),
                        (int*)(D + o_len), (uint32_t*)(D + o_topk), (int*)(D + o_need));
-    PJOK(hipGetLastError());
+    HIPOK(hipGetLastError());
     // parallel rounds, launched init_ahead at a time with the finish and the read-back behind them
     const int* hflags = (const int*)(H + o_flags);
     const dim3 gq((unsigned)std::max(1, (nq0 + 15) / 16));
@@ -1711,11 +1611,11 @@ int init_search(ProjWorkspace* ws, const orbhip_init_frame* F1, const orbhip_ini
                            check_orientation, dk2, (const int*)(D + o_slot), (const int*)(D + o_ql),
                            (const int*)counts, (const uint32_t*)(D + o_pick), (const float*)(D + o_prev),
                            (int32_t*)(D + o_match), (float*)(D + o_pout), counts + 2);
-        PJOK(hipGetLastError());
-        PJOK(hipMemcpyAsync(H + o_match, D + o_match, o_out_end - o_match, hipMemcpyDeviceToHost, st));
-        PJOK(hipMemcpyAsync(H + o_pout, D + o_pout, 8 * (size_t)n1, hipMemcpyDeviceToHost, st));
-        PJOK(hipMemcpyAsync(H + o_flags, flags, 4 * ((size_t)cap + 1), hipMemcpyDeviceToHost, st));
-        PJOK(hipStreamSynchronize(st));
+        HIPOK(hipGetLastError());
+        HIPOK(hipMemcpyAsync(H + o_match, D + o_match, o_out_end - o_match, hipMemcpyDeviceToHost, st));
+        HIPOK(hipMemcpyAsync(H + o_pout, D + o_pout, 8 * (size_t)n1, hipMemcpyDeviceToHost, st));
+        HIPOK(hipMemcpyAsync(H + o_flags, flags, 4 * ((size_t)cap + 1), hipMemcpyDeviceToHost, st));
+        HIPOK(hipStreamSynchronize(st));
         if (hflags[0]) break;   // a rank overflowed its claim slots: the chain decides
         for (int j = 0; j < R && !done; j++)
             if (hflags[1 + r + j] == 0) {
@@ -1734,9 +1634,9 @@ int init_search(ProjWorkspace* ws, const orbhip_init_frame* F1, const orbhip_ini
                        (const int*)(D + o_slot), (const int*)(D + o_ql), (const int*)counts,
                        (const uint32_t*)(D + o_list), (const int*)(D + o_len), (const uint32_t*)(D + o_topk),
                        (const int*)(D + o_need), (int32_t*)(D + o_match), (float*)(D + o_prev), counts + 2);
-    PJOK(hipGetLastError());
-    PJOK(hipMemcpyAsync(H + o_prev, D + o_prev, o_out_end - o_prev, hipMemcpyDeviceToHost, st));
-    PJOK(hipStreamSynchronize(st));
+    HIPOK(hipGetLastError());
+    HIPOK(hipMemcpyAsync(H + o_prev, D + o_prev, o_out_end - o_prev, hipMemcpyDeviceToHost, st));
+    HIPOK(hipStreamSynchronize(st));
     std::memcpy(matches12, H + o_match, 4 * (size_t)n1);
     std::memcpy(prev_matched, H + o_prev, 8 * (size_t)n1);
     return ((int*)(H + o_cnt))[2];

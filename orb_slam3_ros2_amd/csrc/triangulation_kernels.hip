@@ -20,26 +20,34 @@
 // kernel gets without the dynamic-LDS attribute (160 KiB per CU).
 #include <hip/hip_runtime.h>
 
+#include <vector>
+
+#include "geom.h"
 #include "orbhip_device.h"
 #include "orbhip_kernels.h"
+#include "stage.h"
+
+#define HIPOK(x) ORBHIP_HIPOK(" triangulation", x)
 
 namespace orbhip {
 
-// ---- host: per-pair geometry (all fp32, every operation in the order written; no FMA) ----
-static void tri_rot(const float* q, float* R) {   // Eigen's toRotationMatrix, as proj_kernels.hip
-    const float tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];
-    const float twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
-    const float txx = tx * q[0], txy = ty * q[0], txz = tz * q[0];
-    const float tyy = ty * q[1], tyz = tz * q[1], tzz = tz * q[2];
-    R[0] = 1 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
-    R[3] = txy + twz; R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
-}
+constexpr int kTriMax = 2048;     // features per keyframe (LDS-resident keys, 16-bit indices)
+constexpr int kTriMaxPairs = 64;  // neighbours per call
+struct TriSide {                  // one keyframe in the call's staging block (device pointers)
+    const orbhip_kp* kps;
+    const uint8_t* desc;          // n x 32
+    const int32_t* node;
+    const double* weight;
+    const uint8_t* has_mp;
+    int n, pad;
+};
+struct TriGeom { float F[9]; float ep[2]; float pad; };   // F12 row-major, epipole in image 2
 
+// ---- host: per-pair geometry (all fp32, every operation in the order written; no FMA) ----
 void tri_geometry(const orbhip_tri_keyframe& k1, const orbhip_tri_keyframe& k2, float* F, float* ep) {
     float R1[9], R2[9], R12[9], t12[3], Cw[3], C2[3], E[9], G[9];
-    tri_rot(k1.pose_q, R1);
-    tri_rot(k2.pose_q, R2);
+    quat_to_matrix(k1.pose_q, R1);
+    quat_to_matrix(k2.pose_q, R2);
     const float* t1 = k1.pose_t;
     const float* t2 = k2.pose_t;
     for (int i = 0; i < 3; i++)
@@ -72,11 +80,6 @@ void tri_geometry(const orbhip_tri_keyframe& k1, const orbhip_tri_keyframe& k2, 
 }
 
 // ---- device ----
-__device__ __forceinline__ int tri_ham(uint4 a, uint4 b, uint4 c, uint4 d) {
-    return __popc(a.x ^ c.x) + __popc(a.y ^ c.y) + __popc(a.z ^ c.z) + __popc(a.w ^ c.w) + __popc(b.x ^ d.x) +
-           __popc(b.y ^ d.y) + __popc(b.z ^ d.z) + __popc(b.w ^ d.w);
-}
-
 constexpr int kTriOrderThreads = 256;
 struct TriOrderLds {
     unsigned long long raw[kTriMax];
@@ -207,7 +210,7 @@ __global__ __launch_bounds__(kTriThreads) void k_tri_search(const TriSide* __res
             for (int k = 0; k < 4; k++) {   // past the bucket's end: its last entry again, not used below
                 idx2v[k] = S.bucket[min(c + k, c1 - 1)];
                 const uint4* d2 = (const uint4*)(N.desc + (int64_t)idx2v[k] * 32);
-                distv[k] = tri_ham(da, db, d2[0], d2[1]);
+                distv[k] = hamming256(da, db, d2[0], d2[1]);
             }
 #pragma unroll
             for (int k = 0; k < 4; k++) {
@@ -268,13 +271,98 @@ __global__ __launch_bounds__(kTriThreads) void k_tri_search(const TriSide* __res
     if (tid == 0) nmatches[b] = S.total;
 }
 
-void launch_tri_search(const TriSide* sides, const TriGeom* geom, int n1, int B, const float* scale_factors,
-                       const float* level_sigma2, unsigned long long* keys1, int32_t* m1, int check_orientation,
-                       int32_t* match12, int32_t* nmatches, hipStream_t st) {
+// ---- host ----
+// sides[0] = KF1, sides[1 + b] = neighbour b; keys1: kTriMax entries, m1: 1 (both written by the pre-pass)
+static void launch_tri_search(const TriSide* sides, const TriGeom* geom, int n1, int B, const float* scale_factors,
+                              const float* level_sigma2, unsigned long long* keys1, int32_t* m1,
+                              int check_orientation, int32_t* match12, int32_t* nmatches, hipStream_t st) {
     const unsigned order_wgs = (unsigned)((n1 + kTriOrderThreads - 1) / kTriOrderThreads);
     ORBHIP_LAUNCH(k_tri_order, dim3(order_wgs), dim3(kTriOrderThreads), 0, st, sides, keys1, m1);
     ORBHIP_LAUNCH(k_tri_search, dim3((unsigned)B), dim3(kTriThreads), 0, st, sides, geom, scale_factors, level_sigma2,
                   (const unsigned long long*)keys1, (const int32_t*)m1, check_orientation, match12, nmatches);
+}
+
+static int tri_check_side(const orbhip_tri_keyframe& k, int n_levels) {
+    if (k.n < 0) return ORBHIP_ERR_ARG;
+    if (k.n > kTriMax) return ORBHIP_ERR_UNSUPPORTED;
+    if (k.n == 0) return ORBHIP_OK;
+    if (!k.kps || !k.desc || !k.node || !k.weight || !k.has_mp) return ORBHIP_ERR_ARG;
+    for (int i = 0; i < k.n; i++)
+        if (k.kps[i].octave < 0 || k.kps[i].octave >= n_levels) return ORBHIP_ERR_ARG;
+    return ORBHIP_OK;
+}
+
+int tri_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_tri_keyframe* kf1,
+               const orbhip_tri_keyframe* nbrs, int B, const float* scale_factors, const float* level_sigma2,
+               int n_levels, int check_orientation, int32_t* match12, int32_t* nmatches) {
+    if (!kf1 || B < 0) return ORBHIP_ERR_ARG;
+    if (B == 0) return 0;
+    if (B > kTriMaxPairs) return ORBHIP_ERR_UNSUPPORTED;
+    if (!nbrs || !nmatches || !scale_factors || !level_sigma2 || n_levels <= 0) return ORBHIP_ERR_ARG;
+    int rc = tri_check_side(*kf1, n_levels);
+    for (int b = 0; b < B && rc == ORBHIP_OK; b++) rc = tri_check_side(nbrs[b], n_levels);
+    if (rc != ORBHIP_OK) return rc;
+    const int n1 = kf1->n;
+    for (int b = 0; b < B; b++) nmatches[b] = 0;
+    if (n1 == 0) return 0;
+    if (!match12) return ORBHIP_ERR_ARG;
+    // one block, the same layout on the host (pinned) and the device:
+    // [sides (1 + B) | geometry B | scale factors | sigma2 | per keyframe: kps desc node weight has_mp]
+    // then device only [KF1 keys | m1 | match12 B x n1, nmatches B]; the last segment is read back
+    StageLayout lay(16);
+    const size_t o_sides = lay.take((size_t)(1 + B) * sizeof(TriSide));
+    const size_t o_geom = lay.take((size_t)B * sizeof(TriGeom));
+    const size_t o_sf = lay.take((size_t)n_levels * 4), o_s2 = lay.take((size_t)n_levels * 4);
+    struct SideOff { size_t kps, desc, node, weight, mp; };
+    std::vector<SideOff> so(1 + B);
+    for (int s = 0; s <= B; s++) {
+        const size_t n = (size_t)(s ? nbrs[s - 1].n : n1);
+        so[s] = {lay.take(n * sizeof(orbhip_kp)), lay.take(n * 32), lay.take(n * 4), lay.take(n * 8), lay.take(n)};
+    }
+    const size_t up_bytes = lay.total();
+    const size_t o_keys = lay.take((size_t)kTriMax * 8), o_m1 = lay.take(4);
+    const size_t back_bytes = (size_t)B * n1 * 4 + (size_t)B * 4;   // nmatches directly behind match12
+    const size_t o_match = lay.take(back_bytes);
+    HIPOK(S.ensure(lay.total(), up_bytes + back_bytes + 16));
+    uint8_t* const d = S.d;
+    uint8_t* const h = S.h;
+    TriSide* sides = (TriSide*)(h + o_sides);
+    TriGeom* geom = (TriGeom*)(h + o_geom);
+    for (int s = 0; s <= B; s++) {
+        const orbhip_tri_keyframe& k = s ? nbrs[s - 1] : *kf1;
+        const size_t n = (size_t)k.n;
+        sides[s] = {(const orbhip_kp*)(d + so[s].kps), d + so[s].desc, (const int32_t*)(d + so[s].node),
+                    (const double*)(d + so[s].weight), d + so[s].mp, k.n, 0};
+        put_keyframe(S, so[s].kps, so[s].desc, 0, k.kps, k.desc, n);
+        S.put(so[s].node, k.node, n * 4);
+        S.put(so[s].weight, k.weight, n * 8);
+        S.put(so[s].mp, k.has_mp, n);
+        if (s) {
+            geom[s - 1].pad = 0.f;
+            tri_geometry(*kf1, k, geom[s - 1].F, geom[s - 1].ep);
+        }
+    }
+    S.put(o_sf, scale_factors, (size_t)n_levels * 4);
+    S.put(o_s2, level_sigma2, (size_t)n_levels * 4);
+    HIPOK(hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
+    (void)hipGetLastError();
+    {
+        const StageScope scope(timer);
+        timer.begin(7, st);
+        launch_tri_search((const TriSide*)(d + o_sides), (const TriGeom*)(d + o_geom), n1, B, (const float*)(d + o_sf),
+                          (const float*)(d + o_s2), (unsigned long long*)(d + o_keys), (int32_t*)(d + o_m1),
+                          check_orientation, (int32_t*)(d + o_match), (int32_t*)(d + o_match + (size_t)B * n1 * 4), st);
+        timer.end(7, st);
+    }
+    HIPOK(hipGetLastError());
+    uint8_t* const hb = h + up_bytes;   // the read-back lies behind the upload in the pinned image
+    HIPOK(hipMemcpyAsync(hb, d + o_match, back_bytes, hipMemcpyDeviceToHost, st));
+    HIPOK(hipStreamSynchronize(st));
+    std::memcpy(match12, hb, (size_t)B * n1 * 4);
+    std::memcpy(nmatches, hb + (size_t)B * n1 * 4, (size_t)B * 4);
+    int total = 0;
+    for (int b = 0; b < B; b++) total += nmatches[b];
+    return total;
 }
 
 }  // namespace orbhip

@@ -23,6 +23,15 @@ def test_host_adapter_compiles_and_links():
     _build()
 
 
+def test_stage_layout_offsets():
+    """StageLayout (csrc/stage.h), host only: aligned non-decreasing offsets, zero-byte segments,
+    hand-computed 16- and 256-byte layouts, the total as the aligned end."""
+    _build()
+    r = subprocess.run([os.path.join(CPP, "build", "stage_layout_check")], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "stage layout OK" in r.stdout
+
+
 def _unpack(d):
     z = np.load(os.path.join(GOLD, "frame_320x240_s5.npz"))
     z["image"].astype(np.uint8).tofile(os.path.join(d, "image.u8"))

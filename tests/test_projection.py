@@ -148,6 +148,78 @@ def test_proj_frame_view_tracks_pose_and_arrays():
 
 
 @pytest.mark.gpu
+def test_one_staging_block_across_projection_init_and_pose_calls(oracle):
+    """The projection searches and SearchForInitialization stage into ONE block per context, and
+    PoseOptimization uploads through the same helper into its own: a small LastFrame search (4
+    queries x 8 keypoints), a one-frame PoseOptimization of 10 edges, SearchLocalPoints at 300 points
+    x 400 keypoints (the block grows), SearchForInitialization at 50 x 50 (reused, larger than
+    needed), the pose again, the first search again. Every result equals the oracle's (the pose
+    within the existing PoseOptimization tolerance) and, bit for bit, the same call on a fresh context."""
+    from orb_slam3_ros2_amd import Optimizer, ORBmatcher
+    from orb_slam3_ros2_amd._lib import Context
+    from orb_slam3_ros2_amd.synthetic import synthetic_init_pair, synthetic_pose_problem
+    small = synthetic_projection_scene(n_kp=8, n_mp=4, seed=60)
+    big = synthetic_projection_scene(n_kp=400, n_mp=300, seed=61)
+    k1, d1, k2, d2, prev = (a[:50] for a in synthetic_init_pair(n1=120, seed=62))
+    assert len(k1) == 50 and len(k2) == 50 and len(prev) == 50
+    prob, _ = synthetic_pose_problem(n=10, outlier_frac=0.2, seed=63)
+
+    def last(ctx):
+        s = small
+        return ORBmatcher(0.9, True, ctx=ctx).SearchByProjectionLastFrame(
+            _frame(s), s["points"], s["mp_desc"], s["last_octave"], s["last_angle"], 15.0)
+
+    def local(ctx):
+        s = big
+        return ORBmatcher(0.8, False, ctx=ctx).SearchLocalPoints(
+            _frame(s), s["points"], s["normals"], s["min_dist"], s["max_dist"], s["mp_desc"], s["skip"], th=3.0)
+
+    def init(ctx):
+        return ORBmatcher(0.9, True, ctx=ctx).SearchForInitialization(k1, d1, k2, d2, prev, 100)
+
+    def pose(ctx):
+        r = Optimizer(ctx=ctx).PoseOptimization(prob)
+        return r.n_inliers, r.outlier, r.pose_q, r.pose_t
+
+    s = small
+    want_last = oracle.search_by_projection_last(_frame(s), s["points"], s["mp_desc"], s["last_octave"],
+                                                 s["last_angle"], 15.0, True)
+    s = big
+    want_local = oracle.search_local_points(_frame(s), s["points"], s["normals"], s["min_dist"], s["max_dist"],
+                                            s["mp_desc"], s["skip"], th=3.0, nnratio=0.8)
+    want_init = oracle.search_for_initialization(k1, d1, k2, d2, prev, 100, 0.9, True)
+    want_pose = oracle.pose_optimization(prob)
+    assert want_local[0] > 0 and want_init[0] > 0                      # not vacuous
+
+    def same(a, b):
+        return len(a) == len(b) and all(np.array_equal(x, y) for x, y in zip(a, b))
+
+    def check_pose(got):
+        assert got[0] == want_pose["n_inliers"] and np.array_equal(got[1], want_pose["outlier"])
+        qa, qb = got[2] / np.linalg.norm(got[2]), want_pose["pose_q"] / np.linalg.norm(want_pose["pose_q"])
+        assert 1.0 - abs(float(np.dot(qa, qb))) < 1e-8
+        assert np.abs(got[3] - want_pose["pose_t"]).max() <= 1e-4 * max(1.0, float(np.abs(want_pose["pose_t"]).max()))
+
+    shared = Context()
+    try:
+        for step, (call, want) in enumerate([(last, want_last), (pose, None), (local, want_local), (init, want_init),
+                                             (pose, None), (last, want_last)]):
+            got = call(shared)
+            fresh = Context()
+            try:
+                alone = call(fresh)
+            finally:
+                fresh.close()
+            assert same(got, alone), step
+            if want is None:
+                check_pose(got)
+            else:
+                assert same(got, want), step
+    finally:
+        shared.close()
+
+
+@pytest.mark.gpu
 def test_pose_change_between_searches(oracle):
     """The same ProjFrame searched, its Tcw changed in place (PoseOptimization), searched again:
     the second search uses the new pose (oracle on the same frame)."""

@@ -211,6 +211,45 @@ def test_search_equals_fuse_sim3_where_no_best_keypoint_is_shared(ctx):
     assert np.array_equal(mdist[match >= 0], dist[0][match >= 0]) and (mdist[match < 0] == 256).all()
 
 
+def test_one_staging_block_across_fuse_and_sim3_calls():
+    """Fuse, Fuse with a Sim3 and the Sim3 projection search stage into ONE block per context: Fuse at
+    B = 1, 3 points, 5 keypoints; SearchByProjectionSim3 at 200 points x 300 keypoints (the block
+    grows); FuseSim3 at B = 3, 40 points, 60 keypoints (the block is reused, larger than needed); the
+    first Fuse call again. Every result equals the restatement and the same call on a fresh context."""
+    small = synthetic_fuse_scene(5, 3, 1, seed=31)
+    big = synthetic_sim3_scene(300, 200, seed=32, th=4.0, ratio=1.0)
+    mid = synthetic_fuse_scene(60, 40, 3, seed=33)
+    assert small["points"].shape[0] == 3 and [k.kps.shape[0] for k in small["kfs"]] == [5]
+    assert big["points"].shape[0] == 200 and big["kf"].kps.shape[0] == 300
+    want_small = F.fuse_scene(dict(small, ratios=None))[:4]
+    want_big = S.search_scene(big)
+    want_mid = S.fuse_sim3(mid["kfs"], mid["points"], mid["normals"], mid["min_dist"], mid["max_dist"], mid["mp_desc"],
+                           4.0, mid["skip"], mid["pair_skip"])[:4]
+    assert want_big[0] > 20 and want_mid[0].sum() > 0                  # not vacuous
+
+    def fuse(c):
+        s = small
+        return ORBmatcher(0.6, True, ctx=c).Fuse(s["kfs"], s["points"], s["normals"], s["min_dist"], s["max_dist"],
+                                                 s["mp_desc"], s["inv_level_sigma2"], s["th"], s["skip"], s["pair_skip"])
+
+    steps = [(fuse, want_small, _assert_fuse_equal),
+             (lambda c: _mirror(c, big), want_big, _assert_search_equal),
+             (lambda c: _fuse_mirror(c, mid, th=4.0), want_mid, _assert_fuse_equal),
+             (fuse, want_small, _assert_fuse_equal)]
+    shared = Context()
+    try:
+        for call, want, check in steps:
+            got = call(shared)
+            check(got, want)
+            fresh = Context()
+            try:
+                check(call(fresh), got)
+            finally:
+                fresh.close()
+    finally:
+        shared.close()
+
+
 # ---- arguments ----
 
 def _blank_like(kf, n=0, **kw):
