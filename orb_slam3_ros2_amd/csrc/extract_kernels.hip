@@ -2516,23 +2516,6 @@ void launch_fast(const ExtractPlan* dP, const ExtractPlan& hP, const CellGeom* c
 #undef ORBHIP_FAST_LAUNCH
 }
 
-size_t octree_lds_bytes(const ExtractPlan& hP, const OctreeCfg& cfg) {
-    size_t off = 0;
-    auto carve = [&](size_t bytes) { off += (bytes + 15) & ~size_t(15); };
-    const size_t NC = cfg.node_cap;
-    carve(64 * 4);
-    for (int b = 0; b < 2; b++) { carve(NC * 8); carve(NC * 4); carve(NC * 4); carve(NC * 4); }
-    carve(NC * 16); carve(NC * 16); carve(NC * 8);
-    carve(NC * 4); carve(NC * 4); carve(NC * 4); carve(NC * 4);
-    carve((size_t)cfg.sort_cap * 8);
-    carve((size_t)cfg.sort_cap * 8);
-    carve((size_t)(hP.max_cells_level + 1) * 4);
-    carve((size_t)(hP.max_cells_level + 1) * 4);
-    carve((size_t)cfg.key_cap * 4);
-    carve((size_t)cfg.key_cap * 2);
-    return off;
-}
-
 void launch_octree(const ExtractPlan* dP, const ExtractPlan& hP, const CellGeom* cells, const uint16_t* otab,
                    const uint32_t* cand, const uint32_t* cprim,
                    const int* cand_cnt, const int* cand_off, uint32_t* kscratch, uint16_t* nscratch, LevelKp* lvl_kp,

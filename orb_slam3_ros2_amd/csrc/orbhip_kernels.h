@@ -22,15 +22,6 @@ struct FrameBufs {
 };
 constexpr int kStampStride = 8192;   // == StageTimer::kCap
 
-struct OctreeCfg {
-    int node_cap;          // LDS node capacity (>= max list size of any level)
-    int sort_cap;          // power of two >= node_cap
-    int key_cap;           // keys kept in LDS when a level has <= key_cap candidates
-    int lap0, lap1;        // vLappingArea
-    int fast;              // 1: pyramid division first (sweep path as its fallback); 0: sweep path only
-    int max_dh;            // deepest pyramid level allowed (<= 6; tests lower it to force the fallback)
-};
-
 // Live timing of one pipeline stage. The kernels launched between begin() and end() carry the
 // timer's event pair (hipExtLaunchKernelGGL: the first launch the start event, every launch the
 // stop event), so a pair spans the first kernel's start to the last kernel's end on the device:
@@ -116,7 +107,6 @@ struct CandPack {
 constexpr int kCandPrim = 16;
 void launch_fast(const ExtractPlan* dP, const ExtractPlan& hP, const CellGeom* cells, const FrameBufs& fb, int B,
                  uint32_t* cand, int* cand_cnt, int* err, hipStream_t st, int nt_hint = 0, CandPack cp = {});
-size_t octree_lds_bytes(const ExtractPlan& hP, const OctreeCfg& cfg);
 bool octree_set_lds_limit(size_t bytes);
 void launch_octree(const ExtractPlan* dP, const ExtractPlan& hP, const CellGeom* cells, const uint16_t* otab,
                    const uint32_t* cand, const uint32_t* cprim,
@@ -151,6 +141,23 @@ void launch_match_bf(const uint8_t* q, const float* qa, int nq, const uint8_t* t
                      int th_low, float ratio, int check_orientation, int32_t* match, int32_t* best,
                      int32_t* second, int32_t* nmatch, void* part, hipStream_t st,
                      int* sync);
+// the matcher's scratch and its entry points (match.cpp)
+class GraphCache;
+struct MatchWorkspace;
+MatchWorkspace* match_ws_create();
+void match_ws_destroy(MatchWorkspace* ws);
+int match_bf_host(MatchWorkspace* ws, const uint8_t* q, const float* qa, int nq, const uint8_t* t, const float* ta,
+                  int nt, int th_low, float ratio, int check_orientation, int32_t* match, int32_t* best_d,
+                  int32_t* second_d, hipStream_t st);
+int match_pairs_device(MatchWorkspace* ws, GraphCache& graphs, StageTimer& timer, const orbhip_kp* d_kps,
+                       const uint8_t* d_desc, const int32_t* d_n, int B, int cap, int th_low, float ratio,
+                       int check_orientation, int32_t* d_match, int32_t* d_best, int32_t* d_second, int32_t* d_nmatch,
+                       hipStream_t st);
+int match_frames_device(MatchWorkspace* ws, GraphCache& graphs, StageTimer& timer, const orbhip_kp* d_q_kps,
+                        const uint8_t* d_q_desc, const int32_t* d_nq, const orbhip_kp* d_t_kps,
+                        const uint8_t* d_t_desc, const int32_t* d_nt, int cap, int th_low, float ratio,
+                        int check_orientation, int32_t* d_match, int32_t* d_best, int32_t* d_second,
+                        int32_t* d_nmatch, hipStream_t st);
 
 // ---- bag of words ----
 constexpr int kBowMax = 2048;   // features per frame in SearchByBoW (LDS-resident FeatureVectors)
@@ -178,6 +185,23 @@ size_t search_bow_lds_bytes();
 bool search_bow_set_lds_limit();
 void launch_search_bow(const BowSide& K, const BowSide& F, float ratio, int check_orientation, int th_low,
                        int32_t* match, int32_t* nmatch, hipStream_t st);
+// the vocabulary (struct orbhip_vocab) and the host calls with their scratch (bow.cpp)
+int vocab_build(int device, int k, int L, int scoring, int weighting, int N, const int32_t* parent,
+                const uint8_t* is_leaf, const uint8_t* desc32, const double* weight, orbhip_vocab** out);
+int vocab_load_text(int device, const char* path, orbhip_vocab** out);
+int vocab_destroy(orbhip_vocab* v);
+int vocab_info(const orbhip_vocab* v, int32_t* k, int32_t* L, int32_t* n_nodes, int32_t* n_words);
+struct BowWorkspace;
+BowWorkspace* bow_ws_create();
+void bow_ws_destroy(BowWorkspace* ws);
+int bow_transform_host(BowWorkspace* ws, const orbhip_vocab* v, const uint8_t* desc, int n, int levelsup,
+                       int32_t* word, int32_t* node, double* weight, hipStream_t st);
+int bow_transform_device(const orbhip_vocab* v, const uint8_t* d_desc, const int32_t* d_n, int B, int cap,
+                         int levelsup, int32_t* d_word, int32_t* d_node, double* d_weight, hipStream_t st);
+int search_bow_host(BowWorkspace* ws, const uint8_t* kf_desc, const float* kf_angle, const int32_t* kf_node,
+                    const double* kf_weight, const uint8_t* kf_valid, int nkf, const uint8_t* f_desc,
+                    const float* f_angle, const int32_t* f_node, const double* f_weight, int nf, float ratio,
+                    int check_orientation, int th_low, int32_t* match, hipStream_t st);
 
 // ---- host calls that stage one block (stage.h), next to their kernels ----
 struct StageBlock;
@@ -206,6 +230,14 @@ void launch_bgr2gray(const uint8_t* src, int B, int w, int h, int sstride, int64
 void launch_undistort_kps(const orbhip_kp* kps, const int32_t* n_arr, int n_fixed, int B, int cap,
                           const orbhip_pinhole& cam, orbhip_kp* out, hipStream_t st);
 void launch_image_bounds(int cols, int rows, const orbhip_pinhole& cam, float* bounds, hipStream_t st);
+// the host calls with their scratch (camera.cpp)
+struct CameraWorkspace;
+CameraWorkspace* camera_ws_create();
+void camera_ws_destroy(CameraWorkspace* ws);
+int undistort_kps_host(CameraWorkspace* ws, const orbhip_pinhole& cam, const orbhip_kp* kps, int n, orbhip_kp* out,
+                       hipStream_t st);
+int image_bounds_host(CameraWorkspace* ws, const orbhip_pinhole& cam, int cols, int rows, float bounds[4],
+                      hipStream_t st);
 
 // ---- test hooks ----
 constexpr int kTraceStride = 16384;   // u64 per kernel id in the timing trace (orbhip_device.h)

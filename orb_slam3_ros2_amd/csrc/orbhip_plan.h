@@ -1,7 +1,14 @@
 // Host/device shared plan structures for one (image size, ORB params) configuration.
-// Built once on the host per image size (orbhip_api.cpp::build_plan) and uploaded.
+// Built once on the host per image size (extract_plan.cpp::plan_build_host) and uploaded by the
+// extraction workspace (extract.cpp). Plain C++ as well: the planner is compiled without HIP.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
+
+#if !defined(__HIPCC__) && !defined(__host__)
+#define __host__
+#define __device__
+#endif
 
 namespace orbhip {
 
@@ -78,5 +85,32 @@ struct LevelKp {
     int16_t x, y;        // level pixel
     uint32_t srl;        // score (8) | inside-lapping-area (1) << 8 | rank among same-flag kps (23) << 9
 };
+
+struct OctreeCfg {
+    int node_cap;          // LDS node capacity (>= max list size of any level)
+    int sort_cap;          // power of two >= node_cap
+    int key_cap;           // keys kept in LDS when a level has <= key_cap candidates
+    int lap0, lap1;        // vLappingArea
+    int fast;              // 1: pyramid division first (sweep path as its fallback); 0: sweep path only
+    int max_dh;            // deepest pyramid level allowed (<= 6; tests lower it to force the fallback)
+};
+
+// k_octree's dynamic LDS: the carve of its arrays (host side: the planner sizes key_cap by it)
+inline size_t octree_lds_bytes(const ExtractPlan& hP, const OctreeCfg& cfg) {
+    size_t off = 0;
+    auto carve = [&](size_t bytes) { off += (bytes + 15) & ~size_t(15); };
+    const size_t NC = cfg.node_cap;
+    carve(64 * 4);
+    for (int b = 0; b < 2; b++) { carve(NC * 8); carve(NC * 4); carve(NC * 4); carve(NC * 4); }
+    carve(NC * 16); carve(NC * 16); carve(NC * 8);
+    carve(NC * 4); carve(NC * 4); carve(NC * 4); carve(NC * 4);
+    carve((size_t)cfg.sort_cap * 8);
+    carve((size_t)cfg.sort_cap * 8);
+    carve((size_t)(hP.max_cells_level + 1) * 4);
+    carve((size_t)(hP.max_cells_level + 1) * 4);
+    carve((size_t)cfg.key_cap * 4);
+    carve((size_t)cfg.key_cap * 2);
+    return off;
+}
 
 }  // namespace orbhip

@@ -308,6 +308,100 @@ def test_graph_replay_recomputes_from_current_inputs(monkeypatch):
     assert lib().orbhip_launch_graphs(ext.ctx.handle) >= 2   # extract + match replayed
 
 
+@pytest.mark.parametrize("flow", [False, True])
+def test_graph_replay_across_scratch_growth(monkeypatch, flow):
+    """ORBHIP_GRAPH=1 on one context and one stream at 320x240: three extractions at B = 1 (the
+    third replays a captured graph), three at B = 3 (every scratch buffer regrows), then three at
+    B = 1 again from the same input and output buffers. A graph captured before the growth holds
+    freed scratch addresses and must not be replayed after it: every result equals the direct
+    null-stream launch. flow: the k_resize-free batch pyramid (ORBHIP_NO_CONE=1 ORBHIP_RZ_FLOW=1),
+    whose flag buffer regrows with the batch as well."""
+    import torch
+    from orb_slam3_ros2_amd import ORBextractor
+    from orb_slam3_ros2_amd._lib import lib
+    monkeypatch.setenv("ORBHIP_GRAPH", "1")
+    if flow:
+        monkeypatch.setenv("ORBHIP_NO_CONE", "1")
+        monkeypatch.setenv("ORBHIP_RZ_FLOW", "1")
+    ext = ORBextractor(1000, 1.2, 8, 20, 7)
+    H, W = 240, 320
+    cap = ext.max_keypoints(W, H)
+    dev = torch.device("cuda:0")
+    imgs = [torch.from_numpy(synthetic_frame(90 + i, W, H)).to(dev) for i in range(11)]
+
+    def bufs(B):
+        return (torch.zeros((B, cap, 6), dtype=torch.float32, device=dev),
+                torch.zeros((B, cap, 32), dtype=torch.uint8, device=dev),
+                torch.zeros(B, dtype=torch.int32, device=dev), torch.zeros(B, dtype=torch.int32, device=dev))
+
+    st = torch.cuda.Stream()
+    fb = {B: torch.empty((B, H, W), dtype=torch.uint8, device=dev) for B in (1, 3)}
+    got = {B: bufs(B) for B in (1, 3)}
+    ref = {B: bufs(B) for B in (1, 3)}
+    call = 0
+    for B in (1, 3, 1):
+        for _ in range(3):
+            frames = torch.stack([imgs[(call + f) % len(imgs)] for f in range(B)])
+            call += 1
+            fb[B].copy_(frames)
+            torch.cuda.synchronize()
+            with torch.cuda.stream(st):
+                ext.extract_batch_device(fb[B], *got[B], stream=st)
+            st.synchronize()
+            ext.extract_batch_device(frames.contiguous(), *ref[B], stream=None)   # null stream: direct
+            torch.cuda.synchronize()
+            (kps, desc, n, mono), (rk, rd, rn, rmono) = got[B], ref[B]
+            assert torch.equal(n, rn) and torch.equal(mono, rmono), (B, call)
+            assert int(rn.min()) > 0
+            for f in range(B):
+                c = int(rn[f])
+                assert torch.equal(kps[f, :c], rk[f, :c]) and torch.equal(desc[f, :c], rd[f, :c]), (B, call, f)
+    assert lib().orbhip_launch_graphs(ext.ctx.handle) >= 1
+
+
+def test_one_context_interleaved_calls(oracle):
+    """One context through every family that keeps scratch of its own, in turn: extract, match_bf,
+    bow_transform, undistort_keypoints, image_bounds, a larger extract, match_bf again. Each
+    result is the oracle's, and the two match_bf results are equal: a buffer shared between two
+    families would show as one of them reading what another left."""
+    import bow_numpy as BN
+    from orb_slam3_ros2_amd import ORBextractor, ORBmatcher, ORBVocabulary, PinholeCamera
+    from orb_slam3_ros2_amd._lib import KP_DTYPE
+    from orb_slam3_ros2_amd.camera import MILKV
+    ext = ORBextractor(1000, 1.2, 8, 20, 7)
+    mt = ORBmatcher(0.9, True, ctx=ext.ctx)
+    vocab = BN.ragged_vocabulary(5, 5, 1)
+    voc = ORBVocabulary(vocab, ctx=ext.ctx)
+    cam = PinholeCamera.milkv(ctx=ext.ctx)
+    camt = tuple(MILKV[k] for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2"))
+    assert camt[4] != 0.0
+    rng = np.random.default_rng(77)
+    q = rng.integers(0, 256, (300, 32), dtype=np.uint8)
+    t = np.concatenate([q[:200] ^ rng.integers(0, 2, (200, 32), dtype=np.uint8),
+                        rng.integers(0, 256, (57, 32), dtype=np.uint8)])
+    qa = rng.uniform(0, 360, 300).astype(np.float32)
+    ta = rng.uniform(0, 360, 257).astype(np.float32)
+    feats = BN.transform_feats(vocab, 300, seed=3)
+    kp = np.zeros(500, KP_DTYPE)
+    kp["x"] = rng.uniform(0, 640, 500).astype(np.float32)
+    kp["y"] = rng.uniform(0, 360, 500).astype(np.float32)
+    kp["octave"] = rng.integers(0, 8, 500)
+
+    _check(ext, oracle, synthetic_frame(13, 320, 240))
+    m1 = mt.match_bf(q, qa, t, ta)
+    on, om, ob, os_ = oracle.match_bf(q, qa, t, ta, 50, 0.9, True)
+    assert m1[0] == on and np.array_equal(m1[1], om) and np.array_equal(m1[2], ob) and np.array_equal(m1[3], os_)
+    assert on > 0
+    w, nd, wt = voc.transform_features(feats, 2)
+    ow, ond, owt = oracle.bow_transform(vocab, feats, 2)
+    assert np.array_equal(w, ow) and np.array_equal(nd, ond) and np.array_equal(wt, owt)
+    assert np.array_equal(cam.UndistortKeyPoints(kp), oracle.undistort_keypoints(kp, camt))
+    assert cam.ComputeImageBounds() == oracle.image_bounds(640, 360, camt)
+    _check(ext, oracle, synthetic_frame(14, 384, 288))
+    m2 = mt.match_bf(q, qa, t, ta)
+    assert m2[0] == m1[0] and all(np.array_equal(a, b) for a, b in zip(m1[1:], m2[1:]))
+
+
 def _clustered_frame(seed, w=640, h=480):
     """A flat frame with one small, dense, high-contrast patch: thousands of FAST candidates in
     a few cells, so DistributeOctTree divides deep (far below the pyramid depth) around it."""
