@@ -201,7 +201,8 @@ int orbhip_frontend_context(orbhip_frontend* fe, int j, orbhip_ctx** out);
  * descriptor, 5 Hamming top-2, 6 rotation filter, 7 SearchForTriangulation: the ordering pre-pass
  * and the search of one call form one pair, 8 Fuse and Fuse with a Sim3: the grid build and the
  * search of one call form one pair, 9 SearchByProjection with a Sim3: the grid build, the search and
- * the resolve of one call form one pair). orbhip_profile_collect synchronises and
+ * the resolve of one call form one pair, 10 the triangulation of CreateNewMapPoints: k_tri_points
+ * and k_tri_claim of one call form one pair). orbhip_profile_collect synchronises and
  * returns the summed duration (ms) and the number of bracketed launches, then resets. The one-launch
  * pyramid (k_pyr_cone) and the octree also time themselves on the device (first workgroup start to
  * last workgroup end, s_memrealtime: the span rocprofv3's kernel trace reports); their stages
@@ -482,6 +483,59 @@ int orbhip_search_for_triangulation(orbhip_ctx* ctx, const orbhip_tri_keyframe* 
                                     const orbhip_tri_keyframe* nbrs, int B,
                                     const float* scale_factors, const float* level_sigma2, int n_levels,
                                     int check_orientation, int32_t* match12, int32_t* nmatches);
+
+/* ---- new map points: the triangulation of CreateNewMapPoints ----------
+ * U:src/LocalMapping.cc::CreateNewMapPoints after SearchForTriangulation, monocular: per neighbour
+ * the baseline / median-depth gate, per matched pair the parallax, GeometricTools::Triangulate,
+ * the depth, reprojection (5.991 * mvLevelSigma2), distance and scale-ratio checks, in the order
+ * and arithmetic DESIGN.md "CreateNewMapPoints" fixes (fp32 in a fixed order; the null vector of
+ * the 4x4 system by an fp64 one-sided Jacobi). status per (neighbour, KF1 feature): 0 no match,
+ * 1 accepted, 2 cosParallax <= 0, 3 parallax too low, 4 null vector with w == 0, 5 / 6 not in
+ * front of KF1 / KF2, 7 / 8 reprojection error in KF1 / KF2, 9 on a camera centre, 10 beyond
+ * far_threshold, 11 scale ratio. Every status is that of the state at call time. A KF1 feature
+ * accepted by several neighbours becomes ONE new point, that of the first such neighbour
+ * (first[idx1]): with check_orientation = 0 this is upstream's sequential result, where a feature
+ * triangulated with one neighbour has a MapPoint when the next neighbour is searched. The new
+ * points are listed in upstream's creation order: ascending neighbour, then ascending idx1. */
+typedef struct {
+    double cos_parallax_max;   /* 0.9998 (0.9996 in the inertial mode) */
+    float ratio_factor;        /* 1.5f * mfScaleFactor */
+    float far_threshold;       /* mThFarPoints; <= 0: off */
+} orbhip_tri_params;
+
+typedef struct {               /* caller-allocated; optional members may be NULL */
+    int32_t* match12;          /* B x n1, optional */
+    int32_t* nmatches;         /* B */
+    uint8_t* gated;            /* B: 1 = baseline / median depth below 0.01, neighbour not searched */
+    uint8_t* status;           /* B x n1, optional */
+    float* x3d_all;            /* B x n1 x 3, optional: the point of every pair whose status is 1 or >= 5
+                                  (zeros elsewhere); diagnostics and tests, not copied back when NULL */
+    int32_t* first;            /* n1: the first neighbour that accepts the feature, or -1 */
+    int32_t* nnew;             /* B: new points per neighbour */
+    int32_t* new_nbr;          /* n1 entries each; the first <return value> are the list, */
+    int32_t* new_idx1;         /* the rest -1 (new_x3d: n1 x 3, the rest 0) */
+    int32_t* new_idx2;
+    float* new_x3d;
+} orbhip_new_points;
+
+/* SearchForTriangulation of KF1 against the B neighbours and the triangulation of its matches in
+ * one call: one upload, the kernels back to back on the context's stream (match12 never leaves
+ * the device in between), one read-back. median_depth: B values (KF2's ComputeSceneMedianDepth(2))
+ * or NULL = no neighbour is gated; a gated neighbour is not uploaded. Returns the number of new
+ * points. The envelope and the error codes are those of orbhip_search_for_triangulation. */
+int orbhip_create_new_map_points(orbhip_ctx* ctx, const orbhip_tri_keyframe* kf1,
+                                 const orbhip_tri_keyframe* nbrs, int B, const float* median_depth,
+                                 const float* scale_factors, const float* level_sigma2, int n_levels,
+                                 int check_orientation, const orbhip_tri_params* params,
+                                 orbhip_new_points* out);
+
+/* The same from given matches (match12_in: B x n1, idx2 or -1): no search, no gating (gated = 0).
+ * Only n, kps, the intrinsics and the pose of a keyframe are read (desc, node, weight, has_mp may
+ * be NULL). An entry of match12_in outside [-1, n2): ORBHIP_ERR_ARG. */
+int orbhip_triangulate_matches(orbhip_ctx* ctx, const orbhip_tri_keyframe* kf1,
+                               const orbhip_tri_keyframe* nbrs, int B, const int32_t* match12_in,
+                               const float* scale_factors, const float* level_sigma2, int n_levels,
+                               const orbhip_tri_params* params, orbhip_new_points* out);
 
 /* ---- map point fusion: Fuse ------------------------------------------
  * U:src/ORBmatcher.cc::Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, const float th,

@@ -169,6 +169,85 @@ public:
         return std::vector<int>(nm.begin(), nm.end());
     }
 
+    // One new MapPoint of LocalMapping::CreateNewMapPoints: pKF1's feature idx1 and neighbour nbr's
+    // feature idx2 triangulated to x3D.
+    struct NewMapPoint {
+        int nbr, idx1, idx2;
+        float x3D[3];
+    };
+
+    // the mandatory outputs of an orbhip_new_points (the optional diagnostics stay NULL)
+    struct NewPointsBuffers {
+        std::vector<int32_t> nmatches, nnew, first, nbr, idx1, idx2;
+        std::vector<uint8_t> gated;
+        std::vector<float> x3d;
+        orbhip_new_points out{};
+        NewPointsBuffers(int B, int n1)
+            : nmatches(std::max(B, 1)), nnew(std::max(B, 1)), first(std::max(n1, 1)), nbr(std::max(n1, 1)),
+              idx1(std::max(n1, 1)), idx2(std::max(n1, 1)), gated(std::max(B, 1)), x3d(3 * (size_t)std::max(n1, 1)) {
+            out.nmatches = nmatches.data(); out.gated = gated.data(); out.first = first.data();
+            out.nnew = nnew.data(); out.new_nbr = nbr.data(); out.new_idx1 = idx1.data();
+            out.new_idx2 = idx2.data(); out.new_x3d = x3d.data();
+        }
+        std::vector<NewMapPoint> list(int n) const {
+            std::vector<NewMapPoint> v((size_t)n);
+            for (int k = 0; k < n; k++) v[k] = {nbr[k], idx1[k], idx2[k], {x3d[3 * k], x3d[3 * k + 1], x3d[3 * k + 2]}};
+            return v;
+        }
+    };
+
+    // U:src/LocalMapping.cc::CreateNewMapPoints from the search to the accepted points, in one call
+    // (INTEGRATION.md §3d): SearchForTriangulation of pKF1 against every neighbour with this matcher's
+    // mbCheckOrientation, then the triangulation and its checks. vMedianDepth: empty, or per neighbour
+    // its ComputeSceneMedianDepth(2) (the baseline gate; vbGated, optional, receives who it stopped).
+    // ratioFactor = 1.5f * mfScaleFactor; thFarPoints <= 0: off. Returns the new points in upstream's
+    // creation order (ascending neighbour, then ascending idx1), one per feature of pKF1: that of the
+    // first neighbour that accepts it.
+    std::vector<NewMapPoint> CreateNewMapPoints(orbhip_ctx* ctx, const orbhip_tri_keyframe& kf1,
+                                                const std::vector<orbhip_tri_keyframe>& neighbours,
+                                                const std::vector<float>& vMedianDepth,
+                                                const std::vector<float>& mvScaleFactors,
+                                                const std::vector<float>& mvLevelSigma2, float ratioFactor,
+                                                double cosParallaxMax = 0.9998, float thFarPoints = 0.f,
+                                                std::vector<uint8_t>* vbGated = nullptr) const {
+        const int B = (int)neighbours.size();
+        if (!vMedianDepth.empty() && (int)vMedianDepth.size() != B) check(ORBHIP_ERR_ARG, "CreateNewMapPoints");
+        NewPointsBuffers buf(B, kf1.n);
+        const orbhip_tri_params prm{cosParallaxMax, ratioFactor, thFarPoints};
+        const int n = orbhip_create_new_map_points(ctx, &kf1, neighbours.data(), B,
+                                                   vMedianDepth.empty() ? nullptr : vMedianDepth.data(),
+                                                   mvScaleFactors.data(), mvLevelSigma2.data(),
+                                                   (int)std::min(mvScaleFactors.size(), mvLevelSigma2.size()),
+                                                   mbCheckOrientation ? 1 : 0, &prm, &buf.out);
+        check(n, "orbhip_create_new_map_points");
+        if (vbGated) vbGated->assign(buf.gated.begin(), buf.gated.begin() + B);
+        return buf.list(n);
+    }
+
+    // The same from given matches (vMatches12[b][i] = neighbour b's feature or -1): no search, no gate.
+    std::vector<NewMapPoint> TriangulateMatches(orbhip_ctx* ctx, const orbhip_tri_keyframe& kf1,
+                                                const std::vector<orbhip_tri_keyframe>& neighbours,
+                                                const std::vector<std::vector<int>>& vMatches12,
+                                                const std::vector<float>& mvScaleFactors,
+                                                const std::vector<float>& mvLevelSigma2, float ratioFactor,
+                                                double cosParallaxMax = 0.9998, float thFarPoints = 0.f) const {
+        const int B = (int)neighbours.size(), n1 = std::max(kf1.n, 0);
+        if ((int)vMatches12.size() != B) check(ORBHIP_ERR_ARG, "TriangulateMatches");
+        std::vector<int32_t> flat((size_t)B * n1 + 1, -1);
+        for (int b = 0; b < B; b++) {
+            if ((int)vMatches12[b].size() != n1) check(ORBHIP_ERR_ARG, "TriangulateMatches");
+            std::copy(vMatches12[b].begin(), vMatches12[b].end(), flat.begin() + (size_t)b * n1);
+        }
+        NewPointsBuffers buf(B, kf1.n);
+        const orbhip_tri_params prm{cosParallaxMax, ratioFactor, thFarPoints};
+        const int n = orbhip_triangulate_matches(ctx, &kf1, neighbours.data(), B, flat.data(), mvScaleFactors.data(),
+                                                 mvLevelSigma2.data(),
+                                                 (int)std::min(mvScaleFactors.size(), mvLevelSigma2.size()), &prm,
+                                                 &buf.out);
+        check(n, "orbhip_triangulate_matches");
+        return buf.list(n);
+    }
+
     // U:src/ORBmatcher.cc::Fuse(pKF, vpMapPoints, th) of every keyframe against the same MapPoints in
     // one call (LocalMapping::SearchInNeighbors). vbPairSkip: empty, or B x n with
     // pMP->IsInKeyFrame(keyframe b). vBestIdx[b][m] = the keypoint of keyframe b MapPoint m fuses into,

@@ -99,6 +99,18 @@ class TriKeyFrameC(ctypes.Structure):
                 ("pose_q", ctypes.c_float * 4), ("pose_t", ctypes.c_float * 3)]
 
 
+class TriParamsC(ctypes.Structure):
+    _fields_ = [("cos_parallax_max", ctypes.c_double), ("ratio_factor", ctypes.c_float),
+                ("far_threshold", ctypes.c_float)]
+
+
+class NewPointsC(ctypes.Structure):
+    _fields_ = [("match12", ctypes.c_void_p), ("nmatches", ctypes.c_void_p), ("gated", ctypes.c_void_p),
+                ("status", ctypes.c_void_p), ("x3d_all", ctypes.c_void_p), ("first", ctypes.c_void_p),
+                ("nnew", ctypes.c_void_p), ("new_nbr", ctypes.c_void_p), ("new_idx1", ctypes.c_void_p),
+                ("new_idx2", ctypes.c_void_p), ("new_x3d", ctypes.c_void_p)]
+
+
 class KfdbQueryC(ctypes.Structure):
     _fields_ = [("query_id", ctypes.c_int64), ("words", ctypes.c_void_p), ("values", ctypes.c_void_p),
                 ("n", ctypes.c_int32), ("covis", ctypes.c_void_p), ("kf_map", ctypes.c_void_p),
@@ -122,7 +134,8 @@ EXPORTED = ["orbhip_abi_version", "orbhip_create", "orbhip_destroy", "orbhip_lev
             "orbhip_bow_transform", "orbhip_bow_transform_device", "orbhip_search_bow",
             "orbhip_pose_optimization", "orbhip_pose_optimization_batch", "orbhip_search_by_projection_last",
             "orbhip_search_local_points", "orbhip_search_for_initialization",
-            "orbhip_triangulation_geometry", "orbhip_search_for_triangulation", "orbhip_fuse",
+            "orbhip_triangulation_geometry", "orbhip_search_for_triangulation",
+            "orbhip_create_new_map_points", "orbhip_triangulate_matches", "orbhip_fuse",
             "orbhip_fuse_sim3", "orbhip_search_by_projection_sim3",
             "orbhip_kfdb_create", "orbhip_kfdb_destroy", "orbhip_kfdb_add", "orbhip_kfdb_erase",
             "orbhip_kfdb_detect_relocalization", "orbhip_kfdb_detect_nbest",
@@ -191,6 +204,11 @@ def lib():
     L.orbhip_triangulation_geometry.argtypes = [ctypes.POINTER(TriKeyFrameC), ctypes.POINTER(TriKeyFrameC), vp, vp]
     L.orbhip_search_for_triangulation.argtypes = [vp, ctypes.POINTER(TriKeyFrameC), ctypes.POINTER(TriKeyFrameC), i32,
                                                   vp, vp, i32, i32, vp, vp]
+    L.orbhip_create_new_map_points.argtypes = [vp, ctypes.POINTER(TriKeyFrameC), ctypes.POINTER(TriKeyFrameC), i32, vp,
+                                               vp, vp, i32, i32, ctypes.POINTER(TriParamsC),
+                                               ctypes.POINTER(NewPointsC)]
+    L.orbhip_triangulate_matches.argtypes = [vp, ctypes.POINTER(TriKeyFrameC), ctypes.POINTER(TriKeyFrameC), i32, vp,
+                                             vp, vp, i32, ctypes.POINTER(TriParamsC), ctypes.POINTER(NewPointsC)]
     L.orbhip_fuse.argtypes = [vp, ctypes.POINTER(FrameC), i32, ctypes.POINTER(LocalPointsC), vp, vp, f32, vp, vp, vp,
                               vp]
     L.orbhip_fuse_sim3.argtypes = [vp, ctypes.POINTER(FrameC), i32, ctypes.POINTER(LocalPointsC), vp, f32, vp, vp, vp, vp]

@@ -248,7 +248,7 @@ int orbhip_launch_graphs(orbhip_ctx* c) {
 }
 
 int orbhip_profile_stage(orbhip_ctx* c, int stage) {
-    if (!c || stage < 0 || stage > 9) return ORBHIP_ERR_ARG;
+    if (!c || stage < 0 || stage > 10) return ORBHIP_ERR_ARG;
     HIPOK(hipSetDevice(c->device));
     StageTimer& t = c->timer;
     if (!t.created) {
@@ -530,6 +530,26 @@ int orbhip_search_for_triangulation(orbhip_ctx* c, const orbhip_tri_keyframe* kf
     HIPOK(hipSetDevice(c->device));
     return tri_search(c->tri_stage, c->timer, c->stream, kf1, nbrs, B, scale_factors, level_sigma2, n_levels,
                       check_orientation, match12, nmatches);
+}
+
+// ---- CreateNewMapPoints: the search and the triangulation of its matches, or the latter alone ----
+int orbhip_create_new_map_points(orbhip_ctx* c, const orbhip_tri_keyframe* kf1, const orbhip_tri_keyframe* nbrs, int B,
+                                 const float* median_depth, const float* scale_factors, const float* level_sigma2,
+                                 int n_levels, int check_orientation, const orbhip_tri_params* params,
+                                 orbhip_new_points* out) {
+    if (!c) return ORBHIP_ERR_ARG;
+    HIPOK(hipSetDevice(c->device));
+    return tri_new_points(c->tri_stage, c->timer, c->stream, kf1, nbrs, B, nullptr, median_depth, scale_factors,
+                          level_sigma2, n_levels, check_orientation, params, out);
+}
+
+int orbhip_triangulate_matches(orbhip_ctx* c, const orbhip_tri_keyframe* kf1, const orbhip_tri_keyframe* nbrs, int B,
+                               const int32_t* match12_in, const float* scale_factors, const float* level_sigma2,
+                               int n_levels, const orbhip_tri_params* params, orbhip_new_points* out) {
+    if (!c || !match12_in) return ORBHIP_ERR_ARG;
+    HIPOK(hipSetDevice(c->device));
+    return tri_new_points(c->tri_stage, c->timer, c->stream, kf1, nbrs, B, match12_in, nullptr, scale_factors,
+                          level_sigma2, n_levels, 0, params, out);
 }
 
 // ---- Fuse: B keyframes against one list of MapPoints ----

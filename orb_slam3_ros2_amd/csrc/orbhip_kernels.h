@@ -213,6 +213,12 @@ int tri_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_tr
                int n_levels, int check_orientation, int32_t* match12, int32_t* nmatches);
 // Fuse (fuse_kernels.hip); stage 8. chi2 = false: Fuse with a Sim3 (no chi-square gate,
 // inv_level_sigma2 unused)
+// CreateNewMapPoints (triangulation_kernels.hip): the search above (match12_in == nullptr; stage 7) or
+// the given matches, then k_tri_points and k_tri_claim (stage 10)
+int tri_new_points(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_tri_keyframe* kf1,
+                   const orbhip_tri_keyframe* nbrs, int B, const int32_t* match12_in, const float* median_depth,
+                   const float* scale_factors, const float* level_sigma2, int n_levels, int check_orientation,
+                   const orbhip_tri_params* params, orbhip_new_points* out);
 int fuse_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_frame* kfs, int B,
                 const orbhip_local_points* mps, const uint8_t* pair_skip, bool chi2, const float* inv_level_sigma2,
                 float th, int32_t* best_idx, int32_t* best_dist, int32_t* level, int32_t* nfused);

@@ -15,6 +15,8 @@
 //                     the order inside a bucket. Nothing is sequential across KF1 features
 //                     (vbMatched2 is never set upstream): only the rotation histogram and the count
 //                     are per-pair reductions.
+//   k_tri_points, k_tri_claim   the triangulation of the matches and the list of new points
+//                     (CreateNewMapPoints; the second half of this file)
 // LDS of k_tri_search: 3 x 8 KiB (KF1 nodes, bucket counts, bucket starts) + 4 KiB bucket entries +
 // 4 KiB matches + 2 KiB bins + counters = 34.2 KiB static (k_tri_order: 16 KiB), below the 64 KiB a
 // kernel gets without the dynamic-LDS attribute (160 KiB per CU).
@@ -292,6 +294,28 @@ static int tri_check_side(const orbhip_tri_keyframe& k, int n_levels) {
     return ORBHIP_OK;
 }
 
+// A keyframe's segments in the staging block: the keypoints, and for the search (full) its
+// descriptors, FeatureVector and MapPoint flags; tri_put_side copies them in and returns the
+// device's view of them.
+struct TriSideOff { size_t kps, desc, node, weight, mp; };
+static TriSideOff tri_take_side(StageLayout& lay, size_t n, bool full) {
+    TriSideOff o{lay.take(n * sizeof(orbhip_kp)), 0, 0, 0, 0};
+    if (full) o = {o.kps, lay.take(n * 32), lay.take(n * 4), lay.take(n * 8), lay.take(n)};
+    return o;
+}
+static TriSide tri_put_side(StageBlock& S, const TriSideOff& o, const orbhip_tri_keyframe& k, bool full) {
+    const size_t n = (size_t)k.n;
+    uint8_t* const d = S.d;
+    S.put(o.kps, k.kps, n * sizeof(orbhip_kp));
+    if (!full) return {(const orbhip_kp*)(d + o.kps), nullptr, nullptr, nullptr, nullptr, k.n, 0};
+    S.put(o.desc, k.desc, n * 32);
+    S.put(o.node, k.node, n * 4);
+    S.put(o.weight, k.weight, n * 8);
+    S.put(o.mp, k.has_mp, n);
+    return {(const orbhip_kp*)(d + o.kps), d + o.desc, (const int32_t*)(d + o.node), (const double*)(d + o.weight),
+            d + o.mp, k.n, 0};
+}
+
 int tri_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_tri_keyframe* kf1,
                const orbhip_tri_keyframe* nbrs, int B, const float* scale_factors, const float* level_sigma2,
                int n_levels, int check_orientation, int32_t* match12, int32_t* nmatches) {
@@ -313,12 +337,8 @@ int tri_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_tr
     const size_t o_sides = lay.take((size_t)(1 + B) * sizeof(TriSide));
     const size_t o_geom = lay.take((size_t)B * sizeof(TriGeom));
     const size_t o_sf = lay.take((size_t)n_levels * 4), o_s2 = lay.take((size_t)n_levels * 4);
-    struct SideOff { size_t kps, desc, node, weight, mp; };
-    std::vector<SideOff> so(1 + B);
-    for (int s = 0; s <= B; s++) {
-        const size_t n = (size_t)(s ? nbrs[s - 1].n : n1);
-        so[s] = {lay.take(n * sizeof(orbhip_kp)), lay.take(n * 32), lay.take(n * 4), lay.take(n * 8), lay.take(n)};
-    }
+    std::vector<TriSideOff> so(1 + B);
+    for (int s = 0; s <= B; s++) so[s] = tri_take_side(lay, (size_t)(s ? nbrs[s - 1].n : n1), true);
     const size_t up_bytes = lay.total();
     const size_t o_keys = lay.take((size_t)kTriMax * 8), o_m1 = lay.take(4);
     const size_t back_bytes = (size_t)B * n1 * 4 + (size_t)B * 4;   // nmatches directly behind match12
@@ -330,13 +350,7 @@ int tri_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_tr
     TriGeom* geom = (TriGeom*)(h + o_geom);
     for (int s = 0; s <= B; s++) {
         const orbhip_tri_keyframe& k = s ? nbrs[s - 1] : *kf1;
-        const size_t n = (size_t)k.n;
-        sides[s] = {(const orbhip_kp*)(d + so[s].kps), d + so[s].desc, (const int32_t*)(d + so[s].node),
-                    (const double*)(d + so[s].weight), d + so[s].mp, k.n, 0};
-        put_keyframe(S, so[s].kps, so[s].desc, 0, k.kps, k.desc, n);
-        S.put(so[s].node, k.node, n * 4);
-        S.put(so[s].weight, k.weight, n * 8);
-        S.put(so[s].mp, k.has_mp, n);
+        sides[s] = tri_put_side(S, so[s], k, true);
         if (s) {
             geom[s - 1].pad = 0.f;
             tri_geometry(*kf1, k, geom[s - 1].F, geom[s - 1].ep);
@@ -362,6 +376,367 @@ int tri_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_tr
     std::memcpy(nmatches, hb + (size_t)B * n1 * 4, (size_t)B * 4);
     int total = 0;
     for (int b = 0; b < B; b++) total += nmatches[b];
+    return total;
+}
+
+// =====================================================================================
+// CreateNewMapPoints: the triangulation of the matches (DESIGN.md "CreateNewMapPoints")
+//   tri_camera   host, fp32, fixed operation order: R, t, Ow and the intrinsics of a keyframe
+//   k_tri_points one lane per (neighbour, KF1 feature): rays, parallax, the 4x4 system, its null
+//                vector by an fp64 one-sided Jacobi held in registers (U and V: 32 doubles, every
+//                index a constant), depth, reprojection, distance and scale-ratio checks
+//   k_tri_claim  one 1024-thread work-group: first[idx1] = the first neighbour that accepts the
+//                feature, the counts per neighbour, and the list in (neighbour, idx1) order: a
+//                wave per neighbour walks idx1 in 64s, a lane's place is the number of set lanes
+//                below it in the ballot (no atomics decide a position)
+// =====================================================================================
+struct TriCam { float R[9], t[3], Ow[3], fx, fy, cx, cy, pad; };
+
+static void tri_camera(const orbhip_tri_keyframe& k, TriCam& c) {
+    quat_to_matrix(k.pose_q, c.R);
+    for (int i = 0; i < 3; i++) c.t[i] = k.pose_t[i];
+    for (int i = 0; i < 3; i++) c.Ow[i] = -((c.R[i] * c.t[0] + c.R[3 + i] * c.t[1]) + c.R[6 + i] * c.t[2]);
+    c.fx = k.fx; c.fy = k.fy; c.cx = k.cx; c.cy = k.cy; c.pad = 0.f;
+}
+
+// one rotation of the one-sided Jacobi on the columns (P, Q) of U (4x4, row-major), applied to V too
+template <int P, int Q>
+__device__ __forceinline__ void tri_jacobi_pair(double (&U)[16], double (&V)[16]) {
+    const double a = ((U[P] * U[P] + U[4 + P] * U[4 + P]) + U[8 + P] * U[8 + P]) + U[12 + P] * U[12 + P];
+    const double b = ((U[Q] * U[Q] + U[4 + Q] * U[4 + Q]) + U[8 + Q] * U[8 + Q]) + U[12 + Q] * U[12 + Q];
+    const double g = ((U[P] * U[Q] + U[4 + P] * U[4 + Q]) + U[8 + P] * U[8 + Q]) + U[12 + P] * U[12 + Q];
+    if (g == 0.0) return;
+    const double zeta = (b - a) / (2.0 * g);
+    double t = 1.0 / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+    if (zeta < 0.0) t = -t;
+    const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const double x = U[4 * i + P], y = U[4 * i + Q];
+        U[4 * i + P] = c * x - s * y;
+        U[4 * i + Q] = s * x + c * y;
+        const double vx = V[4 * i + P], vy = V[4 * i + Q];
+        V[4 * i + P] = c * vx - s * vy;
+        V[4 * i + Q] = s * vx + c * vy;
+    }
+}
+
+// status of one matched pair (include/orbhip.h); X receives the point once it exists
+__device__ __forceinline__ int tri_point(const TriCam& c1, const TriCam& c2, const orbhip_kp& kp1, const orbhip_kp& kp2,
+                                         const float* __restrict__ scale_factors,
+                                         const float* __restrict__ level_sigma2, double cos_max, float ratio_factor,
+                                         float far, float X[3]) {
+    const float xn1x = (kp1.x - c1.cx) / c1.fx, xn1y = (kp1.y - c1.cy) / c1.fy;
+    const float xn2x = (kp2.x - c2.cx) / c2.fx, xn2y = (kp2.y - c2.cy) / c2.fy;
+    float r1[3], r2[3];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+        r1[i] = (c1.R[i] * xn1x + c1.R[3 + i] * xn1y) + c1.R[6 + i];
+        r2[i] = (c2.R[i] * xn2x + c2.R[3 + i] * xn2y) + c2.R[6 + i];
+    }
+    const float dot = (r1[0] * r2[0] + r1[1] * r2[1]) + r1[2] * r2[2];
+    const float nn1 = (r1[0] * r1[0] + r1[1] * r1[1]) + r1[2] * r1[2];
+    const float nn2 = (r2[0] * r2[0] + r2[1] * r2[1]) + r2[2] * r2[2];
+    const float cosP = dot / (sqrtf(nn1) * sqrtf(nn2));
+    if (!(cosP > 0.0f)) return 2;
+    if (!((double)cosP < cos_max)) return 3;
+    double U[16], V[16];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {   // T = [R | t]
+        const float a0 = j < 3 ? c1.R[j] : c1.t[0], a1 = j < 3 ? c1.R[3 + j] : c1.t[1], a2 = j < 3 ? c1.R[6 + j] : c1.t[2];
+        const float b0 = j < 3 ? c2.R[j] : c2.t[0], b1 = j < 3 ? c2.R[3 + j] : c2.t[1], b2 = j < 3 ? c2.R[6 + j] : c2.t[2];
+        U[j] = (double)(xn1x * a2 - a0);
+        U[4 + j] = (double)(xn1y * a2 - a1);
+        U[8 + j] = (double)(xn2x * b2 - b0);
+        U[12 + j] = (double)(xn2y * b2 - b1);
+    }
+#pragma unroll
+    for (int i = 0; i < 16; i++) V[i] = (i % 5 == 0) ? 1.0 : 0.0;
+#pragma unroll 1
+    for (int sweep = 0; sweep < 6; sweep++) {
+        tri_jacobi_pair<0, 1>(U, V);
+        tri_jacobi_pair<0, 2>(U, V);
+        tri_jacobi_pair<0, 3>(U, V);
+        tri_jacobi_pair<1, 2>(U, V);
+        tri_jacobi_pair<1, 3>(U, V);
+        tri_jacobi_pair<2, 3>(U, V);
+    }
+    double best = ((U[0] * U[0] + U[4] * U[4]) + U[8] * U[8]) + U[12] * U[12];
+    double v0 = V[0], v1 = V[4], v2 = V[8], v3 = V[12];
+#pragma unroll
+    for (int k = 1; k < 4; k++) {
+        const double nk = ((U[k] * U[k] + U[4 + k] * U[4 + k]) + U[8 + k] * U[8 + k]) + U[12 + k] * U[12 + k];
+        if (nk < best) { best = nk; v0 = V[k]; v1 = V[4 + k]; v2 = V[8 + k]; v3 = V[12 + k]; }
+    }
+    if (v3 == 0.0) return 4;
+    const float x = (float)(v0 / v3), y = (float)(v1 / v3), z = (float)(v2 / v3);
+    X[0] = x; X[1] = y; X[2] = z;
+    const float z1 = ((c1.R[6] * x + c1.R[7] * y) + c1.R[8] * z) + c1.t[2];
+    if (z1 <= 0.0f) return 5;
+    const float z2 = ((c2.R[6] * x + c2.R[7] * y) + c2.R[8] * z) + c2.t[2];
+    if (z2 <= 0.0f) return 6;
+    {
+        const float px = ((c1.R[0] * x + c1.R[1] * y) + c1.R[2] * z) + c1.t[0];
+        const float py = ((c1.R[3] * x + c1.R[4] * y) + c1.R[5] * z) + c1.t[1];
+        const float e = ((c1.fx * px) / z1 + c1.cx) - kp1.x;
+        const float f = ((c1.fy * py) / z1 + c1.cy) - kp1.y;
+        if ((double)(e * e + f * f) > 5.991 * (double)level_sigma2[kp1.octave]) return 7;
+    }
+    {
+        const float px = ((c2.R[0] * x + c2.R[1] * y) + c2.R[2] * z) + c2.t[0];
+        const float py = ((c2.R[3] * x + c2.R[4] * y) + c2.R[5] * z) + c2.t[1];
+        const float e = ((c2.fx * px) / z2 + c2.cx) - kp2.x;
+        const float f = ((c2.fy * py) / z2 + c2.cy) - kp2.y;
+        if ((double)(e * e + f * f) > 5.991 * (double)level_sigma2[kp2.octave]) return 8;
+    }
+    const float d1x = x - c1.Ow[0], d1y = y - c1.Ow[1], d1z = z - c1.Ow[2];
+    const float d2x = x - c2.Ow[0], d2y = y - c2.Ow[1], d2z = z - c2.Ow[2];
+    const float dist1 = sqrtf((d1x * d1x + d1y * d1y) + d1z * d1z);
+    const float dist2 = sqrtf((d2x * d2x + d2y * d2y) + d2z * d2z);
+    if (dist1 == 0.0f || dist2 == 0.0f) return 9;
+    if (far > 0.0f && (dist1 >= far || dist2 >= far)) return 10;
+    const float ratioDist = dist2 / dist1;
+    const float ratioOctave = scale_factors[kp1.octave] / scale_factors[kp2.octave];
+    if (ratioDist * ratio_factor < ratioOctave || ratioDist > ratioOctave * ratio_factor) return 11;
+    return 1;
+}
+
+constexpr int kTriPointsThreads = 256;
+// pair = b * n1 + idx1 over the npairs = B x n1 pairs of the call; cams[0] = KF1, cams[1 + b] = neighbour b
+__global__ __launch_bounds__(kTriPointsThreads) void k_tri_points(
+    const TriSide* __restrict__ sides, const TriCam* __restrict__ cams, const float* __restrict__ scale_factors,
+    const float* __restrict__ level_sigma2, const int32_t* __restrict__ match12, int n1, int npairs, double cos_max,
+    float ratio_factor, float far, uint8_t* __restrict__ status, float* __restrict__ x3d_all) {
+    const int pair = blockIdx.x * kTriPointsThreads + threadIdx.x;
+    if (pair >= npairs) return;
+    const int b = pair / n1, idx1 = pair - b * n1;
+    const int idx2 = match12[pair];
+    int st = 0;
+    float X[3] = {0.f, 0.f, 0.f};
+    if (idx2 >= 0)
+        st = tri_point(cams[0], cams[1 + b], sides[0].kps[idx1], sides[1 + b].kps[idx2], scale_factors, level_sigma2,
+                       cos_max, ratio_factor, far, X);
+    status[pair] = (uint8_t)st;
+    x3d_all[3 * (int64_t)pair] = X[0];
+    x3d_all[3 * (int64_t)pair + 1] = X[1];
+    x3d_all[3 * (int64_t)pair + 2] = X[2];
+}
+
+// head: [first n1 | nnew B | total 1]; the lists hold n1 entries each (new_x3d: n1 x 3)
+__global__ __launch_bounds__(kTriThreads) void k_tri_claim(const uint8_t* __restrict__ status,
+                                                           const int32_t* __restrict__ match12,
+                                                           const float* __restrict__ x3d_all, int n1, int B,
+                                                           int32_t* __restrict__ first_out, int32_t* __restrict__ nnew,
+                                                           int32_t* __restrict__ total_out, int32_t* __restrict__ new_nbr,
+                                                           int32_t* __restrict__ new_idx1, int32_t* __restrict__ new_idx2,
+                                                           float* __restrict__ new_x3d) {
+    __shared__ short first[kTriMax];
+    __shared__ int cnt[kTriMaxPairs], base[kTriMaxPairs];
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    if (tid < kTriMaxPairs) cnt[tid] = 0;
+    __syncthreads();
+    for (int i = tid; i < n1; i += kTriThreads) {
+        int f = -1;
+        for (int b = 0; b < B; b++)
+            if (status[(int64_t)b * n1 + i] == 1) { f = b; break; }
+        first[i] = (short)f;
+        first_out[i] = f;
+        if (f >= 0) atomicAdd(&cnt[f], 1);   // a count: the same whatever the order
+    }
+    __syncthreads();
+    if (tid < 64) {
+        const int c = tid < B ? cnt[tid] : 0;
+        const int inc = wave_incl_scan(c);
+        base[tid] = inc - c;
+        if (tid < B) nnew[tid] = c;
+        if (tid == 63) *total_out = inc;
+    }
+    __syncthreads();
+    for (int b = wid; b < B; b += kTriThreads / 64) {   // b is wave-uniform
+        int run = base[b];
+        if (cnt[b] == 0) continue;
+        for (int i0 = 0; i0 < n1; i0 += 64) {
+            const int i = i0 + lane;
+            const bool mine = i < n1 && first[i] == b;
+            const unsigned long long m = __ballot(mine);
+            if (mine) {
+                const int pos = run + __popcll(m & ((1ull << lane) - 1ull));
+                const int64_t pair = (int64_t)b * n1 + i;
+                new_nbr[pos] = b;
+                new_idx1[pos] = i;
+                new_idx2[pos] = match12[pair];
+                new_x3d[3 * pos] = x3d_all[3 * pair];
+                new_x3d[3 * pos + 1] = x3d_all[3 * pair + 1];
+                new_x3d[3 * pos + 2] = x3d_all[3 * pair + 2];
+            }
+            run += __popcll(m);
+        }
+    }
+}
+
+// the keypoints alone (orbhip_triangulate_matches reads nothing else of a keyframe)
+static int tri_check_kps(const orbhip_tri_keyframe& k, int n_levels) {
+    if (k.n < 0) return ORBHIP_ERR_ARG;
+    if (k.n > kTriMax) return ORBHIP_ERR_UNSUPPORTED;
+    if (k.n == 0) return ORBHIP_OK;
+    if (!k.kps) return ORBHIP_ERR_ARG;
+    for (int i = 0; i < k.n; i++)
+        if (k.kps[i].octave < 0 || k.kps[i].octave >= n_levels) return ORBHIP_ERR_ARG;
+    return ORBHIP_OK;
+}
+
+int tri_new_points(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_tri_keyframe* kf1,
+                   const orbhip_tri_keyframe* nbrs, int B, const int32_t* match12_in, const float* median_depth,
+                   const float* scale_factors, const float* level_sigma2, int n_levels, int check_orientation,
+                   const orbhip_tri_params* params, orbhip_new_points* out) {
+    const bool search = match12_in == nullptr;
+    if (!kf1 || B < 0 || !params || !out) return ORBHIP_ERR_ARG;
+    if (B > kTriMaxPairs) return ORBHIP_ERR_UNSUPPORTED;
+    if ((B > 0 && (!nbrs || !out->nmatches || !out->gated || !out->nnew)) || !scale_factors || !level_sigma2 ||
+        n_levels <= 0)
+        return ORBHIP_ERR_ARG;
+    int rc = search ? tri_check_side(*kf1, n_levels) : tri_check_kps(*kf1, n_levels);
+    for (int b = 0; b < B && rc == ORBHIP_OK; b++)
+        rc = search ? tri_check_side(nbrs[b], n_levels) : tri_check_kps(nbrs[b], n_levels);
+    if (rc != ORBHIP_OK) return rc;
+    const int n1 = kf1->n;
+    if (n1 > 0 && (!out->first || !out->new_nbr || !out->new_idx1 || !out->new_idx2 || !out->new_x3d))
+        return ORBHIP_ERR_ARG;
+    if (!search)   // an index past the neighbour's keypoints would be read on the device
+        for (int b = 0; b < B; b++)
+            for (int i = 0; i < n1; i++) {
+                const int32_t m = match12_in[(size_t)b * n1 + i];
+                if (m < -1 || m >= nbrs[b].n) return ORBHIP_ERR_ARG;
+            }
+    const size_t pairs_all = (size_t)B * n1;
+    for (int b = 0; b < B; b++) out->nmatches[b] = out->nnew[b] = 0, out->gated[b] = 0;
+    for (int i = 0; i < n1; i++) out->first[i] = out->new_nbr[i] = out->new_idx1[i] = out->new_idx2[i] = -1;
+    if (n1) std::memset(out->new_x3d, 0, (size_t)n1 * 12);
+    if (out->match12) for (size_t i = 0; i < pairs_all; i++) out->match12[i] = -1;
+    if (out->status && pairs_all) std::memset(out->status, 0, pairs_all);
+    if (out->x3d_all && pairs_all) std::memset(out->x3d_all, 0, pairs_all * 12);
+    if (B == 0 || n1 == 0) return 0;
+    // the cameras, and the neighbours the baseline gate leaves (act): B scalar evaluations on the host
+    std::vector<TriCam> cam(1 + B);
+    tri_camera(*kf1, cam[0]);
+    int act[kTriMaxPairs], Ba = 0;
+    for (int b = 0; b < B; b++) {
+        tri_camera(nbrs[b], cam[1 + b]);
+        if (search && median_depth) {
+            const float dx = cam[1 + b].Ow[0] - cam[0].Ow[0], dy = cam[1 + b].Ow[1] - cam[0].Ow[1],
+                        dz = cam[1 + b].Ow[2] - cam[0].Ow[2];
+            const float baseline = sqrtf((dx * dx + dy * dy) + dz * dz);
+            const float r = baseline / median_depth[b];
+            if ((double)r < 0.01) { out->gated[b] = 1; continue; }
+        }
+        act[Ba++] = b;
+    }
+    if (Ba == 0) return 0;
+    const size_t npairs = (size_t)Ba * n1;
+    // upload: [sides (1 + Ba) | geometry Ba | cameras (1 + Ba) | scale factors | sigma2 | per keyframe: kps (and,
+    // for the search, desc node weight has_mp) | the given matches]; device only: [KF1 keys | m1];
+    // read back, as far as the caller asks: [first n1, nnew Ba, total | nmatches Ba | new_nbr | new_idx1 | new_idx2 |
+    // new_x3d | match12 (of the search) | status | x3d_all]
+    StageLayout lay(16);
+    const size_t o_sides = lay.take((size_t)(1 + Ba) * sizeof(TriSide));
+    const size_t o_geom = lay.take(search ? (size_t)Ba * sizeof(TriGeom) : 0);
+    const size_t o_cams = lay.take((size_t)(1 + Ba) * sizeof(TriCam));
+    const size_t o_sf = lay.take((size_t)n_levels * 4), o_s2 = lay.take((size_t)n_levels * 4);
+    std::vector<TriSideOff> so(1 + Ba);
+    for (int s = 0; s <= Ba; s++) so[s] = tri_take_side(lay, (size_t)(s ? nbrs[act[s - 1]].n : n1), search);
+    const size_t o_min = lay.take(search ? 0 : npairs * 4);
+    const size_t up_bytes = lay.total();
+    const size_t o_keys = lay.take(search ? (size_t)kTriMax * 8 : 0), o_m1 = lay.take(search ? 4 : 0);
+    const size_t o_head = lay.take((size_t)(n1 + Ba + 1) * 4);
+    const size_t o_nm = lay.take((size_t)Ba * 4);
+    const size_t o_nbr = lay.take((size_t)n1 * 4), o_i1 = lay.take((size_t)n1 * 4), o_i2 = lay.take((size_t)n1 * 4);
+    const size_t o_x = lay.take((size_t)n1 * 12);
+    size_t back_end = lay.off;
+    const size_t o_match = search ? lay.take(npairs * 4) : o_min;
+    if (search && out->match12) back_end = lay.off;
+    const size_t o_status = lay.take(npairs);
+    if (out->status) back_end = lay.off;
+    const size_t o_x3d = lay.take(npairs * 12);
+    if (out->x3d_all) back_end = lay.off;
+    const size_t back_bytes = back_end - o_head;
+    HIPOK(S.ensure(lay.total(), up_bytes + back_bytes + 16));
+    uint8_t* const d = S.d;
+    uint8_t* const h = S.h;
+    TriSide* sides = (TriSide*)(h + o_sides);
+    TriCam* cams = (TriCam*)(h + o_cams);
+    for (int s = 0; s <= Ba; s++) {
+        const orbhip_tri_keyframe& k = s ? nbrs[act[s - 1]] : *kf1;
+        cams[s] = cam[s ? 1 + act[s - 1] : 0];
+        sides[s] = tri_put_side(S, so[s], k, search);
+        if (search && s) {
+            TriGeom* geom = (TriGeom*)(h + o_geom);
+            geom[s - 1].pad = 0.f;
+            tri_geometry(*kf1, k, geom[s - 1].F, geom[s - 1].ep);
+        }
+    }
+    S.put(o_sf, scale_factors, (size_t)n_levels * 4);
+    S.put(o_s2, level_sigma2, (size_t)n_levels * 4);
+    if (!search) S.put(o_min, match12_in, npairs * 4);   // no neighbour is gated: the rows are the caller's
+    HIPOK(hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
+    (void)hipGetLastError();
+    int32_t* const d_head = (int32_t*)(d + o_head);
+    {
+        const StageScope scope(timer);
+        if (search) {
+            timer.begin(7, st);
+            launch_tri_search((const TriSide*)(d + o_sides), (const TriGeom*)(d + o_geom), n1, Ba,
+                              (const float*)(d + o_sf), (const float*)(d + o_s2), (unsigned long long*)(d + o_keys),
+                              (int32_t*)(d + o_m1), check_orientation, (int32_t*)(d + o_match), (int32_t*)(d + o_nm),
+                              st);
+            timer.end(7, st);
+        }
+        timer.begin(10, st);
+        const unsigned wgs = (unsigned)((npairs + kTriPointsThreads - 1) / kTriPointsThreads);
+        ORBHIP_LAUNCH(k_tri_points, dim3(wgs), dim3(kTriPointsThreads), 0, st, (const TriSide*)(d + o_sides),
+                      (const TriCam*)(d + o_cams), (const float*)(d + o_sf), (const float*)(d + o_s2),
+                      (const int32_t*)(d + o_match), n1, (int)npairs, params->cos_parallax_max, params->ratio_factor,
+                      params->far_threshold, d + o_status, (float*)(d + o_x3d));
+        ORBHIP_LAUNCH(k_tri_claim, dim3(1), dim3(kTriThreads), 0, st, (const uint8_t*)(d + o_status),
+                      (const int32_t*)(d + o_match), (const float*)(d + o_x3d), n1, Ba, d_head, d_head + n1,
+                      d_head + n1 + Ba, (int32_t*)(d + o_nbr), (int32_t*)(d + o_i1), (int32_t*)(d + o_i2),
+                      (float*)(d + o_x));
+        timer.end(10, st);
+    }
+    HIPOK(hipGetLastError());
+    uint8_t* const hb = h + up_bytes;   // the read-back lies behind the upload in the pinned image
+    HIPOK(hipMemcpyAsync(hb, d + o_head, back_bytes, hipMemcpyDeviceToHost, st));
+    HIPOK(hipStreamSynchronize(st));
+    auto back = [&](size_t o) { return hb + (o - o_head); };
+    const int32_t* r_head = (const int32_t*)back(o_head);
+    int total = r_head[n1 + Ba];
+    if (total < 0 || total > n1) return ORBHIP_ERR_DEVICE;
+    const int32_t *r_nm = (const int32_t*)back(o_nm), *r_nbr = (const int32_t*)back(o_nbr);
+    for (int i = 0; i < n1; i++) out->first[i] = (unsigned)r_head[i] >= (unsigned)Ba ? -1 : act[r_head[i]];
+    for (int a = 0; a < Ba; a++) {
+        const int b = act[a];
+        out->nnew[b] = r_head[n1 + a];
+        if (search) {
+            out->nmatches[b] = r_nm[a];
+        } else {
+            int c = 0;
+            for (int i = 0; i < n1; i++) c += match12_in[(size_t)b * n1 + i] >= 0;
+            out->nmatches[b] = c;
+        }
+        if (out->match12)
+            std::memcpy(out->match12 + (size_t)b * n1, search ? (const void*)(back(o_match) + (size_t)a * n1 * 4)
+                                                               : (const void*)(match12_in + (size_t)b * n1),
+                        (size_t)n1 * 4);
+        if (out->status) std::memcpy(out->status + (size_t)b * n1, back(o_status) + (size_t)a * n1, (size_t)n1);
+        if (out->x3d_all)
+            std::memcpy(out->x3d_all + (size_t)b * n1 * 3, back(o_x3d) + (size_t)a * n1 * 12, (size_t)n1 * 12);
+    }
+    for (int k = 0; k < total; k++) {
+        if ((unsigned)r_nbr[k] >= (unsigned)Ba) return ORBHIP_ERR_DEVICE;
+        out->new_nbr[k] = act[r_nbr[k]];
+    }
+    std::memcpy(out->new_idx1, back(o_i1), (size_t)total * 4);
+    std::memcpy(out->new_idx2, back(o_i2), (size_t)total * 4);
+    std::memcpy(out->new_x3d, back(o_x), (size_t)total * 12);
     return total;
 }
 

@@ -13,8 +13,8 @@ import ctypes
 
 import numpy as np
 
-from ._lib import (KP_DTYPE, FrameC, InitFrameC, LocalPointsC, ProjLastC, TriKeyFrameC, torch_stream, Context, check,
-                   lib, ptr)
+from ._lib import (KP_DTYPE, FrameC, InitFrameC, LocalPointsC, NewPointsC, ProjLastC, TriKeyFrameC, TriParamsC,
+                   torch_stream, Context, check, lib, ptr)
 
 
 class ORBmatcher:
@@ -188,6 +188,59 @@ class ORBmatcher:
               "orbhip_search_for_triangulation")
         return nm, m
 
+    def CreateNewMapPoints(self, kf1: "TriKeyFrame", neighbours, scale_factors, level_sigma2, median_depth=None,
+                           cos_parallax_max: float = 0.9998, ratio_factor=None, far_threshold: float = 0.0,
+                           diagnostics: bool = False) -> "NewPoints":
+        """SearchForTriangulation of kf1 against every neighbour and the triangulation and checks of
+        U:src/LocalMapping.cc::CreateNewMapPoints on its matches, in one call (orbhip_create_new_map_points).
+        median_depth: per neighbour its ComputeSceneMedianDepth(2), or None (no neighbour is gated);
+        ratio_factor: None = 1.5f * mvScaleFactors[1]; far_threshold <= 0: off. diagnostics: also
+        return match12, status and x3d_all (B x n1)."""
+        return self._new_points("orbhip_create_new_map_points", kf1, neighbours, scale_factors, level_sigma2, None,
+                                median_depth, cos_parallax_max, ratio_factor, far_threshold, diagnostics)
+
+    def TriangulateMatches(self, kf1: "TriKeyFrame", neighbours, match12, scale_factors, level_sigma2,
+                           cos_parallax_max: float = 0.9998, ratio_factor=None, far_threshold: float = 0.0,
+                           diagnostics: bool = False) -> "NewPoints":
+        """The triangulation and checks of CreateNewMapPoints on given matches (match12: B x n1, a
+        neighbour feature or -1): no search, no gating (orbhip_triangulate_matches)."""
+        return self._new_points("orbhip_triangulate_matches", kf1, neighbours, scale_factors, level_sigma2, match12,
+                                None, cos_parallax_max, ratio_factor, far_threshold, diagnostics)
+
+    def _new_points(self, what, kf1, neighbours, scale_factors, level_sigma2, match12, median_depth, cos_parallax_max,
+                    ratio_factor, far_threshold, diagnostics):
+        nb = list(neighbours)
+        B, n1 = len(nb), kf1.n
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        s2 = np.ascontiguousarray(level_sigma2, np.float32)
+        if sf.shape[0] != s2.shape[0]:
+            raise ValueError(f"{what}: scale_factors and level_sigma2 differ in length")
+        if ratio_factor is None:
+            ratio_factor = np.float32(1.5) * sf[1]
+        prm = TriParamsC(float(cos_parallax_max), float(np.float32(ratio_factor)), float(np.float32(far_threshold)))
+        r = NewPoints(B, n1, diagnostics)
+        out = NewPointsC(ptr(r.match12), ptr(r.nmatches), ptr(r.gated), ptr(r.status), ptr(r.x3d_all), ptr(r.first),
+                         ptr(r.nnew), ptr(r._nbr), ptr(r._idx1), ptr(r._idx2), ptr(r._x3d))
+        arr = (TriKeyFrameC * max(B, 1))(*[k.to_c() for k in nb])
+        c1 = kf1.to_c()
+        if match12 is None:
+            md = None
+            if median_depth is not None:
+                md = np.ascontiguousarray(median_depth, np.float32)
+                if md.shape != (B,):
+                    raise ValueError(f"{what}: median_depth needs one value per neighbour")
+            n = lib().orbhip_create_new_map_points(self.ctx.handle, ctypes.byref(c1), arr, B, ptr(md), ptr(sf), ptr(s2),
+                                                   sf.shape[0], int(self.mbCheckOrientation), ctypes.byref(prm),
+                                                   ctypes.byref(out))
+        else:
+            m = np.ascontiguousarray(match12, np.int32)
+            if m.shape != (B, n1):
+                raise ValueError(f"{what}: match12 must be B x n1")
+            n = lib().orbhip_triangulate_matches(self.ctx.handle, ctypes.byref(c1), arr, B, ptr(m), ptr(sf), ptr(s2),
+                                                 sf.shape[0], ctypes.byref(prm), ctypes.byref(out))
+        r.n = check(n, what)
+        return r
+
     # ---- map point fusion (LocalMapping::SearchInNeighbors) ----
     def Fuse(self, kfs, points, normals, min_dist, max_dist, mp_desc, inv_level_sigma2, th: float = 3.0,
              skip=None, pair_skip=None):
@@ -280,6 +333,33 @@ class ORBmatcher:
                                                           float(ratioHamming), ptr(match), ptr(dist), ptr(lvl)),
                    "orbhip_search_by_projection_sim3")
         return nm, match, dist, lvl
+
+
+class NewPoints:
+    """What CreateNewMapPoints / TriangulateMatches return. n new points, in upstream's creation
+    order (ascending neighbour, then ascending idx1): new_nbr, new_idx1, new_idx2, new_x3d (views of
+    the first n entries). first[idx1] = the neighbour whose point the feature became or -1;
+    nnew[b], nmatches[b], gated[b] per neighbour. With diagnostics: match12, status and x3d_all
+    (B x n1; status codes in include/orbhip.h), else None."""
+
+    def __init__(self, B: int, n1: int, diagnostics: bool):
+        self.n = 0
+        self.nmatches = np.zeros(B, np.int32)
+        self.gated = np.zeros(B, np.uint8)
+        self.first = np.full(n1, -1, np.int32)
+        self.nnew = np.zeros(B, np.int32)
+        self._nbr = np.full(n1, -1, np.int32)
+        self._idx1 = np.full(n1, -1, np.int32)
+        self._idx2 = np.full(n1, -1, np.int32)
+        self._x3d = np.zeros((n1, 3), np.float32)
+        self.match12 = np.full((B, n1), -1, np.int32) if diagnostics else None
+        self.status = np.zeros((B, n1), np.uint8) if diagnostics else None
+        self.x3d_all = np.zeros((B, n1, 3), np.float32) if diagnostics else None
+
+    new_nbr = property(lambda self: self._nbr[:self.n])
+    new_idx1 = property(lambda self: self._idx1[:self.n])
+    new_idx2 = property(lambda self: self._idx2[:self.n])
+    new_x3d = property(lambda self: self._x3d[:self.n])
 
 
 class TriKeyFrame:

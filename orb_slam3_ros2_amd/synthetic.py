@@ -613,6 +613,195 @@ def synthetic_triangulation_scene(n=300, B=3, seed=0, n_nodes=12, n2=None, mp_fr
 
 
 # ---------------------------------------------------------------------------
+# CreateNewMapPoints scenes: the triangulation and its checks on the matches above
+# ---------------------------------------------------------------------------
+WIDE_CAM = dict(fx=300.0, fy=300.0, cx=320.0, cy=240.0, w=640, h=480)   # 94 x 77 degrees: rays may be > 90 degrees apart
+NEW_POINT_KINDS = ("far", "behind", "between", "apart", "reproj1", "reproj2", "octave")
+
+
+def _pose64(k):
+    return quat_to_rot64(k.pose_q), np.asarray(k.pose_t, np.float64)
+
+
+def new_point_status64(k1, k2, p1, p2, o1, o2, sf, s2, cos_max=0.9998, ratio_factor=None, far=0.0):
+    """The status CreateNewMapPoints gives a pair of pixels, in float64 with numpy's SVD (the
+    library's rule is DESIGN.md's fp32 / Jacobi restatement: the two agree away from the gates). The
+    generator places its plants with this."""
+    ratio_factor = 1.5 * float(sf[1]) if ratio_factor is None else ratio_factor
+    rays, rows, cams = [], [], []
+    for k, p in ((k1, p1), (k2, p2)):
+        R, t = _pose64(k)
+        xn = np.array([(p[0] - k.cx) / k.fx, (p[1] - k.cy) / k.fy, 1.0])
+        rays.append(R.T @ xn)
+        T = np.concatenate([R, t[:, None]], 1)
+        rows += [xn[0] * T[2] - T[0], xn[1] * T[2] - T[1]]
+        cams.append((R, t, k))
+    cosP = rays[0] @ rays[1] / (np.linalg.norm(rays[0]) * np.linalg.norm(rays[1]))
+    if not cosP > 0:
+        return 2
+    if not cosP < cos_max:
+        return 3
+    v = np.linalg.svd(np.array(rows))[2][3]
+    if v[3] == 0:
+        return 4
+    X = v[:3] / v[3]
+    zs = [(R @ X + t)[2] for R, t, _ in cams]
+    if zs[0] <= 0:
+        return 5
+    if zs[1] <= 0:
+        return 6
+    dist = []
+    for code, (R, t, k), p, o in ((7, cams[0], p1, o1), (8, cams[1], p2, o2)):
+        Xc = R @ X + t
+        e = np.array([k.fx * Xc[0] / Xc[2] + k.cx - p[0], k.fy * Xc[1] / Xc[2] + k.cy - p[1]])
+        if e @ e > 5.991 * float(s2[o]):
+            return code
+        dist.append(np.linalg.norm(X + R.T @ t))
+    if dist[0] == 0 or dist[1] == 0:
+        return 9
+    if far > 0 and (dist[0] >= far or dist[1] >= far):
+        return 10
+    rd, ro = dist[1] / dist[0], float(sf[o1]) / float(sf[o2])
+    return 11 if (rd * ratio_factor < ro or rd > ro * ratio_factor) else 1
+
+
+def synthetic_new_points_scene(n=300, B=3, seed=0, cam=None, n_plant=4, far_threshold=7.0, median_depth=4.0,
+                               gated_at=1, scale=0.02, **scene_args):
+    """synthetic_triangulation_scene(n, B, seed, cam=WIDE_CAM by default) prepared for
+    CreateNewMapPoints. Per neighbour and kind, up to n_plant of its matched twins are rewritten
+    (descriptor within 3 bits of the KF1 feature's, same node, no MapPoint, consistent angle, so the
+    search takes them) into
+      far      the projection of the KF1 ray's point at 500 m (parallax too low),
+      behind   ... at a negative depth (the rays diverge: not in front of KF1),
+      between  ... between the two camera centres of a forward neighbour (behind KF2),
+      apart    ... the same with a KF1 feature moved towards a corner: the rays are > 90 degrees apart,
+      reproj1  an octave-0 KF1 feature, the twin at octave 6 and 1.8 of its sigmas off the epipolar
+               line: inside the search's gate, its half across the 5.991 gate of image 1 only,
+      reproj2  on a forward neighbour, a KF1 feature at octave 7 whose point lies 6-25 m away
+               (parallax just inside the gate), the twin at octave 7 and 1.5-1.9 of its sigmas off the
+               epipolar line: see scale,
+      octave   octaves 3 apart against the change of distance of a forward neighbour, or 5 apart.
+    scale: the length of the base scene's metre in map units (every translation, far_threshold and
+    median_depth are multiplied by it; the images do not change). A monocular map has an arbitrary
+    unit, and the null vector of the 4x4 system is not invariant to it: the vector is normalised
+    with its fourth component, so where coordinates are small against 1 the residual of an image
+    weighs with the point's depth in it, and at low parallax the solution slides along KF1's ray
+    towards KF2 until image 2 alone fails its 5.991 gate, although the twin lies inside the 3.84 gate
+    of the search (reproj2; in metres, scale = 1, no searched pair does). far_threshold cuts the
+    points beyond it; a neighbour 1 mm from KF1 (a copy of the first, gated against median_depth,
+    the scene depth given for every neighbour) is inserted at index gated_at (None: not). Returns the base scene's dict with neighbours and median_depth including the gated
+    neighbour, far_threshold, gated (B,), plants = [(kind, neighbour, idx1, idx2)]."""
+    from .matcher import TriKeyFrame
+    cam = dict(WIDE_CAM if cam is None else cam)
+    s = synthetic_triangulation_scene(n, B, seed, cam=cam, **scene_args)
+    m = float(scale)                                               # one metre of the base scene
+    for k in [s["kf1"]] + s["neighbours"]:
+        k.pose_t = (k.pose_t.astype(np.float64) * m).astype(np.float32)
+    far_threshold, median_depth = far_threshold * m, median_depth * m
+    rng = np.random.Generator(np.random.PCG64(1000003 * (seed + 1)))
+    k1, sf, s2 = s["kf1"], s["scale_factors"], s["level_sigma2"]
+    W, H = cam["w"], cam["h"]
+    R1, t1 = _pose64(k1)
+    used = set(int(i) for e in s["epi"] for i in e)
+    plants = []
+
+    def world(p1, lam):   # the point of depth lam on KF1's ray through pixel p1
+        X1 = lam * np.array([(p1[0] - cam["cx"]) / cam["fx"], (p1[1] - cam["cy"]) / cam["fy"], 1.0])
+        return (X1 - t1) @ R1
+
+    def project(k, Xw):
+        R, t = _pose64(k)
+        Xc = R @ Xw + t
+        return np.array([cam["fx"] * Xc[0] / Xc[2] + cam["cx"], cam["fy"] * Xc[1] / Xc[2] + cam["cy"]])
+
+    for b, k2 in enumerate(s["neighbours"]):
+        twin = s["twin"][b]
+        forward = b % 3 == 1
+        e1 = project(k1, -_pose64(k2)[0].T @ _pose64(k2)[1])      # KF2's centre in image 1
+        e2 = project(k2, -R1.T @ t1)                              # KF1's centre in image 2
+        free = [int(i) for i in rng.permutation(n) if twin[i] >= 0 and not k1.has_mp[i] and k1.node[i] >= 0
+                and k1.weight[i] > 0 and int(i) not in used]
+        rot_b = 7.0 + 11.0 * (b % 7)
+        for kind in NEW_POINT_KINDS:
+            want = dict(far=3, behind=5, between=6, apart=2, reproj1=7, reproj2=8, octave=11)[kind]
+            if (kind in ("between", "apart", "reproj2") and not forward) or (kind == "behind" and forward):
+                continue
+            done = tries = 0
+            for _ in range(400 * n_plant):
+                if done == n_plant or not free:
+                    break
+                i = free[0]
+                j = int(twin[i])
+                p1 = np.array([k1.kps["x"][i], k1.kps["y"][i]], np.float64)
+                o1 = int(k1.kps["octave"][i])
+                o2 = int(k2.kps["octave"][j])
+                if kind == "far":
+                    p2 = project(k2, world(p1, 500.0 * m))
+                elif kind == "behind":
+                    p2 = project(k2, world(p1, -rng.uniform(2.0, 8.0) * m))
+                elif kind == "between":
+                    p2 = project(k2, world(p1, rng.uniform(0.1, 0.35) * m))
+                elif kind == "apart":
+                    p1 = np.array([rng.choice([25.0, W - 25.0]), rng.choice([25.0, H - 25.0])]) + rng.uniform(-5, 5, 2)
+                    p2 = project(k2, world(p1, rng.uniform(0.2, 0.225) * m))
+                elif kind == "reproj1":
+                    o1, o2 = 0, 6
+                    z = rng.uniform(2.0, 8.0) * m
+                    a, c = project(k2, world(p1, z)), project(k2, world(p1, z + 0.5 * m))
+                    nrm = np.array([-(c - a)[1], (c - a)[0]]) / np.linalg.norm(c - a)
+                    p2 = a + rng.choice([-1.0, 1.0]) * 1.8 * float(sf[o2]) * nrm
+                elif kind == "reproj2":
+                    o1 = o2 = 7
+                    p1 = np.array([rng.uniform(5.0, W - 5.0), rng.uniform(5.0, H - 5.0)])
+                    z = rng.uniform(6.0, 25.0) * m
+                    a, c = project(k2, world(p1, z)), project(k2, world(p1, 1.05 * z))
+                    nrm = np.array([-(c - a)[1], (c - a)[0]]) / np.linalg.norm(c - a)
+                    p2 = a + rng.choice([-1.0, 1.0]) * rng.uniform(1.5, 1.9) * float(sf[o2]) * nrm
+                else:
+                    if forward:
+                        o2 = int(rng.integers(0, 5)); o1 = o2 + 3
+                    else:
+                        o1, o2 = (0, 5) if rng.random() < 0.5 else (5, 0)
+                    p2 = project(k2, world(p1, rng.uniform(2.0, 5.5) * m))
+                p1 = p1.astype(np.float32).astype(np.float64)
+                p2 = p2.astype(np.float32).astype(np.float64)
+                inside = all(1 <= p[0] < W - 1 and 1 <= p[1] < H - 1 for p in (p1, p2))
+                clear = np.linalg.norm(p2 - e2) > 12.0 * np.sqrt(float(sf[o2]))
+                if not (inside and clear and new_point_status64(k1, k2, p1, p2, o1, o2, sf, s2,
+                                                                far=far_threshold) == want):
+                    tries += 1
+                    if tries >= (60 if kind in ("between", "apart") else 400 if kind == "reproj2" else 1):   # the next feature
+                        free.pop(0)
+                        tries = 0
+                    continue
+                free.pop(0)
+                tries = 0
+                used.add(i)
+                k1.kps["x"][i], k1.kps["y"][i], k1.kps["octave"][i] = p1[0], p1[1], o1
+                k2.kps["x"][j], k2.kps["y"][j], k2.kps["octave"][j] = p2[0], p2[1], o2
+                k2.kps["angle"][j] = np.float32((float(k1.kps["angle"][i]) - rot_b) % 360.0) % np.float32(360.0)
+                k2.desc[j] = _flip_bits(rng, k1.desc[i], int(rng.integers(0, 4)))
+                k2.node[j], k2.weight[j], k2.has_mp[j] = k1.node[i], 0.5, 0
+                plants.append((kind, b, i, j))
+                done += 1
+    nbrs, md = list(s["neighbours"]), [float(median_depth)] * B
+    gated = np.zeros(B, np.uint8)
+    if gated_at is not None and B > 0:
+        g0 = nbrs[0]
+        t2 = (np.asarray(k1.pose_t, np.float64) - np.array([0.001 * m, 0.0, 0.0])).astype(np.float32)
+        near = TriKeyFrame(g0.kps.copy(), g0.desc.copy(), g0.node.copy(), g0.weight.copy(), g0.has_mp.copy(),
+                           k1.pose_q.copy(), t2, k1.fx, k1.fy, k1.cx, k1.cy)
+        nbrs.insert(gated_at, near)
+        md.insert(gated_at, float(median_depth))
+        gated = np.insert(gated, gated_at, 1).astype(np.uint8)
+        plants = [(kind, b + (b >= gated_at), i, j) for kind, b, i, j in plants]
+    s.update(neighbours=nbrs, median_depth=np.array(md, np.float32), far_threshold=float(far_threshold), gated=gated,
+             plants=plants)
+    s["twin"] = None   # the base scene's twin table does not describe the rewritten neighbours
+    return s
+
+
+# ---------------------------------------------------------------------------
 # Fuse scenes (LocalMapping::SearchInNeighbors)
 # ---------------------------------------------------------------------------
 FUSE_KINDS = ("plain", "th_low", "chi2", "level", "twin_same", "twin_cell", "none", "behind", "outside", "far",
