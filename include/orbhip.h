@@ -94,6 +94,38 @@ int orbhip_extract_batch_device(orbhip_ctx* ctx, const uint8_t* d_imgs, int B, i
                                 int64_t frame_stride, int lap0, int lap1, orbhip_kp* d_kps, uint8_t* d_desc,
                                 int cap, int32_t* d_n, int32_t* d_mono, void* stream);
 
+/* ---- rectified stereo frames ---------------------------------------------------------
+ * U:src/Frame.cc Frame(imLeft, imRight, ...): ExtractORB(0, left, 0, 0), ExtractORB(1, right, 0, 0),
+ * then Frame::ComputeStereoMatches (DESIGN.md section 4 "Stereo"): mvuRight / mvDepth per left
+ * keypoint, -1 where there is no match. bf = mbf (baseline x fx), b = mb (baseline in metres);
+ * center_patch != 0 subtracts each 11x11 patch's centre pixel before the L1 distance (ORB_SLAM2 and
+ * early ORB_SLAM3; 0 = the raw patches of ORB_SLAM3 v1.0). status (may be NULL) per left keypoint:
+ * 1 accepted, 2 no candidate in its row or maxU < 0, 3 best descriptor distance >= 75, 4 the
+ * iniu / endu test, 5 best SAD at +-L, 6 |deltaR| > 1, 7 disparity outside [0, bf / b), 8 removed by
+ * the median cut, 9 a window outside its pyramid level or an octave outside [0, n_levels).
+ * u_right, depth and status have cap entries per left frame; entries at or past the left frame's
+ * keypoint count are left untouched; *n_stereo counts the status-1 keypoints. NULL pointers (status
+ * excepted), bf <= 0, b <= 0, P < 1: ORBHIP_ERR_ARG; an empty image: ORBHIP_ERR_EMPTY; cap below
+ * orbhip_max_keypoints(w, h): ORBHIP_ERR_CAPACITY. */
+typedef struct {
+    float bf, b;
+    int32_t center_patch;
+} orbhip_stereo_params;
+
+/* Host images (row stride in bytes) and host outputs. */
+int orbhip_extract_stereo(orbhip_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h, int stride,
+                          const orbhip_stereo_params* params, orbhip_kp* kps_l, uint8_t* desc_l, int* n_l,
+                          orbhip_kp* kps_r, uint8_t* desc_r, int* n_r, int cap, float* u_right, float* depth,
+                          int32_t* status, int* n_stereo);
+
+/* P pairs, device-resident: frames 2p (left) and 2p + 1 (right) of d_imgs, and the keypoint outputs
+ * of the 2P frames, laid out as orbhip_extract_batch_device lays them out. Stereo outputs of pair p
+ * at p*cap, d_n_stereo[p]. Asynchronous on `stream`, no host synchronisation. */
+int orbhip_extract_stereo_device(orbhip_ctx* ctx, const uint8_t* d_imgs, int P, int w, int h, int stride,
+                                 int64_t frame_stride, const orbhip_stereo_params* params, orbhip_kp* d_kps,
+                                 uint8_t* d_desc, int cap, int32_t* d_n, int32_t* d_mono, float* d_u_right,
+                                 float* d_depth, int32_t* d_status, int32_t* d_n_stereo, void* stream);
+
 /* ---- distorted pinhole camera -----------------------------------
  * U:src/CameraModels/Pinhole (fx fy cx cy) + U:src/Frame.cc mDistCoef (k1 k2 p1 p2 [k3]), as the
  * node's camera file gives them (R:config/Monocular/MilkV.yaml:10-25). k1 == 0 means no

@@ -107,6 +107,50 @@ private:
     std::vector<orbhip_kp> kp_;
 };
 
+// U:src/Frame.cc, Frame(imLeft, imRight, ...): what the stereo constructor computes up to
+// ComputeStereoMatches (both ExtractORB calls with vLappingArea {0, 0}, then mvuRight / mvDepth,
+// -1 where a left keypoint has no stereo match).
+struct StereoFrame {
+    std::vector<KeyPoint> mvKeys, mvKeysRight;
+    std::vector<uint8_t> mDescriptors, mDescriptorsRight;   // N rows of 32 bytes
+    std::vector<float> mvuRight, mvDepth;
+    std::vector<int32_t> status;                            // orbhip.h: 1 accepted, 2..9 the rejecting step
+    int n_stereo = 0;
+};
+
+// mbf, mb as Frame holds them; center_patch: ORB_SLAM2's centre-subtracted patches. Returns false
+// on an empty image. Both sides use the extractor's parameters (the reference builds
+// mpORBextractorLeft / Right from the same settings).
+inline bool ExtractStereo(ORBextractor& ext, const uint8_t* left, const uint8_t* right, int w, int h, int stride,
+                          float mbf, float mb, StereoFrame& out, bool center_patch = false) {
+    out = StereoFrame();
+    if (!left || !right || w <= 0 || h <= 0) return false;
+    const int cap = orbhip_max_keypoints(ext.context(), w, h);
+    check(cap, "orbhip_max_keypoints");
+    std::vector<orbhip_kp> kl(cap), kr(cap);
+    out.mDescriptors.resize((size_t)cap * 32);
+    out.mDescriptorsRight.resize((size_t)cap * 32);
+    out.mvuRight.resize(cap);
+    out.mvDepth.resize(cap);
+    out.status.resize(cap);
+    const orbhip_stereo_params prm{mbf, mb, center_patch ? 1 : 0};
+    int nl = 0, nr = 0;
+    check(orbhip_extract_stereo(ext.context(), left, right, w, h, stride, &prm, kl.data(), out.mDescriptors.data(), &nl,
+                                kr.data(), out.mDescriptorsRight.data(), &nr, cap, out.mvuRight.data(),
+                                out.mvDepth.data(), out.status.data(), &out.n_stereo),
+          "orbhip_extract_stereo");
+    for (int i = 0; i < nl; i++)
+        out.mvKeys.push_back(KeyPoint{kl[i].x, kl[i].y, kl[i].size, kl[i].angle, kl[i].response, kl[i].octave});
+    for (int i = 0; i < nr; i++)
+        out.mvKeysRight.push_back(KeyPoint{kr[i].x, kr[i].y, kr[i].size, kr[i].angle, kr[i].response, kr[i].octave});
+    out.mDescriptors.resize((size_t)nl * 32);
+    out.mDescriptorsRight.resize((size_t)nr * 32);
+    out.mvuRight.resize(nl);
+    out.mvDepth.resize(nl);
+    out.status.resize(nl);
+    return true;
+}
+
 // U:include/ORBmatcher.h — the constants and the brute-force acceptance rule (a11/a12).
 class ORBmatcher {
 public:

@@ -18,6 +18,8 @@ Host-side mirror of the reference's hot-path interfaces over th
   ORBmatcher.FuseSim3 / SearchByProjectionSim3(...)   (LoopClosing)         U:src/ORBmatcher.cc
   KeyFrameDatabase(max_kf).DetectRelocalizationCandidates / DetectNBestCandidates
                                                                             U:src/KeyFrameDatabase.cc
+  stereo_frame(ext, left, right, bf, b) -> StereoFrame   Frame's stereo ctor: both ExtractORB
+                                                    calls + ComputeStereoMatches       U:src/Frame.cc
   FrameStream(w, h, frames_in_flight).push(frame)   Frame ctor -> ExtractORB + match to the last
                                                     frame, pipelined on the device
 
@@ -34,7 +36,8 @@ from .bow import ORBVocabulary  # noqa: F401
 from .kfdb import KeyFrameDatabase  # noqa: F401
 from .frontend import FrameStream  # noqa: F401
 from .camera import PinholeCamera  # noqa: F401
+from .stereo import StereoFrame, stereo_frame  # noqa: F401
 
-__all__ = ["ORBextractor", "KeyPoint", "ORBmatcher", "Optimizer", "BAProblem", "BAResult", "PoseProblem", "PoseResult", "ORBVocabulary", "KeyFrameDatabase", "FrameStream", "PinholeCamera",
+__all__ = ["StereoFrame", "stereo_frame", "ORBextractor", "KeyPoint", "ORBmatcher", "Optimizer", "BAProblem", "BAResult", "PoseProblem", "PoseResult", "ORBVocabulary", "KeyFrameDatabase", "FrameStream", "PinholeCamera",
            "OrbHipError",
            "lib", "library_path"]

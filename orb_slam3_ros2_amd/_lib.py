@@ -39,6 +39,10 @@ class OrbParams(ctypes.Structure):
                 ("ini_th_fast", ctypes.c_int32), ("min_th_fast", ctypes.c_int32)]
 
 
+class StereoParams(ctypes.Structure):
+    _fields_ = [("bf", ctypes.c_float), ("b", ctypes.c_float), ("center_patch", ctypes.c_int32)]
+
+
 class BAProblemC(ctypes.Structure):
     _fields_ = [("n_poses", ctypes.c_int32), ("n_points", ctypes.c_int32), ("n_edges", ctypes.c_int32),
                 ("pose_q", ctypes.c_void_p), ("pose_t", ctypes.c_void_p), ("pose_fixed", ctypes.c_void_p),
@@ -125,7 +129,8 @@ class LocalPointsC(ctypes.Structure):
 
 # every symbol include/orbhip.h declares (tests check the export table against this list)
 EXPORTED = ["orbhip_abi_version", "orbhip_create", "orbhip_destroy", "orbhip_level_info", "orbhip_max_keypoints",
-            "orbhip_extract", "orbhip_extract_batch_device", "orbhip_descriptor_distance", "orbhip_match_bf",
+            "orbhip_extract", "orbhip_extract_batch_device", "orbhip_extract_stereo", "orbhip_extract_stereo_device",
+            "orbhip_descriptor_distance", "orbhip_match_bf",
             "orbhip_match_pairs_device", "orbhip_match_frames_device", "orbhip_profile_stage",
             "orbhip_profile_collect", "orbhip_launch_graphs", "orbhip_ba_solve", "orbhip_ba_solve_batch", "orbhip_ba_stats", "orbhip_bgr_to_gray_device",
             "orbhip_comm_unique_id", "orbhip_comm_init", "orbhip_ba_solve_sharded", "orbhip_ba_solve_sharded_segments",
@@ -170,6 +175,14 @@ def lib():
                                  ctypes.POINTER(i32)]
     L.orbhip_extract_batch_device.argtypes = [vp, vp, i32, i32, i32, i32, ctypes.c_int64, i32, i32, vp, vp, i32,
                                               vp, vp, vp]
+    sp = ctypes.POINTER(StereoParams)
+    L.orbhip_extract_stereo.argtypes = [vp, vp, vp, i32, i32, i32, sp, vp, vp, ctypes.POINTER(i32), vp, vp,
+                                        ctypes.POINTER(i32), i32, vp, vp, vp, ctypes.POINTER(i32)]
+    L.orbhip_extract_stereo_device.argtypes = [vp, vp, i32, i32, i32, i32, ctypes.c_int64, sp, vp, vp, i32, vp, vp,
+                                               vp, vp, vp, vp, vp]
+    # the stereo kernels alone on caller-supplied keypoints (tests compare them with the restatement)
+    L.orbhip_test_stereo_match.argtypes = [vp, vp, vp, i32, i32, sp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp,
+                                           ctypes.POINTER(i32)]
     L.orbhip_descriptor_distance.argtypes = [vp, vp]
     L.orbhip_match_bf.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, f32, i32, vp, vp, vp]
     L.orbhip_match_pairs_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp, vp, vp, vp]

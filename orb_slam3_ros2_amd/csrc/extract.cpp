@@ -1,5 +1,6 @@
 // ORB extraction, host side (extract.h): plan lookup and upload, scratch, the launch sequence of
-// one batch, the host-image call and the extractor's test hooks.
+// one batch, the host-image call, what the stereo stage reads of the workspace and the
+// extractor's test hooks.
 #include "extract.h"
 
 #include <algorithm>
@@ -136,6 +137,9 @@ struct ExtractWorkspace {
     DevBuf<uint8_t> d_in, d_desc;
     DevBuf<orbhip_kp> d_kps;
     DevBuf<int32_t> d_n, d_mono;
+    // the stereo stage (stereo.cpp): per-keypoint scratch and the host call's outputs
+    DevBuf<int32_t> d_st_status, d_st_sad, d_st_best, d_st_nst;
+    DevBuf<float> d_st_u, d_st_depth;
     // Bumped whenever a buffer above is reallocated. A captured launch sequence holds the scratch
     // addresses, so its key (run_extract) names the workspace and this count: a key that lists
     // the pointers is only as sound as the list, and d_flow was once missing from it.
@@ -205,6 +209,56 @@ static int ensure_batch(ExtractWorkspace* ws, const Plan* pl, int B) {
     return ORBHIP_OK;
 }
 
+// The pyramid stage: levels 1..L-1 of B frames into ws->d_pyr (ensure_batch first). Every route
+// writes every level of every frame there, and no later stage of the extraction writes to it.
+static void launch_pyramid(ExtractWorkspace* ws, Plan* pl, FrameBufs& fb, int B, const RunSwitches& sw, bool flow_on,
+                           hipStream_t st) {
+    const ExtractPlan& P = pl->hp.h;
+    StageTimer& tm = *ws->timer;
+    // the cone recomputes each tile's halo on every level: it pays only while the per-level
+    // cascade is launch-latency bound (a few work-groups per CU); big batches keep the cascade
+    static const size_t cone_max = std::getenv("ORBHIP_CONE_MAX_WG")
+                                       ? (size_t)std::atol(std::getenv("ORBHIP_CONE_MAX_WG"))
+                                       : (size_t)1024;
+    const bool cone_path = pl->hp.cone_tiles && !sw.no_cone && (size_t)B * pl->hp.cone_tiles <= cone_max;
+    const bool cone_hi = !cone_path && pl->hp.cone_hi_tiles && sw.cone_hi;
+    // the one-launch pyramid stamps its own execution span for the stage timer
+    fb.stamp = (cone_path && tm.stage == 1 && tm.dstamp && tm.n < StageTimer::kCap) ? tm.dstamp + tm.n : nullptr;
+    if (cone_path) {
+        static const int cone_nt = [] {   // threads per tile (A/B: ORBHIP_CONE_NT = 256 / 512)
+            const char* e = std::getenv("ORBHIP_CONE_NT");
+            const int v = e ? std::atoi(e) : 1024;
+            return (v == 256 || v == 512) ? v : 1024;
+        }();
+        launch_pyr_cone(pl->d_plan.p, pl->hp.cone_tiles, pl->hp.cone_lds, fb, B, pl->d_cone.p, pl->d_cone_tab.p,
+                        pl->hp.cone_tab_stride, st, 0, cone_nt, pl->d_xofs.p, pl->d_xalpha.p, pl->d_yofs.p,
+                        pl->d_ybeta.p);
+    } else if (flow_on) {
+        PyrFlow fa{};
+        fa.ctl = ws->d_flow.p;
+        fa.flags = ws->d_flow.p + kFlowCtl;
+        fa.dep = (const int2*)pl->d_flow_dep.p;
+        for (int l = 0; l <= kMaxLevels; l++) fa.boff[l] = pl->hp.flow_boff[l];
+        fa.B = B;
+        fa.nbt = pl->hp.flow_nbt;
+        fa.pyr_limit = (int)((int64_t)B * P.pyr_bytes);
+        launch_pyr_flow(pl->d_plan.p, fb, pl->d_xofs.p, pl->d_xalpha.p, pl->d_yofs.p, pl->d_ybeta.p, fa, st);
+    } else {
+        const bool bands = !cone_hi && pl->hp.nbands > 0;
+        const int lr = cone_hi ? kConeHiStart + 1 : (bands ? kBandStart + 1 : P.n_levels);
+        for (int l = 1; l < lr; l++)
+            launch_resize(pl->d_plan.p, P, fb, B, l, pl->d_xofs.p, pl->d_xalpha.p, pl->d_yofs.p, pl->d_ybeta.p,
+                          st);
+        if (cone_hi)
+            launch_pyr_cone(pl->d_plan.p, pl->hp.cone_hi_tiles, pl->hp.cone_hi_lds, fb, B, pl->d_cone_hi.p,
+                            pl->d_cone_hi_tab.p, pl->hp.cone_hi_tab_stride, st, kConeHiStart, cone_hi_threads(),
+                            pl->d_xofs.p, pl->d_xalpha.p, pl->d_yofs.p, pl->d_ybeta.p);
+        if (bands)
+            launch_resize_bands(pl->d_plan.p, pl->hp.nbands, fb, B, kBandStart, (const int2*)pl->d_bands.p,
+                                pl->d_xofs.p, pl->d_xalpha.p, pl->d_yofs.p, pl->d_ybeta.p, st);
+    }
+}
+
 static int run_extract(ExtractWorkspace* ws, Plan* pl, const uint8_t* d_imgs, int B, int stride, int64_t fstride,
                        int lap0, int lap1, orbhip_kp* d_kps, uint8_t* d_desc, int cap, int32_t* d_n, int32_t* d_mono,
                        hipStream_t st) {
@@ -226,48 +280,7 @@ static int run_extract(ExtractWorkspace* ws, Plan* pl, const uint8_t* d_imgs, in
         StageTimer& tm = *ws->timer;
         const StageScope scope(tm);
         tm.begin(1, st);
-        // the cone recomputes each tile's halo on every level: it pays only while the per-level
-        // cascade is launch-latency bound (a few work-groups per CU); big batches keep the cascade
-        static const size_t cone_max = std::getenv("ORBHIP_CONE_MAX_WG")
-                                           ? (size_t)std::atol(std::getenv("ORBHIP_CONE_MAX_WG"))
-                                           : (size_t)1024;
-        const bool cone_path = pl->hp.cone_tiles && !sw.no_cone && (size_t)B * pl->hp.cone_tiles <= cone_max;
-        const bool cone_hi = !cone_path && pl->hp.cone_hi_tiles && sw.cone_hi;
-        // the one-launch pyramid stamps its own execution span for the stage timer
-        fb.stamp = (cone_path && tm.stage == 1 && tm.dstamp && tm.n < StageTimer::kCap) ? tm.dstamp + tm.n : nullptr;
-        if (cone_path) {
-            static const int cone_nt = [] {   // threads per tile (A/B: ORBHIP_CONE_NT = 256 / 512)
-                const char* e = std::getenv("ORBHIP_CONE_NT");
-                const int v = e ? std::atoi(e) : 1024;
-                return (v == 256 || v == 512) ? v : 1024;
-            }();
-            launch_pyr_cone(pl->d_plan.p, pl->hp.cone_tiles, pl->hp.cone_lds, fb, B, pl->d_cone.p, pl->d_cone_tab.p,
-                            pl->hp.cone_tab_stride, st, 0, cone_nt, pl->d_xofs.p, pl->d_xalpha.p, pl->d_yofs.p,
-                            pl->d_ybeta.p);
-        } else if (flow_on) {
-            PyrFlow fa{};
-            fa.ctl = ws->d_flow.p;
-            fa.flags = ws->d_flow.p + kFlowCtl;
-            fa.dep = (const int2*)pl->d_flow_dep.p;
-            for (int l = 0; l <= kMaxLevels; l++) fa.boff[l] = pl->hp.flow_boff[l];
-            fa.B = B;
-            fa.nbt = pl->hp.flow_nbt;
-            fa.pyr_limit = (int)((int64_t)B * P.pyr_bytes);
-            launch_pyr_flow(pl->d_plan.p, fb, pl->d_xofs.p, pl->d_xalpha.p, pl->d_yofs.p, pl->d_ybeta.p, fa, st);
-        } else {
-            const bool bands = !cone_hi && pl->hp.nbands > 0;
-            const int lr = cone_hi ? kConeHiStart + 1 : (bands ? kBandStart + 1 : P.n_levels);
-            for (int l = 1; l < lr; l++)
-                launch_resize(pl->d_plan.p, P, fb, B, l, pl->d_xofs.p, pl->d_xalpha.p, pl->d_yofs.p, pl->d_ybeta.p,
-                              st);
-            if (cone_hi)
-                launch_pyr_cone(pl->d_plan.p, pl->hp.cone_hi_tiles, pl->hp.cone_hi_lds, fb, B, pl->d_cone_hi.p,
-                                pl->d_cone_hi_tab.p, pl->hp.cone_hi_tab_stride, st, kConeHiStart, cone_hi_threads(),
-                                pl->d_xofs.p, pl->d_xalpha.p, pl->d_yofs.p, pl->d_ybeta.p);
-            if (bands)
-                launch_resize_bands(pl->d_plan.p, pl->hp.nbands, fb, B, kBandStart, (const int2*)pl->d_bands.p,
-                                    pl->d_xofs.p, pl->d_xalpha.p, pl->d_yofs.p, pl->d_ybeta.p, st);
-        }
+        launch_pyramid(ws, pl, fb, B, sw, flow_on, st);
         tm.end(1, st);
         tm.begin(2, st);
         CandPack cp;
@@ -313,18 +326,72 @@ int extract_batch(ExtractWorkspace* ws, const uint8_t* d_imgs, int B, int w, int
     return run_extract(ws, pl, d_imgs, B, stride, fstride, lap0, lap1, d_kps, d_desc, cap, d_n, d_mono, st);
 }
 
-// one host image through the workspace's own frame and output buffers, on the context's stream
+// B host images (1 or 2) through the workspace's own frame and output buffers, on the context's
+// stream; frame f's outputs at f * kp_cap_frame. pyramid_only: the pyramid stage alone.
+static int run_host_frames(ExtractWorkspace* ws, Plan* pl, const uint8_t* const* imgs, int B, int w, int h, int stride,
+                           int lap0, int lap1, bool pyramid_only = false) {
+    const int kcap = pl->hp.kp_cap_frame;
+    HIPOK(ws->grow(ws->d_in, (size_t)B * w * h));
+    HIPOK(ws->grow(ws->d_kps, (size_t)B * kcap));
+    HIPOK(ws->grow(ws->d_desc, (size_t)B * kcap * 32));
+    HIPOK(ws->grow(ws->d_n, B));
+    HIPOK(ws->grow(ws->d_mono, B));
+    for (int f = 0; f < B; f++)
+        HIPOK(hipMemcpy2DAsync(ws->d_in.p + (size_t)f * w * h, w, imgs[f], stride, w, h, hipMemcpyHostToDevice,
+                               ws->stream));
+    if (pyramid_only) {
+        (void)hipGetLastError();
+        if (int rc = ensure_batch(ws, pl, B)) return rc;
+        const RunSwitches sw = read_run_switches();
+        const bool flow_on = sw.flow && pl->hp.flow_nbt > 0 && (int64_t)B * pl->hp.h.pyr_bytes < (1ll << 31);
+        FrameBufs fb;
+        fb.in = ws->d_in.p; fb.in_stride = w; fb.in_fstride = (int64_t)w * h; fb.pyr = ws->d_pyr.p;
+        launch_pyramid(ws, pl, fb, B, sw, flow_on, ws->stream);
+        HIPOK(hipGetLastError());
+        return ORBHIP_OK;
+    }
+    return run_extract(ws, pl, ws->d_in.p, B, w, (int64_t)w * h, lap0, lap1, ws->d_kps.p, ws->d_desc.p, kcap,
+                       ws->d_n.p, ws->d_mono.p, ws->stream);
+}
 static int run_host_frame(ExtractWorkspace* ws, Plan* pl, const uint8_t* img, int w, int h, int stride, int lap0,
                           int lap1) {
-    const int kcap = pl->hp.kp_cap_frame;
-    HIPOK(ws->grow(ws->d_in, (size_t)w * h));
-    HIPOK(ws->grow(ws->d_kps, kcap));
-    HIPOK(ws->grow(ws->d_desc, (size_t)kcap * 32));
-    HIPOK(ws->grow(ws->d_n, 1));
-    HIPOK(ws->grow(ws->d_mono, 1));
-    HIPOK(hipMemcpy2DAsync(ws->d_in.p, w, img, stride, w, h, hipMemcpyHostToDevice, ws->stream));
-    return run_extract(ws, pl, ws->d_in.p, 1, w, (int64_t)w * h, lap0, lap1, ws->d_kps.p, ws->d_desc.p, kcap,
-                       ws->d_n.p, ws->d_mono.p, ws->stream);
+    return run_host_frames(ws, pl, &img, 1, w, h, stride, lap0, lap1);
+}
+
+// ---- what the stereo stage (stereo.cpp) needs of the workspace ----
+int extract_view(ExtractWorkspace* ws, int w, int h, ExtractView* v) {
+    Plan* pl = nullptr;
+    if (int rc = find_plan(ws, w, h, &pl)) return rc;
+    v->plan = &pl->hp.h;
+    v->d_plan = pl->d_plan.p;
+    v->kp_cap = pl->hp.kp_cap_frame;
+    v->stream = ws->stream;
+    // (the buffers as they are now: read them after the extraction of the same call)
+    v->d_pyr = ws->d_pyr.p; v->d_in = ws->d_in.p; v->d_kps = ws->d_kps.p; v->d_desc = ws->d_desc.p;
+    v->d_n = ws->d_n.p; v->d_err = ws->d_err.p;
+    return ORBHIP_OK;
+}
+
+int extract_stereo_scratch(ExtractWorkspace* ws, size_t entries, int pairs, bool outputs, StereoScratch* s) {
+    HIPOK(ws->grow(ws->d_st_status, entries));
+    HIPOK(ws->grow(ws->d_st_sad, entries));
+    if (outputs) {
+        HIPOK(ws->grow(ws->d_st_best, entries));
+        HIPOK(ws->grow(ws->d_st_u, entries));
+        HIPOK(ws->grow(ws->d_st_depth, entries));
+        HIPOK(ws->grow(ws->d_st_nst, pairs));
+    }
+    s->status = ws->d_st_status.p; s->sad = ws->d_st_sad.p; s->best = ws->d_st_best.p;
+    s->u_right = ws->d_st_u.p; s->depth = ws->d_st_depth.p; s->n_stereo = ws->d_st_nst.p;
+    return ORBHIP_OK;
+}
+
+int extract_host_pair(ExtractWorkspace* ws, const uint8_t* left, const uint8_t* right, int w, int h, int stride,
+                      bool pyramid_only) {
+    Plan* pl = nullptr;
+    if (int rc = find_plan(ws, w, h, &pl)) return rc;
+    const uint8_t* imgs[2] = {left, right};
+    return run_host_frames(ws, pl, imgs, 2, w, h, stride, 0, 0, pyramid_only);
 }
 
 int extract_host(ExtractWorkspace* ws, const uint8_t* img, int w, int h, int stride, int lap0, int lap1,

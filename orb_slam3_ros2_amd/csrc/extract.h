@@ -24,6 +24,32 @@ int extract_batch(ExtractWorkspace* ws, const uint8_t* d_imgs, int B, int w, int
                   hipStream_t st);
 int extract_host(ExtractWorkspace* ws, const uint8_t* img, int w, int h, int stride, int lap0, int lap1,
                  orbhip_kp* kps, uint8_t* desc32, int cap, int* n_out, int* mono_index);
+// ---- for the stereo stage (stereo.cpp), which runs behind an extraction of the same call ----
+// The plan of a frame size and the workspace's buffers as they are at the call (so: after the
+// extraction). Frame f's pyramid levels >= 1 lie at d_pyr + f * plan->pyr_bytes + lv[l].pyr_off.
+struct ExtractView {
+    const ExtractPlan *plan, *d_plan;   // host / device copy
+    int kp_cap;                         // orbhip_max_keypoints
+    hipStream_t stream;                 // the context's
+    const uint8_t* d_pyr;
+    // the host-image path's frames (w x h, packed) and outputs (frame f at f * kp_cap)
+    const uint8_t* d_in;
+    orbhip_kp* d_kps;
+    uint8_t* d_desc;
+    int32_t *d_n, *d_err;
+};
+int extract_view(ExtractWorkspace* ws, int w, int h, ExtractView* v);
+// stereo scratch of `entries` keypoints through the workspace's grow(); outputs: also the
+// device-side outputs of a host call (best, u_right, depth, `pairs` n_stereo)
+struct StereoScratch {
+    int32_t *status, *sad, *best, *n_stereo;
+    float *u_right, *depth;
+};
+int extract_stereo_scratch(ExtractWorkspace* ws, size_t entries, int pairs, bool outputs, StereoScratch* s);
+// two host images as frames 0 and 1 of the host-image path with vLappingArea {0, 0} (the context's
+// stream, no synchronisation); pyramid_only: upload and pyramid stage alone
+int extract_host_pair(ExtractWorkspace* ws, const uint8_t* left, const uint8_t* right, int w, int h, int stride,
+                      bool pyramid_only);
 // test hooks (orbhip_test_extract_debug, _candidates, _cells)
 int extract_test_debug(ExtractWorkspace* ws, const uint8_t* img, int w, int h, int lap0, int lap1, uint8_t* pyr,
                        uint32_t* cand, int32_t* cand_cnt, void* lvl, int32_t* lvl_cnt, int32_t* lvl_nlap,

@@ -22,6 +22,7 @@
 #include "orbhip_kernels.h"
 #include "graph_cache.h"
 #include "stage.h"
+#include "stereo.h"
 
 using namespace orbhip;
 
@@ -194,6 +195,33 @@ int orbhip_extract(orbhip_ctx* c, const uint8_t* img, int w, int h, int stride, 
     if (stride < w || (cap > 0 && (!kps || !desc32))) return ORBHIP_ERR_ARG;
     HIPOK(hipSetDevice(c->device));
     return extract_host(c->ext, img, w, h, stride, lap0, lap1, kps, desc32, cap, n_out, mono_index);
+}
+
+// ---- rectified stereo frames: both extractions and Frame::ComputeStereoMatches (stereo.cpp) ----
+int orbhip_extract_stereo(orbhip_ctx* c, const uint8_t* left, const uint8_t* right, int w, int h, int stride,
+                          const orbhip_stereo_params* params, orbhip_kp* kps_l, uint8_t* desc_l, int* n_l,
+                          orbhip_kp* kps_r, uint8_t* desc_r, int* n_r, int cap, float* u_right, float* depth,
+                          int32_t* status, int* n_stereo) {
+    if (!c || !n_l || !n_r || !n_stereo || !params) return ORBHIP_ERR_ARG;
+    *n_l = *n_r = *n_stereo = 0;
+    if (!left || !right || w <= 0 || h <= 0) return ORBHIP_ERR_EMPTY;
+    if (stride < w || !kps_l || !desc_l || !kps_r || !desc_r || !u_right || !depth) return ORBHIP_ERR_ARG;
+    HIPOK(hipSetDevice(c->device));
+    return stereo_host(c->ext, left, right, w, h, stride, *params, kps_l, desc_l, n_l, kps_r, desc_r, n_r, cap,
+                       u_right, depth, status, n_stereo);
+}
+
+int orbhip_extract_stereo_device(orbhip_ctx* c, const uint8_t* d_imgs, int P, int w, int h, int stride,
+                                 int64_t frame_stride, const orbhip_stereo_params* params, orbhip_kp* d_kps,
+                                 uint8_t* d_desc, int cap, int32_t* d_n, int32_t* d_mono, float* d_u_right,
+                                 float* d_depth, int32_t* d_status, int32_t* d_n_stereo, void* stream) {
+    if (!c || !params || P < 1 || !d_kps || !d_desc || !d_n || !d_mono || !d_u_right || !d_depth || !d_n_stereo)
+        return ORBHIP_ERR_ARG;
+    if (!d_imgs || w <= 0 || h <= 0) return ORBHIP_ERR_EMPTY;
+    if (stride < w || frame_stride < (int64_t)stride * h) return ORBHIP_ERR_ARG;
+    HIPOK(hipSetDevice(c->device));
+    return stereo_device(c->ext, d_imgs, P, w, h, stride, frame_stride, *params, d_kps, d_desc, cap, d_n, d_mono,
+                         d_u_right, d_depth, d_status, d_n_stereo, (hipStream_t)stream);
 }
 
 int orbhip_descriptor_distance(const uint8_t* a, const uint8_t* b) {
@@ -684,6 +712,21 @@ int orbhip_test_extract_debug(orbhip_ctx* c, const uint8_t* img, int w, int h, i
     if (!c || !img) return ORBHIP_ERR_ARG;
     HIPOK(hipSetDevice(c->device));
     return extract_test_debug(c->ext, img, w, h, lap0, lap1, pyr, cand, cand_cnt, lvl, lvl_cnt, lvl_nlap, sizes);
+}
+
+// The stereo kernels alone on caller-supplied keypoints and descriptors of both sides (n_l outputs
+// each; best_r: the search's winner or -1; sad: the best SAD or -1 where none was formed). The
+// pyramids come from the extractor's own pyramid stage.
+int orbhip_test_stereo_match(orbhip_ctx* c, const uint8_t* left, const uint8_t* right, int w, int h,
+                             const orbhip_stereo_params* params, const orbhip_kp* kps_l, const uint8_t* desc_l,
+                             int n_l, const orbhip_kp* kps_r, const uint8_t* desc_r, int n_r, float* u_right,
+                             float* depth, int32_t* status, int32_t* best_r, int32_t* sad, int* n_stereo) {
+    if (!c || !left || !right || w <= 0 || h <= 0 || !params || !n_stereo || (n_l > 0 && (!kps_l || !desc_l)) ||
+        (n_r > 0 && (!kps_r || !desc_r)) || (n_l > 0 && (!u_right || !depth || !status || !best_r || !sad)))
+        return ORBHIP_ERR_ARG;
+    HIPOK(hipSetDevice(c->device));
+    return stereo_test_match(c->ext, left, right, w, h, *params, kps_l, desc_l, n_l, kps_r, desc_r, n_r, u_right,
+                             depth, status, best_r, sad, n_stereo);
 }
 
 int orbhip_test_candidates(orbhip_ctx* c, int w, int h, int frame, int64_t* n) {

@@ -67,6 +67,35 @@ def synthetic_stream(n: int, width: int, height: int, seed0: int, noise_sigma: f
     return out
 
 
+def synthetic_stereo_pair(seed: int, width: int = 640, height: int = 480, n_rect: int = 300,
+                          noise_sigma: float = 4.0, max_disparity: float = 24.0):
+    """A rectified stereo pair of the rectangle scene (SURVEY.md 8d image spec): (left, right) u8.
+    Every rectangle has its own disparity, a multiple of a quarter pixel in [0, max_disparity];
+    the rectangles are drawn in order of increasing disparity, so nearer ones are drawn later and
+    shifted further (x_right = x_left - disparity). The background has disparity 0. The right image
+    is rendered at 4x width and box-averaged down, which gives the non-integer disparities their
+    blended edges. Both images get fresh N(0, noise_sigma) noise."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    left = np.full((height, width), 128.0, dtype=np.float64)
+    right4 = np.full((height, 4 * width), 128.0, dtype=np.float64)
+    quarters = np.sort(rng.integers(0, int(4 * max_disparity) + 1, size=n_rect))
+    for q in quarters:
+        sw, sh = rng.integers(8, 97, size=2)
+        x0 = int(rng.integers(-int(sw) + 1, width))
+        y0 = int(rng.integers(-int(sh) + 1, height))
+        val = float(rng.integers(0, 256))
+        ya, yb = max(y0, 0), max(min(y0 + int(sh), height), 0)
+        left[ya:yb, max(x0, 0):max(min(x0 + int(sw), width), 0)] = val
+        xa, xb = 4 * x0 - int(q), 4 * (x0 + int(sw)) - int(q)
+        right4[ya:yb, max(xa, 0):max(min(xb, 4 * width), 0)] = val
+    right = right4.reshape(height, width, 4).mean(axis=2)
+    if noise_sigma > 0:
+        left += rng.normal(0.0, noise_sigma, size=left.shape)
+        right += rng.normal(0.0, noise_sigma, size=right.shape)
+    to_u8 = lambda a: np.clip(np.rint(a), 0, 255).astype(np.uint8)   # noqa: E731
+    return to_u8(left), to_u8(right)
+
+
 # ---------------------------------------------------------------------------
 # Bundle-adjustment problems (SURVEY.md §8(d) C4 / C5)
 # ---------------------------------------------------------------------------
