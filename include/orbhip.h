@@ -361,6 +361,31 @@ int orbhip_search_local_points(orbhip_ctx* ctx, const orbhip_frame* frame, const
                                float view_cos_limit, float th, float nnratio, int far_points, float th_far,
                                uint8_t* in_view, int32_t* level, int32_t* match);
 
+/* The two searches on a rectified-stereo Frame (the stereo branches of both SearchByProjection
+ * forms): u_right = mvuRight (n entries), bf = mbf, b = mb. A candidate keypoint k with
+ * u_right[k] > 0 is skipped when |ur - u_right[k]| > the query's window radius, ur = u - bf * invz
+ * the query's projection into the right image.
+ * orbhip_search_by_projection_last_stereo is SearchByProjection(CurrentFrame, LastFrame, th,
+ * bMono = false): last_pose_q / last_pose_t = LastFrame.GetPose() (Tlw); with tlc = Rlw twc + tlw
+ * the camera moved forward (tlc.z > b: levels nLastOctave and up), backward (-tlc.z > b: levels 0
+ * .. nLastOctave) or neither (nLastOctave - 1 .. nLastOctave + 1). direction (may be NULL)
+ * receives 1 / -1 / 0. orbhip_search_local_points_stereo also returns proj_xr (may be NULL):
+ * mTrackProjXR where in_view[m], untouched elsewhere. Both return ORBHIP_ERR_ARG when u_right is
+ * NULL with n > 0, or bf <= 0 or b <= 0. */
+typedef struct {
+    orbhip_frame frame;
+    const float* u_right;       /* frame.n: mvuRight */
+    float bf, b;                /* mbf, mb */
+} orbhip_stereo_view;
+int orbhip_search_by_projection_last_stereo(orbhip_ctx* ctx, const orbhip_stereo_view* cur,
+                                            const orbhip_proj_last* last, const float last_pose_q[4],
+                                            const float last_pose_t[3], float th, int check_orientation,
+                                            int32_t* match, int32_t* direction);
+int orbhip_search_local_points_stereo(orbhip_ctx* ctx, const orbhip_stereo_view* frame,
+                                      const orbhip_local_points* mps, float view_cos_limit, float th, float nnratio,
+                                      int far_points, float th_far, uint8_t* in_view, int32_t* level, float* proj_xr,
+                                      int32_t* match);
+
 /* ---- monocular initialisation matching -------------------------------------------
  * U:src/ORBmatcher.cc::SearchForInitialization(Frame& F1, Frame& F2, vector<cv::Point2f>&
  * vbPrevMatched, vector<int>& vnMatches12, int windowSize), called by
@@ -446,6 +471,30 @@ int orbhip_pose_optimization(orbhip_ctx* ctx, const orbhip_pose_problem* prob, o
 /* B frames (e.g. every camera of a rig, or a batch of agents) in one launch, one wavefront each. */
 int orbhip_pose_optimization_batch(orbhip_ctx* ctx, const orbhip_pose_problem* probs, int B,
                                    orbhip_pose_result* res);
+
+/* PoseOptimization of a rectified-stereo Frame, as upstream builds the problem: observation i
+ * with u_right[i] >= 0 (mvuRight; 0.0f counts) is an EdgeStereoSE3ProjectXYZOnlyPose (obs (u, v,
+ * u_right), projection (fx x/z + cx, fy y/z + cy, fx x/z + cx - bf/z), information
+ * I3 * mvInvLevelSigma2[octave], Huber sqrt(7.815), outlier iff chi2 > 7.815), every other
+ * observation the monocular edge above, unchanged. Rounds, early stop and return value as
+ * orbhip_pose_optimization. ORBHIP_ERR_ARG (before anything runs, no result written) when u_right
+ * is NULL with n > 0, an octave is out of range, or bf <= 0 while some u_right[i] >= 0. */
+typedef struct {
+    int32_t n;                  /* correspondences */
+    const float* pose_q;        /* 4 */
+    const float* pose_t;        /* 3 */
+    const float* points;        /* n x 3 */
+    const float* uv;            /* n x 2 */
+    const int32_t* octave;      /* n */
+    const float* inv_sigma2;    /* per octave */
+    int32_t n_octaves;
+    float fx, fy, cx, cy;
+    const float* u_right;       /* n: mvuRight[i] (< 0: monocular observation) */
+    float bf;                   /* mbf = baseline * fx */
+} orbhip_pose_stereo_problem;
+int orbhip_pose_optimization_stereo(orbhip_ctx* ctx, const orbhip_pose_stereo_problem* prob, orbhip_pose_result* res);
+int orbhip_pose_optimization_stereo_batch(orbhip_ctx* ctx, const orbhip_pose_stereo_problem* probs, int B,
+                                          orbhip_pose_result* res);
 
 /* ---- bag of words -----------------------------------------
  * DBoW2 vocabulary in the ORBvoc.txt node order (Thirdparty/DBoW2 TemplatedVocabulary):

@@ -192,6 +192,41 @@ public:
         return rc;
     }
 
+    // U:src/ORBmatcher.cc::SearchByProjection(CurrentFrame, LastFrame, th, bMono = false) on a
+    // rectified-stereo Frame (orbhip_stereo_view: the frame, mvuRight, mbf, mb). last: the LastFrame
+    // entries with a non-outlier MapPoint; Tlw = LastFrame.GetPose(). vnMatches[q] = CurrentFrame
+    // keypoint or -1; *direction (optional) = 1 forward, -1 backward, 0 neither. Returns nmatches.
+    int SearchByProjectionStereo(orbhip_ctx* ctx, const orbhip_stereo_view& CurrentFrame, const orbhip_proj_last& last,
+                                 const float Tlw_q[4], const float Tlw_t[3], float th, std::vector<int>& vnMatches,
+                                 int* direction = nullptr) const {
+        vnMatches.assign((size_t)std::max(last.n, 0), -1);
+        int32_t dir = 0;
+        const int rc = orbhip_search_by_projection_last_stereo(ctx, &CurrentFrame, &last, Tlw_q, Tlw_t, th,
+                                                               mbCheckOrientation ? 1 : 0, vnMatches.data(), &dir);
+        check(rc, "orbhip_search_by_projection_last_stereo");
+        if (direction) *direction = dir;
+        return rc;
+    }
+
+    // Tracking::SearchLocalPoints on a rectified-stereo Frame: Frame::isInFrustum (mbTrackInView,
+    // mnTrackScaleLevel, mTrackProjXR) + SearchByProjection(F, vpMapPoints, th, bFarPoints,
+    // thFarPoints) with the right-coordinate gate. mTrackProjXR is written where mbTrackInView.
+    int SearchLocalPointsStereo(orbhip_ctx* ctx, const orbhip_stereo_view& F, const orbhip_local_points& mps, float th,
+                                bool bFarPoints, float thFarPoints, std::vector<uint8_t>& mbTrackInView,
+                                std::vector<int>& mnTrackScaleLevel, std::vector<float>& mTrackProjXR,
+                                std::vector<int>& vnMatches, float viewingCosLimit = 0.5f) const {
+        const size_t n = (size_t)std::max(mps.n, 0);
+        mbTrackInView.assign(n, 0);
+        mnTrackScaleLevel.assign(n, -1);
+        mTrackProjXR.resize(n);
+        vnMatches.assign(n, -1);
+        const int rc = orbhip_search_local_points_stereo(ctx, &F, &mps, viewingCosLimit, th, mfNNratio,
+                                                         bFarPoints ? 1 : 0, thFarPoints, mbTrackInView.data(),
+                                                         mnTrackScaleLevel.data(), mTrackProjXR.data(), vnMatches.data());
+        check(rc, "orbhip_search_local_points_stereo");
+        return rc;
+    }
+
     // U:src/ORBmatcher.cc::SearchForTriangulation(pKF1, pKF2, vMatchedPairs, false, false) of pKF1
     // against every neighbour in one call (LocalMapping::CreateNewMapPoints).
     // vMatches12[b][i] = neighbour b's feature matched to pKF1's feature i, or -1 (vMatchedPairs of
@@ -440,6 +475,24 @@ public:
         p.iterations = nIterations;
         p.huber_delta = bRobust ? std::sqrt(5.99f) : 0.0f;
         return solve(ctx, p, pbStopFlag);
+    }
+
+    // PoseOptimization(Frame*) of a rectified-stereo Frame: observations with u_right >= 0 are
+    // EdgeStereoSE3ProjectXYZOnlyPose edges, the others monocular. Tcw (q: x, y, z, w) is updated in
+    // place (pFrame->SetPose), mvbOutlier gets one flag per correspondence. Returns
+    // nInitialCorrespondences - nBad.
+    static int PoseOptimizationStereo(orbhip_ctx* ctx, orbhip_pose_stereo_problem p, float Tcw_q[4], float Tcw_t[3],
+                                      std::vector<uint8_t>& mvbOutlier) {
+        p.pose_q = Tcw_q;
+        p.pose_t = Tcw_t;
+        mvbOutlier.assign((size_t)std::max(p.n, 0), 0);
+        orbhip_pose_result r{};
+        r.outlier = mvbOutlier.data();
+        const int rc = orbhip_pose_optimization_stereo(ctx, &p, &r);
+        check(rc, "orbhip_pose_optimization_stereo");
+        for (int k = 0; k < 4; k++) Tcw_q[k] = r.pose_q[k];
+        for (int k = 0; k < 3; k++) Tcw_t[k] = r.pose_t[k];
+        return rc;
     }
 
 private:

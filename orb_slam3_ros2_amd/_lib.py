@@ -67,6 +67,10 @@ class PoseProblemC(ctypes.Structure):
                 ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float)]
 
 
+class PoseStereoProblemC(ctypes.Structure):
+    _fields_ = PoseProblemC._fields_ + [("u_right", ctypes.c_void_p), ("bf", ctypes.c_float)]
+
+
 class PoseResultC(ctypes.Structure):
     _fields_ = [("pose_q", ctypes.c_float * 4), ("pose_t", ctypes.c_float * 3), ("outlier", ctypes.c_void_p),
                 ("n_inliers", ctypes.c_int32), ("lm_trials", ctypes.c_int32)]
@@ -84,6 +88,10 @@ class FrameC(ctypes.Structure):
                 ("scale_factors", ctypes.c_void_p), ("n_levels", ctypes.c_int32), ("log_scale_factor", ctypes.c_float),
                 ("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float), ("cy", ctypes.c_float),
                 ("pose_q", ctypes.c_float * 4), ("pose_t", ctypes.c_float * 3)]
+
+
+class StereoViewC(ctypes.Structure):
+    _fields_ = [("frame", FrameC), ("u_right", ctypes.c_void_p), ("bf", ctypes.c_float), ("b", ctypes.c_float)]
 
 
 class ProjLastC(ctypes.Structure):
@@ -139,6 +147,8 @@ EXPORTED = ["orbhip_abi_version", "orbhip_create", "orbhip_destroy", "orbhip_lev
             "orbhip_bow_transform", "orbhip_bow_transform_device", "orbhip_search_bow",
             "orbhip_pose_optimization", "orbhip_pose_optimization_batch", "orbhip_search_by_projection_last",
             "orbhip_search_local_points", "orbhip_search_for_initialization",
+            "orbhip_pose_optimization_stereo", "orbhip_pose_optimization_stereo_batch",
+            "orbhip_search_by_projection_last_stereo", "orbhip_search_local_points_stereo",
             "orbhip_triangulation_geometry", "orbhip_search_for_triangulation",
             "orbhip_create_new_map_points", "orbhip_triangulate_matches", "orbhip_fuse",
             "orbhip_fuse_sim3", "orbhip_search_by_projection_sim3",
@@ -212,6 +222,13 @@ def lib():
                                                    vp]
     L.orbhip_search_local_points.argtypes = [vp, ctypes.POINTER(FrameC), ctypes.POINTER(LocalPointsC), f32, f32, f32,
                                              i32, f32, vp, vp, vp]
+    L.orbhip_pose_optimization_stereo.argtypes = [vp, ctypes.POINTER(PoseStereoProblemC), ctypes.POINTER(PoseResultC)]
+    L.orbhip_pose_optimization_stereo_batch.argtypes = [vp, ctypes.POINTER(PoseStereoProblemC), i32,
+                                                        ctypes.POINTER(PoseResultC)]
+    L.orbhip_search_by_projection_last_stereo.argtypes = [vp, ctypes.POINTER(StereoViewC), ctypes.POINTER(ProjLastC),
+                                                          vp, vp, f32, i32, vp, ctypes.POINTER(i32)]
+    L.orbhip_search_local_points_stereo.argtypes = [vp, ctypes.POINTER(StereoViewC), ctypes.POINTER(LocalPointsC),
+                                                    f32, f32, f32, i32, f32, vp, vp, vp, vp]
     L.orbhip_search_for_initialization.argtypes = [vp, ctypes.POINTER(InitFrameC), ctypes.POINTER(InitFrameC), vp,
                                                    i32, f32, i32, vp]
     L.orbhip_triangulation_geometry.argtypes = [ctypes.POINTER(TriKeyFrameC), ctypes.POINTER(TriKeyFrameC), vp, vp]

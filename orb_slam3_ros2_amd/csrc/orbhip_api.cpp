@@ -391,6 +391,47 @@ int orbhip_search_local_points(orbhip_ctx* c, const orbhip_frame* frame, const o
                              match, nullptr, c->stream);
 }
 
+int orbhip_pose_optimization_stereo_batch(orbhip_ctx* c, const orbhip_pose_stereo_problem* probs, int B,
+                                          orbhip_pose_result* res) {
+    if (!c || !probs || !res || B <= 0) return ORBHIP_ERR_ARG;
+    HIPOK(hipSetDevice(c->device));
+    if (!c->pose) c->pose = pose_ws_create();
+    if (!c->pose) return ORBHIP_ERR_DEVICE;
+    return pose_opt_stereo_batch(c->pose, probs, B, res, c->stream);
+}
+
+int orbhip_pose_optimization_stereo(orbhip_ctx* c, const orbhip_pose_stereo_problem* prob, orbhip_pose_result* res) {
+    const int rc = orbhip_pose_optimization_stereo_batch(c, prob, 1, res);
+    return rc < 0 ? rc : res->n_inliers;
+}
+
+int orbhip_search_by_projection_last_stereo(orbhip_ctx* c, const orbhip_stereo_view* cur, const orbhip_proj_last* last,
+                                            const float last_pose_q[4], const float last_pose_t[3], float th,
+                                            int check_orientation, int32_t* match, int32_t* direction) {
+    if (!c || !cur || !last_pose_q || !last_pose_t || (cur->frame.n > 0 && !cur->u_right) || !(cur->bf > 0.0f) ||
+        !(cur->b > 0.0f))
+        return ORBHIP_ERR_ARG;
+    HIPOK(hipSetDevice(c->device));
+    if (!c->proj) c->proj = proj_ws_create();
+    const ProjStereo sx{cur->u_right, cur->bf,
+                        proj_direction(cur->frame.pose_q, cur->frame.pose_t, last_pose_q, last_pose_t, cur->b), nullptr};
+    const int rc = proj_search_last(c->proj, &cur->frame, last, th, check_orientation, match, nullptr, c->stream, &sx);
+    if (rc >= 0 && direction) *direction = sx.dir;
+    return rc;
+}
+
+int orbhip_search_local_points_stereo(orbhip_ctx* c, const orbhip_stereo_view* frame, const orbhip_local_points* mps,
+                                      float view_cos_limit, float th, float nnratio, int far_points, float th_far,
+                                      uint8_t* in_view, int32_t* level, float* proj_xr, int32_t* match) {
+    if (!c || !frame || (frame->frame.n > 0 && !frame->u_right) || !(frame->bf > 0.0f) || !(frame->b > 0.0f))
+        return ORBHIP_ERR_ARG;
+    HIPOK(hipSetDevice(c->device));
+    if (!c->proj) c->proj = proj_ws_create();
+    const ProjStereo sx{frame->u_right, frame->bf, 0, proj_xr};
+    return proj_search_local(c->proj, &frame->frame, mps, view_cos_limit, th, nnratio, far_points, th_far, in_view,
+                             level, match, nullptr, c->stream, &sx);
+}
+
 int orbhip_search_for_initialization(orbhip_ctx* c, const orbhip_init_frame* f1, const orbhip_init_frame* f2,
                                      float* prev_matched, int window_size, float nnratio, int check_orientation,
                                      int32_t* matches12) {

@@ -11,6 +11,12 @@
 // solves it redundantly (dense LDL^T), so the lanes never exchange anything but the edge sums.
 // Edge sums are fixed-order LDS reductions (partials -> strip sums -> totals) with the same bits in
 // every lane, the per-trial chi2 a DPP/permlane wave sum then the W wave sums in order.
+// Stereo form (k_pose_opt<W, true>, rectified stereo frames): an observation with u_right >= 0 is an
+// EdgeStereoSE3ProjectXYZOnlyPose: e = (u, v, u_right) - (fx x/z + cx, fy y/z + cy, fx x/z + cx - bf/z),
+// Omega = I3 invSigma2[oct], Huber deltaStereo = (float)sqrt(7.815), outlier iff chi2 > 7.815; its
+// Jacobian rows 0, 1 are the monocular ones and row 2 = row 0 + bf/z^2 (-y, x, 0, 0, ., -1) (column 4
+// is 0). The other observations of the frame are the monocular edge above with the same expressions
+// (their third residual and Jacobian row are zeros, which add nothing to any sum).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,6 +26,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/orbhip.h"
@@ -36,6 +43,7 @@ struct PoseHdr {
     double T0[8];            // initial Tcw (normalised quaternion, translation)
     double fx, fy, cx, cy, delta;
     int n, off;              // edges [off, off + n) of the packed edge arrays
+    double delta_s, bf;      // stereo form: deltaStereo, mbf
 };
 struct PoseOut {
     double T[8];
@@ -44,6 +52,11 @@ struct PoseOut {
 struct PoseEdgeIn {          // float inputs as the reference holds them
     float X[3], u, v, info;
 };
+struct PoseEdgeStereoIn {    // the stereo form's record: ur = mvuRight (< 0: a monocular edge)
+    float X[3], u, v, info, ur;
+};
+template <bool Stereo> struct PoseEdgeOf { using type = PoseEdgeIn; };
+template <> struct PoseEdgeOf<true> { using type = PoseEdgeStereoIn; };
 
 namespace {
 
@@ -116,6 +129,20 @@ __device__ __forceinline__ void edge_err(const double* T, const PoseEdgeIn& ed, 
     chi2 = (double)ed.info * (e0 * e0 + e1 * e1);
 }
 
+// the stereo form's record. A monocular record (ur < 0) has e2 = 0, and (e0^2 + e1^2) + 0 is the
+// monocular chi2 bit for bit
+__device__ __forceinline__ void edge_err(const double* T, const PoseEdgeStereoIn& ed, const PoseHdr& h, double& e0,
+                                         double& e1, double& e2, double& chi2, double& x, double& y, double& z) {
+    const DQ q = load_q(T);
+    qrot(q, (double)ed.X[0], (double)ed.X[1], (double)ed.X[2], x, y, z);
+    x += T[4]; y += T[5]; z += T[6];
+    const double iz = 1.0 / z;
+    e0 = (double)ed.u - (h.fx * x * iz + h.cx);
+    e1 = (double)ed.v - (h.fy * y * iz + h.cy);
+    e2 = ed.ur >= 0.0f ? (double)ed.ur - (h.fx * x * iz + h.cx - h.bf * iz) : 0.0;
+    chi2 = (double)ed.info * (e0 * e0 + e1 * e1 + e2 * e2);
+}
+
 __device__ __forceinline__ void huber(double chi2, double delta, bool robust, double& rho0, double& rho1) {
     rho0 = chi2; rho1 = 1.0;
     if (robust && delta > 0) {
@@ -164,16 +191,18 @@ __device__ __forceinline__ bool ldlt6(double S[36], const double b[6], double x[
 
 // g2o optimize(10) over the level-0 edges of one frame (one wave). chi2_last[e] = the chi2 of
 // the last computeActiveErrors that saw edge e (stale after a rejected final trial, as g2o).
-template <int W>
-__device__ void pose_optimize(FrameGroup<W>& g, double* T, const PoseHdr& h, const PoseEdgeIn* __restrict__ ed,
+template <int W, bool Stereo>
+__device__ void pose_optimize(FrameGroup<W>& g, double* T, const PoseHdr& h,
+                              const typename PoseEdgeOf<Stereo>::type* __restrict__ ed,
                               const uint8_t* __restrict__ level, double* __restrict__ chi2_last, bool robust,
                               int& trials) {
+    using Edge = typename PoseEdgeOf<Stereo>::type;
     constexpr int NT = FrameGroup<W>::T;
     // the first EC edges of every thread stay in registers for all trials (their level is fixed
     // during optimize(): a bit mask); the rest are re-read each pass
     constexpr int EC = W == 1 ? 2 : 4;
     const int tid = g.tid, n = h.n;
-    PoseEdgeIn ec[EC];
+    Edge ec[EC];
     unsigned act = 0;
     int na = 0;
 #pragma unroll
@@ -193,10 +222,17 @@ __device__ void pose_optimize(FrameGroup<W>& g, double* T, const PoseHdr& h, con
         double acc[kAcc];
 #pragma unroll
         for (int k = 0; k < kAcc; k++) acc[k] = 0.0;
-        auto build = [&](const PoseEdgeIn& E, int e) {
+        auto build = [&](const Edge& E, int e) {
             double e0, e1, c2, x, y, z, r0, r1;
-            edge_err(T, E, h, e0, e1, c2, x, y, z);
-            huber(c2, h.delta, robust, r0, r1);
+            [[maybe_unused]] double e2 = 0.0;
+            double delta = h.delta;
+            if constexpr (Stereo) {
+                edge_err(T, E, h, e0, e1, e2, c2, x, y, z);
+                if (E.ur >= 0.0f) delta = h.delta_s;
+            } else {
+                edge_err(T, E, h, e0, e1, c2, x, y, z);
+            }
+            huber(c2, delta, robust, r0, r1);
             chi2_last[e] = c2;
             acc[27] += r0;
             double J[6];
@@ -213,12 +249,28 @@ __device__ void pose_optimize(FrameGroup<W>& g, double* T, const PoseHdr& h, con
             const double w = r1 * (double)E.info;
             const double om0 = -(double)E.info * e0 * r1, om1 = -(double)E.info * e1 * r1;
             int t = 0;
+            if constexpr (Stereo) {
+                // row 2 from row 0; all zeros (and om2 = -0) for a monocular record
+                const bool st = E.ur >= 0.0f;
+                const double k = h.bf * iz2;
+                const double B2[6] = {st ? B[0] - k * y : 0.0, st ? B[1] + k * x : 0.0, st ? B[2] : 0.0,
+                                      st ? B[3] : 0.0, 0.0, st ? B[5] - k : 0.0};
+                const double om2 = -(double)E.info * e2 * r1;
 #pragma unroll
-            for (int r = 0; r < 6; r++)
+                for (int r = 0; r < 6; r++)
 #pragma unroll
-                for (int c = r; c < 6; c++) acc[t++] += w * (B[r] * B[c] + B[6 + r] * B[6 + c]);
+                    for (int c = r; c < 6; c++)
+                        acc[t++] += w * (B[r] * B[c] + B[6 + r] * B[6 + c] + B2[r] * B2[c]);
 #pragma unroll
-            for (int r = 0; r < 6; r++) acc[21 + r] += B[r] * om0 + B[6 + r] * om1;
+                for (int r = 0; r < 6; r++) acc[21 + r] += B[r] * om0 + B[6 + r] * om1 + B2[r] * om2;
+            } else {
+#pragma unroll
+                for (int r = 0; r < 6; r++)
+#pragma unroll
+                    for (int c = r; c < 6; c++) acc[t++] += w * (B[r] * B[c] + B[6 + r] * B[6 + c]);
+#pragma unroll
+                for (int r = 0; r < 6; r++) acc[21 + r] += B[r] * om0 + B[6 + r] * om1;
+            }
         };
 #pragma unroll
         for (int c = 0; c < EC; c++)
@@ -260,10 +312,17 @@ __device__ void pose_optimize(FrameGroup<W>& g, double* T, const PoseHdr& h, con
             for (int k = 0; k < 8; k++) Tn[k] = T[k];
             se3_update(x, Tn);
             double tc = 0;
-            auto chi = [&](const PoseEdgeIn& E, int e) {
+            auto chi = [&](const Edge& E, int e) {
                 double e0, e1, c2, px, py, pz, r0, r1;
-                edge_err(Tn, E, h, e0, e1, c2, px, py, pz);
-                huber(c2, h.delta, robust, r0, r1);
+                double delta = h.delta;
+                if constexpr (Stereo) {
+                    double e2;
+                    edge_err(Tn, E, h, e0, e1, e2, c2, px, py, pz);
+                    if (E.ur >= 0.0f) delta = h.delta_s;
+                } else {
+                    edge_err(Tn, E, h, e0, e1, c2, px, py, pz);
+                }
+                huber(c2, delta, robust, r0, r1);
                 chi2_last[e] = c2;
                 tc += r0;
             };
@@ -301,8 +360,9 @@ __device__ void pose_optimize(FrameGroup<W>& g, double* T, const PoseHdr& h, con
 }  // namespace
 
 // W wavefronts per frame, 4 / W frames per 256-thread work-group
-template <int W>
-__global__ __launch_bounds__(256) void k_pose_opt(const PoseHdr* __restrict__ hdr, const PoseEdgeIn* __restrict__ edges,
+template <int W, bool Stereo>
+__global__ __launch_bounds__(256) void k_pose_opt(const PoseHdr* __restrict__ hdr,
+                                                   const typename PoseEdgeOf<Stereo>::type* __restrict__ edges,
                                                    uint8_t* __restrict__ level, uint8_t* __restrict__ outlier,
                                                    double* __restrict__ chi2_last, PoseOut* __restrict__ out,
                                                    uint8_t* __restrict__ outlier_copy, int B) {
@@ -316,7 +376,7 @@ __global__ __launch_bounds__(256) void k_pose_opt(const PoseHdr* __restrict__ hd
     g.tid = threadIdx.x - grp * NT;
     const int tid = g.tid;
     const PoseHdr h = hdr[f];
-    const PoseEdgeIn* ed = edges + h.off;
+    const typename PoseEdgeOf<Stereo>::type* ed = edges + h.off;
     uint8_t* lv = level + h.off;
     uint8_t* ol = outlier + h.off;
     double* c2 = chi2_last + h.off;
@@ -330,15 +390,22 @@ __global__ __launch_bounds__(256) void k_pose_opt(const PoseHdr* __restrict__ hd
         for (int round = 0; round < 4; round++) {
 #pragma unroll
             for (int k = 0; k < 8; k++) T[k] = h.T0[k];   // vSE3->setEstimate(pFrame->GetPose())
-            pose_optimize<W>(g, T, h, ed, lv, c2, robust, trials);
+            pose_optimize<W, Stereo>(g, T, h, ed, lv, c2, robust, trials);
             int nb = 0;
             for (int e = tid; e < h.n; e += NT) {   // each thread only touches its own edges
                 double chi = c2[e];
-                if (ol[e]) {   // level-1 edge: e->computeError() at the current estimate
+                double th = (double)5.991f;
+                if constexpr (Stereo) {
+                    if (ed[e].ur >= 0.0f) th = (double)7.815f;   // chi2Stereo
+                    if (ol[e]) {
+                        double e0, e1, e2, x, y, z;
+                        edge_err(T, ed[e], h, e0, e1, e2, chi, x, y, z);
+                    }
+                } else if (ol[e]) {   // level-1 edge: e->computeError() at the current estimate
                     double e0, e1, x, y, z;
                     edge_err(T, ed[e], h, e0, e1, chi, x, y, z);
                 }
-                const bool bad = chi > (double)5.991f;
+                const bool bad = chi > th;
                 ol[e] = bad; lv[e] = bad; nb += bad;
             }
             nbad = (int)g.sum1((double)nb);
@@ -367,21 +434,29 @@ struct PoseWorkspace {
 PoseWorkspace* pose_ws_create() { return new PoseWorkspace(); }
 void pose_ws_destroy(PoseWorkspace* w) { delete w; }
 
-int pose_opt_batch(PoseWorkspace* ws, const orbhip_pose_problem* probs, int B, orbhip_pose_result* res,
-                   hipStream_t st) {
+// Problem = orbhip_pose_problem (monocular kernels) or orbhip_pose_stereo_problem (stereo kernels)
+template <class Problem>
+static int pose_opt_batch_t(PoseWorkspace* ws, const Problem* probs, int B, orbhip_pose_result* res, hipStream_t st) {
+    constexpr bool Stereo = std::is_same<Problem, orbhip_pose_stereo_problem>::value;
+    using Edge = typename PoseEdgeOf<Stereo>::type;
     if (!ws || !probs || !res || B <= 0) return ORBHIP_ERR_ARG;
     size_t E = 0;
     for (int b = 0; b < B; b++) {
-        const orbhip_pose_problem& p = probs[b];
+        const Problem& p = probs[b];
         if (p.n < 0 || !p.pose_q || !p.pose_t || (p.n && (!p.points || !p.uv || !p.octave || !p.inv_sigma2)))
             return ORBHIP_ERR_ARG;
         for (int e = 0; e < p.n; e++)
             if (p.octave[e] < 0 || p.octave[e] >= p.n_octaves) return ORBHIP_ERR_ARG;
+        if constexpr (Stereo) {
+            if (p.n && !p.u_right) return ORBHIP_ERR_ARG;
+            for (int e = 0; e < p.n; e++)
+                if (p.u_right[e] >= 0.0f && !(p.bf > 0.0f)) return ORBHIP_ERR_ARG;
+        }
         E += p.n;
     }
     // packed: [hdr B][edges E] (one upload) [out B][outlier E] (one download) [chi2 E][level E]
     StageLayout lay(256);
-    const size_t o_hdr = lay.take(sizeof(PoseHdr) * B), o_edge = lay.take(sizeof(PoseEdgeIn) * E);
+    const size_t o_hdr = lay.take(sizeof(PoseHdr) * B), o_edge = lay.take(sizeof(Edge) * E);
     const size_t o_out = lay.take(sizeof(PoseOut) * B), o_ol = lay.take(E), o_c2 = lay.take(sizeof(double) * E);
     const size_t o_lv = lay.take(E), total = lay.total();
     HIPOK(ws->s.ensure(total, total));
@@ -389,11 +464,11 @@ int pose_opt_batch(PoseWorkspace* ws, const orbhip_pose_problem* probs, int B, o
     char* D = (char*)ws->s.d;
     char* HD = (char*)ws->s.hd;
     PoseHdr* hh = (PoseHdr*)(H + o_hdr);
-    PoseEdgeIn* he = (PoseEdgeIn*)(H + o_edge);
+    Edge* he = (Edge*)(H + o_edge);
     const float deltaMono = (float)std::sqrt(5.991);
     size_t off = 0;
     for (int b = 0; b < B; b++) {
-        const orbhip_pose_problem& p = probs[b];
+        const Problem& p = probs[b];
         PoseHdr& h = hh[b];
         // g2o::SE3Quat(q.cast<double>(), t.cast<double>()) normalises the rotation
         double x = p.pose_q[0], y = p.pose_q[1], z = p.pose_q[2], w = p.pose_q[3];
@@ -403,17 +478,20 @@ int pose_opt_batch(PoseWorkspace* ws, const orbhip_pose_problem* probs, int B, o
         h.T0[4] = p.pose_t[0]; h.T0[5] = p.pose_t[1]; h.T0[6] = p.pose_t[2]; h.T0[7] = 0;
         h.fx = p.fx; h.fy = p.fy; h.cx = p.cx; h.cy = p.cy; h.delta = deltaMono;
         h.n = p.n; h.off = (int)off;
+        h.delta_s = 0; h.bf = 0;
+        if constexpr (Stereo) { h.delta_s = (float)std::sqrt(7.815); h.bf = p.bf; }
         for (int e = 0; e < p.n; e++) {
-            PoseEdgeIn& E_ = he[off + e];
+            Edge& E_ = he[off + e];
             E_.X[0] = p.points[3 * e]; E_.X[1] = p.points[3 * e + 1]; E_.X[2] = p.points[3 * e + 2];
             E_.u = p.uv[2 * e]; E_.v = p.uv[2 * e + 1];
             E_.info = p.inv_sigma2[p.octave[e]];
+            if constexpr (Stereo) E_.ur = p.u_right[e];
         }
         off += p.n;
     }
     // small batches (one tracking frame): a shader upload and results written straight into the
     // pinned block (no DMA-engine copies); large batches: DMA both ways
-    const size_t in_bytes = o_edge + sizeof(PoseEdgeIn) * E;
+    const size_t in_bytes = o_edge + sizeof(Edge) * E;
     const bool small = in_bytes <= ((size_t)1 << 20);
     if (small) HIPOK(upload_inputs(HD, D, H, in_bytes, st));
     else HIPOK(hipMemcpyAsync(D, H, in_bytes, hipMemcpyHostToDevice, st));
@@ -421,17 +499,18 @@ int pose_opt_batch(PoseWorkspace* ws, const orbhip_pose_problem* probs, int B, o
     int W = B <= 512 ? 4 : 1;
     if (const char* s = std::getenv("ORBHIP_POSE_WAVES")) W = std::atoi(s) == 1 ? 1 : 4;
     const PoseHdr* dh = (const PoseHdr*)(D + o_hdr);
-    const PoseEdgeIn* de = (const PoseEdgeIn*)(D + o_edge);
+    const Edge* de = (const Edge*)(D + o_edge);
     uint8_t* dlv = (uint8_t*)(D + o_lv);
     uint8_t* dol = (uint8_t*)(D + o_ol);
     double* dc2 = (double*)(D + o_c2);
     PoseOut* dout = (PoseOut*)((small ? HD : D) + o_out);
     uint8_t* olc = small ? (uint8_t*)HD + o_ol : nullptr;
     if (W == 4)
-        hipLaunchKernelGGL(k_pose_opt<4>, dim3((unsigned)B), dim3(256), 0, st, dh, de, dlv, dol, dc2, dout, olc, B);
+        hipLaunchKernelGGL((k_pose_opt<4, Stereo>), dim3((unsigned)B), dim3(256), 0, st, dh, de, dlv, dol, dc2, dout,
+                           olc, B);
     else
-        hipLaunchKernelGGL(k_pose_opt<1>, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, dh, de, dlv, dol, dc2,
-                           dout, olc, B);
+        hipLaunchKernelGGL((k_pose_opt<1, Stereo>), dim3((unsigned)((B + 3) / 4)), dim3(256), 0, st, dh, de, dlv, dol,
+                           dc2, dout, olc, B);
     HIPOK(hipGetLastError());
     if (!small) HIPOK(hipMemcpyAsync(H + o_out, D + o_out, o_ol - o_out + E, hipMemcpyDeviceToHost, st));
     HIPOK(hipStreamSynchronize(st));
@@ -446,6 +525,16 @@ int pose_opt_batch(PoseWorkspace* ws, const orbhip_pose_problem* probs, int B, o
         if (r.outlier) std::memcpy(r.outlier, hol + hh[b].off, probs[b].n);
     }
     return ORBHIP_OK;
+}
+
+int pose_opt_batch(PoseWorkspace* ws, const orbhip_pose_problem* probs, int B, orbhip_pose_result* res,
+                   hipStream_t st) {
+    return pose_opt_batch_t(ws, probs, B, res, st);
+}
+
+int pose_opt_stereo_batch(PoseWorkspace* ws, const orbhip_pose_stereo_problem* probs, int B, orbhip_pose_result* res,
+                          hipStream_t st) {
+    return pose_opt_batch_t(ws, probs, B, res, st);
 }
 
 }  // namespace orbhip

@@ -17,6 +17,10 @@
 // picks" (owner[k] < i, an atomicMin over the picks); query i is final once queries < i are, and
 // a round that changes nothing is exactly the sequential result (each pick equals its greedy
 // definition given the picks before it). Typically 2-3 rounds.
+// Rectified-stereo frames (the stereo branches of both functions): the query also carries its
+// projection into the right image, a candidate with a right coordinate further than the window
+// radius from it is skipped (stereo_gate, in every device form), and the last-frame search takes
+// its level window from the direction of motion (proj_direction, decided on the host).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -50,11 +54,19 @@ struct ProjFrame {     // the current Frame
     float minx, maxx, miny, maxy, invw, invh;
     float q[4], t[3], fx, fy, cx, cy;
     float R[9], Ow[3];   // mRcw, mOw (isInFrustum)
+    float bf;            // mbf of a rectified-stereo Frame (0: monocular, ur = u)
 };
 struct Query {         // one projected MapPoint: GetFeaturesInArea(u, v, r, minL, maxL)
     float u, v, r;
     int minL, maxL, valid;
+    float ur;          // its projection into the right image, u - bf / z (the stereo gate)
 };
+// The stereo gate of both searches, a property of the (query, keypoint) pair: a keypoint with a
+// right coordinate (mvuRight > 0) further than the window radius from the query's is skipped.
+// u_right < 0 (or no u_right array: the monocular searches) never gates.
+__device__ __forceinline__ bool stereo_gate(const Query& Q, float u_right) {
+    return u_right > 0.0f && fabsf(Q.ur - u_right) > Q.r;
+}
 
 __global__ void k_proj_cells(ProjFrame f, const orbhip_kp* __restrict__ kps, int* __restrict__ cell) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -63,12 +75,14 @@ __global__ void k_proj_cells(ProjFrame f, const orbhip_kp* __restrict__ kps, int
 }
 
 // SearchByProjection(CurrentFrame, LastFrame, th, bMono): window th * scale[lastOctave], levels
-// lastOctave - 1 .. lastOctave + 1
+// lastOctave - 1 .. lastOctave + 1; !bMono and the camera moved forward (dir 1): lastOctave and up,
+// backward (dir -1): 0 .. lastOctave
 struct PrepLast {
     const float* pts;
     const int* oct;
     const float* scale;
     float th;
+    int dir;
 };
 __device__ __forceinline__ Query prep_last(const ProjFrame& f, const PrepLast& a, int i) {
     Query Q{0, 0, 0, 0, 0, 0};
@@ -81,7 +95,10 @@ __device__ __forceinline__ Query prep_last(const ProjFrame& f, const PrepLast& a
         const float u = f.fx * Xc[0] / Xc[2] + f.cx, v = f.fy * Xc[1] / Xc[2] + f.cy;
         if (!(u < f.minx || u > f.maxx || v < f.miny || v > f.maxy)) {
             const int lo = a.oct[i];
-            Q = Query{u, v, a.th * a.scale[lo], lo - 1, lo + 1, 1};
+            const float ur = u - f.bf * invzc;
+            const int minL = a.dir > 0 ? lo : a.dir < 0 ? 0 : lo - 1;
+            const int maxL = a.dir > 0 ? -1 : a.dir < 0 ? lo : lo + 1;
+            Q = Query{u, v, a.th * a.scale[lo], minL, maxL, 1, ur};
         }
     }
     return Q;
@@ -103,10 +120,11 @@ struct PrepLocal {
     float th_far;
 };
 __device__ __forceinline__ Query prep_local(const ProjFrame& f, const PrepLocal& a, int m, uint8_t* iv_out,
-                                            int* lvl_out) {
+                                            int* lvl_out, float* xr_out) {
     Query Q{0, 0, 0, 0, 0, 0};
     uint8_t iv = 0;
     int lvl = -1;
+    float xr = 0.0f;
     do {
         if (a.skip && a.skip[m]) break;
         const float* P = a.pts + 3 * m;
@@ -132,24 +150,30 @@ __device__ __forceinline__ Query prep_local(const ProjFrame& f, const PrepLocal&
         else if (nScale >= a.n_levels) nScale = a.n_levels - 1;
         iv = 1;
         lvl = nScale;
+        const float invz = 1.0f / Pc[2];
+        xr = u - f.bf * invz;   // mTrackProjXR
         if (a.far_points && Pc_dist > a.th_far) break;
         float r = viewCos > 0.998 ? 2.5f : 4.0f;   // RadiusByViewingCos
         if (a.th != 1.0f) r *= a.th;
-        Q = Query{u, v, r * a.scale[nScale], nScale - 1, nScale, 1};
+        Q = Query{u, v, r * a.scale[nScale], nScale - 1, nScale, 1, xr};
     } while (false);
     *iv_out = iv;
     *lvl_out = lvl;
+    *xr_out = xr;
     return Q;
 }
 __global__ void k_proj_prep_local(ProjFrame f, int nq, PrepLocal a, Query* __restrict__ qs,
-                                  uint8_t* __restrict__ in_view, int* __restrict__ level) {
+                                  uint8_t* __restrict__ in_view, int* __restrict__ level,
+                                  float* __restrict__ proj_xr) {
     const int m = blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= nq) return;
     uint8_t iv;
     int lvl;
-    qs[m] = prep_local(f, a, m, &iv, &lvl);
+    float xr;
+    qs[m] = prep_local(f, a, m, &iv, &lvl, &xr);
     in_view[m] = iv;
     level[m] = lvl;
+    if (proj_xr) proj_xr[m] = xr;
 }
 
 // lexicographic (dist, key) top-2 with the level of each
@@ -171,7 +195,7 @@ __global__ __launch_bounds__(256) void k_proj_round(ProjFrame f, int nq, int mod
                                                     const uint8_t* __restrict__ kdesc, const int* __restrict__ cell,
                                                     const uint8_t* __restrict__ claimed, int* __restrict__ own3,
                                                     const uint8_t* __restrict__ qdesc, int* __restrict__ pick,
-                                                    int* __restrict__ chg) {
+                                                    int* __restrict__ chg, const float* __restrict__ u_right) {
     if (r > 0 && chg[r - 1] == 0) return;   // converged: uniform over the grid
     const int n = f.n;
     const int* __restrict__ owner = own3 + (size_t)(r % 3) * n;
@@ -206,6 +230,7 @@ __global__ __launch_bounds__(256) void k_proj_round(ProjFrame f, int nq, int mod
                 }
                 if (!(fabsf(kp.x - Q.u) < Q.r && fabsf(kp.y - Q.v) < Q.r)) continue;
                 if ((claimed && claimed[k]) || owner[k] < i) continue;
+                if (u_right && stereo_gate(Q, u_right[k])) continue;
                 const uint4* kd4 = (const uint4*)(kdesc + 32 * (size_t)k);
                 const uint4 ka = kd4[0], kb = kd4[1];
                 const int d = hamming256(qa, qb, ka, kb);
@@ -354,7 +379,7 @@ __device__ void resolve_body(unsigned char* rsm, int n, int nq, float nnratio, i
                              unsigned long long* tr = nullptr);
 
 // the frame's keypoints are staged once per work-group in LDS as (x, y, cell << 16 | claimed << 8 |
-// octave, 0): PosInGrid computed as k_proj_cells does, a 16-byte read per lane and keypoint. The
+// octave, u_right or -1): PosInGrid computed as k_proj_cells does, a 16-byte read per lane and keypoint. The
 // query's window is computed first, so its loads overlap the staging. A list entry is written for
 // every keypoint passing the window tests (distance 256 included, skipped by the rounds): the
 // ballot does not wait on the descriptor load, so the loads of all the scan's steps overlap.
@@ -367,7 +392,9 @@ __global__ __launch_bounds__(1024) void k_proj_lists(ProjFrame f, int nq, PrepLa
                                                      const uint8_t* __restrict__ qdesc,
                                                      uint64_t* __restrict__ lists, int* __restrict__ lcnt,
                                                      int* __restrict__ pick0, uint8_t* __restrict__ in_view,
-                                                     int* __restrict__ level, ResolveArgs ra) {
+                                                     int* __restrict__ level, ResolveArgs ra,
+                                                     const float* __restrict__ u_right,
+                                                     float* __restrict__ proj_xr) {
     extern __shared__ uint4 kl[];
     TR_BEGIN()
     const int n = f.n, nt = blockDim.x;
@@ -383,9 +410,10 @@ __global__ __launch_bounds__(1024) void k_proj_lists(ProjFrame f, int nq, PrepLa
     uint4 qa{0u, 0u, 0u, 0u}, qb{0u, 0u, 0u, 0u};
     uint8_t iv = 0;
     int lvl = 0;
+    float xr = 0.0f;
     if (i < nq) {
         if constexpr (MODE == 0) Q = prep_last(f, pl, i);
-        else Q = prep_local(f, pc, i, &iv, &lvl);
+        else Q = prep_local(f, pc, i, &iv, &lvl, &xr);
         const uint4* qd4 = (const uint4*)(qdesc + 32 * (size_t)i);
         qa = qd4[0];
         qb = qd4[1];
@@ -395,11 +423,13 @@ __global__ __launch_bounds__(1024) void k_proj_lists(ProjFrame f, int nq, PrepLa
     for (int k0 = threadIdx.x; k0 < n; k0 += 2 * nt) {
         orbhip_kp kp[2];
         uint32_t cl[2];
+        float kur[2];
 #pragma unroll
         for (int u = 0; u < 2; u++) {
             const int k = min(k0 + u * nt, n - 1);
             kp[u] = kps[k];
             cl[u] = (claimed && claimed[k]) ? 1u : 0u;
+            kur[u] = u_right ? u_right[k] : -1.0f;
         }
 #pragma unroll
         for (int u = 0; u < 2; u++) {
@@ -407,7 +437,7 @@ __global__ __launch_bounds__(1024) void k_proj_lists(ProjFrame f, int nq, PrepLa
             if (k >= n) break;
             const int c = grid_cell(f.minx, f.miny, f.invw, f.invh, kp[u].x, kp[u].y, 0xFFFF);
             kl[k] = uint4{__float_as_uint(kp[u].x), __float_as_uint(kp[u].y), ((uint32_t)c << 16) | (cl[u] << 8) |
-                          (uint32_t)(kp[u].octave & 0xFF), 0u};
+                          (uint32_t)(kp[u].octave & 0xFF), __float_as_uint(kur[u])};
             kc[k] = (uint16_t)c;
         }
     }
@@ -450,8 +480,8 @@ __global__ __launch_bounds__(1024) void k_proj_lists(ProjFrame f, int nq, PrepLa
         }
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        // 1b: the level / radius / claimed tests on the rectangle's keypoints (every keypoint when
-        // the rectangle held more than kRectCap), compacted into wl
+        // 1b: the level / radius / claimed tests and the stereo gate on the rectangle's keypoints
+        // (every keypoint when the rectangle held more than kRectCap), compacted into wl
         const bool all = nr > kRectCap;
         const int nb = all ? n : nr;
         for (int j0 = 0; any && j0 < nb; j0 += 64) {
@@ -465,7 +495,8 @@ __global__ __launch_bounds__(1024) void k_proj_lists(ProjFrame f, int nq, PrepLa
                 const float x = __uint_as_float(e.x), y = __uint_as_float(e.y);
                 ok = !all || in_rect((int)(e.z >> 16));
                 if (ok && bCheckLevels) ok = (int)oct >= Q.minL && !(Q.maxL >= 0 && (int)oct > Q.maxL);
-                ok = ok && fabsf(x - Q.u) < Q.r && fabsf(y - Q.v) < Q.r && !((e.z >> 8) & 1u);
+                ok = ok && fabsf(x - Q.u) < Q.r && fabsf(y - Q.v) < Q.r && !((e.z >> 8) & 1u) &&
+                     !stereo_gate(Q, __uint_as_float(e.w));
             }
             const uint64_t m = __ballot(ok);
             const int pos = cnt + __popcll(m & lt);
@@ -516,7 +547,11 @@ __global__ __launch_bounds__(1024) void k_proj_lists(ProjFrame f, int nq, PrepLa
     // after the resolve in the resolving work-group, whose barriers drain stores), not before it
     auto host_outputs = [&]() {
         if constexpr (MODE == 1)
-            if (lane == 0 && i < nq) { in_view[i] = iv; level[i] = lvl; }
+            if (lane == 0 && i < nq) {
+                in_view[i] = iv;
+                level[i] = lvl;
+                if (proj_xr) proj_xr[i] = xr;
+            }
     };
     if (!ra.fuse) { host_outputs(); TR_END(7) return; }   // uniform
     // one launch: every wave's list stores drained, then the last work-group to arrive resolves
@@ -1274,7 +1309,7 @@ int ensure(ProjWorkspace* ws, size_t total) {
 template <typename Tail>
 int run_rounds(ProjWorkspace* ws, const ProjFrame& f, int nq, int mode, float nnratio, char* D, size_t o_q,
                size_t o_kps, size_t o_kd, size_t o_cell, const uint8_t* claimed, size_t o_own, size_t o_qd,
-               size_t o_pick, size_t o_chg, char* H, hipStream_t st, Tail&& tail) {
+               size_t o_pick, size_t o_chg, char* H, hipStream_t st, const float* u_right, Tail&& tail) {
     const dim3 gq((unsigned)std::max(1, (nq + 3) / 4));
     const int cap = nq + 2;   // a fixed point is reached within nq + 1 rounds
     int* chg = (int*)(D + o_chg);
@@ -1288,7 +1323,7 @@ int run_rounds(ProjWorkspace* ws, const ProjFrame& f, int nq, int mode, float nn
             hipLaunchKernelGGL(k_proj_round, gq, dim3(256), 0, st, f, nq, mode, nnratio, r + j,
                                (const Query*)(D + o_q), (const orbhip_kp*)(D + o_kps), (const uint8_t*)(D + o_kd),
                                (const int*)(D + o_cell), claimed, (int*)(D + o_own), (const uint8_t*)(D + o_qd),
-                               (int*)(D + o_pick), chg);
+                               (int*)(D + o_pick), chg, u_right);
         HIPOK(hipGetLastError());
         if (int rc = tail()) return rc;
         HIPOK(hipMemcpyAsync(H + o_chg + sizeof(int) * r, chg + r, sizeof(int) * R, hipMemcpyDeviceToHost, st));
@@ -1353,11 +1388,24 @@ struct OutBlock {
 
 }  // namespace
 
+// twc = -Rcw^T tcw, tlc = Rlw twc + tlw (float, in the order written); forward: tlc.z > b,
+// backward: -tlc.z > b. Decided on the host and passed to the kernels as a uniform.
+int proj_direction(const float cur_q[4], const float cur_t[3], const float last_q[4], const float last_t[3], float b) {
+    float Rc[9], Rl[9];
+    quat_to_matrix(cur_q, Rc);
+    quat_to_matrix(last_q, Rl);
+    float twc[3];
+    for (int j = 0; j < 3; j++) twc[j] = -(Rc[j] * cur_t[0] + Rc[3 + j] * cur_t[1] + Rc[6 + j] * cur_t[2]);
+    const float tlcz = Rl[6] * twc[0] + Rl[7] * twc[1] + Rl[8] * twc[2] + last_t[2];
+    return tlcz > b ? 1 : (-tlcz > b ? -1 : 0);
+}
+
 int proj_search_last(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_proj_last* L, float th,
-                     int check_orientation, int32_t* match, int* rounds_out, hipStream_t st) {
+                     int check_orientation, int32_t* match, int* rounds_out, hipStream_t st, const ProjStereo* sx) {
     if (!ws || !F || !L || !match || F->n < 0 || L->n < 0 || F->n > 65535 || !F->scale_factors ||
         (F->n && (!F->kps || !F->desc)) || (L->n && (!L->points || !L->desc || !L->octave || !L->angle)))
         return ORBHIP_ERR_ARG;
+    if (sx && ((F->n && !sx->u_right) || !(sx->bf > 0.0f))) return ORBHIP_ERR_ARG;
     for (int i = 0; i < L->n; i++)
         if (L->octave[i] < 0 || L->octave[i] >= F->n_levels) return ORBHIP_ERR_ARG;
     const int n = F->n, nq = L->n;
@@ -1373,7 +1421,7 @@ int proj_search_last(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_proj
     const size_t o_kps = lay.take(sizeof(orbhip_kp) * n), o_kd = lay.take(32 * (size_t)n), o_cl = lay.take(n);
     const size_t o_scale = lay.take(sizeof(float) * F->n_levels);
     const size_t o_pts = lay.take(12 * (size_t)nq), o_qd = lay.take(32 * (size_t)nq), o_oct = lay.take(4 * (size_t)nq);
-    const size_t o_ang = lay.take(4 * (size_t)nq), o_in_end = lay.total();
+    const size_t o_ang = lay.take(4 * (size_t)nq), o_ur = lay.take(sx ? 4 * (size_t)n : 0), o_in_end = lay.total();
     const size_t o_cell = lay.take(4 * (size_t)n), o_own = lay.take(12 * (size_t)std::max(n, 1));
     const size_t o_q = lay.take(sizeof(Query) * nq), o_chg = lay.take(4 * ((size_t)nq + 2));
     const size_t o_pick = lay.take(4 * (size_t)nq), o_out = lay.take(ob.bytes);
@@ -1391,9 +1439,13 @@ int proj_search_last(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_proj
     S.put(o_qd, L->desc, 32 * (size_t)nq);
     S.put(o_oct, L->octave, 4 * (size_t)nq);
     S.put(o_ang, L->angle, 4 * (size_t)nq);
+    if (sx) S.put(o_ur, sx->u_right, 4 * (size_t)n);
     HIPOK(upload_inputs(S.hd, D, H, o_in_end, st));
-    const ProjFrame f = make_frame(F);
-    const PrepLast pl{(const float*)(D + o_pts), (const int*)(D + o_oct), (const float*)(D + o_scale), th};
+    ProjFrame f = make_frame(F);
+    if (sx) f.bf = sx->bf;
+    const float* dur = sx ? (const float*)(D + o_ur) : nullptr;   // mvuRight on the device (null: no gate)
+    const PrepLast pl{(const float*)(D + o_pts), (const int*)(D + o_oct), (const float*)(D + o_scale), th,
+                      sx ? sx->dir : 0};
     const uint8_t* dcl = F->claimed ? (const uint8_t*)(D + o_cl) : nullptr;
     int* hres = (int*)(H + o_out + ob.res);
     if (onepass) {
@@ -1404,7 +1456,8 @@ int proj_search_last(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_proj
         hipLaunchKernelGGL(k_proj_lists<0>, dim3((unsigned)((nq + kListQ - 1) / kListQ)), dim3(1024),
                            fused ? kResolveLds : list_lds_bytes(n), st, f, nq, pl, PrepLocal{}, cap, 0.f,
                            (const orbhip_kp*)(D + o_kps), (const uint8_t*)(D + o_kd), dcl, (const uint8_t*)(D + o_qd),
-                           (uint64_t*)(D + o_list), (int*)(D + o_lcnt), (int*)(D + o_pick0), nullptr, nullptr, ra);
+                           (uint64_t*)(D + o_list), (int*)(D + o_lcnt), (int*)(D + o_pick0), nullptr, nullptr, ra, dur,
+                           nullptr);
         if (!fused)
             hipLaunchKernelGGL(k_proj_resolve<0>, dim3(1), dim3(1024), kResolveLds, st, n, nq, 0.f, check_orientation,
                                cap, ra.ent_cap, ra.qangle, (const orbhip_kp*)(D + o_kps), (const uint64_t*)(D + o_list),
@@ -1430,7 +1483,7 @@ int proj_search_last(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_proj
         return 0;
     };
     const int rounds = run_rounds(ws, f, nq, 0, 0.f, D, o_q, o_kps, o_kd, o_cell, dcl, o_own, o_qd, o_pick, o_chg, H,
-                                  st, tail);
+                                  st, dur, tail);
     if (rounds < 0) return rounds;
     std::memcpy(match, H + o_out + ob.match, 4 * (size_t)nq);
     if (rounds_out) *rounds_out = rounds;
@@ -1439,11 +1492,12 @@ int proj_search_last(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_proj
 
 int proj_search_local(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_local_points* M, float view_cos_limit,
                       float th, float nnratio, int far_points, float th_far, uint8_t* in_view, int32_t* level,
-                      int32_t* match, int* rounds_out, hipStream_t st) {
+                      int32_t* match, int* rounds_out, hipStream_t st, const ProjStereo* sx) {
     if (!ws || !F || !M || !match || !in_view || !level || F->n < 0 || M->n < 0 || F->n > 65535 ||
         !F->scale_factors || (F->n && (!F->kps || !F->desc)) ||
         (M->n && (!M->points || !M->normals || !M->min_dist || !M->max_dist || !M->desc)))
         return ORBHIP_ERR_ARG;
+    if (sx && ((F->n && !sx->u_right) || !(sx->bf > 0.0f))) return ORBHIP_ERR_ARG;
     const int n = F->n, nq = M->n;
     if (nq == 0) return 0;
     const bool onepass = onepass_ok(F, nq);
@@ -1457,12 +1511,15 @@ int proj_search_local(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_loc
     const size_t o_scale = lay.take(sizeof(float) * F->n_levels);
     const PointsLayout o_mp(lay, (size_t)nq);
     const size_t o_qd = o_mp.desc;
+    const size_t o_ur = lay.take(sx ? 4 * (size_t)n : 0);
     const size_t o_in_end = lay.total();
     const size_t o_cell = lay.take(4 * (size_t)n), o_own = lay.take(12 * (size_t)std::max(n, 1));
     const size_t o_q = lay.take(sizeof(Query) * nq), o_chg = lay.take(4 * ((size_t)nq + 2));
     const size_t o_pick = lay.take(4 * (size_t)nq), o_out = lay.take(ob.bytes);
     const size_t o_list = onepass ? lay.take(8 * (size_t)nq * cap) : 0, o_lcnt = lay.take(4 * (size_t)nq);
     const size_t o_pick0 = lay.take(4 * (size_t)nq);
+    const bool want_xr = sx && sx->proj_xr;
+    const size_t o_xr = lay.take(want_xr ? 4 * (size_t)nq : 0);   // mTrackProjXR (an output of its own)
     if (int rc = ensure(ws, lay.total())) return rc;
     StageBlock& S = ws->s;
     char* H = (char*)S.h;
@@ -1472,8 +1529,11 @@ int proj_search_local(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_loc
     if (F->claimed) S.put(o_cl, F->claimed, n);
     S.put(o_scale, F->scale_factors, sizeof(float) * F->n_levels);
     const DevPoints mp = o_mp.put(S, *M, false);   // no skip array: a null pointer
+    if (sx) S.put(o_ur, sx->u_right, 4 * (size_t)n);
     HIPOK(upload_inputs(S.hd, D, H, o_in_end, st));
-    const ProjFrame f = make_frame(F);
+    ProjFrame f = make_frame(F);
+    if (sx) f.bf = sx->bf;
+    const float* dur = sx ? (const float*)(D + o_ur) : nullptr;
     const PrepLocal pc{mp.pts, mp.nrm, mp.mind, mp.maxd, mp.skip,
                        (const float*)(D + o_scale), F->n_levels, F->log_scale_factor, view_cos_limit, th, far_points,
                        th_far};
@@ -1485,6 +1545,11 @@ int proj_search_local(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_loc
         std::memcpy(match, H + o_out + ob.match, 4 * (size_t)nq);
         std::memcpy(level, H + o_out + ob.lvl, 4 * (size_t)nq);
         std::memcpy(in_view, H + o_out + ob.iv, nq);
+        if (want_xr) {   // only where in view: the rest of the caller's array stays as it was
+            const float* hx = (const float*)(H + o_xr);
+            for (int m = 0; m < nq; m++)
+                if (in_view[m]) sx->proj_xr[m] = hx[m];
+        }
     };
     if (onepass) {
         const bool fused = proj_fused();
@@ -1494,7 +1559,8 @@ int proj_search_local(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_loc
                            fused ? kResolveLds : list_lds_bytes(n), st, f, nq, PrepLast{}, pc, cap, nnratio,
                            (const orbhip_kp*)(D + o_kps), (const uint8_t*)(D + o_kd), dcl, (const uint8_t*)(D + o_qd),
                            (uint64_t*)(D + o_list), (int*)(D + o_lcnt), (int*)(D + o_pick0),
-                           (uint8_t*)(HD + o_out + ob.iv), (int*)(HD + o_out + ob.lvl), ra);
+                           (uint8_t*)(HD + o_out + ob.iv), (int*)(HD + o_out + ob.lvl), ra, dur,
+                           want_xr ? (float*)(HD + o_xr) : nullptr);
         if (!fused)
             hipLaunchKernelGGL(k_proj_resolve<1>, dim3(1), dim3(1024), kResolveLds, st, n, nq, nnratio, 0, cap,
                                ra.ent_cap, (const float*)nullptr, (const orbhip_kp*)(D + o_kps),
@@ -1512,16 +1578,17 @@ int proj_search_local(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_loc
     if (n) hipLaunchKernelGGL(k_proj_cells, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, f,
                               (const orbhip_kp*)(D + o_kps), (int*)(D + o_cell));
     hipLaunchKernelGGL(k_proj_prep_local, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, f, nq, pc,
-                       (Query*)(D + o_q), d_iv, d_lvl);
+                       (Query*)(D + o_q), d_iv, d_lvl, want_xr ? (float*)(D + o_xr) : nullptr);
     auto tail = [&]() -> int {
         hipLaunchKernelGGL(k_proj_finish, dim3(1), dim3(1024), 0, st, nq, 0, (const float*)nullptr,
                            (const orbhip_kp*)(D + o_kps), (const int*)(D + o_pick), (int*)(D + o_out + ob.match),
                            (int*)(D + o_out + ob.res));
         HIPOK(hipMemcpyAsync(H + o_out, D + o_out, ob.bytes, hipMemcpyDeviceToHost, st));
+        if (want_xr) HIPOK(hipMemcpyAsync(H + o_xr, D + o_xr, 4 * (size_t)nq, hipMemcpyDeviceToHost, st));
         return 0;
     };
     const int rounds = run_rounds(ws, f, nq, 1, nnratio, D, o_q, o_kps, o_kd, o_cell, dcl, o_own, o_qd, o_pick, o_chg,
-                                  H, st, tail);
+                                  H, st, dur, tail);
     if (rounds < 0) return rounds;
     outputs();
     if (rounds_out) *rounds_out = rounds;

@@ -13,8 +13,8 @@ import ctypes
 
 import numpy as np
 
-from ._lib import (KP_DTYPE, FrameC, InitFrameC, LocalPointsC, NewPointsC, ProjLastC, TriKeyFrameC, TriParamsC,
-                   torch_stream, Context, check, lib, ptr)
+from ._lib import (KP_DTYPE, FrameC, InitFrameC, LocalPointsC, NewPointsC, ProjLastC, StereoViewC, TriKeyFrameC,
+                   TriParamsC, torch_stream, Context, check, lib, ptr)
 
 
 class ORBmatcher:
@@ -27,6 +27,7 @@ class ORBmatcher:
         self.mbCheckOrientation = bool(checkOri)
         self.ctx = ctx or Context(device)
         self._lp_cache = None   # SearchLocalPoints: the C view of the last call's map-point arrays
+        self.last_direction = None   # the stereo SearchByProjectionLastFrame's direction of motion
 
     @staticmethod
     def DescriptorDistance(a, b) -> int:
@@ -113,17 +114,35 @@ class ORBmatcher:
 
     # ---- projection-guided matching ----
     def SearchByProjectionLastFrame(self, frame: "ProjFrame", points, mp_desc, last_octave, last_angle,
-                                    th: float = 15.0):
-        """U:src/ORBmatcher.cc::SearchByProjection(CurrentFrame, LastFrame, th, bMono=true).
+                                    th: float = 15.0, last_pose=None):
+        """U:src/ORBmatcher.cc::SearchByProjection(CurrentFrame, LastFrame, th, bMono).
         Queries = LastFrame entries with a non-outlier MapPoint (index order). Returns
-        (nmatches, match[q] = CurrentFrame keypoint or -1)."""
+        (nmatches, match[q] = CurrentFrame keypoint or -1). A frame that carries u_right takes the
+        stereo branch (bMono = false): last_pose = (q, t) of LastFrame.GetPose() is then required, the
+        level window follows the direction of motion and candidates are gated on their right
+        coordinate; the direction found (1 forward, -1 backward, 0 neither) is left in
+        self.last_direction."""
         pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
         d = np.ascontiguousarray(mp_desc, np.uint8).reshape(-1, 32)
         oc = np.ascontiguousarray(last_octave, np.int32)
         an = np.ascontiguousarray(last_angle, np.float32)
         match = np.empty(pts.shape[0], np.int32)   # written in full by the call
-        fc = frame.to_c()
         lc = ProjLastC(pts.shape[0], ptr(pts), ptr(d), ptr(oc), ptr(an))
+        if frame.u_right is not None:
+            if last_pose is None:
+                raise ValueError("SearchByProjectionLastFrame: a stereo frame needs last_pose = (q, t) of the last frame")
+            lq = np.ascontiguousarray(last_pose[0], np.float32).reshape(4)
+            lt = np.ascontiguousarray(last_pose[1], np.float32).reshape(3)
+            sc = frame.to_c_stereo()
+            direction = ctypes.c_int32(0)
+            n = check(lib().orbhip_search_by_projection_last_stereo(self.ctx.handle, ctypes.byref(sc), ctypes.byref(lc),
+                                                                    ptr(lq), ptr(lt), float(th),
+                                                                    int(self.mbCheckOrientation), ptr(match),
+                                                                    ctypes.byref(direction)),
+                      "orbhip_search_by_projection_last_stereo")
+            self.last_direction = int(direction.value)
+            return n, match
+        fc = frame.to_c()
         n = check(lib().orbhip_search_by_projection_last(self.ctx.handle, ctypes.byref(fc), ctypes.byref(lc),
                                                          float(th), int(self.mbCheckOrientation), ptr(match)),
                   "orbhip_search_by_projection_last")
@@ -133,7 +152,9 @@ class ORBmatcher:
                           th: float = 1.0, view_cos_limit: float = 0.5, far_points: bool = False,
                           th_far: float = 0.0):
         """Tracking::SearchLocalPoints: Frame::isInFrustum + SearchByProjection(F, vpMapPoints, th,
-        bFarPoints, thFarPoints) with this matcher's nnratio. Returns (nmatches, match, in_view, level)."""
+        bFarPoints, thFarPoints) with this matcher's nnratio. Returns (nmatches, match, in_view, level).
+        A frame that carries u_right takes the stereo branch (candidates gated on their right
+        coordinate) and also returns proj_xr (mTrackProjXR where in_view, NaN elsewhere)."""
         key = (id(points), id(normals), id(min_dist), id(max_dist), id(mp_desc), id(skip))
         hit = self._lp_cache
         if hit is not None and hit[0] == key and all(a is b for a, b in zip(hit[1], (points, normals, min_dist,
@@ -157,6 +178,15 @@ class ORBmatcher:
         match = np.empty(m, np.int32)      # written in full by the call (m > 0)
         in_view = np.empty(m, np.uint8)
         level = np.empty(m, np.int32)
+        if frame.u_right is not None:
+            proj_xr = np.full(m, np.nan, np.float32)
+            sc = frame.to_c_stereo()
+            n = check(lib().orbhip_search_local_points_stereo(self.ctx.handle, ctypes.byref(sc), ctypes.byref(lc),
+                                                              float(view_cos_limit), float(th), float(self.mfNNratio),
+                                                              int(far_points), float(th_far), ptr(in_view), ptr(level),
+                                                              ptr(proj_xr), ptr(match)),
+                      "orbhip_search_local_points_stereo")
+            return n, match, in_view, level, proj_xr
         fc = frame.to_c()
         n = check(lib().orbhip_search_local_points(self.ctx.handle, ctypes.byref(fc), ctypes.byref(lc),
                                                    float(view_cos_limit), float(th), float(self.mfNNratio),
@@ -427,10 +457,11 @@ class ProjFrame:
     mvKeysUn — PinholeCamera.UndistortKeyPoints for a distorted camera, mvKeys otherwise),
     descriptors, claimed mask, image bounds (Frame::ComputeImageBounds: PinholeCamera
     .ComputeImageBounds, or [0, width] x [0, height] without distortion), scale tables,
-    intrinsics and Tcw."""
+    intrinsics and Tcw. A rectified-stereo Frame also carries u_right (mvuRight, one per keypoint),
+    bf (mbf) and b (mb); the searches then take their stereo branches."""
 
     def __init__(self, kps, desc, pose_q, pose_t, fx, fy, cx, cy, width=640, height=480, scale_factor=1.2,
-                 n_levels=8, claimed=None, bounds=None):
+                 n_levels=8, claimed=None, bounds=None, u_right=None, bf=0.0, b=0.0):
         self.kps = np.ascontiguousarray(kps, KP_DTYPE)
         self.desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
         self.claimed = None if claimed is None else np.ascontiguousarray(claimed, np.uint8)
@@ -443,7 +474,26 @@ class ProjFrame:
             sf[i] = np.float32(np.float64(sf[i - 1]) * np.float64(np.float32(scale_factor)))
         self.scale_factors = sf
         self.log_scale_factor = float(np.log(np.float32(scale_factor)).astype(np.float32))
-        self._c = None
+        self._c = self._cs = None
+        self.u_right = None if u_right is None else np.ascontiguousarray(u_right, np.float32).reshape(-1)
+        self.bf, self.b = float(bf), float(b)
+
+    def to_c_stereo(self) -> StereoViewC:
+        """The stereo view: to_c() plus u_right / bf / b. The u_right pointer is cached while
+        u_right is the same array object (as to_c caches its arrays); the frame, bf and b are
+        re-filled on every call."""
+        hit = self._cs
+        if hit is None or hit[0] is not self.u_right:
+            self.u_right = np.ascontiguousarray(self.u_right, np.float32).reshape(-1)
+            c = StereoViewC()
+            c.u_right = ptr(self.u_right)
+            self._cs = hit = (self.u_right, c)   # the view keeps the array it points into alive
+        c = hit[1]
+        c.frame = self.to_c()
+        if hit[0].shape[0] != c.frame.n:
+            raise ValueError("ProjFrame.u_right needs one entry per keypoint")
+        c.bf, c.b = self.bf, self.b
+        return c
 
     def to_c(self) -> FrameC:
         """The C view. The pointer fields are cached while kps / desc / claimed / scale_factors are

@@ -14,7 +14,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import BAProblemC, BAResultC, Context, PoseProblemC, PoseResultC, check, lib, ptr
+from ._lib import (BAProblemC, BAResultC, Context, PoseProblemC, PoseResultC, PoseStereoProblemC, check, lib,
+                   ptr)
 
 TH_HUBER_MONO = float(np.sqrt(np.float32(5.991)))
 
@@ -73,8 +74,10 @@ class BAResult:
 
 @dataclass
 class PoseProblem:
-    """The g2o problem Optimizer::PoseOptimization(Frame*) builds for one monocular Frame: the
-    initial Tcw and, per matched MapPoint, its world position and the undistorted keypoint."""
+    """The g2o problem Optimizer::PoseOptimization(Frame*) builds for one Frame: the initial Tcw
+    and, per matched MapPoint, its world position and the undistorted keypoint. A rectified-stereo
+    Frame also gives u_right (mvuRight; an entry >= 0 makes that observation a stereo edge, < 0
+    leaves it monocular) and bf (mbf); without them the problem is the monocular one."""
     pose_q: np.ndarray          # [4] float32 (x,y,z,w), pFrame->GetPose() rotation
     pose_t: np.ndarray          # [3] float32
     points: np.ndarray          # [N,3] float32 MapPoint::GetWorldPos
@@ -85,18 +88,31 @@ class PoseProblem:
     fy: float
     cx: float
     cy: float
+    u_right: np.ndarray | None = None   # [N] float32 mvuRight (None: a monocular Frame)
+    bf: float = 0.0                     # mbf
 
     def normalized(self) -> "PoseProblem":
         c = lambda a, dt: np.ascontiguousarray(a, dtype=dt)  # noqa: E731
-        return PoseProblem(c(self.pose_q, np.float32).reshape(4), c(self.pose_t, np.float32).reshape(3),
-                           c(self.points, np.float32).reshape(-1, 3), c(self.uv, np.float32).reshape(-1, 2),
-                           c(self.octave, np.int32).reshape(-1), c(self.inv_sigma2, np.float32),
-                           float(self.fx), float(self.fy), float(self.cx), float(self.cy))
+        p = PoseProblem(c(self.pose_q, np.float32).reshape(4), c(self.pose_t, np.float32).reshape(3),
+                        c(self.points, np.float32).reshape(-1, 3), c(self.uv, np.float32).reshape(-1, 2),
+                        c(self.octave, np.int32).reshape(-1), c(self.inv_sigma2, np.float32),
+                        float(self.fx), float(self.fy), float(self.cx), float(self.cy))
+        if self.u_right is not None:
+            p.u_right, p.bf = c(self.u_right, np.float32).reshape(-1), float(self.bf)
+            if p.u_right.shape[0] != p.points.shape[0]:
+                raise ValueError("PoseProblem: u_right needs one entry per correspondence")
+        return p
 
     def to_c(self) -> PoseProblemC:
         return PoseProblemC(self.points.shape[0], ptr(self.pose_q), ptr(self.pose_t), ptr(self.points), ptr(self.uv),
                             ptr(self.octave), ptr(self.inv_sigma2), self.inv_sigma2.shape[0], self.fx, self.fy,
                             self.cx, self.cy)
+
+    def to_c_stereo(self) -> PoseStereoProblemC:
+        """The stereo entry's view of a normalized problem that carries u_right."""
+        return PoseStereoProblemC(self.points.shape[0], ptr(self.pose_q), ptr(self.pose_t), ptr(self.points),
+                                  ptr(self.uv), ptr(self.octave), ptr(self.inv_sigma2), self.inv_sigma2.shape[0],
+                                  self.fx, self.fy, self.cx, self.cy, ptr(self.u_right), self.bf)
 
 
 @dataclass
@@ -250,14 +266,24 @@ class Optimizer:
         return self.PoseOptimization_batch([prob])[0]
 
     def PoseOptimization_batch(self, probs) -> list:
-        """Several frames in one launch (one wavefront per frame)."""
+        """Several frames in one launch (one wavefront per frame). When any problem carries u_right
+        the batch takes the stereo entry, and every problem of it must carry one (all -1 for a
+        monocular frame)."""
         ps = [p.normalized() for p in probs]
         outl = [np.zeros(p.points.shape[0], np.uint8) for p in ps]
-        cprobs = (PoseProblemC * len(ps))(*[p.to_c() for p in ps])
         cres = (PoseResultC * len(ps))()
         for i, o in enumerate(outl):
             cres[i].outlier = ptr(o)
-        check(lib().orbhip_pose_optimization_batch(self.ctx.handle, cprobs, len(ps), cres),
-              "orbhip_pose_optimization_batch")
+        if any(p.u_right is not None for p in ps):
+            if any(p.u_right is None for p in ps):
+                raise ValueError("PoseOptimization_batch: a stereo batch needs u_right in every problem "
+                                 "(all -1 for a monocular frame)")
+            cprobs = (PoseStereoProblemC * len(ps))(*[p.to_c_stereo() for p in ps])
+            check(lib().orbhip_pose_optimization_stereo_batch(self.ctx.handle, cprobs, len(ps), cres),
+                  "orbhip_pose_optimization_stereo_batch")
+        else:
+            cprobs = (PoseProblemC * len(ps))(*[p.to_c() for p in ps])
+            check(lib().orbhip_pose_optimization_batch(self.ctx.handle, cprobs, len(ps), cres),
+                  "orbhip_pose_optimization_batch")
         return [PoseResult(np.array(r.pose_q[:], np.float32), np.array(r.pose_t[:], np.float32), o, r.n_inliers,
                            r.lm_trials) for r, o in zip(cres, outl)]

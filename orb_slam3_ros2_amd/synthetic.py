@@ -1034,3 +1034,91 @@ def synthetic_sim3_scene(n_kp=300, n_mp=400, seed=0, th=3.0, ratio=1.5, n_claime
     out.update(kf=kf, th=float(th), ratio=float(ratio), scale_factors=s["scale_factors"],
                inv_level_sigma2=s["inv_level_sigma2"], copy_of=np.concatenate([np.full(base, -1), src]))
     return out
+
+
+# ---------------------------------------------------------------------------
+# Rectified-stereo tracking: PoseOptimization with stereo edges, the stereo branches of the
+# projection matchers
+# ---------------------------------------------------------------------------
+STEREO_B = 0.08                                                    # mb, metres
+
+
+def synthetic_stereo_pose_problem(n=600, outlier_frac=0.15, seed=3, stereo_frac=0.5, ur_outlier_frac=0.06,
+                                  b=STEREO_B, **pose_args):
+    """synthetic_pose_problem(n, outlier_frac, seed, ...) seen by a rectified-stereo Frame: about
+    stereo_frac of the observations carry u_right = the projection into the right image (u - bf / z,
+    bf = fx * b) + 1.2^octave px noise, the others -1 (monocular). A gross mismatch keeps a right
+    coordinate consistent with its own (wrong) keypoint at a random depth; ur_outlier_frac of the
+    good stereo observations get a right coordinate 4-15 sigma off (a wrong stereo match: an outlier
+    as a stereo edge only). A right coordinate that would be negative is dropped (-1).
+    Returns (PoseProblem with u_right / bf, ground truth dict + stereo, ur_bad masks)."""
+    prob, gt = synthetic_pose_problem(n=n, outlier_frac=outlier_frac, seed=seed, **pose_args)
+    rng = np.random.Generator(np.random.PCG64(7919 * (seed + 1) + 17))
+    fx = float(np.float32(prob.fx))
+    bf = float(np.float32(fx * b))
+    Xc = prob.points.astype(np.float64) @ gt["R"].T + gt["t"]
+    z = Xc[:, 2]
+    sig = np.power(1.2, prob.octave.astype(np.float64))
+    u_true = fx * Xc[:, 0] / z + float(np.float32(prob.cx))
+    ur = u_true - bf / z + rng.normal(size=n) * sig
+    bad = gt["bad"]
+    ur[bad] = prob.uv[bad, 0].astype(np.float64) - bf / rng.uniform(2.0, 6.0, int(bad.sum()))
+    stereo = rng.random(n) < stereo_frac
+    ur_bad = stereo & ~bad & (rng.random(n) < ur_outlier_frac)
+    ur[ur_bad] += rng.choice([-1.0, 1.0], int(ur_bad.sum())) * rng.uniform(4.0, 15.0, int(ur_bad.sum())) * sig[ur_bad]
+    stereo &= ur >= 0.5
+    ur_bad &= stereo
+    prob.u_right = np.where(stereo, ur, -1.0).astype(np.float32)
+    prob.bf = bf
+    return prob, dict(gt, stereo=stereo, ur_bad=ur_bad)
+
+
+def synthetic_stereo_projection_scene(n_kp=1000, n_mp=900, seed=5, motion="forward", b=STEREO_B, mono_frac=0.2,
+                                      wrong_frac=0.25, level_frac=0.8, **scene_args):
+    """synthetic_projection_scene(n_kp, n_mp, seed, ...) seen by a rectified-stereo Frame, plus the
+    last frame's pose. Every keypoint gets u_right = x - bf / z (bf = fx * b) + a quarter pixel of
+    noise, z the depth of the first MapPoint made from it (1-8 m at random for the others; the other
+    MapPoints stacked on one keypoint have depths of their own, so the gate tells them apart);
+    mono_frac have no stereo match (-1), wrong_frac a wrong one (30-120 px off: the gate rejects the
+    true candidate and the query falls to its next best). level_frac of the MapPoints get distance
+    bounds that predict their keypoint's octave or the one above (the base scene's are random, so few
+    of its points pass SearchLocalPoints' level window and the gate would have little to reject). The
+    last frame looks the same way from 0.3 m behind (motion 'forward': tlc.z > b), 0.3 m ahead
+    ('backward') or 2 cm aside ('neutral').
+    Returns the base scene's dict + u_right, bf, b, last_pose_q, last_pose_t, direction."""
+    s = synthetic_projection_scene(n_kp=n_kp, n_mp=n_mp, seed=seed, **scene_args)
+    rng = np.random.Generator(np.random.PCG64(104729 * (seed + 1) + 5))
+    if n_mp:
+        Ow = -quat_to_rot64(s["pose_q"]).T @ s["pose_t"].astype(np.float64)
+        dist = np.linalg.norm(s["points"].astype(np.float64) - Ow, axis=1)
+        lvl = s["kps"]["octave"][s["src"]] + rng.integers(0, 2, n_mp) - rng.uniform(0.1, 0.9, n_mp)
+        fit = rng.random(n_mp) < level_frac
+        n_levels = scene_args.get("n_levels", 8)
+        max_dist = dist * np.power(1.2, lvl)
+        s["max_dist"] = np.where(fit, max_dist.astype(np.float32), s["max_dist"])
+        s["min_dist"] = np.where(fit, (max_dist / np.float64(1.2) ** (n_levels - 1)).astype(np.float32), s["min_dist"])
+    fx = float(np.float32(s["fx"]))
+    bf = float(np.float32(fx * b))
+    q, t = s["pose_q"], s["pose_t"]
+    R = quat_to_rot64(q)
+    zk = rng.uniform(1.0, 8.0, n_kp)
+    if n_mp:
+        zmp = (s["points"].astype(np.float64) @ R.T + t.astype(np.float64))[:, 2]
+        first = np.full(n_kp, -1)
+        for m in range(n_mp - 1, -1, -1):
+            first[s["src"][m]] = m
+        has = first >= 0
+        zk[has] = zmp[first[has]]
+    ur = s["kps"]["x"].astype(np.float64) - bf / zk + rng.normal(size=n_kp) * 0.25
+    wrong = rng.random(n_kp) < wrong_frac
+    ur[wrong] += rng.choice([-1.0, 1.0], int(wrong.sum())) * rng.uniform(30.0, 120.0, int(wrong.sum()))
+    none = (rng.random(n_kp) < mono_frac) | (ur < 0.5)
+    u_right = np.where(none, -1.0, ur).astype(np.float32)
+    tlc = dict(forward=np.array([0.01, -0.02, 0.3]), backward=np.array([-0.02, 0.01, -0.3]),
+               neutral=np.array([0.02, 0.005, 0.02]))[motion]
+    Rl = _rodrigues(rng.normal(size=3) * 0.01) @ R
+    ql = _mat_to_quat(Rl).astype(np.float32)
+    twc = -R.T @ t.astype(np.float64)
+    tl = (tlc - quat_to_rot64(ql) @ twc).astype(np.float32)
+    return dict(s, u_right=u_right, bf=bf, b=float(np.float32(b)), last_pose_q=ql, last_pose_t=tl,
+                direction=dict(forward=1, backward=-1, neutral=0)[motion])
