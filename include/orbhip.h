@@ -89,7 +89,18 @@ int orbhip_extract(orbhip_ctx* ctx, const uint8_t* img, int w, int h, int stride
 /* Batched, fully device-resident form (torch-ROCm ingest, benchmarks). d_imgs: B frames,
  * frame f at d_imgs + f*frame_stride, rows `stride` bytes apart. Outputs per frame f:
  * d_kps[f*cap ...], d_desc[(f*cap ...)*32], d_n[f], d_mono[f]. Asynchronous on `stream`
- * (hipStream_t; NULL = the HIP null stream, as in every HIP API — torch's default stream). */
+ * (hipStream_t; NULL = the HIP null stream, as in every HIP API — torch's default stream).
+ *
+ * Input layout contract (also orbhip_extract_stereo_device and orbhip_frontend_push): d_imgs may
+ * have any byte alignment; stride >= w, and frame_stride >= stride*h when B > 1 (neither needs to
+ * be a multiple of anything), else ORBHIP_ERR_ARG and nothing is launched. Of each row the library
+ * reads only the first w bytes, plus padding up to the next 4-byte boundary when that boundary lies
+ * within `stride` (rows are read as aligned 4-byte words when the frame's address and `stride` are
+ * both multiples of 4, byte by byte otherwise), and it reads nothing past the last row: every read
+ * of frame f lies in [d_imgs + f*frame_stride, + (h-1)*stride + w rounded up as above). One
+ * exception inside that range: for a keypoint within 23 columns of the right edge the descriptor
+ * stage may read up to 5 bytes past w of a row that another row of the frame follows (padding or
+ * that next row's first bytes). Padding bytes never influence a result. */
 int orbhip_extract_batch_device(orbhip_ctx* ctx, const uint8_t* d_imgs, int B, int w, int h, int stride,
                                 int64_t frame_stride, int lap0, int lap1, orbhip_kp* d_kps, uint8_t* d_desc,
                                 int cap, int32_t* d_n, int32_t* d_mono, void* stream);

@@ -129,7 +129,9 @@ __device__ __forceinline__ void resize_tile_g(const ExtractPlan* __restrict__ P,
     auto clampr = [&](int r) { return r < 0 ? 0 : (r < Sh ? r : Sh - 1); };
     const int rbase = clampr(sy[0]);
     // interior lanes: 4 full columns inside xmax / vend, the source span as 3 aligned dwords of
-    // each row, every row the outputs read within kRzSrc rows of rbase
+    // each row, every row the outputs read within kRzSrc rows of rbase. base + 12 <= Sw: the three
+    // dwords [base, base + 12) lie within the row's first Sw bytes (no padding byte is read at
+    // all), and the rows are clamped to Sh - 1
     const bool interior = ((src.pitch & 3) == 0) && ((((uintptr_t)src.p) & 3) == 0) && base + 12 <= Sw &&
                           sxa[3] - base <= 10 &&
                           dx0 + 3 < xmax && dx0 + 3 < vend && nrow == kRzRows &&
@@ -481,6 +483,9 @@ __device__ __forceinline__ void pyr_cone_body(const ExtractPlan* __restrict__ P,
         const uint8_t* src0 = in0.p + (int64_t)r.ny0 * in0.pitch + r.nx0;
         const bool dw = ((in0.pitch & 3) == 0) && ((((uintptr_t)in0.p) & 3) == 0);
         if (dw) sh0 = (int)(((uintptr_t)src0) & 3);
+        // rows start 4-byte aligned on the dword path, so sh0 = nx0 & 3 and a row's nwd dwords are
+        // columns [nx0 & ~3, round_up(nx1, 4)): with nx1 <= w, never past round_up(w, 4) <= pitch,
+        // and only rows ny0..ny1-1 < h (the frame-layout contract of include/orbhip.h)
         const int nwd = dw ? (nw + sh0 + 3) >> 2 : 0;   // dwords per row (<= P0 / 4)
         const int tot0 = dw ? nwd * nh : nw * nh;
         const float inv_n = 1.0f / (float)(dw ? nwd : nw);
@@ -716,6 +721,9 @@ __device__ __forceinline__ void fast_cell_body(const ExtractPlan* __restrict__ P
         if (dw) {
             sh = (int)(((uintptr_t)base) & 3);
             const uint32_t* b4 = (const uint32_t*)(base - sh);
+            // sh = x0 & 3 (rows start aligned), so the nwd dwords are columns [x0 & ~3,
+            // round_up(x0 + wc, 4)): with x0 + wc <= w, never past round_up(w, 4) <= pitch; rows
+            // r < RW <= hc and r + R < hc stay inside the cell, hence inside the level
             const int nwd = (wc + sh + 3) >> 2;   // <= PWP / 4
             const int p4 = im.pitch >> 2;
             auto put = [&](int r, int j, uint32_t a, uint32_t b) {
@@ -1993,6 +2001,17 @@ constexpr int kHrP = 48;                         // k_desc transposed row-pass p
 __device__ __forceinline__ constexpr uint32_t blur_tap(int i) {
     return i == 0 || i == 6 ? 18u : (i == 1 || i == 5 ? 34u : (i == 2 || i == 4 ? 48u : 56u));
 }
+// The dword path of k_desc / k_desc_kp (rows 4-byte aligned, patch inside the level) loads 12
+// aligned dwords per patch row: columns [a, a + kDpP), a = (cx - kPatchR) & ~3. For the two columns
+// cx = lw - 22, lw - 23 that span ends up to 5 bytes past the level's width (lw % 4 == 0: 4 bytes;
+// lw % 4 == 3: 5). While another row of the level follows the patch, those bytes are that row's or
+// the padding before it: inside the image block, and never part of a result. In the level's last
+// row they can lie past the caller's frame buffer (level 0) or past the pyramid block, so there the
+// span has to end within the row's width rounded up to 4 bytes (<= the pitch, itself a multiple of
+// 4 on this path); otherwise the keypoint takes the byte path, which builds the same patch.
+__device__ __forceinline__ bool desc_dword_span_ok(int cx, int cy, int lw, int lh) {
+    return ((cx - kPatchR) & ~3) + kDpP <= ((lw + 3) & ~3) || cy + kPatchR + 1 < lh;
+}
 
 __global__ __launch_bounds__(256) void k_desc(const ExtractPlan* __restrict__ P, FrameBufs fb,
                                               const LevelKp* __restrict__ lvl_kp, const int* __restrict__ lvl_cnt,
@@ -2048,7 +2067,8 @@ __global__ __launch_bounds__(256) void k_desc(const ExtractPlan* __restrict__ P,
         cx = kp.x; cy = kp.y;
         const int lw = G.w, lh = G.h;
         const bool inside = cx - kPatchR >= 0 && cy - kPatchR >= 0 && cx + kPatchR < lw && cy + kPatchR < lh;
-        const bool dw = inside && ((im.pitch & 3) == 0) && ((((uintptr_t)im.p) & 3) == 0);
+        const bool dw = inside && ((im.pitch & 3) == 0) && ((((uintptr_t)im.p) & 3) == 0) &&
+                        desc_dword_span_ok(cx, cy, lw, lh);
         if (dw) {
             // 43 rows x 12 aligned dwords (the 43 + sh <= 46 patch bytes of a row), 9 per lane
             const uint8_t* src = im.p + (int64_t)(cy - kPatchR) * im.pitch + (cx - kPatchR);
@@ -2290,7 +2310,8 @@ __global__ __launch_bounds__(256) void k_desc_kp(const ExtractPlan* __restrict__
         ImgRef im = level_img(P, fb, f, l);
         const int lw = G.w, lh = G.h;
         const bool inside = cx - kPatchR >= 0 && cy - kPatchR >= 0 && cx + kPatchR < lw && cy + kPatchR < lh;
-        if (inside && ((im.pitch & 3) == 0) && ((((uintptr_t)im.p) & 3) == 0)) {
+        if (inside && ((im.pitch & 3) == 0) && ((((uintptr_t)im.p) & 3) == 0) &&
+            desc_dword_span_ok(cx, cy, lw, lh)) {
             // 43 rows x 12 aligned dwords, 3 per thread
             const uint8_t* src = im.p + (int64_t)(cy - kPatchR) * im.pitch + (cx - kPatchR);
             sh = (int)(((uintptr_t)src) & 3);

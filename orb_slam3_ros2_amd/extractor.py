@@ -105,7 +105,11 @@ class ORBextractor:
     # ---- batched, device-resident (torch-ROCm ingest / benchmarks) ----
     def extract_batch_device(self, frames, kps_out, desc_out, n_out, mono_out, vLappingArea=(0, 1000),
                              stream=None):
-        """frames: uint8 CUDA tensor [B, H, W] (rows may be padded: stride(1) bytes per row).
+        """frames: uint8 CUDA tensor [B, H, W] (rows may be padded: stride(1) bytes per row, frames
+        stride(0) bytes apart, stride(2) == 1). Any byte alignment of the view is accepted,
+        stride(1) >= W and, for B > 1, stride(0) >= stride(1) * H. Of each row only the first W
+        bytes are read, plus padding up to the next 4-byte boundary when that boundary lies within
+        stride(1), and nothing past the last row (include/orbhip.h states the contract in full).
         kps_out: int32/float32 CUDA tensor with >= B*cap*6 elements; desc_out uint8 [B, cap, 32];
         n_out / mono_out int32 [B]. Asynchronous on ``stream`` (torch stream or None)."""
         B, H, W = frames.shape

@@ -58,7 +58,8 @@ class FrameStream:
         return _CtxRef(c)
 
     def push(self, frame, vLappingArea=(0, 1000)) -> int:
-        """frame: uint8 CUDA tensor (H, W), rows stride(0) bytes apart. Returns the slot."""
+        """frame: uint8 CUDA tensor (H, W), rows stride(0) >= W bytes apart, at any byte alignment
+        (the layout contract of orbhip_extract_batch_device, include/orbhip.h). Returns the slot."""
         rc = self._push(self._h, frame.data_ptr(), frame.stride(0), int(vLappingArea[0]), int(vLappingArea[1]))
         return check(rc, "orbhip_frontend_push")
 

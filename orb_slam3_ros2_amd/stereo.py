@@ -61,7 +61,10 @@ def stereo_frame(ext, left, right, bf: float, b: float, center_patch: bool = Fal
 def extract_stereo_device(ext, frames, bf: float, b: float, kps_out, desc_out, n_out, mono_out, u_right_out,
                           depth_out, n_stereo_out, status_out=None, center_patch: bool = False, stream=None):
     """frames: uint8 CUDA tensor [2P, H, W], frame 2p the left and 2p + 1 the right image of pair p
-    (rows may be padded). kps_out / desc_out / n_out / mono_out as ORBextractor.extract_batch_device
+    (rows may be padded: any byte alignment of the view, stride(1) >= W, stride(0) >= stride(1) * H;
+    of each row only the first W bytes are read, plus padding up to the next 4-byte boundary when
+    that boundary lies within stride(1), and nothing past the last row, as include/orbhip.h states
+    for orbhip_extract_batch_device). kps_out / desc_out / n_out / mono_out as ORBextractor.extract_batch_device
     takes them for 2P frames (cap = desc_out.shape[1] >= ext.max_keypoints(W, H)); u_right_out /
     depth_out float32 [P, cap], status_out int32 [P, cap] or None, n_stereo_out int32 [P].
     Asynchronous on ``stream`` (torch stream or None); entries at or past a left frame's keypoint

@@ -1,7 +1,8 @@
 """Shared test helpers: compare product keypoints/descriptors with the oracle's; the numerics of
 the dense-solver tests (SPD test matrices, a long-double reference solve, the backward error);
 the BA result comparison against the oracle; the brute-force matcher's route hook and data sets
-with matches planted by construction."""
+with matches planted by construction; device frame layouts (padded rows, offset base pointers, odd
+strides inside a poisoned buffer) for the extraction tests."""
 import numpy as np
 
 from orb_slam3_ros2_amd._lib import KP_DTYPE
@@ -259,3 +260,92 @@ MATCH_HISTOGRAMS = [
     ({1: 5, 2: 6, 3: 7, 4: 8}, (4, 3, 2), 21),
 ]
 MATCH_HIST_IDS = ["-".join(f"{b}x{c}" for b, c in h.items()) or "empty" for h, _, _ in MATCH_HISTOGRAMS]
+
+
+# ---- device frame layouts: padded rows, offset base pointers, odd strides ----
+
+POISONS = (0xFF, "random")   # a constant, and a seeded byte stream (FAST corners wherever it is sampled)
+
+
+def place_frames(frames_u8: np.ndarray, stride: int, offset: int, frame_stride: int, poison):
+    """frames_u8 [B, H, W] inside one poisoned uint8 CUDA buffer of offset + (B - 1) * frame_stride +
+    H * stride + 64 bytes: row r of frame f at byte offset + f * frame_stride + r * stride. Every
+    byte that is not a pixel (row padding, frame gaps, the bytes before and after) holds `poison`:
+    an int = that constant, "random" = a seeded random stream. Returns the [B, H, W] view
+    (stride(0) = frame_stride, stride(1) = stride, storage offset = offset)."""
+    import torch
+    B, H, W = frames_u8.shape
+    assert frames_u8.dtype == np.uint8 and stride >= W and offset >= 0 and (B == 1 or frame_stride >= stride * H)
+    size = offset + (B - 1) * frame_stride + H * stride + 64
+    if poison == "random":
+        fill = np.random.default_rng(0xB0B).integers(0, 256, size, dtype=np.uint8)
+    else:
+        fill = np.full(size, int(poison), np.uint8)
+    buf = torch.from_numpy(fill).to("cuda")
+    assert buf.data_ptr() % 256 == 0, "the base allocation is expected to be 256-byte aligned"
+    view = torch.as_strided(buf, (B, H, W), (frame_stride, stride, 1), offset)
+    view.copy_(torch.from_numpy(np.ascontiguousarray(frames_u8)).to("cuda"))
+    torch.cuda.synchronize()
+    return view
+
+
+def frame_layout(lid: str, w: int, h: int) -> tuple:
+    """(stride, offset, frame_stride) of a named layout at frame size w x h. P packed; A rows and
+    frames padded, all 4-byte aligned; A4 the stride rounded up to 4 (w % 4 != 0): a row's last
+    dword straddles image and padding; M1 / M2 / M3 an aligned stride behind a base pointer off by
+    1 / 2 / 3; O / O2 / O3 the smallest stride >= w that is 1 / 2 / 3 mod 4; X an aligned stride
+    with a frame stride that is 2 mod 4: even frames aligned, odd frames not."""
+    r4 = (w + 3) & ~3
+    if lid == "P":
+        return w, 0, w * h
+    if lid == "A":
+        return r4 + 64, 0, (r4 + 64) * h + 256
+    if lid == "A4":
+        assert w % 4 != 0
+        return r4, 0, r4 * h
+    if lid in ("M1", "M2", "M3"):
+        return r4 + 64, int(lid[1]), (r4 + 64) * h
+    if lid in ("O", "O2", "O3"):
+        m = 1 if lid == "O" else int(lid[1])
+        s = w + ((m - w) % 4)
+        return s, 0, s * h
+    if lid == "X":
+        return r4 + 64, 0, (r4 + 64) * h + 2
+    raise ValueError(lid)
+
+
+def layout_class(lid: str) -> str:
+    return {"P": "packed", "A": "dword-padded", "A4": "dword-padded", "X": "mixed-per-frame"}.get(
+        lid, "misaligned-byte" if lid.startswith("M") else "odd-stride-byte")
+
+
+def extract_device_frames(ext, frames_t, lap=(0, 1000)) -> list:
+    """extract_batch_device on a [B, H, W] CUDA view -> per frame (n, mono, keypoints as KP_DTYPE,
+    descriptors [n, 32])."""
+    import torch
+    B, H, W = frames_t.shape
+    cap = ext.max_keypoints(W, H)
+    dev = frames_t.device
+    kps = torch.zeros((B, cap, 6), dtype=torch.float32, device=dev)
+    desc = torch.zeros((B, cap, 32), dtype=torch.uint8, device=dev)
+    n = torch.full((B,), -1, dtype=torch.int32, device=dev)
+    mono = torch.full((B,), -1, dtype=torch.int32, device=dev)
+    ext.extract_batch_device(frames_t, kps, desc, n, mono, lap)
+    torch.cuda.synchronize()
+    kh, dh, nh, mh = kps.cpu().numpy(), desc.cpu().numpy(), n.cpu().numpy(), mono.cpu().numpy()
+    out = []
+    for f in range(B):
+        c = max(int(nh[f]), 0)
+        out.append((int(nh[f]), int(mh[f]), np.frombuffer(kh[f, :c].tobytes(), KP_DTYPE), dh[f, :c].copy()))
+    return out
+
+
+def assert_frames_equal_oracle(got: list, want: list, what="") -> None:
+    """got: extract_device_frames' list; want: per frame (mono, keypoints KP_DTYPE, descriptors).
+    n, monoIndex, all six keypoint fields and the descriptor bytes are equal, and n > 0."""
+    assert len(got) == len(want)
+    for f, ((n, mono, gk, gd), (omono, ok, od)) in enumerate(zip(got, want)):
+        same = (n == len(ok) and mono == omono and all(np.array_equal(gk[k], ok[k]) for k in KP_DTYPE.names)
+                and np.array_equal(gd, od))
+        assert same, f"{what} frame {f}: n gpu={n} monoIndex gpu={mono} oracle={omono}\n" + diff_report(gk, gd, ok, od)
+        assert n > 0, f"{what} frame {f}: no keypoints"
