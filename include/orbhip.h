@@ -318,6 +318,29 @@ int orbhip_ba_stats(orbhip_ctx* ctx, int64_t out[4]);
 int orbhip_ba_solve_batch(orbhip_ctx* ctx, const orbhip_ba_problem* probs, int B, orbhip_ba_result* res,
                           const volatile int* stop_flag);
 
+/* LocalBundleAdjustment / BundleAdjustment of a rectified-stereo system: an observation with
+ * edge_ur[e] >= 0 (the keyframe's mvuRight; 0.0f counts) is g2o's EdgeStereoSE3ProjectXYZ:
+ * observation (u, v, ur), error obs - (fx x/z + cx, fy y/z + cy, fx x/z + cx - bf/z), information
+ * I3 * invSigma2[octave], chi2 over the three terms, and a Huber delta of its own
+ * (thHuberStereo = thHuber3D = sqrt(7.815)). Every other observation is the monocular edge of
+ * orbhip_ba_problem, unchanged, and so is the LM schedule. orbhip_ba_result is unchanged:
+ * edge_chi2 of a stereo edge is the three-term chi2 (the caller erases at 7.815 on stereo edges,
+ * 5.991 on monocular ones). ORBHIP_ERR_ARG, before anything runs and with no result written:
+ * edge_ur NULL with n_edges > 0, bf <= 0 while some edge_ur[e] >= 0, and whatever
+ * orbhip_ba_solve rejects. A call whose problems hold no stereo edge runs orbhip_ba_solve's
+ * kernels (the same bits). The sharded entries (orbhip_ba_solve_sharded, _sharded_segments,
+ * _shards_local) have no stereo form. */
+typedef struct {
+    orbhip_ba_problem mono;      /* every field as in orbhip_ba_solve */
+    const float* edge_ur;        /* n_edges: mvuRight of the observation (< 0: monocular edge) */
+    float bf;                    /* mbf */
+    float huber_delta_stereo;    /* sqrt(7.815); <= 0: no robust kernel on stereo edges */
+} orbhip_ba_stereo_problem;
+int orbhip_ba_solve_stereo(orbhip_ctx* ctx, const orbhip_ba_stereo_problem* prob, orbhip_ba_result* res,
+                           const volatile int* stop_flag);
+int orbhip_ba_solve_stereo_batch(orbhip_ctx* ctx, const orbhip_ba_stereo_problem* probs, int B,
+                                 orbhip_ba_result* res, const volatile int* stop_flag);
+
 /* ---- projection-guided matching ---------------------------
  * The current Frame as U:src/Frame.cc holds it after extraction: keypoints mvKeysUn (= mvKeys,
  * distortion k1 == 0), descriptors, image bounds mnMinX..mnMaxY (ComputeImageBounds), the

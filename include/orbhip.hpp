@@ -461,6 +461,14 @@ struct BAResult {
     int iterations_done = 0, lm_trials = 0;
 };
 
+// A BAProblem of a rectified-stereo system: an observation with edge_ur[e] >= 0 (mvuRight; 0.0f counts)
+// is an EdgeStereoSE3ProjectXYZ with the Huber delta huber_delta_stereo, the others monocular edges
+struct StereoBAProblem : BAProblem {
+    std::vector<float> edge_ur;          // one per edge (< 0: a monocular edge)
+    float bf = 0.0f;                     // mbf
+    float huber_delta_stereo = 2.7955321f;   // sqrt(7.815): thHuberStereo (LBA), thHuber3D (GBA)
+};
+
 class Optimizer {
 public:
     // LocalBundleAdjustment's optimize(10) with Huber sqrt(5.991). The reference's bool*
@@ -475,6 +483,20 @@ public:
         p.iterations = nIterations;
         p.huber_delta = bRobust ? std::sqrt(5.99f) : 0.0f;
         return solve(ctx, p, pbStopFlag);
+    }
+
+    // The same two with stereo edges (orbhip_ba_solve_stereo): edge_chi2 of a stereo edge is the
+    // three-term chi2, which the caller erases at 7.815 (5.991 on the monocular edges)
+    static BAResult LocalBundleAdjustment(orbhip_ctx* ctx, const StereoBAProblem& p,
+                                          const volatile int* pbStopFlag = nullptr) {
+        return solve(ctx, p, pbStopFlag, &p);
+    }
+    static BAResult BundleAdjustment(orbhip_ctx* ctx, StereoBAProblem p, int nIterations = 5,
+                                     const volatile int* pbStopFlag = nullptr, bool bRobust = true) {
+        p.iterations = nIterations;
+        p.huber_delta = bRobust ? std::sqrt(5.99f) : 0.0f;
+        p.huber_delta_stereo = bRobust ? std::sqrt(7.815f) : 0.0f;
+        return solve(ctx, p, pbStopFlag, &p);
     }
 
     // PoseOptimization(Frame*) of a rectified-stereo Frame: observations with u_right >= 0 are
@@ -496,7 +518,8 @@ public:
     }
 
 private:
-    static BAResult solve(orbhip_ctx* ctx, const BAProblem& p, const volatile int* stop) {
+    static BAResult solve(orbhip_ctx* ctx, const BAProblem& p, const volatile int* stop,
+                          const StereoBAProblem* stereo = nullptr) {
         const int P = (int)p.pose_fixed.size(), M = (int)(p.points.size() / 3), E = (int)p.edge_pose.size();
         orbhip_ba_problem c{P, M, E, p.pose_q.data(), p.pose_t.data(), p.pose_fixed.data(), p.points.data(),
                             p.edge_pose.data(), p.edge_point.data(), p.edge_uv.data(), p.edge_octave.data(),
@@ -507,7 +530,13 @@ private:
         r.edge_chi2.resize(E); r.edge_depth_ok.resize(E);
         orbhip_ba_result o{r.pose_q.data(), r.pose_t.data(), r.points.data(), r.edge_chi2.data(), r.edge_depth_ok.data(),
                            0, 0, 0, 0};
-        check(orbhip_ba_solve(ctx, &c, &o, stop), "orbhip_ba_solve");
+        if (stereo) {
+            if (stereo->edge_ur.size() != (size_t)E) throw std::invalid_argument("StereoBAProblem: edge_ur needs one entry per edge");
+            orbhip_ba_stereo_problem sc{c, stereo->edge_ur.data(), stereo->bf, stereo->huber_delta_stereo};
+            check(orbhip_ba_solve_stereo(ctx, &sc, &o, stop), "orbhip_ba_solve_stereo");
+        } else {
+            check(orbhip_ba_solve(ctx, &c, &o, stop), "orbhip_ba_solve");
+        }
         r.initial_chi2 = o.initial_chi2; r.final_chi2 = o.final_chi2;
         r.iterations_done = o.iterations_done; r.lm_trials = o.lm_trials;
         return r;

@@ -31,13 +31,13 @@ from __future__ import annotations
 from ._lib import OrbHipError, lib, library_path  # noqa: F401
 from .extractor import KeyPoint, ORBextractor  # noqa: F401
 from .matcher import ORBmatcher  # noqa: F401
-from .optimizer import BAProblem, BAResult, Optimizer, PoseProblem, PoseResult  # noqa: F401
+from .optimizer import BAProblem, BAResult, Optimizer, PoseProblem, PoseResult, StereoBAProblem  # noqa: F401
 from .bow import ORBVocabulary  # noqa: F401
 from .kfdb import KeyFrameDatabase  # noqa: F401
 from .frontend import FrameStream  # noqa: F401
 from .camera import PinholeCamera  # noqa: F401
 from .stereo import StereoFrame, stereo_frame  # noqa: F401
 
-__all__ = ["StereoFrame", "stereo_frame", "ORBextractor", "KeyPoint", "ORBmatcher", "Optimizer", "BAProblem", "BAResult", "PoseProblem", "PoseResult", "ORBVocabulary", "KeyFrameDatabase", "FrameStream", "PinholeCamera",
+__all__ = ["StereoFrame", "stereo_frame", "ORBextractor", "KeyPoint", "ORBmatcher", "Optimizer", "BAProblem", "StereoBAProblem", "BAResult", "PoseProblem", "PoseResult", "ORBVocabulary", "KeyFrameDatabase", "FrameStream", "PinholeCamera",
            "OrbHipError",
            "lib", "library_path"]

@@ -53,6 +53,11 @@ class BAProblemC(ctypes.Structure):
                 ("iterations", ctypes.c_int32), ("early_stop", ctypes.c_int32)]
 
 
+class BAStereoProblemC(ctypes.Structure):
+    _fields_ = [("mono", BAProblemC), ("edge_ur", ctypes.c_void_p), ("bf", ctypes.c_float),
+                ("huber_delta_stereo", ctypes.c_float)]
+
+
 class BAResultC(ctypes.Structure):
     _fields_ = [("pose_q", ctypes.c_void_p), ("pose_t", ctypes.c_void_p), ("points", ctypes.c_void_p),
                 ("edge_chi2", ctypes.c_void_p), ("edge_depth_ok", ctypes.c_void_p),
@@ -140,7 +145,8 @@ EXPORTED = ["orbhip_abi_version", "orbhip_create", "orbhip_destroy", "orbhip_lev
             "orbhip_extract", "orbhip_extract_batch_device", "orbhip_extract_stereo", "orbhip_extract_stereo_device",
             "orbhip_descriptor_distance", "orbhip_match_bf",
             "orbhip_match_pairs_device", "orbhip_match_frames_device", "orbhip_profile_stage",
-            "orbhip_profile_collect", "orbhip_launch_graphs", "orbhip_ba_solve", "orbhip_ba_solve_batch", "orbhip_ba_stats", "orbhip_bgr_to_gray_device",
+            "orbhip_profile_collect", "orbhip_launch_graphs", "orbhip_ba_solve", "orbhip_ba_solve_batch", "orbhip_ba_stats",
+            "orbhip_ba_solve_stereo", "orbhip_ba_solve_stereo_batch", "orbhip_bgr_to_gray_device",
             "orbhip_comm_unique_id", "orbhip_comm_init", "orbhip_ba_solve_sharded", "orbhip_ba_solve_sharded_segments",
             "orbhip_ba_solve_shards_local",
             "orbhip_vocab_create", "orbhip_vocab_load_text", "orbhip_vocab_destroy", "orbhip_vocab_info",
@@ -215,6 +221,9 @@ def lib():
     L.orbhip_launch_graphs.argtypes = [vp]
     L.orbhip_ba_solve.argtypes = [vp, ctypes.POINTER(BAProblemC), ctypes.POINTER(BAResultC), vp]
     L.orbhip_ba_solve_batch.argtypes = [vp, ctypes.POINTER(BAProblemC), i32, ctypes.POINTER(BAResultC), vp]
+    L.orbhip_ba_solve_stereo.argtypes = [vp, ctypes.POINTER(BAStereoProblemC), ctypes.POINTER(BAResultC), vp]
+    L.orbhip_ba_solve_stereo_batch.argtypes = [vp, ctypes.POINTER(BAStereoProblemC), i32, ctypes.POINTER(BAResultC),
+                                               vp]
     L.orbhip_ba_stats.argtypes = [vp, vp]
     L.orbhip_pose_optimization.argtypes = [vp, ctypes.POINTER(PoseProblemC), ctypes.POINTER(PoseResultC)]
     L.orbhip_pose_optimization_batch.argtypes = [vp, ctypes.POINTER(PoseProblemC), i32, ctypes.POINTER(PoseResultC)]

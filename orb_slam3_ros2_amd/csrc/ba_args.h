@@ -74,6 +74,12 @@ struct BaArgs {
     double* part;      // workgroup partial sums of a trial: chi2 (npart_e = ceil(E / 256)), then the
     int npart_e, npart_m;   // landmark scale terms (npart_m = ceil(M / 256)); in the build phase
                             // k_ba_lin's per-workgroup max diagonal (ceil(M / 256) + ceil(np / 4))
+    // Stereo edges (EdgeStereoSE3ProjectXYZ), read by the Stereo = true kernels only (null / 0 in
+    // every other solve): e_obs, e_err and e_lin keep their layouts, the third row has its own arrays
+    const double* e_ur;    // E: the observation's right coordinate (< 0: a monocular edge)
+    double* e_err2;        // E: the third error row (0 for a monocular edge)
+    double bf;             // mbf
+    double delta_s;        // Huber delta of the stereo edges (<= 0: none)
 };
 
 }  // namespace orbhip

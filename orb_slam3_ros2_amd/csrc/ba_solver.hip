@@ -22,6 +22,11 @@
 //                      and T <- exp(xp) * T (SE3Quat::exp, operator*)   (push: old T saved)
 //   k_ba_reduce        activeRobustChi2, computeScale, max diag (host-driven rounds)
 //   k_ba_pop           restore the pushed state of problems whose trial was rejected
+// The kernels that form an edge's error or Jacobians (k_ba_errors, k_ba_lin, k_ba_schur_items,
+// k_ba_backsub, k_ba_backsub_errs) are templates on Stereo: false is the monocular problem
+// (EdgeSE3ProjectXYZ alone, every entry point but the stereo ones), true adds the third row of
+// EdgeStereoSE3ProjectXYZ on the edges with e_ur >= 0 (orbhip_ba_solve_stereo*, DESIGN.md §4
+// "Stereo bundle adjustment").
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
@@ -134,27 +139,55 @@ __device__ void ctl_begin_body(const BaArgs& a, int nlin, int* done_flags, int p
 // one edge: error, chi2, robust rho (EdgeSE3ProjectXYZ::computeError + RobustKernelHuber::robustify);
 // returns rho0
 // the error terms of edge e from its camera-frame point
-__device__ __forceinline__ void edge_terms(const BaArgs& a, int e, double cx, double cy, double cz, double& e0,
-                                           double& e1, double& chi2, double& r0, double& r1) {
+// Stereo (template <bool Stereo> below): the problem may hold EdgeStereoSE3ProjectXYZ edges, those
+// with e_ur[e] >= 0 (the observation's right coordinate): a third error row
+//   e2 = ur - (fx x / z + cx - bf / z), the same information, a Huber delta of its own (delta_s),
+// and a third Jacobian row: the first row's formula with j02 replaced by j22 = j02 - bf / z^2.
+// A monocular edge of such a problem has a zero third row (error and Jacobian): every sum below
+// receives +0 from it. Stereo = false is the monocular code, word for word.
+// The terms from the observation's words (o0, o1: the keypoint, ur: its right coordinate, unused
+// unless Stereo)
+template <bool Stereo>
+__device__ __forceinline__ void edge_terms_of(const BaArgs& a, double o0, double o1, double ur, double info, double cx,
+                                              double cy, double cz, double& e0, double& e1, double& e2, double& chi2,
+                                              double& r0, double& r1) {
     const double u = a.fx * cx / cz + a.cx, v = a.fy * cy / cz + a.cy;
-    e0 = a.e_obs[2 * e] - u;
-    e1 = a.e_obs[2 * e + 1] - v;
-    chi2 = a.e_info[e] * (e0 * e0 + e1 * e1);
+    e0 = o0 - u;
+    e1 = o1 - v;
+    double delta = a.delta;
+    if constexpr (Stereo) {
+        const bool st = ur >= 0.0;
+        e2 = st ? ur - (u - a.bf / cz) : 0.0;
+        chi2 = info * (e0 * e0 + e1 * e1 + e2 * e2);
+        delta = st ? a.delta_s : a.delta;
+    } else {
+        e2 = 0.0;
+        chi2 = info * (e0 * e0 + e1 * e1);
+    }
     r0 = chi2;
     r1 = 1.0;
-    if (a.delta > 0) {
-        const double dsqr = a.delta * a.delta;
+    if (delta > 0) {
+        const double dsqr = delta * delta;
         if (chi2 > dsqr) {
             const double sq = sqrt(chi2);
-            r0 = 2 * sq * a.delta - dsqr;
-            r1 = a.delta / sq;
+            r0 = 2 * sq * delta - dsqr;
+            r1 = delta / sq;
         }
     }
 }
-__device__ __forceinline__ void store_terms(const BaArgs& a, int e, double e0, double e1, double chi2, double r0,
-                                            double r1) {
+template <bool Stereo>
+__device__ __forceinline__ void edge_terms(const BaArgs& a, int e, double cx, double cy, double cz, double& e0,
+                                           double& e1, double& e2, double& chi2, double& r0, double& r1) {
+    double ur = -1.0;
+    if constexpr (Stereo) ur = a.e_ur[e];
+    edge_terms_of<Stereo>(a, a.e_obs[2 * e], a.e_obs[2 * e + 1], ur, a.e_info[e], cx, cy, cz, e0, e1, e2, chi2, r0, r1);
+}
+template <bool Stereo>
+__device__ __forceinline__ void store_terms(const BaArgs& a, int e, double e0, double e1, double e2, double chi2,
+                                            double r0, double r1) {
     a.e_err[2 * e] = e0;
     a.e_err[2 * e + 1] = e1;
+    if constexpr (Stereo) a.e_err2[e] = e2;
     a.e_chi2[e] = chi2;
     a.e_rho0[e] = r0;
     a.e_rho1[e] = r1;
@@ -162,17 +195,19 @@ __device__ __forceinline__ void store_terms(const BaArgs& a, int e, double e0, d
 // Plain stores: no launch rewrites these words after another workgroup of the same launch wrote
 // them (a rejected small problem's refresh is done by the next build, k_ba_lin, not by the
 // trial's last workgroup; r05: the agent-scope stores cost ~4 us per C4 trial)
+template <bool Stereo>
 __device__ __forceinline__ double edge_error_at(const BaArgs& a, int e, const double* T, const double* X) {
     double cx, cy, cz;
     qrot(load_q(T), X[0], X[1], X[2], cx, cy, cz);
     cx += T[4]; cy += T[5]; cz += T[6];
-    double e0, e1, chi2, r0, r1;
-    edge_terms(a, e, cx, cy, cz, e0, e1, chi2, r0, r1);
-    store_terms(a, e, e0, e1, chi2, r0, r1);
+    double e0, e1, e2, chi2, r0, r1;
+    edge_terms<Stereo>(a, e, cx, cy, cz, e0, e1, e2, chi2, r0, r1);
+    store_terms<Stereo>(a, e, e0, e1, e2, chi2, r0, r1);
     return r0;
 }
+template <bool Stereo>
 __device__ __forceinline__ double edge_error(const BaArgs& a, int e) {
-    return edge_error_at(a, e, a.pose + 8 * a.e_pose[e], a.pts + 3 * a.e_pt[e]);
+    return edge_error_at<Stereo>(a, e, a.pose + 8 * a.e_pose[e], a.pts + 3 * a.e_pt[e]);
 }
 
 // when == 2 (a trial) ends in the trial's controller step, run by the last workgroup of each
@@ -207,6 +242,7 @@ __device__ __forceinline__ void relay_host_stop(const BaArgs* args, const int* a
     }
 }
 
+template <bool Stereo>
 __global__ __launch_bounds__(256) void k_ba_errors(const BaArgs* __restrict__ args, const int* __restrict__ act,
                                                    int when, int* const* donep) {
     BA_PROLOGUE
@@ -227,7 +263,7 @@ __global__ __launch_bounds__(256) void k_ba_errors(const BaArgs* __restrict__ ar
     const bool has = bx_ * (int)blockDim.x < a.E;   // uniform
     if (when != 2 && !has) return;
     const int e = bx_ * blockDim.x + threadIdx.x;
-    const double r0 = (has && e < a.E) ? edge_error(a, e) : 0.0;
+    const double r0 = (has && e < a.E) ? edge_error<Stereo>(a, e) : 0.0;
     if (when == 2) {   // uniform: every thread reaches the workgroup sum's barriers once
         __shared__ double sh[4];
         __shared__ int lastf;
@@ -253,15 +289,38 @@ __device__ __forceinline__ void proj_jac(double fx, double fy, double x, double 
     j[2] = -(fy / z);
     j[3] = fy * y / (z * z);
 }
-__device__ __forceinline__ void jac_ab(const double j[4], double x, double y, double z, const double R[9],
-                                       double A[6], double B[12]) {
+// Stereo: the third row's pair js = (j00, j22 = j02 - bf / z^2) of a stereo edge (ur >= 0), (0, 0)
+// of a monocular one; A is then 3x3 (third row js0 R[0,:] + js1 R[2,:]) and B 3x6 (third row
+// [js1 y, js0 z - js1 x, -js0 y, js0, 0, js1])
+template <bool Stereo>
+struct JacDim {
+    static constexpr int kA = Stereo ? 9 : 6, kB = Stereo ? 18 : 12;
+};
+__device__ __forceinline__ void stereo_jac(double bf, double ur, const double j[4], double z, double js[2]) {
+    const bool st = ur >= 0.0;
+    js[0] = st ? j[0] : 0.0;
+    js[1] = st ? j[1] - bf / (z * z) : 0.0;
+}
+template <bool Stereo>
+__device__ __forceinline__ void jac_ab(const double j[4], const double js[2], double x, double y, double z,
+                                       const double R[9], double* A, double* B) {
 #pragma unroll
     for (int c = 0; c < 3; c++) {
         A[c] = j[0] * R[c] + j[1] * R[6 + c];
         A[3 + c] = j[2] * R[3 + c] + j[3] * R[6 + c];
+        if constexpr (Stereo) A[6 + c] = js[0] * R[c] + js[1] * R[6 + c];
     }
     B[0] = j[1] * y; B[1] = j[0] * z - j[1] * x; B[2] = -j[0] * y; B[3] = j[0]; B[4] = 0.0; B[5] = j[1];
     B[6] = j[3] * y - j[2] * z; B[7] = -j[3] * x; B[8] = j[2] * x; B[9] = 0.0; B[10] = j[2]; B[11] = j[3];
+    if constexpr (Stereo) {
+        B[12] = js[1] * y; B[13] = js[0] * z - js[1] * x; B[14] = -js[0] * y; B[15] = js[0]; B[16] = 0.0; B[17] = js[1];
+    }
+}
+// a0 b0 + a1 b1 (+ a2 b2): the rows' sum of one product term
+template <bool Stereo>
+__device__ __forceinline__ double rows_dot(double a0, double b0, double a1, double b1, double a2, double b2) {
+    if constexpr (Stereo) return a0 * b0 + a1 * b1 + a2 * b2;
+    else return a0 * b0 + a1 * b1;
 }
 
 // camera-frame point of edge e at the current state + the pose's rotation matrix
@@ -275,14 +334,16 @@ __device__ __forceinline__ void edge_pc(const BaArgs& a, int e, double& x, doubl
 }
 
 // A, B of edge e from its stored linearisation (e_lin) and its pose's R_lin (optimised poses only)
-__device__ __forceinline__ double lin_ab(const BaArgs& a, int e, int oi, double A[6], double B[12]) {
+template <bool Stereo>
+__device__ __forceinline__ double lin_ab(const BaArgs& a, int e, int oi, double* A, double* B) {
     const double4 l = ((const double4*)a.e_lin)[e];
-    double j[4];
+    double j[4], js[2] = {0.0, 0.0};
     proj_jac(a.fx, a.fy, l.x, l.y, l.z, j);
+    if constexpr (Stereo) stereo_jac(a.bf, a.e_ur[e], j, l.z, js);
     double R[9];
 #pragma unroll
     for (int k = 0; k < 9; k++) R[k] = a.R_lin[9 * oi + k];
-    jac_ab(j, l.x, l.y, l.z, R, A, B);
+    jac_ab<Stereo>(j, js, l.x, l.y, l.z, R, A, B);
     return l.w;
 }
 
@@ -293,33 +354,38 @@ __device__ __forceinline__ double lin_ab(const BaArgs& a, int e, int oi, double 
 // returns the largest |diagonal| of Hll (0 for m >= M)
 // fresh: the stored errors belong to a rejected trial (an unsharded problem whose iteration ended
 // on one): each edge's terms are taken from the restored state here, and stored, instead of read
+template <bool Stereo>
 __device__ __forceinline__ double lin_point(const BaArgs& a, int m, bool fresh = false) {
     if (m >= a.M) return 0.0;
     double H[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, bl[3] = {0, 0, 0};
     for (int k = a.pt_ptr[m]; k < a.pt_ptr[m + 1]; k++) {
         const int e = a.pt_edges[k];
-        double x, y, z, R[9], j[4], A[6], B[12];
+        double x, y, z, R[9], j[4], js[2] = {0.0, 0.0}, A[JacDim<Stereo>::kA], B[JacDim<Stereo>::kB];
         edge_pc(a, e, x, y, z, R);
         proj_jac(a.fx, a.fy, x, y, z, j);
-        jac_ab(j, x, y, z, R, A, B);
-        double r1, er0, er1;
+        if constexpr (Stereo) stereo_jac(a.bf, a.e_ur[e], j, z, js);
+        jac_ab<Stereo>(j, js, x, y, z, R, A, B);
+        double r1, er0, er1, er2 = 0.0;
         if (fresh) {   // uniform
             double chi2, r0;
-            edge_terms(a, e, x, y, z, er0, er1, chi2, r0, r1);
-            store_terms(a, e, er0, er1, chi2, r0, r1);
+            edge_terms<Stereo>(a, e, x, y, z, er0, er1, er2, chi2, r0, r1);
+            store_terms<Stereo>(a, e, er0, er1, er2, chi2, r0, r1);
         } else {
             r1 = a.e_rho1[e];
             er0 = a.e_err[2 * e];
             er1 = a.e_err[2 * e + 1];
+            if constexpr (Stereo) er2 = a.e_err2[e];
         }
         const double info = a.e_info[e];
         const double w = r1 * info;
         const double om0 = -info * er0 * r1, om1 = -info * er1 * r1;
+        const double om2 = Stereo ? -info * er2 * r1 : 0.0;
+        [[maybe_unused]] constexpr int a2 = Stereo ? 6 : 0, b2 = Stereo ? 12 : 0;   // the third rows of A and B (unused unless Stereo)
 #pragma unroll
         for (int r = 0; r < 3; r++) {
-            bl[r] += A[r] * om0 + A[3 + r] * om1;
+            bl[r] += rows_dot<Stereo>(A[r], om0, A[3 + r], om1, A[a2 + r], om2);
 #pragma unroll
-            for (int c = 0; c < 3; c++) H[3 * r + c] += w * (A[r] * A[c] + A[3 + r] * A[3 + c]);
+            for (int c = 0; c < 3; c++) H[3 * r + c] += w * rows_dot<Stereo>(A[r], A[c], A[3 + r], A[3 + c], A[a2 + r], A[a2 + c]);
         }
         ((double4*)a.e_lin)[e] = make_double4(x, y, z, w);
     }
@@ -333,33 +399,38 @@ __device__ __forceinline__ double lin_point(const BaArgs& a, int m, bool fresh =
 // of landmark m, the 12 sums are added over the quad (butterfly: the same bits in its lanes) and
 // lane 0 stores them; returns the largest |diagonal| of Hll in every lane of the quad
 constexpr int kLinL = 64;   // landmarks per workgroup of k_ba_lin
+template <bool Stereo>
 __device__ __forceinline__ double lin_point_quad(const BaArgs& a, int m, int sub, bool fresh) {
     if (m >= a.M) return 0.0;
     double H[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, bl[3] = {0, 0, 0};
     for (int k = a.pt_ptr[m] + sub; k < a.pt_ptr[m + 1]; k += 4) {
         const int e = a.pt_edges[k];
-        double x, y, z, R[9], j[4], A[6], B[12];
+        double x, y, z, R[9], j[4], js[2] = {0.0, 0.0}, A[JacDim<Stereo>::kA], B[JacDim<Stereo>::kB];
         edge_pc(a, e, x, y, z, R);
         proj_jac(a.fx, a.fy, x, y, z, j);
-        jac_ab(j, x, y, z, R, A, B);
-        double r1, er0, er1;
+        if constexpr (Stereo) stereo_jac(a.bf, a.e_ur[e], j, z, js);
+        jac_ab<Stereo>(j, js, x, y, z, R, A, B);
+        double r1, er0, er1, er2 = 0.0;
         if (fresh) {   // uniform
             double chi2, r0;
-            edge_terms(a, e, x, y, z, er0, er1, chi2, r0, r1);
-            store_terms(a, e, er0, er1, chi2, r0, r1);
+            edge_terms<Stereo>(a, e, x, y, z, er0, er1, er2, chi2, r0, r1);
+            store_terms<Stereo>(a, e, er0, er1, er2, chi2, r0, r1);
         } else {
             r1 = a.e_rho1[e];
             er0 = a.e_err[2 * e];
             er1 = a.e_err[2 * e + 1];
+            if constexpr (Stereo) er2 = a.e_err2[e];
         }
         const double info = a.e_info[e];
         const double w = r1 * info;
         const double om0 = -info * er0 * r1, om1 = -info * er1 * r1;
+        const double om2 = Stereo ? -info * er2 * r1 : 0.0;
+        [[maybe_unused]] constexpr int a2 = Stereo ? 6 : 0, b2 = Stereo ? 12 : 0;   // the third rows of A and B (unused unless Stereo)
 #pragma unroll
         for (int r = 0; r < 3; r++) {
-            bl[r] += A[r] * om0 + A[3 + r] * om1;
+            bl[r] += rows_dot<Stereo>(A[r], om0, A[3 + r], om1, A[a2 + r], om2);
 #pragma unroll
-            for (int c = 0; c < 3; c++) H[3 * r + c] += w * (A[r] * A[c] + A[3 + r] * A[3 + c]);
+            for (int c = 0; c < 3; c++) H[3 * r + c] += w * rows_dot<Stereo>(A[r], A[c], A[3 + r], A[3 + c], A[a2 + r], A[a2 + c]);
         }
         ((double4*)a.e_lin)[e] = make_double4(x, y, z, w);
     }
@@ -381,7 +452,7 @@ __device__ __forceinline__ double lin_point_quad(const BaArgs& a, int m, int sub
 __global__ __launch_bounds__(256) void k_ba_lin_points(const BaArgs* __restrict__ args, const int* __restrict__ act) {
     BA_PROLOGUE
     BA_PHASE(kPhBuild)
-    (void)lin_point(a, bx_ * blockDim.x + threadIdx.x);
+    (void)lin_point<false>(a, bx_ * blockDim.x + threadIdx.x);
 }
 
 // one wave per optimised pose: 21 upper Hpp terms + 6 b terms, lanes over the pose's edges; lane 0
@@ -400,6 +471,7 @@ __device__ __forceinline__ void reduce_half(double* acc, int lane, int m) {
 }
 
 // one wave per pose i; returns (in every lane) the largest |diagonal| of the pose's Hpp block
+template <bool Stereo>
 __device__ __forceinline__ double lin_pose(const BaArgs& a, int i, int lane, bool fresh = false) {
     if (i >= a.np) return 0.0;   // wave-uniform
     double acc[32];   // 27 sums (21 of the upper Hpp triangle, 6 of b_p), padded to 32
@@ -407,29 +479,33 @@ __device__ __forceinline__ double lin_pose(const BaArgs& a, int i, int lane, boo
     for (int k = 0; k < 32; k++) acc[k] = 0;
     for (int k = a.ps_ptr[i] + lane; k < a.ps_ptr[i + 1]; k += 64) {
         const int e = a.ps_edges[k];
-        double x, y, z, R[9], j[4], A[6], B[12];
+        double x, y, z, R[9], j[4], js[2] = {0.0, 0.0}, A[JacDim<Stereo>::kA], B[JacDim<Stereo>::kB];
         edge_pc(a, e, x, y, z, R);
         proj_jac(a.fx, a.fy, x, y, z, j);
-        jac_ab(j, x, y, z, R, A, B);
-        double r1, er0, er1;
+        if constexpr (Stereo) stereo_jac(a.bf, a.e_ur[e], j, z, js);
+        jac_ab<Stereo>(j, js, x, y, z, R, A, B);
+        double r1, er0, er1, er2 = 0.0;
         if (fresh) {   // uniform; the landmark side stores the same values
             double chi2, r0;
-            edge_terms(a, e, x, y, z, er0, er1, chi2, r0, r1);
+            edge_terms<Stereo>(a, e, x, y, z, er0, er1, er2, chi2, r0, r1);
         } else {
             r1 = a.e_rho1[e];
             er0 = a.e_err[2 * e];
             er1 = a.e_err[2 * e + 1];
+            if constexpr (Stereo) er2 = a.e_err2[e];
         }
         const double info = a.e_info[e];
         const double w = r1 * info;
         const double om0 = -info * er0 * r1, om1 = -info * er1 * r1;
+        const double om2 = Stereo ? -info * er2 * r1 : 0.0;
+        [[maybe_unused]] constexpr int a2 = Stereo ? 6 : 0, b2 = Stereo ? 12 : 0;   // the third rows of A and B (unused unless Stereo)
         int t = 0;
 #pragma unroll
         for (int r = 0; r < 6; r++)
 #pragma unroll
-            for (int c = r; c < 6; c++) acc[t++] += w * (B[r] * B[c] + B[6 + r] * B[6 + c]);
+            for (int c = r; c < 6; c++) acc[t++] += w * rows_dot<Stereo>(B[r], B[c], B[6 + r], B[6 + c], B[b2 + r], B[b2 + c]);
 #pragma unroll
-        for (int r = 0; r < 6; r++) acc[21 + r] += B[r] * om0 + B[6 + r] * om1;
+        for (int r = 0; r < 6; r++) acc[21 + r] += rows_dot<Stereo>(B[r], om0, B[6 + r], om1, B[b2 + r], om2);
     }
     // transpose-reduce over the 64 lanes: at each step a lane keeps half of its values and adds
     // its partner's copy of them (16 + 8 + 4 + 2 + 1 shuffles, then one for the last pair instead
@@ -474,6 +550,7 @@ __device__ __forceinline__ double lin_pose(const BaArgs& a, int i, int lane, boo
 // the same with the whole work-group on pose i (r06, k_ba_lin with one pose per work-group): its
 // four waves take edges lane, lane + 256, ... of the pose, each reduces its 27 sums as above, and
 // wave 0 adds the four in wave order; returns the largest |diagonal| in wave 0 (0 in the others)
+template <bool Stereo>
 __device__ __forceinline__ double lin_pose_wg(const BaArgs& a, int i, bool fresh, double* sh27) {
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
     if (i >= a.np) return 0.0;   // work-group-uniform
@@ -482,29 +559,33 @@ __device__ __forceinline__ double lin_pose_wg(const BaArgs& a, int i, bool fresh
     for (int k = 0; k < 32; k++) acc[k] = 0;
     for (int k = a.ps_ptr[i] + (int)threadIdx.x; k < a.ps_ptr[i + 1]; k += blockDim.x) {
         const int e = a.ps_edges[k];
-        double x, y, z, R[9], j[4], A[6], B[12];
+        double x, y, z, R[9], j[4], js[2] = {0.0, 0.0}, A[JacDim<Stereo>::kA], B[JacDim<Stereo>::kB];
         edge_pc(a, e, x, y, z, R);
         proj_jac(a.fx, a.fy, x, y, z, j);
-        jac_ab(j, x, y, z, R, A, B);
-        double r1, er0, er1;
+        if constexpr (Stereo) stereo_jac(a.bf, a.e_ur[e], j, z, js);
+        jac_ab<Stereo>(j, js, x, y, z, R, A, B);
+        double r1, er0, er1, er2 = 0.0;
         if (fresh) {
             double chi2, r0;
-            edge_terms(a, e, x, y, z, er0, er1, chi2, r0, r1);
+            edge_terms<Stereo>(a, e, x, y, z, er0, er1, er2, chi2, r0, r1);
         } else {
             r1 = a.e_rho1[e];
             er0 = a.e_err[2 * e];
             er1 = a.e_err[2 * e + 1];
+            if constexpr (Stereo) er2 = a.e_err2[e];
         }
         const double info = a.e_info[e];
         const double w = r1 * info;
         const double om0 = -info * er0 * r1, om1 = -info * er1 * r1;
+        const double om2 = Stereo ? -info * er2 * r1 : 0.0;
+        [[maybe_unused]] constexpr int a2 = Stereo ? 6 : 0, b2 = Stereo ? 12 : 0;   // the third rows of A and B (unused unless Stereo)
         int t = 0;
 #pragma unroll
         for (int r = 0; r < 6; r++)
 #pragma unroll
-            for (int c = r; c < 6; c++) acc[t++] += w * (B[r] * B[c] + B[6 + r] * B[6 + c]);
+            for (int c = r; c < 6; c++) acc[t++] += w * rows_dot<Stereo>(B[r], B[c], B[6 + r], B[6 + c], B[b2 + r], B[b2 + c]);
 #pragma unroll
-        for (int r = 0; r < 6; r++) acc[21 + r] += B[r] * om0 + B[6 + r] * om1;
+        for (int r = 0; r < 6; r++) acc[21 + r] += rows_dot<Stereo>(B[r], om0, B[6 + r], om1, B[b2 + r], om2);
     }
     reduce_half<16>(acc, lane, 32);
     reduce_half<8>(acc, lane, 16);
@@ -549,7 +630,7 @@ __device__ __forceinline__ double lin_pose_wg(const BaArgs& a, int i, bool fresh
 __global__ __launch_bounds__(256) void k_ba_lin_poses(const BaArgs* __restrict__ args, const int* __restrict__ act) {
     BA_PROLOGUE
     BA_PHASE(kPhBuild)
-    (void)lin_pose(a, bx_ * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
+    (void)lin_pose<false>(a, bx_ * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
 }
 
 // the device-driven build in one launch: workgroups [0, nbp) linearise landmarks (kLinL each,
@@ -557,6 +638,7 @@ __global__ __launch_bounds__(256) void k_ba_lin_poses(const BaArgs* __restrict__
 // problem's last workgroup runs the controller's trial start (ctl_begin_body: lambda from the
 // maxima on the first iteration)
 // ppw: poses per pose work-group, 4 (a wave each) or 1 (the whole work-group, lin_pose_wg)
+template <bool Stereo>
 __global__ __launch_bounds__(256) void k_ba_lin(const BaArgs* __restrict__ args, const int* __restrict__ act,
                                                int nbp, int ppw, int* const* donep) {
     BA_PROLOGUE
@@ -573,11 +655,12 @@ __global__ __launch_bounds__(256) void k_ba_lin(const BaArgs* __restrict__ args,
     double d;
     int slot;
     if (bx_ < nbp) {
-        d = lin_point_quad(a, bx_ * kLinL + (threadIdx.x >> 2), threadIdx.x & 3, fresh);
+        d = lin_point_quad<Stereo>(a, bx_ * kLinL + (threadIdx.x >> 2), threadIdx.x & 3, fresh);
         slot = bx_ < mP ? bx_ : -1;
     } else {
         const int q = bx_ - nbp;
-        d = ppw == 1 ? lin_pose_wg(a, q, fresh, sh27) : lin_pose(a, q * 4 + (threadIdx.x >> 6), threadIdx.x & 63, fresh);
+        d = ppw == 1 ? lin_pose_wg<Stereo>(a, q, fresh, sh27)
+                     : lin_pose<Stereo>(a, q * 4 + (threadIdx.x >> 6), threadIdx.x & 63, fresh);
         slot = q < nP ? mP + q : -1;
     }
 #pragma unroll
@@ -659,9 +742,14 @@ __global__ __launch_bounds__(256) void k_ba_zero_s(const BaArgs* __restrict__ ar
 // with A, B rebuilt from the edges' stored (Pc, w) and the poses' R_lin: 17 doubles read per pair
 // (edge records + Dinv) instead of the 36 of stored W / Hpl blocks, and no W written per trial.
 constexpr int kItemsWg = 128;   // Schur work items per k_ba_schur_items work-group (two lanes each)
+template <bool Stereo>
 __device__ __forceinline__ void schur_b_pose(const BaArgs& a, int i, int lane);
 // work-groups [nbi, gridDim.x) run k_ba_schur_b's poses instead (it reads only k_ba_schur_points'
 // db and the linearisation: no dependence on the items, one launch less per trial)
+// Stereo: A_a, A_b get their third rows (sa, sb: the stereo_jac pairs), so T = A_a Dinv and
+// C = w_a w_b A_a Dinv A_b^T are 3x3, and B_b, B_a^T get a third row / column; the same two lanes
+// per item and the same 18 sums per lane
+template <bool Stereo>
 __global__ __launch_bounds__(256) void k_ba_schur_items(const BaArgs* __restrict__ args, const int* __restrict__ act,
                                                         int nbi, int* const* donep) {
     BA_PROLOGUE
@@ -671,7 +759,7 @@ __global__ __launch_bounds__(256) void k_ba_schur_items(const BaArgs* __restrict
     }
     BA_PHASE(kPhTrial)
     if (bx_ >= nbi) {
-        schur_b_pose(a, (bx_ - nbi) * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
+        schur_b_pose<Stereo>(a, (bx_ - nbi) * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
         return;
     }
     const int gt = bx_ * blockDim.x + threadIdx.x;
@@ -703,7 +791,12 @@ __global__ __launch_bounds__(256) void k_ba_schur_items(const BaArgs* __restrict
         proj_jac(fx, fy, lb.x, lb.y, lb.z, jb);
         const double a00 = ja[0], a02 = ja[1], a11 = ja[2], a12 = ja[3];
         const double b00 = jb[0], b02 = jb[1], b11 = jb[2], b12 = jb[3];
-        double T[6];   // A_a Dinv (2x3), A_a = [a00 Ri0 + a02 Ri2; a11 Ri1 + a12 Ri2]
+        double sa[2] = {0.0, 0.0}, sb[2] = {0.0, 0.0};   // the third rows' (j00, j22) of both edges
+        if constexpr (Stereo) {
+            stereo_jac(a.bf, a.e_ur[pr.x], ja, la.z, sa);
+            stereo_jac(a.bf, a.e_ur[pr.y], jb, lb.z, sb);
+        }
+        double T[Stereo ? 9 : 6];   // A_a Dinv (2x3), A_a = [a00 Ri0 + a02 Ri2; a11 Ri1 + a12 Ri2] (; sa0 Ri0 + sa1 Ri2)
 #pragma unroll
         for (int c = 0; c < 3; c++) {
             const double d0 = Di[c], d1 = Di[3 + c], d2 = Di[6 + c];
@@ -712,41 +805,57 @@ __global__ __launch_bounds__(256) void k_ba_schur_items(const BaArgs* __restrict
             const double r2 = Ri[6] * d0 + Ri[7] * d1 + Ri[8] * d2;
             T[c] = a00 * r0 + a02 * r2;
             T[3 + c] = a11 * r1 + a12 * r2;
+            if constexpr (Stereo) T[6 + c] = sa[0] * r0 + sa[1] * r2;
         }
         const double ww = la.w * lb.w;
-        double C[4];   // w_a w_b A_a Dinv A_b^T (2x2)
+        constexpr int NR = Stereo ? 3 : 2;   // rows of an edge
+        double C[NR * NR];   // w_a w_b A_a Dinv A_b^T (2x2; 3x3)
 #pragma unroll
-        for (int c = 0; c < 2; c++) {
-            const double jb0 = c == 0 ? b00 : b11, jb2 = c == 0 ? b02 : b12;
+        for (int c = 0; c < NR; c++) {
+            const double jb0 = c == 0 ? b00 : c == 1 ? b11 : sb[0], jb2 = c == 0 ? b02 : c == 1 ? b12 : sb[1];
+            const int rj = c == 1 ? 3 : 0;   // A_b's row c = jb0 Rj[c == 1 ? 1 : 0, :] + jb2 Rj[2, :]
             double ab[3];
 #pragma unroll
-            for (int q = 0; q < 3; q++) ab[q] = jb0 * Rj[3 * c + q] + jb2 * Rj[6 + q];
+            for (int q = 0; q < 3; q++) ab[q] = jb0 * Rj[rj + q] + jb2 * Rj[6 + q];
 #pragma unroll
-            for (int r = 0; r < 2; r++) C[2 * r + c] = ww * (T[3 * r] * ab[0] + T[3 * r + 1] * ab[1] + T[3 * r + 2] * ab[2]);
+            for (int r = 0; r < NR; r++) C[NR * r + c] = ww * (T[3 * r] * ab[0] + T[3 * r + 1] * ab[1] + T[3 * r + 2] * ab[2]);
         }
         // B_b rows: [b02 y, b00 z - b02 x, -b00 y, b00, 0, b02], [b12 y - b11 z, -b12 x, b11 x, 0, b11, b12]
+        // (, [sb1 y, sb0 z - sb1 x, -sb0 y, sb0, 0, sb1])
         const double Bb0[6] = {b02 * lb.y, b00 * lb.z - b02 * lb.x, -b00 * lb.y, b00, 0.0, b02};
         const double Bb1[6] = {b12 * lb.y - b11 * lb.z, -b12 * lb.x, b11 * lb.x, 0.0, b11, b12};
-        double CB0[6], CB1[6];   // C B_b (2x6)
+        const double Bb2[6] = {sb[1] * lb.y, sb[0] * lb.z - sb[1] * lb.x, -sb[0] * lb.y, sb[0], 0.0, sb[1]};
+        double CB0[6], CB1[6], CB2[6];   // C B_b (2x6; 3x6)
 #pragma unroll
         for (int c = 0; c < 6; c++) {
-            CB0[c] = C[0] * Bb0[c] + C[1] * Bb1[c];
-            CB1[c] = C[2] * Bb0[c] + C[3] * Bb1[c];
+            if constexpr (Stereo) {
+                CB0[c] = C[0] * Bb0[c] + C[1] * Bb1[c] + C[2] * Bb2[c];
+                CB1[c] = C[3] * Bb0[c] + C[4] * Bb1[c] + C[5] * Bb2[c];
+                CB2[c] = C[6] * Bb0[c] + C[7] * Bb1[c] + C[8] * Bb2[c];
+            } else {
+                CB0[c] = C[0] * Bb0[c] + C[1] * Bb1[c];
+                CB1[c] = C[2] * Bb0[c] + C[3] * Bb1[c];
+                CB2[c] = 0.0;
+                (void)Bb2;
+            }
         }
         // this lane's rows of B_a^T: rows 3h..3h+2 of [a02 y, a00 z - a02 x, -a00 y, a00, 0, a02] and
         // [a12 y - a11 z, -a12 x, a11 x, 0, a11, a12]
-        double u0[3], u1[3];
+        // (and of [sa1 y, sa0 z - sa1 x, -sa0 y, sa0, 0, sa1])
+        double u0[3], u1[3], u2[3];
         if (h == 0) {
             u0[0] = a02 * la.y; u0[1] = a00 * la.z - a02 * la.x; u0[2] = -a00 * la.y;
             u1[0] = a12 * la.y - a11 * la.z; u1[1] = -a12 * la.x; u1[2] = a11 * la.x;
+            u2[0] = sa[1] * la.y; u2[1] = sa[0] * la.z - sa[1] * la.x; u2[2] = -sa[0] * la.y;
         } else {
             u0[0] = a00; u0[1] = 0.0; u0[2] = a02;
             u1[0] = 0.0; u1[1] = a11; u1[2] = a12;
+            u2[0] = sa[0]; u2[1] = 0.0; u2[2] = sa[1];
         }
 #pragma unroll
         for (int rr = 0; rr < 3; rr++)
 #pragma unroll
-            for (int cc = 0; cc < 6; cc++) s[6 * rr + cc] -= u0[rr] * CB0[cc] + u1[rr] * CB1[cc];
+            for (int cc = 0; cc < 6; cc++) s[6 * rr + cc] -= rows_dot<Stereo>(u0[rr], CB0[cc], u1[rr], CB1[cc], u2[rr], CB2[cc]);
     }
     // r06: a block's chunks (consecutive items, all in this work-group: prepare pads) are summed
     // here, not by a finisher launch: every chunk's 36 values go to LDS at its item position and
@@ -800,13 +909,15 @@ __global__ __launch_bounds__(256) void k_ba_schur_items(const BaArgs* __restrict
 }
 
 // one wave per optimised pose: b_schur = b_p - sum_e Hpl_e db, Hpl_e db = w B^T (A db)
+template <bool Stereo>
 __device__ __forceinline__ void schur_b_pose(const BaArgs& a, int i, int lane) {
     if (i >= a.np) return;
     double acc[6] = {0, 0, 0, 0, 0, 0};
     for (int k = a.ps_ptr[i] + lane; k < a.ps_ptr[i + 1]; k += 64) {
         const int e = a.ps_edges[k];
-        double A[6], B[12];
-        const double w = lin_ab(a, e, i, A, B);
+        double A[JacDim<Stereo>::kA], B[JacDim<Stereo>::kB];
+        const double w = lin_ab<Stereo>(a, e, i, A, B);
+        [[maybe_unused]] constexpr int a2 = Stereo ? 6 : 0, b2 = Stereo ? 12 : 0;   // the third rows (unused unless Stereo)
         double d0, d1, d2;
         if (a.fused) {   // db = Dinv b_l, formed here
             const int m = a.e_pt[e];
@@ -821,8 +932,9 @@ __device__ __forceinline__ void schur_b_pose(const BaArgs& a, int i, int lane) {
             d0 = d[0]; d1 = d[1]; d2 = d[2];
         }
         const double v0 = w * (A[0] * d0 + A[1] * d1 + A[2] * d2), v1 = w * (A[3] * d0 + A[4] * d1 + A[5] * d2);
+        const double v2 = Stereo ? w * (A[a2] * d0 + A[a2 + 1] * d1 + A[a2 + 2] * d2) : 0.0;
 #pragma unroll
-        for (int r = 0; r < 6; r++) acc[r] += B[r] * v0 + B[6 + r] * v1;
+        for (int r = 0; r < 6; r++) acc[r] += rows_dot<Stereo>(B[r], v0, B[6 + r], v1, B[b2 + r], v2);
     }
 #pragma unroll
     for (int r = 0; r < 6; r++) {
@@ -835,7 +947,7 @@ __device__ __forceinline__ void schur_b_pose(const BaArgs& a, int i, int lane) {
 __global__ __launch_bounds__(256) void k_ba_schur_b(const BaArgs* __restrict__ args, const int* __restrict__ act) {
     BA_PROLOGUE
     BA_PHASE(kPhTrial)
-    schur_b_pose(a, bx_ * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
+    schur_b_pose<false>(a, bx_ * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
 }
 
 // ---------------------------------------------------------------------------
@@ -1053,6 +1165,7 @@ __global__ __launch_bounds__(512) void k_chol_test(double* S, const double* bs, 
 // back-substitution + updates (push saves the old state)
 // ---------------------------------------------------------------------------
 // landmark m: xl = Dinv (b_l - Hpl^T xp), X += xl (old X saved); returns xl (lambda xl + b_l)
+template <bool Stereo>
 __device__ __forceinline__ double backsub_point(const BaArgs& a, int m) {
     const double* bl = a.b + a.n + 3 * m;
     double c[3] = {bl[0], bl[1], bl[2]};
@@ -1060,15 +1173,19 @@ __device__ __forceinline__ double backsub_point(const BaArgs& a, int m) {
         const int e = a.pt_edges[k];
         const int oi = a.opt[a.e_pose[e]];
         if (oi < 0) continue;
-        double A[6], B[12];
-        const double w = lin_ab(a, e, oi, A, B);   // Hpl_e^T xp = w A^T (B xp)
+        double A[JacDim<Stereo>::kA], B[JacDim<Stereo>::kB];
+        const double w = lin_ab<Stereo>(a, e, oi, A, B);   // Hpl_e^T xp = w A^T (B xp)
+        [[maybe_unused]] constexpr int a2 = Stereo ? 6 : 0, b2 = Stereo ? 12 : 0;   // the third rows (unused unless Stereo)
         const double* xp = a.x + 6 * oi;
-        double u0 = 0.0, u1 = 0.0;
+        double u0 = 0.0, u1 = 0.0, u2 = 0.0;
 #pragma unroll
-        for (int r = 0; r < 6; r++) { u0 += B[r] * xp[r]; u1 += B[6 + r] * xp[r]; }
-        u0 *= w; u1 *= w;
+        for (int r = 0; r < 6; r++) {
+            u0 += B[r] * xp[r]; u1 += B[6 + r] * xp[r];
+            if constexpr (Stereo) u2 += B[b2 + r] * xp[r];
+        }
+        u0 *= w; u1 *= w; u2 *= w;
 #pragma unroll
-        for (int cc = 0; cc < 3; cc++) c[cc] -= A[cc] * u0 + A[3 + cc] * u1;
+        for (int cc = 0; cc < 3; cc++) c[cc] -= rows_dot<Stereo>(A[cc], u0, A[3 + cc], u1, A[a2 + cc], u2);
     }
     double Di[9];
     if (a.fused) {
@@ -1102,6 +1219,7 @@ __device__ __forceinline__ double backsub_point(const BaArgs& a, int m) {
 // one thread per landmark (back-substitution) and, in the first workgroups, one per pose
 // (T <- exp(xp) T, the former k_ba_update_poses: it reads xp and writes the poses, which the
 // landmarks' back-substitution does not touch)
+template <bool Stereo>
 __global__ __launch_bounds__(256) void k_ba_backsub(const BaArgs* __restrict__ args, const int* __restrict__ act) {
     BA_PROLOGUE
     BA_PHASE(kPhTrial)
@@ -1117,7 +1235,7 @@ __global__ __launch_bounds__(256) void k_ba_backsub(const BaArgs* __restrict__ a
     // the landmark part of computeScale, sum of xl (lambda xl + b_l), per workgroup (uniform: every
     // thread reaches the workgroup sum's barriers once)
     __shared__ double sh[4];
-    const double t = block_sum(m < a.M ? backsub_point(a, m) : 0.0, sh);
+    const double t = block_sum(m < a.M ? backsub_point<Stereo>(a, m) : 0.0, sh);
     if (threadIdx.x == 0) a.part[a.npart_e + bx_] = t;
     if (bx_ == 0)   // the scale slots past this launch's workgroups (npart_m counts k_ba_backsub_errs')
         for (int i = (max(a.M, a.P) + 255) / 256 + (int)threadIdx.x; i < a.npart_m; i += blockDim.x)
@@ -1136,6 +1254,7 @@ __global__ __launch_bounds__(256) void k_ba_backsub(const BaArgs* __restrict__ a
 // step (ctl_end_body: commit the poses or take the points back)
 constexpr int kFusedMaxP = 512;
 constexpr int kBsL = 64;   // landmarks per workgroup of k_ba_backsub_errs
+template <bool Stereo>
 __global__ __launch_bounds__(256) void k_ba_backsub_errs(const BaArgs* __restrict__ args, const int* __restrict__ act,
                                                          int* const* donep) {
     BA_PROLOGUE
@@ -1161,6 +1280,7 @@ __global__ __launch_bounds__(256) void k_ba_backsub_errs(const BaArgs* __restric
     }
     int ce[2] = {-1, -1}, cp[2] = {0, 0};
     double co0[2] = {0, 0}, co1[2] = {0, 0}, ci[2] = {0, 0};
+    double cur[2] = {-1.0, -1.0};   // Stereo: the preloaded edges' right coordinates
     double c0 = 0.0, c1 = 0.0, c2 = 0.0;   // - sum_e Hpl_e^T xp over this lane's edges
     for (int k = k0 + sub, j = 0; k < k1; k += 4, j++) {
         const int e = a.pt_edges[k];
@@ -1168,19 +1288,24 @@ __global__ __launch_bounds__(256) void k_ba_backsub_errs(const BaArgs* __restric
         if (j < 2) {
             ce[j] = e; cp[j] = pe;
             co0[j] = a.e_obs[2 * e]; co1[j] = a.e_obs[2 * e + 1]; ci[j] = a.e_info[e];
+            if constexpr (Stereo) cur[j] = a.e_ur[e];
         }
         const int oi = a.opt[pe];
         if (oi < 0) continue;
-        double A[6], B[12];
-        const double w = lin_ab(a, e, oi, A, B);   // Hpl_e^T xp = w A^T (B xp)
+        double A[JacDim<Stereo>::kA], B[JacDim<Stereo>::kB];
+        const double w = lin_ab<Stereo>(a, e, oi, A, B);   // Hpl_e^T xp = w A^T (B xp)
+        [[maybe_unused]] constexpr int a2 = Stereo ? 6 : 0, b2 = Stereo ? 12 : 0;   // the third rows (unused unless Stereo)
         const double* xp = a.x + 6 * oi;
-        double u0 = 0.0, u1 = 0.0;
+        double u0 = 0.0, u1 = 0.0, u2 = 0.0;
 #pragma unroll
-        for (int r = 0; r < 6; r++) { u0 += B[r] * xp[r]; u1 += B[6 + r] * xp[r]; }
-        u0 *= w; u1 *= w;
-        c0 -= A[0] * u0 + A[3] * u1;
-        c1 -= A[1] * u0 + A[4] * u1;
-        c2 -= A[2] * u0 + A[5] * u1;
+        for (int r = 0; r < 6; r++) {
+            u0 += B[r] * xp[r]; u1 += B[6 + r] * xp[r];
+            if constexpr (Stereo) u2 += B[b2 + r] * xp[r];
+        }
+        u0 *= w; u1 *= w; u2 *= w;
+        c0 -= rows_dot<Stereo>(A[0], u0, A[3], u1, A[a2], u2);
+        c1 -= rows_dot<Stereo>(A[1], u0, A[4], u1, A[a2 + 1], u2);
+        c2 -= rows_dot<Stereo>(A[2], u0, A[5], u1, A[a2 + 2], u2);
     }
     for (int p = threadIdx.x; p < a.P; p += blockDim.x) {
         double T[8];
@@ -1231,23 +1356,13 @@ __global__ __launch_bounds__(256) void k_ba_backsub_errs(const BaArgs* __restric
             double cx, cy, cz;
             qrot(load_q(T), Xn[0], Xn[1], Xn[2], cx, cy, cz);
             cx += T[4]; cy += T[5]; cz += T[6];
-            const double u = a.fx * cx / cz + a.cx, v = a.fy * cy / cz + a.cy;
-            const double e0 = co0[j] - u, e1 = co1[j] - v;
-            const double chi2 = ci[j] * (e0 * e0 + e1 * e1);
-            double r0 = chi2, r1 = 1.0;
-            if (a.delta > 0) {
-                const double dsqr = a.delta * a.delta;
-                if (chi2 > dsqr) {
-                    const double sq = sqrt(chi2);
-                    r0 = 2 * sq * a.delta - dsqr;
-                    r1 = a.delta / sq;
-                }
-            }
-            store_terms(a, e, e0, e1, chi2, r0, r1);
+            double e0, e1, e2, chi2, r0, r1;
+            edge_terms_of<Stereo>(a, co0[j], co1[j], cur[j], ci[j], cx, cy, cz, e0, e1, e2, chi2, r0, r1);
+            store_terms<Stereo>(a, e, e0, e1, e2, chi2, r0, r1);
             chi += r0;
         } else {
             const int e = a.pt_edges[k];
-            chi += edge_error_at(a, e, Tn + 8 * a.e_pose[e], Xn);
+            chi += edge_error_at<Stereo>(a, e, Tn + 8 * a.e_pose[e], Xn);
         }
     }
     const double tc = block_sum(chi, sh);
@@ -2119,13 +2234,28 @@ struct LmState {
 };
 
 int ba_solve_batch(BaWorkspace* ws, const orbhip_ba_problem* const* probs, int B, orbhip_ba_result* const* res,
-                   const volatile int* stop, hipStream_t st, int shard_mode, bool no_dag, bool no_nd) {
+                   const volatile int* stop, hipStream_t st, int shard_mode, bool no_dag, bool no_nd,
+                   const BaStereoExt* sx) {
     if (B <= 0 || !probs || !res) return ORBHIP_ERR_ARG;
+    if (sx && shard_mode != kShardNone) return ORBHIP_ERR_ARG;   // the sharded forms have no stereo edges
     // RCCL: this rank holds B consecutive shards (segments rank*B .. rank*B+B-1 of nranks*B), the
     // same B on every rank; the shards of one rank are summed on the device before the all-reduce
     if (shard_mode == kShardRccl && !ws->comm) return ORBHIP_ERR_ARG;
     for (int b = 0; b < B; b++)
         if (!probs[b] || !res[b]) return ORBHIP_ERR_ARG;
+    // a call with stereo edges (orbhip_ba_solve_stereo*: some edge_ur >= 0) runs the Stereo = true
+    // kernels on every problem of it; every other call runs today's monocular kernels
+    bool stereo = false;
+    if (sx) {
+        for (int b = 0; b < B; b++) {
+            const int E = probs[b]->n_edges;
+            if (E > 0 && !sx[b].edge_ur) return ORBHIP_ERR_ARG;
+            bool any = false;
+            for (int e = 0; e < E && !any; e++) any = sx[b].edge_ur[e] >= 0.0f;
+            if (any && !(sx[b].bf > 0.0f)) return ORBHIP_ERR_ARG;
+            stereo = stereo || any;
+        }
+    }
     static const bool timing = std::getenv("ORBHIP_BA_TIMING") != nullptr;
     // the state words (8 P + 3 M) up to which the trial's last work-group restores a rejected
     // trial itself ("small"); larger problems restore in k_ba_pop. ORBHIP_BA_SMALL_WORDS (read per
@@ -2324,7 +2454,7 @@ int ba_solve_batch(BaWorkspace* ws, const orbhip_ba_problem* const* probs, int B
     // ---- packed layout: fp64 segments, each contiguous over all problems ----
     //   C  e_chi2 (E)                 downloaded with A in one transfer
     //   A  pose (8P) + pts (3M)       uploaded, optimised in place, downloaded
-    //   U  obs (2E) + info (E)        uploaded
+    //   U  obs (2E) + info (E)        uploaded (a call with stereo edges: + ur (E))
     //   R  the rest (scratch), then the edge linearisations e_lin (32-byte aligned), S (n*n) and
     //      the panel inverses Lsave, 16-byte aligned
     size_t nC = 0, nA = 0, nU = 0, nR = 0, ni = 0;
@@ -2333,10 +2463,11 @@ int ba_solve_batch(BaWorkspace* ws, const orbhip_ba_problem* const* probs, int B
         const size_t P = p.P, M = p.M, E = p.E, np_ = p.np, n = p.n;
         p.o_chi2 = nC; nC += E;
         p.o_state = nA; nA += 8 * P + 3 * M;
-        p.o_obs = nU; nU += 3 * E;
+        p.o_obs = nU; nU += (stereo ? 4 : 3) * E;
         p.o_scr = nR;
         nR += 8 * P + 3 * M                          // pose_bak, pts_bak
               + 2 * E + 3 * E                        // e_err, e_rho0, e_rho1 (+ pad)
+              + (stereo ? E : 0)                     // e_err2
               + 36 * np_ + 9 * np_ + 18 * M + 3 * M  // Hpp, R_lin, Hll, Dinv, db
               + (sharded ? 36 * np_ : 0)             // Hpp_g: Hpp summed over the shards
               + 2 * (n + 3 * M) + n + 4;             // b, x, bs, red
@@ -2404,6 +2535,8 @@ int ba_solve_batch(BaWorkspace* ws, const orbhip_ba_problem* const* probs, int B
             ob[2 * e + 1] = pr->edge_uv[2 * e + 1];
             ob[2 * E + e] = (double)pr->inv_sigma2[pr->edge_octave[e]];
         }
+        if (stereo)
+            for (size_t e = 0; e < E; e++) ob[3 * E + e] = (double)sx[b].edge_ur[e];
         int* q = hi + p.o_int;
         auto put = [&](const int* src, size_t cnt) { int* at = q; std::memcpy(q, src, cnt * sizeof(int)); q += cnt; return at; };
         BaArgs& a = ha[b];
@@ -2469,6 +2602,12 @@ int ba_solve_batch(BaWorkspace* ws, const orbhip_ba_problem* const* probs, int B
         a.e_err = r; r += 2 * E;
         a.e_rho0 = r; r += E;
         a.e_rho1 = r; r += 2 * E;
+        a.e_ur = nullptr; a.e_err2 = nullptr; a.bf = 0.0; a.delta_s = 0.0;
+        if (stereo) {
+            a.e_ur = a.e_info + E;
+            a.e_err2 = r; r += E;
+            a.bf = sx[b].bf; a.delta_s = sx[b].delta_s;
+        }
         a.Hpp = r; r += 36 * (size_t)p.np;
         a.R_lin = r; r += 9 * (size_t)p.np;
         a.Hll = r; r += 9 * M;
@@ -2581,6 +2720,12 @@ int ba_solve_batch(BaWorkspace* ws, const orbhip_ba_problem* const* probs, int B
         return ORBHIP_OK;
     };
     const BaArgs* dA = dArgs;
+    // the edge kernels of this call
+    const auto kErrors = stereo ? k_ba_errors<true> : k_ba_errors<false>;
+    const auto kLin = stereo ? k_ba_lin<true> : k_ba_lin<false>;
+    const auto kSchurItems = stereo ? k_ba_schur_items<true> : k_ba_schur_items<false>;
+    const auto kBacksub = stereo ? k_ba_backsub<true> : k_ba_backsub<false>;
+    const auto kBacksubErrs = stereo ? k_ba_backsub_errs<true> : k_ba_backsub_errs<false>;
     // stop flag: one consistent decision across ranks (all-reduce max) per batch of slots
     auto stop_now = [&]() -> bool {
         const bool local = stop && *stop;
@@ -2645,7 +2790,7 @@ int ba_solve_batch(BaWorkspace* ws, const orbhip_ba_problem* const* probs, int B
                 // guard): the same problem again on the plain DAG solve, nothing was run yet
                 if (rc == -5) {
                     if (hipStreamSynchronize(st) != hipSuccess) return ORBHIP_ERR_DEVICE;
-                    return ba_solve_batch(ws, probs, B, res, stop, st, shard_mode, no_dag, true);
+                    return ba_solve_batch(ws, probs, B, res, stop, st, shard_mode, no_dag, true, sx);
                 }
                 if (rc != 0) return ORBHIP_ERR_DEVICE;
             }
@@ -2741,7 +2886,7 @@ int ba_solve_batch(BaWorkspace* ws, const orbhip_ba_problem* const* probs, int B
             if (!large(b)) h_act[2 * B + ns++] = b;
         if (ns) BAOK(hipMemcpyAsync(d_act + 2 * B, h_act + 2 * B, ns * sizeof(int), hipMemcpyHostToDevice, st));
         if (s_readonly) hipLaunchKernelGGL(k_ba_zero_s, dim3(64, B), dim3(256), 0, st, dA, d_act, 1);
-        hipLaunchKernelGGL(k_ba_errors, dim3(gx(maxE, 256), B), dim3(256), 0, st, dA, d_act, 0, nullptr);
+        hipLaunchKernelGGL(kErrors, dim3(gx(maxE, 256), B), dim3(256), 0, st, dA, d_act, 0, nullptr);
         if (!sharded) {
             hipLaunchKernelGGL(k_ba_ctl_init, dim3(B), dim3(1024), 0, st, dA, d_act);
         } else {   // the initial chi2 over every shard's edges
@@ -2790,8 +2935,8 @@ int ba_solve_batch(BaWorkspace* ws, const orbhip_ba_problem* const* probs, int B
             // the sharded slots' error refresh and budget check; an unsharded problem's iteration
             // ends in its controller (ctl_end_decide) and its stale errors are refreshed by k_ba_lin
             if (!all_small && sharded)
-                hipLaunchKernelGGL(k_ba_errors, dim3(gx(maxE, 256), B), b256, 0, st, dA, d_act, 1, donep);
-            hipLaunchKernelGGL(k_ba_lin, dim3(gx(maxM, kLinL) + gx(maxNp, lin_ppw), B), b256, 0, st, dA, d_act,
+                hipLaunchKernelGGL(kErrors, dim3(gx(maxE, 256), B), b256, 0, st, dA, d_act, 1, donep);
+            hipLaunchKernelGGL(kLin, dim3(gx(maxM, kLinL) + gx(maxNp, lin_ppw), B), b256, 0, st, dA, d_act,
                                (int)gx(maxM, kLinL), lin_ppw, donep);
             if (sharded) {   // the trial start on the shards' sums: Hpp, then the largest diagonal
                 if (coll(kHpp)) return ORBHIP_ERR_DEVICE;
@@ -2801,7 +2946,7 @@ int ba_solve_batch(BaWorkspace* ws, const orbhip_ba_problem* const* probs, int B
             }
             if (!s_readonly) hipLaunchKernelGGL(k_ba_zero_s, dim3(64, B), b256, 0, st, dA, d_act, 0);
             if (!fused) hipLaunchKernelGGL(k_ba_schur_points, dim3(gx(maxM, 256), B), b256, 0, st, dA, d_act);
-            hipLaunchKernelGGL(k_ba_schur_items, dim3(gx(2 * maxItems, 256) + gx(maxNp, 4) + 1, B), b256, 0, st, dA,
+            hipLaunchKernelGGL(kSchurItems, dim3(gx(2 * maxItems, 256) + gx(maxNp, 4) + 1, B), b256, 0, st, dA,
                                d_act, (int)gx(2 * maxItems, 256), donep);
             if (nd_sh) {   // each shard its segment; the separator system and x summed over the shards
                 for (int b = 0; b < B; b++) BAOK(nd_factor_assemble(ws->nds[b], st));
@@ -2821,10 +2966,10 @@ int ba_solve_batch(BaWorkspace* ws, const orbhip_ba_problem* const* probs, int B
                     if (large(b) && large_solve(b, &dctl[b].phase)) return ORBHIP_ERR_DEVICE;
             }
             if (fused) {
-                hipLaunchKernelGGL(k_ba_backsub_errs, dim3(gbs, B), b256, 0, st, dA, d_act, donep);
+                hipLaunchKernelGGL(kBacksubErrs, dim3(gbs, B), b256, 0, st, dA, d_act, donep);
             } else {
-                hipLaunchKernelGGL(k_ba_backsub, dim3(gx(std::max(maxM, maxP), 256), B), b256, 0, st, dA, d_act);
-                hipLaunchKernelGGL(k_ba_errors, dim3(gx(maxE, 256), B), b256, 0, st, dA, d_act, 2, donep);
+                hipLaunchKernelGGL(kBacksub, dim3(gx(std::max(maxM, maxP), 256), B), b256, 0, st, dA, d_act);
+                hipLaunchKernelGGL(kErrors, dim3(gx(maxE, 256), B), b256, 0, st, dA, d_act, 2, donep);
             }
             if (sharded) {   // the trial's end on the shards' sums of chi2 and the scale
                 hipLaunchKernelGGL(k_ba_sh_sums, dim3(B), dim3(1024), 0, st, dA, d_act);
@@ -2969,7 +3114,7 @@ int ba_solve_batch(BaWorkspace* ws, const orbhip_ba_problem* const* probs, int B
             const char* e = std::getenv("ORBHIP_DAG_RERUN");
             if (no_dag || (e && e[0] == '0')) return ORBHIP_ERR_TIMEOUT;
             ws->dag_reruns++;
-            return ba_solve_batch(ws, probs, B, res, stop, st, shard_mode, true, no_nd);
+            return ba_solve_batch(ws, probs, B, res, stop, st, shard_mode, true, no_nd, sx);
         }
     }
     // the outputs of problem b, edges [e0, e1) (the poses, points and LM words with the first range)

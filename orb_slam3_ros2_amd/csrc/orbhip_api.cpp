@@ -359,6 +359,28 @@ int orbhip_ba_solve_batch(orbhip_ctx* c, const orbhip_ba_problem* probs, int B, 
     return ba_solve_batch(c->ba, pp.data(), B, rr.data(), stop, c->stream, kShardNone);
 }
 
+int orbhip_ba_solve_stereo_batch(orbhip_ctx* c, const orbhip_ba_stereo_problem* probs, int B, orbhip_ba_result* res,
+                                 const volatile int* stop) {
+    if (!c || !probs || !res || B <= 0) return ORBHIP_ERR_ARG;
+    HIPOK(hipSetDevice(c->device));
+    if (!c->ba) c->ba = ba_create();
+    if (!c->ba) return ORBHIP_ERR_DEVICE;
+    std::vector<const orbhip_ba_problem*> pp(B);
+    std::vector<orbhip_ba_result*> rr(B);
+    std::vector<BaStereoExt> sx(B);
+    for (int b = 0; b < B; b++) {
+        pp[b] = &probs[b].mono;
+        rr[b] = res + b;
+        sx[b] = BaStereoExt{probs[b].edge_ur, probs[b].bf, probs[b].huber_delta_stereo};
+    }
+    return ba_solve_batch(c->ba, pp.data(), B, rr.data(), stop, c->stream, kShardNone, false, false, sx.data());
+}
+
+int orbhip_ba_solve_stereo(orbhip_ctx* c, const orbhip_ba_stereo_problem* prob, orbhip_ba_result* res,
+                           const volatile int* stop) {
+    return orbhip_ba_solve_stereo_batch(c, prob, 1, res, stop);
+}
+
 int orbhip_pose_optimization_batch(orbhip_ctx* c, const orbhip_pose_problem* probs, int B,
                                    orbhip_pose_result* res) {
     if (!c || !probs || !res || B <= 0) return ORBHIP_ERR_ARG;

@@ -16,9 +16,15 @@ int ba_solve(BaWorkspace* ws, const orbhip_ba_problem* prob, orbhip_ba_result* r
 constexpr int kShardNone = 0, kShardLocal = 1, kShardRccl = 2;
 // no_dag: never the persistent DAG Cholesky (the re-run after a DAG hand-off timeout); no_nd: no
 // nested dissection of a lone problem (the re-run when its device setup refuses the plan)
+// sx: null, or per problem the stereo part of an orbhip_ba_stereo_problem (kShardNone only): the
+// call runs the stereo-edge kernels when some edge_ur of it is >= 0, else the monocular ones
+struct BaStereoExt {
+    const float* edge_ur;
+    float bf, delta_s;
+};
 int ba_solve_batch(BaWorkspace* ws, const orbhip_ba_problem* const* probs, int B, orbhip_ba_result* const* res,
                    const volatile int* stop, hipStream_t st, int shard_mode, bool no_dag = false,
-                   bool no_nd = false);
+                   bool no_nd = false, const BaStereoExt* sx = nullptr);
 // DAG hand-off timeouts this workspace saw, and the solves it re-ran on the other solvers
 void ba_stats(BaWorkspace* ws, long long* timeouts, long long* reruns);
 int ba_comm_init(BaWorkspace* ws, int nranks, int rank, const void* id);

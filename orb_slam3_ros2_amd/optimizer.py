@@ -14,10 +14,11 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import (BAProblemC, BAResultC, Context, PoseProblemC, PoseResultC, PoseStereoProblemC, check, lib,
+from ._lib import (BAProblemC, BAResultC, BAStereoProblemC, Context, PoseProblemC, PoseResultC, PoseStereoProblemC, check, lib,
                    ptr)
 
 TH_HUBER_MONO = float(np.sqrt(np.float32(5.991)))
+TH_HUBER_STEREO = float(np.sqrt(np.float32(7.815)))
 
 
 @dataclass
@@ -56,6 +57,39 @@ class BAProblem:
 
 
 @dataclass
+class StereoBAProblem(BAProblem):
+    """A BAProblem of a rectified-stereo system: an observation with edge_ur >= 0 (the keyframe's
+    mvuRight; 0.0 counts) is an EdgeStereoSE3ProjectXYZ with observation (u, v, ur) and the Huber
+    delta huber_delta_stereo; the others stay monocular edges."""
+    edge_ur: np.ndarray = None          # [E] float32 (< 0: a monocular edge)
+    bf: float = 0.0                     # mbf
+    huber_delta_stereo: float = TH_HUBER_STEREO
+
+    def normalized(self) -> "StereoBAProblem":
+        b = BAProblem.normalized(self)
+        E = b.edge_pose.shape[0]
+        ur = np.full(E, -1.0, np.float32) if self.edge_ur is None else \
+            np.ascontiguousarray(self.edge_ur, dtype=np.float32).reshape(-1)
+        if ur.shape[0] != E:
+            raise ValueError("StereoBAProblem: edge_ur needs one entry per edge")
+        return StereoBAProblem(**b.__dict__, edge_ur=ur, bf=float(self.bf),
+                               huber_delta_stereo=float(self.huber_delta_stereo))
+
+    def to_c(self) -> BAStereoProblemC:
+        return BAStereoProblemC(BAProblem.to_c(self), ptr(self.edge_ur), self.bf, self.huber_delta_stereo)
+
+    def mono(self) -> BAProblem:
+        """The same problem without its right coordinates."""
+        return BAProblem(**{k: v for k, v in self.__dict__.items()
+                            if k not in ("edge_ur", "bf", "huber_delta_stereo")})
+
+    def edge_thresholds(self) -> np.ndarray:
+        """The chi2 at which upstream erases each observation: 7.815 stereo, 5.991 monocular."""
+        ur = np.asarray(self.edge_ur, np.float32).reshape(-1)
+        return np.where(ur >= 0, 7.815, 5.991)
+
+
+@dataclass
 class BAResult:
     pose_q: np.ndarray
     pose_t: np.ndarray
@@ -67,9 +101,11 @@ class BAResult:
     iterations_done: int
     lm_trials: int
 
-    def outlier_edges(self, th: float = 5.991) -> np.ndarray:
-        """Edges LocalBundleAdjustment erases: chi2 > 5.991 || !isDepthPositive()."""
-        return np.nonzero((self.edge_chi2 > th) | (self.edge_depth_ok == 0))[0]
+    def outlier_edges(self, th=5.991) -> np.ndarray:
+        """Edges LocalBundleAdjustment erases: chi2 > th || !isDepthPositive(). th: one threshold
+        (5.991, monocular edges) or one per edge (StereoBAProblem.edge_thresholds(): 7.815 where
+        edge_ur >= 0)."""
+        return np.nonzero((self.edge_chi2 > np.asarray(th)) | (self.edge_depth_ok == 0))[0]
 
 
 @dataclass
@@ -151,6 +187,25 @@ class Optimizer:
         out.initial_chi2, out.final_chi2 = rc.initial_chi2, rc.final_chi2
         out.iterations_done, out.lm_trials = rc.iterations_done, rc.lm_trials
         return out
+
+    def solve_stereo(self, prob: StereoBAProblem, stop_flag: ctypes.c_int | None = None) -> BAResult:
+        """orbhip_ba_solve_stereo: one problem with EdgeStereoSE3ProjectXYZ edges where edge_ur >= 0."""
+        p = prob.normalized()
+        outs, cres = self._results_for([p])
+        pc = p.to_c()
+        sf = ctypes.addressof(stop_flag) if stop_flag is not None else None
+        check(lib().orbhip_ba_solve_stereo(self.ctx.handle, ctypes.byref(pc), cres, sf), "orbhip_ba_solve_stereo")
+        return self._fill(outs, cres)[0]
+
+    def solve_stereo_batch(self, probs, stop_flag: ctypes.c_int | None = None):
+        """orbhip_ba_solve_stereo_batch: B independent StereoBAProblems in one batched solve."""
+        ps = [p.normalized() for p in probs]
+        outs, cres = self._results_for(ps)
+        cprobs = (BAStereoProblemC * len(ps))(*[p.to_c() for p in ps])
+        sf = ctypes.addressof(stop_flag) if stop_flag is not None else None
+        check(lib().orbhip_ba_solve_stereo_batch(self.ctx.handle, cprobs, len(ps), cres, sf),
+              "orbhip_ba_solve_stereo_batch")
+        return self._fill(outs, cres)
 
     def prepare_single(self, prob: BAProblem) -> "BABatch":
         """The C-ABI view of one problem (orbhip_ba_problem / orbhip_ba_result over the problem's
@@ -252,13 +307,19 @@ class Optimizer:
         return dict(dag_launches=out[0], dag_handoffs=out[1], dag_timeouts=out[2], dag_reruns=out[3])
 
     def LocalBundleAdjustment(self, prob: BAProblem, stop_flag=None) -> BAResult:
+        """A BAProblem or a StereoBAProblem (thHuberMono sqrt(5.991), thHuberStereo sqrt(7.815))."""
+        if isinstance(prob, StereoBAProblem):
+            return self.solve_stereo(prob, stop_flag)
         return self.solve(prob, stop_flag)
 
     def BundleAdjustment(self, prob: BAProblem, nIterations: int = 20, bRobust: bool = True,
                          stop_flag=None) -> BAResult:
-        p = BAProblem(**{**prob.__dict__, "iterations": nIterations,
-                         "huber_delta": float(np.sqrt(5.99)) if bRobust else 0.0})
-        return self.solve(p, stop_flag)
+        """A BAProblem or a StereoBAProblem (thHuber2D sqrt(5.99), thHuber3D sqrt(7.815))."""
+        kw = {**prob.__dict__, "iterations": nIterations, "huber_delta": float(np.sqrt(5.99)) if bRobust else 0.0}
+        if isinstance(prob, StereoBAProblem):
+            kw["huber_delta_stereo"] = float(np.sqrt(7.815)) if bRobust else 0.0
+            return self.solve_stereo(StereoBAProblem(**kw), stop_flag)
+        return self.solve(BAProblem(**kw), stop_flag)
 
     # ---- motion-only BA (SURVEY.md §8f rank 2) ----
     def PoseOptimization(self, prob: PoseProblem) -> PoseResult:

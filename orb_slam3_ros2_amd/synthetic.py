@@ -1122,3 +1122,29 @@ def synthetic_stereo_projection_scene(n_kp=1000, n_mp=900, seed=5, motion="forwa
     tl = (tlc - quat_to_rot64(ql) @ twc).astype(np.float32)
     return dict(s, u_right=u_right, bf=bf, b=float(np.float32(b)), last_pose_q=ql, last_pose_t=tl,
                 direction=dict(forward=1, backward=-1, neutral=0)[motion])
+
+
+def synthetic_stereo_ba_problem(n_kf=50, n_pts=2000, stereo_frac=0.7, seed=7, ur_noise=1.0, b=0.05, **ba_args):
+    """synthetic_ba_problem(n_kf, n_pts, seed=seed, ...) seen by rectified-stereo keyframes: about
+    stereo_frac of the observations carry edge_ur = the ground-truth point's projection into the
+    right image (u - bf / z, bf = fx * b, a 50 mm baseline) + ur_noise * 1.2^octave px of noise, the
+    others -1 (monocular edges). A right coordinate that would be negative is dropped (-1). The
+    stereo draws come from a generator of their own, so the monocular problem's arrays are those of
+    synthetic_ba_problem for the same seed.
+    Returns (StereoBAProblem with perturbed initial state, ground-truth dict + `stereo`, the mask of
+    the stereo edges, and `ur`, every edge's right coordinate before the mask)."""
+    from .optimizer import StereoBAProblem, TH_HUBER_STEREO
+    prob, gt = synthetic_ba_problem(n_kf=n_kf, n_pts=n_pts, seed=seed, **ba_args)
+    rng = np.random.Generator(np.random.PCG64(104729 * (seed + 1) + 31))
+    E = prob.edge_pose.shape[0]
+    fx = float(np.float32(prob.fx))
+    bf = float(np.float32(fx * b))
+    Xc = np.einsum("eij,ej->ei", gt["R"][prob.edge_pose], gt["points"][prob.edge_point]) + gt["t"][prob.edge_pose]
+    z = Xc[:, 2]
+    sig = np.power(np.float64(ba_args.get("scale_factor", 1.2)), prob.edge_octave.astype(np.float64))
+    stereo = rng.random(E) < stereo_frac
+    ur = fx * Xc[:, 0] / z + float(np.float32(prob.cx)) - bf / z + rng.normal(size=E) * sig * ur_noise
+    stereo &= ur >= 0.0
+    sp = StereoBAProblem(**prob.__dict__, edge_ur=np.where(stereo, ur, -1.0).astype(np.float32), bf=bf,
+                         huber_delta_stereo=TH_HUBER_STEREO)
+    return sp, dict(gt, stereo=stereo, ur=ur)
