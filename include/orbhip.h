@@ -652,12 +652,53 @@ int orbhip_triangulate_matches(orbhip_ctx* ctx, const orbhip_tri_keyframe* kf1,
                                const float* scale_factors, const float* level_sigma2, int n_levels,
                                const orbhip_tri_params* params, orbhip_new_points* out);
 
+/* ---- new map points of a rectified-stereo system ---------------------------------------
+ * The stereo branches of SearchForTriangulation (bOnlyStereo = false, bCoarse = false) and of
+ * CreateNewMapPoints (DESIGN.md "Stereo LocalMapping"). A keyframe carries u_right = mvuRight and
+ * depth = mvDepth per feature and bf = mbf, b = mb; a feature is stereo when u_right >= 0 (0.0f
+ * counts). Differences from the monocular calls above, everything else being their rule:
+ *  - search: the epipole exclusion applies only when neither feature is stereo;
+ *  - neighbour b is gated when baseline < nbrs[b].b (there is no median_depth);
+ *  - per pair: with cosS the stereo parallax of the features (feature 1's when it is stereo, else
+ *    feature 2's) the point is triangulated when cosP < cosS && cosP > 0 && (a feature is stereo ||
+ *    cosP < cos_parallax_max); else unprojected from KF1 (feature 1 stereo and the better stereo
+ *    parallax) or from KF2; else status 2 / 3. Unprojecting a feature with depth <= 0 (or NaN):
+ *    status 12;
+ *  - the reprojection test of a stereo feature is (eX, eY, eR) against 7.8 * mvLevelSigma2
+ *    (status 7 / 8), eR = (u - bf / z) - u_right.
+ * source (B x n1, optional): 0 no point, 1 triangulated, 2 / 3 unprojected from KF1 / KF2.
+ * Envelopes and errors of the monocular calls; also ORBHIP_ERR_ARG, before anything is uploaded or
+ * launched, when u_right or depth is NULL with n > 0, or bf <= 0 or b <= 0, in any keyframe. With
+ * every u_right < 0 and b below every baseline they compute what the monocular calls compute
+ * without median_depth. */
+typedef struct {
+    orbhip_tri_keyframe kf;
+    const float* u_right;      /* kf.n: mvuRight */
+    const float* depth;        /* kf.n: mvDepth */
+    float bf, b;               /* mbf, mb */
+} orbhip_tri_stereo_keyframe;
+int orbhip_search_for_triangulation_stereo(orbhip_ctx* ctx, const orbhip_tri_stereo_keyframe* kf1,
+                                           const orbhip_tri_stereo_keyframe* nbrs, int B,
+                                           const float* scale_factors, const float* level_sigma2, int n_levels,
+                                           int check_orientation, int32_t* match12, int32_t* nmatches);
+int orbhip_create_new_map_points_stereo(orbhip_ctx* ctx, const orbhip_tri_stereo_keyframe* kf1,
+                                        const orbhip_tri_stereo_keyframe* nbrs, int B,
+                                        const float* scale_factors, const float* level_sigma2, int n_levels,
+                                        int check_orientation, const orbhip_tri_params* params,
+                                        orbhip_new_points* out, uint8_t* source /* B x n1 or NULL */);
+int orbhip_triangulate_matches_stereo(orbhip_ctx* ctx, const orbhip_tri_stereo_keyframe* kf1,
+                                      const orbhip_tri_stereo_keyframe* nbrs, int B, const int32_t* match12_in,
+                                      const float* scale_factors, const float* level_sigma2, int n_levels,
+                                      const orbhip_tri_params* params, orbhip_new_points* out,
+                                      uint8_t* source /* B x n1 or NULL */);
+
 /* ---- map point fusion: Fuse ------------------------------------------
  * U:src/ORBmatcher.cc::Fuse(KeyFrame* pKF, const vector<MapPoint*>& vpMapPoints, const float th,
  * bRight = false), as U:src/LocalMapping.cc::SearchInNeighbors calls it: monocular, one pinhole
- * camera, mvKeysUn, no stereo coordinate. B keyframes are searched for the same list of MapPoints in
- * one call. Per (keyframe b, MapPoint m) not skipped: the point is projected with Tcw (quaternion
- * form), must lie in front of the camera, inside the image (IsInImage: the maximum is strict),
+ * camera, mvKeysUn, no stereo coordinate (orbhip_fuse_stereo below is the stereo branch). B
+ * keyframes are searched for the same list of MapPoints in one call. Per (keyframe b, MapPoint m)
+ * not skipped: the point is projected with Tcw (quaternion form), must lie in front of the
+ * camera, inside the image (IsInImage: the maximum is strict),
  * within [0.8 mfMinDistance, 1.2 mfMaxDistance] of the camera centre and within 60 degrees of its
  * normal; PredictScale gives the level, th * mvScaleFactors[level] the window of
  * KeyFrame::GetFeaturesInArea; a candidate keypoint needs octave in [level - 1, level] and a squared
@@ -683,6 +724,22 @@ int orbhip_fuse(orbhip_ctx* ctx, const orbhip_frame* kfs, int B, const orbhip_lo
                 const float* inv_level_sigma2 /* n_levels */, float th,
                 int32_t* best_idx /* B x n */, int32_t* best_dist /* B x n or NULL */,
                 int32_t* level /* B x n or NULL */, int32_t* nfused /* B */);
+
+/* Fuse on rectified-stereo keyframes (the stereo branch of the same upstream function, bRight =
+ * false): kfs[b] = the keyframe as orbhip_fuse takes it plus u_right = mvuRight, bf = mbf, b = mb.
+ * Everything is the rule of orbhip_fuse except the chi-square gate of a candidate keypoint k with
+ * u_right[k] >= 0 (0.0f counts): with invz = 1.0f / Pc.z and er = (u - bf * invz) - u_right[k] the
+ * candidate needs ((ex^2 + ey^2) + er^2) * inv_level_sigma2[octave] <= 7.8. A candidate with
+ * u_right[k] < 0 (or NaN) takes the two-term test at 5.99; the window has no right-coordinate gate
+ * (DESIGN.md "Stereo LocalMapping"). Arguments, outputs, envelope and errors of orbhip_fuse; also
+ * ORBHIP_ERR_ARG, before anything is uploaded or launched, when u_right is NULL with n > 0 or bf <= 0
+ * or b <= 0 in any keyframe. With every u_right < 0 it computes what orbhip_fuse computes. Fuse with a
+ * Sim3 has no chi-square gate and therefore no stereo form. */
+int orbhip_fuse_stereo(orbhip_ctx* ctx, const orbhip_stereo_view* kfs, int B, const orbhip_local_points* mps,
+                       const uint8_t* pair_skip /* B x mps->n or NULL */,
+                       const float* inv_level_sigma2 /* n_levels */, float th,
+                       int32_t* best_idx /* B x n */, int32_t* best_dist /* B x n or NULL */,
+                       int32_t* level /* B x n or NULL */, int32_t* nfused /* B */);
 
 /* ---- LoopClosing: Fuse and SearchByProjection with a Sim3 ------------------------------
  * U:src/ORBmatcher.cc::Fuse(KeyFrame* pKF, Sophus::Sim3f& Scw, const vector<MapPoint*>& vpPoints,

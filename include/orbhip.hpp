@@ -327,6 +327,77 @@ public:
         return buf.list(n);
     }
 
+    // The three calls above for a rectified-stereo system (orbhip_tri_stereo_keyframe: the keyframe,
+    // mvuRight, mvDepth, mbf, mb): no epipole exclusion for a pair with a stereo
+    // feature, a neighbour gated when the baseline is below its mb (there is no vMedianDepth), the
+    // stereo parallax with UnprojectStereo and the three-term reprojection test. vSource (optional,
+    // B x n1 flat) receives upstream's bPointStereo per pair: 0 none, 1 triangulated, 2 / 3
+    // unprojected from pKF1 / the neighbour.
+    std::vector<int> SearchForTriangulation(orbhip_ctx* ctx, const orbhip_tri_stereo_keyframe& kf1,
+                                            const std::vector<orbhip_tri_stereo_keyframe>& neighbours,
+                                            const std::vector<float>& mvScaleFactors,
+                                            const std::vector<float>& mvLevelSigma2,
+                                            std::vector<std::vector<int>>& vMatches12) const {
+        const int B = (int)neighbours.size(), n1 = kf1.kf.n;
+        std::vector<int32_t> flat((size_t)B * (size_t)std::max(n1, 0), -1), nm(B, 0);
+        const int rc = orbhip_search_for_triangulation_stereo(ctx, &kf1, neighbours.data(), B, mvScaleFactors.data(),
+                                                              mvLevelSigma2.data(),
+                                                              (int)std::min(mvScaleFactors.size(), mvLevelSigma2.size()),
+                                                              mbCheckOrientation ? 1 : 0, flat.data(), nm.data());
+        check(rc, "orbhip_search_for_triangulation_stereo");
+        vMatches12.assign(B, std::vector<int>());
+        for (int b = 0; b < B; b++) vMatches12[b].assign(flat.begin() + (size_t)b * n1, flat.begin() + (size_t)(b + 1) * n1);
+        return std::vector<int>(nm.begin(), nm.end());
+    }
+
+    std::vector<NewMapPoint> CreateNewMapPoints(orbhip_ctx* ctx, const orbhip_tri_stereo_keyframe& kf1,
+                                                const std::vector<orbhip_tri_stereo_keyframe>& neighbours,
+                                                const std::vector<float>& mvScaleFactors,
+                                                const std::vector<float>& mvLevelSigma2, float ratioFactor,
+                                                double cosParallaxMax = 0.9998, float thFarPoints = 0.f,
+                                                std::vector<uint8_t>* vbGated = nullptr,
+                                                std::vector<uint8_t>* vSource = nullptr) const {
+        const int B = (int)neighbours.size();
+        NewPointsBuffers buf(B, kf1.kf.n);
+        if (vSource) vSource->assign((size_t)B * (size_t)std::max(kf1.kf.n, 0) + 1, 0);
+        const orbhip_tri_params prm{cosParallaxMax, ratioFactor, thFarPoints};
+        const int n = orbhip_create_new_map_points_stereo(ctx, &kf1, neighbours.data(), B, mvScaleFactors.data(),
+                                                          mvLevelSigma2.data(),
+                                                          (int)std::min(mvScaleFactors.size(), mvLevelSigma2.size()),
+                                                          mbCheckOrientation ? 1 : 0, &prm, &buf.out,
+                                                          vSource ? vSource->data() : nullptr);
+        check(n, "orbhip_create_new_map_points_stereo");
+        if (vbGated) vbGated->assign(buf.gated.begin(), buf.gated.begin() + B);
+        if (vSource) vSource->pop_back();
+        return buf.list(n);
+    }
+
+    std::vector<NewMapPoint> TriangulateMatches(orbhip_ctx* ctx, const orbhip_tri_stereo_keyframe& kf1,
+                                                const std::vector<orbhip_tri_stereo_keyframe>& neighbours,
+                                                const std::vector<std::vector<int>>& vMatches12,
+                                                const std::vector<float>& mvScaleFactors,
+                                                const std::vector<float>& mvLevelSigma2, float ratioFactor,
+                                                double cosParallaxMax = 0.9998, float thFarPoints = 0.f,
+                                                std::vector<uint8_t>* vSource = nullptr) const {
+        const int B = (int)neighbours.size(), n1 = std::max(kf1.kf.n, 0);
+        if ((int)vMatches12.size() != B) check(ORBHIP_ERR_ARG, "TriangulateMatches");
+        std::vector<int32_t> flat((size_t)B * n1 + 1, -1);
+        for (int b = 0; b < B; b++) {
+            if ((int)vMatches12[b].size() != n1) check(ORBHIP_ERR_ARG, "TriangulateMatches");
+            std::copy(vMatches12[b].begin(), vMatches12[b].end(), flat.begin() + (size_t)b * n1);
+        }
+        NewPointsBuffers buf(B, kf1.kf.n);
+        if (vSource) vSource->assign((size_t)B * n1 + 1, 0);
+        const orbhip_tri_params prm{cosParallaxMax, ratioFactor, thFarPoints};
+        const int n = orbhip_triangulate_matches_stereo(ctx, &kf1, neighbours.data(), B, flat.data(),
+                                                        mvScaleFactors.data(), mvLevelSigma2.data(),
+                                                        (int)std::min(mvScaleFactors.size(), mvLevelSigma2.size()), &prm,
+                                                        &buf.out, vSource ? vSource->data() : nullptr);
+        check(n, "orbhip_triangulate_matches_stereo");
+        if (vSource) vSource->pop_back();
+        return buf.list(n);
+    }
+
     // U:src/ORBmatcher.cc::Fuse(pKF, vpMapPoints, th) of every keyframe against the same MapPoints in
     // one call (LocalMapping::SearchInNeighbors). vbPairSkip: empty, or B x n with
     // pMP->IsInKeyFrame(keyframe b). vBestIdx[b][m] = the keypoint of keyframe b MapPoint m fuses into,
@@ -338,17 +409,45 @@ public:
                           const std::vector<float>& mvInvLevelSigma2, float th,
                           std::vector<std::vector<int>>& vBestIdx, std::vector<std::vector<int>>* vBestDist = nullptr,
                           std::vector<std::vector<int>>* vLevel = nullptr) const {
-        const int B = (int)keyframes.size();
-        const size_t n = (size_t)std::max(vpMapPoints.n, 0);
-        if (!vbPairSkip.empty() && vbPairSkip.size() != (size_t)B * n) throw Error(ORBHIP_ERR_ARG, "Fuse: vbPairSkip");
         for (const orbhip_frame& f : keyframes)
             if ((size_t)std::max(f.n_levels, 0) > mvInvLevelSigma2.size()) throw Error(ORBHIP_ERR_ARG, "Fuse: mvInvLevelSigma2");
+        return fuseRows((int)keyframes.size(), vpMapPoints, vbPairSkip, vBestIdx, vBestDist, vLevel, "orbhip_fuse",
+                        [&](const uint8_t* skip, int32_t* idx, int32_t* dist, int32_t* lvl, int32_t* nf) {
+                            return orbhip_fuse(ctx, keyframes.data(), (int)keyframes.size(), &vpMapPoints, skip,
+                                               mvInvLevelSigma2.data(), th, idx, dist, lvl, nf);
+                        });
+    }
+
+    // Fuse on rectified-stereo keyframes (orbhip_stereo_view: the keyframe, mvuRight, mbf, mb): a
+    // candidate keypoint with mvuRight >= 0 is gated on (ex, ey, er) at 7.8, the others as above
+    // (orbhip_fuse_stereo). Arguments and results as the monocular overload.
+    std::vector<int> Fuse(orbhip_ctx* ctx, const std::vector<orbhip_stereo_view>& keyframes,
+                          const orbhip_local_points& vpMapPoints, const std::vector<uint8_t>& vbPairSkip,
+                          const std::vector<float>& mvInvLevelSigma2, float th,
+                          std::vector<std::vector<int>>& vBestIdx, std::vector<std::vector<int>>* vBestDist = nullptr,
+                          std::vector<std::vector<int>>* vLevel = nullptr) const {
+        for (const orbhip_stereo_view& f : keyframes)
+            if ((size_t)std::max(f.frame.n_levels, 0) > mvInvLevelSigma2.size())
+                throw Error(ORBHIP_ERR_ARG, "Fuse: mvInvLevelSigma2");
+        return fuseRows((int)keyframes.size(), vpMapPoints, vbPairSkip, vBestIdx, vBestDist, vLevel, "orbhip_fuse_stereo",
+                        [&](const uint8_t* skip, int32_t* idx, int32_t* dist, int32_t* lvl, int32_t* nf) {
+                            return orbhip_fuse_stereo(ctx, keyframes.data(), (int)keyframes.size(), &vpMapPoints, skip,
+                                                      mvInvLevelSigma2.data(), th, idx, dist, lvl, nf);
+                        });
+    }
+
+    // What the Fuse overloads share: the pair-skip check, the flat outputs, the call (call(pair_skip,
+    // best_idx, best_dist, level, nfused) returns the entry point's status) and the rows per keyframe.
+    template <class Call>
+    static std::vector<int> fuseRows(int B, const orbhip_local_points& vpMapPoints, const std::vector<uint8_t>& vbPairSkip,
+                                     std::vector<std::vector<int>>& vBestIdx, std::vector<std::vector<int>>* vBestDist,
+                                     std::vector<std::vector<int>>* vLevel, const char* what, Call call) {
+        const size_t n = (size_t)std::max(vpMapPoints.n, 0);
+        if (!vbPairSkip.empty() && vbPairSkip.size() != (size_t)B * n) throw Error(ORBHIP_ERR_ARG, "Fuse: vbPairSkip");
         std::vector<int32_t> idx((size_t)B * n, -1), dist(vBestDist ? (size_t)B * n : 0), lvl(vLevel ? (size_t)B * n : 0);
         std::vector<int32_t> nf(B, 0);
-        const int rc = orbhip_fuse(ctx, keyframes.data(), B, &vpMapPoints, vbPairSkip.empty() ? nullptr : vbPairSkip.data(),
-                                   mvInvLevelSigma2.data(), th, idx.data(), vBestDist ? dist.data() : nullptr,
-                                   vLevel ? lvl.data() : nullptr, nf.data());
-        check(rc, "orbhip_fuse");
+        check(call(vbPairSkip.empty() ? nullptr : vbPairSkip.data(), idx.data(), vBestDist ? dist.data() : nullptr,
+                   vLevel ? lvl.data() : nullptr, nf.data()), what);
         auto rows = [&](const std::vector<int32_t>& flat, std::vector<std::vector<int>>& out) {
             out.assign(B, std::vector<int>());
             for (int b = 0; b < B; b++) out[b].assign(flat.begin() + (size_t)b * n, flat.begin() + (size_t)(b + 1) * n);

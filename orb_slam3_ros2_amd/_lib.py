@@ -116,6 +116,11 @@ class TriKeyFrameC(ctypes.Structure):
                 ("pose_q", ctypes.c_float * 4), ("pose_t", ctypes.c_float * 3)]
 
 
+class TriStereoKeyFrameC(ctypes.Structure):
+    _fields_ = [("kf", TriKeyFrameC), ("u_right", ctypes.c_void_p), ("depth", ctypes.c_void_p),
+                ("bf", ctypes.c_float), ("b", ctypes.c_float)]
+
+
 class TriParamsC(ctypes.Structure):
     _fields_ = [("cos_parallax_max", ctypes.c_double), ("ratio_factor", ctypes.c_float),
                 ("far_threshold", ctypes.c_float)]
@@ -156,7 +161,9 @@ EXPORTED = ["orbhip_abi_version", "orbhip_create", "orbhip_destroy", "orbhip_lev
             "orbhip_pose_optimization_stereo", "orbhip_pose_optimization_stereo_batch",
             "orbhip_search_by_projection_last_stereo", "orbhip_search_local_points_stereo",
             "orbhip_triangulation_geometry", "orbhip_search_for_triangulation",
-            "orbhip_create_new_map_points", "orbhip_triangulate_matches", "orbhip_fuse",
+            "orbhip_create_new_map_points", "orbhip_triangulate_matches", "orbhip_fuse", "orbhip_fuse_stereo",
+            "orbhip_search_for_triangulation_stereo", "orbhip_create_new_map_points_stereo",
+            "orbhip_triangulate_matches_stereo",
             "orbhip_fuse_sim3", "orbhip_search_by_projection_sim3",
             "orbhip_kfdb_create", "orbhip_kfdb_destroy", "orbhip_kfdb_add", "orbhip_kfdb_erase",
             "orbhip_kfdb_detect_relocalization", "orbhip_kfdb_detect_nbest",
@@ -248,8 +255,16 @@ def lib():
                                                ctypes.POINTER(NewPointsC)]
     L.orbhip_triangulate_matches.argtypes = [vp, ctypes.POINTER(TriKeyFrameC), ctypes.POINTER(TriKeyFrameC), i32, vp,
                                              vp, vp, i32, ctypes.POINTER(TriParamsC), ctypes.POINTER(NewPointsC)]
+    tsk = ctypes.POINTER(TriStereoKeyFrameC)
+    L.orbhip_search_for_triangulation_stereo.argtypes = [vp, tsk, tsk, i32, vp, vp, i32, i32, vp, vp]
+    L.orbhip_create_new_map_points_stereo.argtypes = [vp, tsk, tsk, i32, vp, vp, i32, i32, ctypes.POINTER(TriParamsC),
+                                                      ctypes.POINTER(NewPointsC), vp]
+    L.orbhip_triangulate_matches_stereo.argtypes = [vp, tsk, tsk, i32, vp, vp, vp, i32, ctypes.POINTER(TriParamsC),
+                                                    ctypes.POINTER(NewPointsC), vp]
     L.orbhip_fuse.argtypes = [vp, ctypes.POINTER(FrameC), i32, ctypes.POINTER(LocalPointsC), vp, vp, f32, vp, vp, vp,
                               vp]
+    L.orbhip_fuse_stereo.argtypes = [vp, ctypes.POINTER(StereoViewC), i32, ctypes.POINTER(LocalPointsC), vp, vp, f32, vp,
+                                     vp, vp, vp]
     L.orbhip_fuse_sim3.argtypes = [vp, ctypes.POINTER(FrameC), i32, ctypes.POINTER(LocalPointsC), vp, f32, vp, vp, vp, vp]
     L.orbhip_search_by_projection_sim3.argtypes = [vp, ctypes.POINTER(FrameC), ctypes.POINTER(LocalPointsC), f32, f32,
                                                    vp, vp, vp]

@@ -18,6 +18,10 @@
 //                     one global atomic per work-group.
 //                     k_fuse_search<S, false> is the rule of Fuse with a Sim3 (LoopClosing::SearchAndFuse):
 //                     the same walk without the chi-square gate.
+//                     The stereo forms (k_fuse_grid<true>, k_fuse_search<S, true, true>; DESIGN.md "Stereo
+//                     LocalMapping"): the grid also scatters mvuRight into a cell-ordered float array beside
+//                     the records, and a candidate with ur >= 0 that passed the window and level gates takes
+//                     the three-term chi-square at 7.8 against the point's right projection u - bf / z.
 // and LoopClosing's SearchByProjection with a Sim3, one keyframe, upstream's sequential greedy pass
 // (DESIGN.md "Sim3 functions of LoopClosing"):
 //   k_sim3_search     the walk again, four lanes per point, also testing `claimed` and the distance
@@ -40,7 +44,6 @@
 
 namespace orbhip {
 
-constexpr int kFuseMaxKf = 64;         // keyframes per call
 constexpr int kFuseMaxPoints = 65536;  // MapPoints per call
 constexpr int kFuseMaxLevels = 256;    // the octave shares a word with the cell
 struct FuseKf {                        // one keyframe of the call
@@ -88,11 +91,15 @@ struct FuseGridLds {
     int scan[kFuseGridThreads / 64 + 1];
 };
 
+// STEREO: ur (mvuRight, in keypoint order like kps) goes to ur_cell in the order of recs
+template <bool STEREO>
 __global__ __launch_bounds__(kFuseGridThreads) void k_fuse_grid(const FuseKf* __restrict__ kfs,
                                                                 const orbhip_kp* __restrict__ kps,
                                                                 int32_t* __restrict__ cell_start,
                                                                 FuseRec* __restrict__ recs,
-                                                                int32_t* __restrict__ nfused) {
+                                                                int32_t* __restrict__ nfused,
+                                                                const float* __restrict__ ur,
+                                                                float* __restrict__ ur_cell) {
     __shared__ FuseGridLds L;
     const int tid = threadIdx.x, b = blockIdx.x;
     const FuseKf f = kfs[b];
@@ -126,7 +133,11 @@ __global__ __launch_bounds__(kFuseGridThreads) void k_fuse_grid(const FuseKf* __
     for (int i = tid; i < f.n; i += kFuseGridThreads) {
         const orbhip_kp k = kp[i];
         const int c = grid_cell(f.minx, f.miny, f.invw, f.invh, k.x, k.y);
-        if (c >= 0) out[atomicAdd(&L.cursor[c], 1)] = FuseRec{k.x, k.y, (c << 8) | k.octave, i};
+        if (c >= 0) {
+            const int slot = atomicAdd(&L.cursor[c], 1);
+            out[slot] = FuseRec{k.x, k.y, (c << 8) | k.octave, i};
+            if (STEREO) ur_cell[f.base + slot] = ur[f.base + i];
+        }
     }
 }
 
@@ -138,7 +149,8 @@ constexpr int kFuseSplit = 4;
 
 // Steps 1-8 of the rule for one (keyframe, point) that is not skipped: false at a gate. lvl is set
 // from step 6 on (-1 before it), so a pair rejected by GetFeaturesInArea's early returns keeps it.
-struct FuseWin { float u, v, r; int lvl, x0, x1, y0, y1; };
+// z = Pc.z, read by the stereo form only (set from step 2 on).
+struct FuseWin { float u, v, r; int lvl, x0, x1, y0, y1; float z; };
 __device__ __forceinline__ bool fuse_gates(const FuseKf& f, const DevPoints& mp, int m,
                                            const float* __restrict__ scale_factors, int n_levels, float log_sf,
                                            float th, FuseWin& w) {
@@ -151,6 +163,7 @@ __device__ __forceinline__ bool fuse_gates(const FuseKf& f, const DevPoints& mp,
     if (Pc[2] < 0.0f) return false;
     // 2., 3. Pinhole::project, KeyFrame::IsInImage (the maximum is strict)
     const float u = (f.fx * Pc[0]) / Pc[2] + f.cx, v = (f.fy * Pc[1]) / Pc[2] + f.cy;
+    w.z = Pc[2];
     if (!(u >= f.minx && u < f.maxx && v >= f.miny && v < f.maxy)) return false;
     // 4. distance range
     const float PO[3] = {P[0] - f.Ow[0], P[1] - f.Ow[1], P[2] - f.Ow[2]};
@@ -190,7 +203,9 @@ __device__ __forceinline__ unsigned long long fuse_key(unsigned dist, const Fuse
 // S neighbouring lanes share a point: each computes the gates of steps 1-7 (the same values, so the
 // same exits), they take the candidates of a column span in turns and merge their minima.
 // CHI2 = false: the rule of Fuse with a Sim3, which has no chi-square gate (inv_level_sigma2 unread)
-template <int S, bool CHI2>
+// STEREO (with CHI2): ur_cell = mvuRight in the order of recs, kf_bf[b] = mbf; a candidate with
+// ur >= 0 takes (ex^2 + ey^2) + er^2 against 7.8, er = (u - bf * (1 / Pc.z)) - ur; the others 5.99
+template <int S, bool CHI2, bool STEREO = false>
 __global__ __launch_bounds__(kFuseThreads) void k_fuse_search(const FuseKf* __restrict__ kfs, DevPoints mp,
                                                               const uint8_t* __restrict__ pair_skip,
                                                               const float* __restrict__ scale_factors,
@@ -202,8 +217,11 @@ __global__ __launch_bounds__(kFuseThreads) void k_fuse_search(const FuseKf* __re
                                                               int32_t* __restrict__ best_idx,
                                                               int32_t* __restrict__ best_dist,
                                                               int32_t* __restrict__ level,
-                                                              int32_t* __restrict__ nfused) {
+                                                              int32_t* __restrict__ nfused,
+                                                              const float* __restrict__ ur_cell,
+                                                              const float* __restrict__ kf_bf) {
     static_assert(S >= 1 && S <= 64 && (S & (S - 1)) == 0, "the lanes of a point lie in one wave");
+    static_assert(CHI2 || !STEREO, "the stereo form is a form of the chi-square gate");
     __shared__ int s_count;
     const int b = blockIdx.y, m = (blockIdx.x * kFuseThreads + threadIdx.x) / S, sub = threadIdx.x % S;
     if (threadIdx.x == 0) s_count = 0;
@@ -226,6 +244,13 @@ __global__ __launch_bounds__(kFuseThreads) void k_fuse_search(const FuseKf* __re
         const int32_t* cs = cell_start + (int64_t)b * (kGridCells + 1);
         const FuseRec* rc = recs + f.base;
         const uint8_t* kd = kf_desc + (int64_t)f.base * 32;
+        float urp = 0.0f;          // the point's projection into the right image
+        const float* urc = nullptr;
+        if (STEREO) {
+            const float invz = 1.0f / w.z;
+            urp = u - kf_bf[b] * invz;
+            urc = ur_cell + f.base;
+        }
         for (int ix = w.x0; ix <= w.x1; ix++) {
             // the cells (ix, y0..y1) are neighbours in the cell-ordered array: one span per column
             const int j0 = cs[ix * kGridRows + w.y0], j1 = cs[ix * kGridRows + w.y1 + 1];
@@ -239,7 +264,12 @@ __global__ __launch_bounds__(kFuseThreads) void k_fuse_search(const FuseKf* __re
                 if (CHI2) {
                     const float ex = u - k.x, ey = v - k.y;
                     const float e2 = ex * ex + ey * ey;
-                    if ((double)(e2 * inv_level_sigma2[octave]) > 5.99) continue;
+                    const float kur = STEREO ? urc[j] : -1.0f;
+                    if (STEREO && kur >= 0.0f) {
+                        const float er = urp - kur;
+                        const float e3 = e2 + er * er;
+                        if ((double)(e3 * inv_level_sigma2[octave]) > 7.8) continue;
+                    } else if ((double)(e2 * inv_level_sigma2[octave]) > 5.99) continue;
                 }
                 const unsigned long long key = fuse_key(fuse_hamming(da, db, kd + (int64_t)k.idx * 32), k);
                 best = key < best ? key : best;
@@ -309,7 +339,7 @@ __global__ __launch_bounds__(kFuseThreads) void k_sim3_search(const FuseKf* __re
     for (int i = 0; i < K; i++) a[i] = kSim3None;
     int cnt = 0;
     FuseWin w;
-    w.lvl = -1; w.u = w.v = w.r = 0.0f; w.x0 = w.x1 = w.y0 = w.y1 = 0;
+    w.lvl = -1; w.u = w.v = w.r = w.z = 0.0f; w.x0 = w.x1 = w.y0 = w.y1 = 0;
     bool in = false;
     if (m < mp.n && !mp.skip[m]) in = fuse_gates(f, mp, m, scale_factors, n_levels, log_sf, th, w);
     if (in) {
@@ -478,7 +508,8 @@ static void launch_sim3_search(const FuseKf* kf, const DevPoints& mp, const uint
                                const orbhip_kp* kps, const uint8_t* kf_desc, int nk, int32_t* cell_start,
                                FuseRec* recs, const Sim3Work& w, int32_t* match, int32_t* match_dist, int32_t* level,
                                int32_t* nmatches, hipStream_t st) {
-    ORBHIP_LAUNCH(k_fuse_grid, dim3(1), dim3(kFuseGridThreads), 0, st, kf, kps, cell_start, recs, nmatches);
+    ORBHIP_LAUNCH(k_fuse_grid<false>, dim3(1), dim3(kFuseGridThreads), 0, st, kf, kps, cell_start, recs, nmatches,
+                  (const float*)nullptr, (float*)nullptr);
     const unsigned tiles = (unsigned)(((int64_t)mp.n * kFuseSplit + kFuseThreads - 1) / kFuseThreads);
     ORBHIP_LAUNCH(k_sim3_search<kFuseSplit>, dim3(tiles), dim3(kFuseThreads), 0, st, kf, mp, claimed, scale_factors,
                   n_levels, log_sf, th, thr, (const int32_t*)cell_start, (const FuseRec*)recs, kf_desc, w, level);
@@ -489,20 +520,33 @@ static void launch_sim3_search(const FuseKf* kf, const DevPoints& mp, const uint
 // cell_start: B x 3073, recs: one per keypoint of the call (both written by k_fuse_grid);
 // best_idx / best_dist / level: B x n, nfused: B (zeroed by k_fuse_grid).
 // inv_level_sigma2 == nullptr: the rule without the chi-square gate (Fuse with a Sim3)
+// ur != nullptr: the stereo form (inv_level_sigma2 is then required)
 static void launch_fuse(const FuseKf* kfs, int B, const DevPoints& mp, const uint8_t* pair_skip,
                         const float* scale_factors, const float* inv_level_sigma2, int n_levels, float log_sf,
                         float th, const orbhip_kp* kps, const uint8_t* kf_desc, int32_t* cell_start, FuseRec* recs,
-                        int32_t* best_idx, int32_t* best_dist, int32_t* level, int32_t* nfused, hipStream_t st) {
-    ORBHIP_LAUNCH(k_fuse_grid, dim3((unsigned)B), dim3(kFuseGridThreads), 0, st, kfs, kps, cell_start, recs, nfused);
+                        int32_t* best_idx, int32_t* best_dist, int32_t* level, int32_t* nfused, hipStream_t st,
+                        const float* ur = nullptr, float* ur_cell = nullptr, const float* kf_bf = nullptr) {
     const unsigned tiles = (unsigned)(((int64_t)mp.n * kFuseSplit + kFuseThreads - 1) / kFuseThreads);
+    if (ur) {   // the stereo form: ur / ur_cell one per keypoint of the call, kf_bf B
+        ORBHIP_LAUNCH(k_fuse_grid<true>, dim3((unsigned)B), dim3(kFuseGridThreads), 0, st, kfs, kps, cell_start, recs,
+                      nfused, ur, ur_cell);
+        ORBHIP_LAUNCH((k_fuse_search<kFuseSplit, true, true>), dim3(tiles, (unsigned)B), dim3(kFuseThreads), 0, st, kfs,
+                      mp, pair_skip, scale_factors, inv_level_sigma2, n_levels, log_sf, th, (const int32_t*)cell_start,
+                      (const FuseRec*)recs, kf_desc, best_idx, best_dist, level, nfused, (const float*)ur_cell, kf_bf);
+        return;
+    }
+    ORBHIP_LAUNCH(k_fuse_grid<false>, dim3((unsigned)B), dim3(kFuseGridThreads), 0, st, kfs, kps, cell_start, recs,
+                  nfused, (const float*)nullptr, (float*)nullptr);
     if (inv_level_sigma2)
         ORBHIP_LAUNCH((k_fuse_search<kFuseSplit, true>), dim3(tiles, (unsigned)B), dim3(kFuseThreads), 0, st, kfs, mp,
                       pair_skip, scale_factors, inv_level_sigma2, n_levels, log_sf, th, (const int32_t*)cell_start,
-                      (const FuseRec*)recs, kf_desc, best_idx, best_dist, level, nfused);
+                      (const FuseRec*)recs, kf_desc, best_idx, best_dist, level, nfused, (const float*)nullptr,
+                      (const float*)nullptr);
     else
         ORBHIP_LAUNCH((k_fuse_search<kFuseSplit, false>), dim3(tiles, (unsigned)B), dim3(kFuseThreads), 0, st, kfs, mp,
                       pair_skip, scale_factors, inv_level_sigma2, n_levels, log_sf, th, (const int32_t*)cell_start,
-                      (const FuseRec*)recs, kf_desc, best_idx, best_dist, level, nfused);
+                      (const FuseRec*)recs, kf_desc, best_idx, best_dist, level, nfused, (const float*)nullptr,
+                      (const float*)nullptr);
 }
 
 // The envelope and argument checks Fuse and the Sim3 searches share: the keyframes of a call have one
@@ -529,13 +573,15 @@ static int fuse_check_keyframes(const orbhip_frame* kfs, int B, size_t* nk_total
 
 int fuse_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_frame* kfs, int B,
                 const orbhip_local_points* mps, const uint8_t* pair_skip, bool chi2, const float* inv_level_sigma2,
-                float th, int32_t* best_idx, int32_t* best_dist, int32_t* level, int32_t* nfused) {
+                float th, int32_t* best_idx, int32_t* best_dist, int32_t* level, int32_t* nfused,
+                const FuseStereo* sx) {
     if (B < 0 || !mps || mps->n < 0) return ORBHIP_ERR_ARG;
     if (B == 0) return 0;
     if (B > kFuseMaxKf || mps->n > kFuseMaxPoints) return ORBHIP_ERR_UNSUPPORTED;
     if (!kfs || !nfused) return ORBHIP_ERR_ARG;
     const int n = mps->n, L = kfs[0].n_levels;
     if (chi2 && !inv_level_sigma2) return ORBHIP_ERR_ARG;
+    if (sx && (!chi2 || !sx->u_right || !sx->bf)) return ORBHIP_ERR_ARG;   // (per keyframe: the caller's checks)
     size_t nk_total = 0;
     if (const int rc = fuse_check_keyframes(kfs, B, &nk_total)) return rc;
     for (int b = 0; b < B; b++) nfused[b] = 0;
@@ -544,8 +590,9 @@ int fuse_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_f
         return ORBHIP_ERR_ARG;
     // one block, the same layout on the host (pinned) and the device:
     // [keyframes B | scale factors | inv sigma2 | points normals min max desc skip | pair_skip B x n |
-    //  keypoints | keyframe descriptors], then device only [cell_start B x 3073 | records |
-    //  nfused B, best_idx B x n, best_dist B x n, level B x n]; the last segment is read back
+    //  keypoints | keyframe descriptors | stereo: mvuRight, mbf B], then device only [cell_start B x 3073 |
+    //  records | stereo: mvuRight in cell order | nfused B, best_idx B x n, best_dist B x n, level B x n];
+    //  the last segment is read back
     StageLayout lay(16);
     const size_t bn = (size_t)B * (size_t)n;
     const size_t o_kf = lay.take((size_t)B * sizeof(FuseKf));
@@ -553,8 +600,10 @@ int fuse_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_f
     const PointsLayout o_mp(lay, (size_t)n);
     const size_t o_pskip = lay.take(pair_skip ? bn : 0);
     const size_t o_kps = lay.take(nk_total * sizeof(orbhip_kp)), o_kdesc = lay.take(nk_total * 32);
+    const size_t o_ur = lay.take(sx ? nk_total * 4 : 0), o_bf = lay.take(sx ? (size_t)B * 4 : 0);
     const size_t up_bytes = lay.total();
     const size_t o_cs = lay.take((size_t)B * (kGridCells + 1) * 4), o_rec = lay.take(nk_total * sizeof(FuseRec));
+    const size_t o_urc = lay.take(sx ? nk_total * 4 : 0);
     const size_t nf_bytes = ((size_t)B * 4 + 15) & ~size_t(15);   // best_idx starts 16-byte aligned behind nfused
     const size_t n_out = level ? 3 : (best_dist ? 2 : 1);         // arrays read back: a prefix of idx, dist, level
     const size_t back_bytes = nf_bytes + n_out * bn * 4;
@@ -568,8 +617,10 @@ int fuse_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_f
         const orbhip_frame& f = kfs[b];
         fuse_kf_params(f, (int)base, &hk[b]);
         put_keyframe(S, o_kps, o_kdesc, base, f.kps, f.desc, (size_t)f.n);
+        if (sx && f.n > 0) S.put(o_ur + base * 4, sx->u_right[b], (size_t)f.n * 4);
         base += (size_t)f.n;
     }
+    if (sx) S.put(o_bf, sx->bf, (size_t)B * 4);
     S.put(o_sf, kfs[0].scale_factors, (size_t)L * 4);
     if (chi2) S.put(o_s2, inv_level_sigma2, (size_t)L * 4);
     const DevPoints mp = o_mp.put(S, *mps, true);   // the kernels read skip unconditionally
@@ -584,7 +635,9 @@ int fuse_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_f
         launch_fuse((const FuseKf*)(d + o_kf), B, mp, pair_skip ? d + o_pskip : nullptr, (const float*)(d + o_sf),
                     chi2 ? (const float*)(d + o_s2) : nullptr, L, kfs[0].log_scale_factor, th,
                     (const orbhip_kp*)(d + o_kps), d + o_kdesc,
-                    (int32_t*)(d + o_cs), (FuseRec*)(d + o_rec), d_idx, d_idx + bn, d_idx + 2 * bn, d_nf, st);
+                    (int32_t*)(d + o_cs), (FuseRec*)(d + o_rec), d_idx, d_idx + bn, d_idx + 2 * bn, d_nf, st,
+                    sx ? (const float*)(d + o_ur) : nullptr, sx ? (float*)(d + o_urc) : nullptr,
+                    sx ? (const float*)(d + o_bf) : nullptr);
         timer.end(8, st);
     }
     HIPOK(hipGetLastError());

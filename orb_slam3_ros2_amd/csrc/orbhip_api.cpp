@@ -643,6 +643,69 @@ int orbhip_triangulate_matches(orbhip_ctx* c, const orbhip_tri_keyframe* kf1, co
                           level_sigma2, n_levels, 0, params, out);
 }
 
+// ---- the same three calls on rectified-stereo keyframes ----
+// The stereo keyframes of a call taken apart (entry 0: KF1): the argument checks of the stereo part,
+// before anything is uploaded. B outside [0, kTriMaxPairs] or null pointers are the inner call's to
+// refuse (count = 0 then).
+struct TriStereoCall {
+    orbhip_tri_keyframe kf[1 + kTriMaxPairs];
+    const float* ur[1 + kTriMaxPairs];
+    const float* depth[1 + kTriMaxPairs];
+    float bf[1 + kTriMaxPairs], b[1 + kTriMaxPairs];
+    TriStereo sx{ur, depth, bf, b};
+    int count = 0;
+    int take(const orbhip_tri_stereo_keyframe* kf1, const orbhip_tri_stereo_keyframe* nbrs, int B) {
+        if (!kf1) return ORBHIP_OK;
+        const int nb = (B > 0 && B <= kTriMaxPairs && nbrs) ? B : 0;
+        for (int s = 0; s <= nb; s++) {
+            const orbhip_tri_stereo_keyframe& k = s ? nbrs[s - 1] : *kf1;
+            if ((k.kf.n > 0 && (!k.u_right || !k.depth)) || !(k.bf > 0.0f) || !(k.b > 0.0f)) return ORBHIP_ERR_ARG;
+            kf[s] = k.kf; ur[s] = k.u_right; depth[s] = k.depth; bf[s] = k.bf; b[s] = k.b;
+        }
+        count = 1 + nb;
+        return ORBHIP_OK;
+    }
+    const orbhip_tri_keyframe* kf1() const { return count ? &kf[0] : nullptr; }
+    const orbhip_tri_keyframe* nbrs() const { return count > 1 ? &kf[1] : nullptr; }
+    const TriStereo* stereo() const { return count ? &sx : nullptr; }
+};
+
+int orbhip_search_for_triangulation_stereo(orbhip_ctx* c, const orbhip_tri_stereo_keyframe* kf1,
+                                           const orbhip_tri_stereo_keyframe* nbrs, int B, const float* scale_factors,
+                                           const float* level_sigma2, int n_levels, int check_orientation,
+                                           int32_t* match12, int32_t* nmatches) {
+    if (!c) return ORBHIP_ERR_ARG;
+    TriStereoCall t;
+    if (const int rc = t.take(kf1, nbrs, B)) return rc;
+    HIPOK(hipSetDevice(c->device));
+    return tri_search(c->tri_stage, c->timer, c->stream, t.kf1(), t.nbrs(), B, scale_factors, level_sigma2, n_levels,
+                      check_orientation, match12, nmatches, t.stereo());
+}
+
+int orbhip_create_new_map_points_stereo(orbhip_ctx* c, const orbhip_tri_stereo_keyframe* kf1,
+                                        const orbhip_tri_stereo_keyframe* nbrs, int B, const float* scale_factors,
+                                        const float* level_sigma2, int n_levels, int check_orientation,
+                                        const orbhip_tri_params* params, orbhip_new_points* out, uint8_t* source) {
+    if (!c) return ORBHIP_ERR_ARG;
+    TriStereoCall t;
+    if (const int rc = t.take(kf1, nbrs, B)) return rc;
+    HIPOK(hipSetDevice(c->device));
+    return tri_new_points(c->tri_stage, c->timer, c->stream, t.kf1(), t.nbrs(), B, nullptr, nullptr, scale_factors,
+                          level_sigma2, n_levels, check_orientation, params, out, t.stereo(), source);
+}
+
+int orbhip_triangulate_matches_stereo(orbhip_ctx* c, const orbhip_tri_stereo_keyframe* kf1,
+                                      const orbhip_tri_stereo_keyframe* nbrs, int B, const int32_t* match12_in,
+                                      const float* scale_factors, const float* level_sigma2, int n_levels,
+                                      const orbhip_tri_params* params, orbhip_new_points* out, uint8_t* source) {
+    if (!c || !match12_in) return ORBHIP_ERR_ARG;
+    TriStereoCall t;
+    if (const int rc = t.take(kf1, nbrs, B)) return rc;
+    HIPOK(hipSetDevice(c->device));
+    return tri_new_points(c->tri_stage, c->timer, c->stream, t.kf1(), t.nbrs(), B, match12_in, nullptr, scale_factors,
+                          level_sigma2, n_levels, 0, params, out, t.stereo(), source);
+}
+
 // ---- Fuse: B keyframes against one list of MapPoints ----
 int orbhip_fuse(orbhip_ctx* c, const orbhip_frame* kfs, int B, const orbhip_local_points* mps,
                 const uint8_t* pair_skip, const float* inv_level_sigma2, float th, int32_t* best_idx,
@@ -651,6 +714,29 @@ int orbhip_fuse(orbhip_ctx* c, const orbhip_frame* kfs, int B, const orbhip_loca
     HIPOK(hipSetDevice(c->device));
     return fuse_search(c->fuse_stage, c->timer, c->stream, kfs, B, mps, pair_skip, true, inv_level_sigma2, th,
                        best_idx, best_dist, level, nfused);
+}
+
+// Fuse on rectified-stereo keyframes. The argument checks of the stereo part come first (nothing is
+// uploaded before them); B outside (0, kFuseMaxKf] or a null kfs is fuse_search's to refuse.
+int orbhip_fuse_stereo(orbhip_ctx* c, const orbhip_stereo_view* kfs, int B, const orbhip_local_points* mps,
+                       const uint8_t* pair_skip, const float* inv_level_sigma2, float th, int32_t* best_idx,
+                       int32_t* best_dist, int32_t* level, int32_t* nfused) {
+    if (!c) return ORBHIP_ERR_ARG;
+    const int nb = (kfs && B > 0 && B <= kFuseMaxKf) ? B : 0;
+    orbhip_frame frames[kFuseMaxKf];   // the views taken apart, on the stack: no allocation per call
+    const float* ur[kFuseMaxKf];
+    float bf[kFuseMaxKf];
+    for (int b = 0; b < nb; b++) {
+        const orbhip_stereo_view& v = kfs[b];
+        if ((v.frame.n > 0 && !v.u_right) || !(v.bf > 0.0f) || !(v.b > 0.0f)) return ORBHIP_ERR_ARG;
+        frames[b] = v.frame;
+        ur[b] = v.u_right;
+        bf[b] = v.bf;
+    }
+    HIPOK(hipSetDevice(c->device));
+    const FuseStereo sx{ur, bf};
+    return fuse_search(c->fuse_stage, c->timer, c->stream, nb ? frames : nullptr, B, mps, pair_skip, true,
+                       inv_level_sigma2, th, best_idx, best_dist, level, nfused, nb ? &sx : nullptr);
 }
 
 // ---- LoopClosing: Fuse and SearchByProjection with a Sim3 (the pose arrives as Tcw = (R, t / s)) ----

@@ -208,9 +208,19 @@ struct StageBlock;
 // SearchForTriangulation (triangulation_kernels.hip); stage 7 of the timer
 // host, fp32 in a fixed operation order: the geometry k_tri_search consumes
 void tri_geometry(const orbhip_tri_keyframe& k1, const orbhip_tri_keyframe& k2, float* F, float* ep);
+// The rectified-stereo part of a triangulation call (a null pointer: the monocular rule): entry 0
+// is KF1's, entry 1 + b neighbour b's: mvuRight and mvDepth (one per feature), mbf and mb
+struct TriStereo {
+    const float* const* u_right;
+    const float* const* depth;
+    const float* bf;
+    const float* b;
+};
+constexpr int kTriMaxPairs = 64;  // neighbours per call
 int tri_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_tri_keyframe* kf1,
                const orbhip_tri_keyframe* nbrs, int B, const float* scale_factors, const float* level_sigma2,
-               int n_levels, int check_orientation, int32_t* match12, int32_t* nmatches);
+               int n_levels, int check_orientation, int32_t* match12, int32_t* nmatches,
+               const TriStereo* sx = nullptr);
 // Fuse (fuse_kernels.hip); stage 8. chi2 = false: Fuse with a Sim3 (no chi-square gate,
 // inv_level_sigma2 unused)
 // CreateNewMapPoints (triangulation_kernels.hip): the search above (match12_in == nullptr; stage 7) or
@@ -218,10 +228,19 @@ int tri_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_tr
 int tri_new_points(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_tri_keyframe* kf1,
                    const orbhip_tri_keyframe* nbrs, int B, const int32_t* match12_in, const float* median_depth,
                    const float* scale_factors, const float* level_sigma2, int n_levels, int check_orientation,
-                   const orbhip_tri_params* params, orbhip_new_points* out);
+                   const orbhip_tri_params* params, orbhip_new_points* out, const TriStereo* sx = nullptr,
+                   uint8_t* source = nullptr);
+constexpr int kFuseMaxKf = 64;   // keyframes per Fuse call
+// The rectified-stereo part of a Fuse call (a null pointer: the monocular rule): per keyframe its
+// mvuRight (one per keypoint) and mbf. A candidate with ur >= 0 takes the three-term chi-square at 7.8
+struct FuseStereo {
+    const float* const* u_right;   // B pointers
+    const float* bf;               // B
+};
 int fuse_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_frame* kfs, int B,
                 const orbhip_local_points* mps, const uint8_t* pair_skip, bool chi2, const float* inv_level_sigma2,
-                float th, int32_t* best_idx, int32_t* best_dist, int32_t* level, int32_t* nfused);
+                float th, int32_t* best_idx, int32_t* best_dist, int32_t* level, int32_t* nfused,
+                const FuseStereo* sx = nullptr);
 // SearchByProjection with a Sim3 (fuse_kernels.hip); stage 9
 constexpr int kSim3ListCap = 8;        // smallest keys k_sim3_search stores per point
 int sim3_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_frame* kf,

@@ -34,14 +34,13 @@
 namespace orbhip {
 
 constexpr int kTriMax = 2048;     // features per keyframe (LDS-resident keys, 16-bit indices)
-constexpr int kTriMaxPairs = 64;  // neighbours per call
 struct TriSide {                  // one keyframe in the call's staging block (device pointers)
     const orbhip_kp* kps;
     const uint8_t* desc;          // n x 32
     const int32_t* node;
     const double* weight;
     const uint8_t* has_mp;
-    int n, pad;
+    int n, pad;                   // pad: stereo calls, where this keyframe's [mvuRight n | mvDepth n] starts in sx
 };
 struct TriGeom { float F[9]; float ep[2]; float pad; };   // F12 row-major, epipole in image 2
 
@@ -140,6 +139,9 @@ __device__ __forceinline__ int tri_lower_bound(const int* a, int m, int v) {
     return lo;
 }
 
+// STEREO: sx holds every keyframe's [mvuRight | mvDepth] (TriSide::pad); the epipole exclusion then
+// applies only when neither feature is stereo (mvuRight >= 0)
+template <bool STEREO>
 __global__ __launch_bounds__(kTriThreads) void k_tri_search(const TriSide* __restrict__ sides,
                                                             const TriGeom* __restrict__ geom,
                                                             const float* __restrict__ scale_factors,
@@ -147,7 +149,8 @@ __global__ __launch_bounds__(kTriThreads) void k_tri_search(const TriSide* __res
                                                             const unsigned long long* __restrict__ keys1,
                                                             const int32_t* __restrict__ m1_in, int check_orientation,
                                                             int32_t* __restrict__ match12,
-                                                            int32_t* __restrict__ nmatches) {
+                                                            int32_t* __restrict__ nmatches,
+                                                            const float* __restrict__ sx) {
     __shared__ TriLds S;
     const int tid = threadIdx.x, lane = tid & 63, b = blockIdx.x;
     const TriSide A = sides[0], N = sides[1 + b];
@@ -202,6 +205,7 @@ __global__ __launch_bounds__(kTriThreads) void k_tri_search(const TriSide* __res
         const float lb = (x1 * F[1] + y1 * F[4]) + F[7];
         const float lc = (x1 * F[2] + y1 * F[5]) + F[8];
         const float den = la * la + lb * lb;
+        const bool stereo1 = STEREO && sx[A.pad + idx1] >= 0.0f;
         // (distance, -index): the least key is the reference's result in any visiting order
         int bestDist = kThLow, bestKey = 0x7fffffff;
         // four candidates' descriptors in flight at once (the loads of one candidate after the
@@ -220,7 +224,8 @@ __global__ __launch_bounds__(kTriThreads) void k_tri_search(const TriSide* __res
                 if (c + k >= c1 || dist > kThLow || dist > bestDist) continue;
                 const orbhip_kp kp2 = N.kps[idx2];
                 const float dex = ex - kp2.x, dey = ey - kp2.y;
-                if (dex * dex + dey * dey < 100.0f * scale_factors[kp2.octave]) continue;
+                const bool either = STEREO && (stereo1 || sx[N.pad + idx2] >= 0.0f);
+                if (!either && dex * dex + dey * dey < 100.0f * scale_factors[kp2.octave]) continue;
                 const float num = (la * kp2.x + lb * kp2.y) + lc;
                 if (den == 0.0f) continue;
                 const float dsqr = (num * num) / den;
@@ -277,11 +282,44 @@ __global__ __launch_bounds__(kTriThreads) void k_tri_search(const TriSide* __res
 // sides[0] = KF1, sides[1 + b] = neighbour b; keys1: kTriMax entries, m1: 1 (both written by the pre-pass)
 static void launch_tri_search(const TriSide* sides, const TriGeom* geom, int n1, int B, const float* scale_factors,
                               const float* level_sigma2, unsigned long long* keys1, int32_t* m1,
-                              int check_orientation, int32_t* match12, int32_t* nmatches, hipStream_t st) {
+                              int check_orientation, int32_t* match12, int32_t* nmatches, hipStream_t st,
+                              const float* sx = nullptr) {
     const unsigned order_wgs = (unsigned)((n1 + kTriOrderThreads - 1) / kTriOrderThreads);
     ORBHIP_LAUNCH(k_tri_order, dim3(order_wgs), dim3(kTriOrderThreads), 0, st, sides, keys1, m1);
-    ORBHIP_LAUNCH(k_tri_search, dim3((unsigned)B), dim3(kTriThreads), 0, st, sides, geom, scale_factors, level_sigma2,
-                  (const unsigned long long*)keys1, (const int32_t*)m1, check_orientation, match12, nmatches);
+    if (sx)
+        ORBHIP_LAUNCH(k_tri_search<true>, dim3((unsigned)B), dim3(kTriThreads), 0, st, sides, geom, scale_factors,
+                      level_sigma2, (const unsigned long long*)keys1, (const int32_t*)m1, check_orientation, match12,
+                      nmatches, sx);
+    else
+        ORBHIP_LAUNCH(k_tri_search<false>, dim3((unsigned)B), dim3(kTriThreads), 0, st, sides, geom, scale_factors,
+                      level_sigma2, (const unsigned long long*)keys1, (const int32_t*)m1, check_orientation, match12,
+                      nmatches, (const float*)nullptr);
+}
+
+// The stereo arrays of a call in its staging block: one segment of [mvuRight n | mvDepth n] per
+// keyframe of `ks` in order (TriSide::pad = where a keyframe's part starts, in floats), and (mbf, mb)
+// per keyframe. ks[0] = KF1.
+static size_t tri_stereo_floats(const orbhip_tri_keyframe* const* ks, int count) {
+    size_t n = 0;
+    for (int s = 0; s < count; s++) n += 2 * (size_t)ks[s]->n;
+    return n;
+}
+static void tri_put_stereo(StageBlock& S, size_t o_sx, size_t o_sb, const TriStereo& x, const int* which, int count,
+                           TriSide* sides) {
+    size_t at = 0;
+    float* sb = (float*)(S.h + o_sb);
+    for (int s = 0; s < count; s++) {
+        const int k = which[s];
+        const size_t n = (size_t)sides[s].n;
+        sides[s].pad = (int)at;
+        if (n) {
+            S.put(o_sx + at * 4, x.u_right[k], n * 4);
+            S.put(o_sx + (at + n) * 4, x.depth[k], n * 4);
+        }
+        at += 2 * n;
+        sb[2 * s] = x.bf[k];
+        sb[2 * s + 1] = x.b[k];
+    }
 }
 
 static int tri_check_side(const orbhip_tri_keyframe& k, int n_levels) {
@@ -318,7 +356,7 @@ static TriSide tri_put_side(StageBlock& S, const TriSideOff& o, const orbhip_tri
 
 int tri_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_tri_keyframe* kf1,
                const orbhip_tri_keyframe* nbrs, int B, const float* scale_factors, const float* level_sigma2,
-               int n_levels, int check_orientation, int32_t* match12, int32_t* nmatches) {
+               int n_levels, int check_orientation, int32_t* match12, int32_t* nmatches, const TriStereo* sx) {
     if (!kf1 || B < 0) return ORBHIP_ERR_ARG;
     if (B == 0) return 0;
     if (B > kTriMaxPairs) return ORBHIP_ERR_UNSUPPORTED;
@@ -339,6 +377,11 @@ int tri_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_tr
     const size_t o_sf = lay.take((size_t)n_levels * 4), o_s2 = lay.take((size_t)n_levels * 4);
     std::vector<TriSideOff> so(1 + B);
     for (int s = 0; s <= B; s++) so[s] = tri_take_side(lay, (size_t)(s ? nbrs[s - 1].n : n1), true);
+    const orbhip_tri_keyframe* ks[1 + kTriMaxPairs];
+    int which[1 + kTriMaxPairs];
+    for (int s = 0; s <= B; s++) { ks[s] = s ? &nbrs[s - 1] : kf1; which[s] = s; }
+    const size_t o_sx = lay.take(sx ? tri_stereo_floats(ks, 1 + B) * 4 : 0);   // stereo: [mvuRight | mvDepth] per keyframe
+    const size_t o_sb = lay.take(sx ? (size_t)(1 + B) * 8 : 0);                // and (mbf, mb)
     const size_t up_bytes = lay.total();
     const size_t o_keys = lay.take((size_t)kTriMax * 8), o_m1 = lay.take(4);
     const size_t back_bytes = (size_t)B * n1 * 4 + (size_t)B * 4;   // nmatches directly behind match12
@@ -356,6 +399,7 @@ int tri_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_tr
             tri_geometry(*kf1, k, geom[s - 1].F, geom[s - 1].ep);
         }
     }
+    if (sx) tri_put_stereo(S, o_sx, o_sb, *sx, which, 1 + B, sides);
     S.put(o_sf, scale_factors, (size_t)n_levels * 4);
     S.put(o_s2, level_sigma2, (size_t)n_levels * 4);
     HIPOK(hipMemcpyAsync(d, h, up_bytes, hipMemcpyHostToDevice, st));
@@ -365,7 +409,8 @@ int tri_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_tr
         timer.begin(7, st);
         launch_tri_search((const TriSide*)(d + o_sides), (const TriGeom*)(d + o_geom), n1, B, (const float*)(d + o_sf),
                           (const float*)(d + o_s2), (unsigned long long*)(d + o_keys), (int32_t*)(d + o_m1),
-                          check_orientation, (int32_t*)(d + o_match), (int32_t*)(d + o_match + (size_t)B * n1 * 4), st);
+                          check_orientation, (int32_t*)(d + o_match), (int32_t*)(d + o_match + (size_t)B * n1 * 4), st,
+                          sx ? (const float*)(d + o_sx) : nullptr);
         timer.end(7, st);
     }
     HIPOK(hipGetLastError());
@@ -421,11 +466,43 @@ __device__ __forceinline__ void tri_jacobi_pair(double (&U)[16], double (&V)[16]
     }
 }
 
-// status of one matched pair (include/orbhip.h); X receives the point once it exists
+// The stereo members of one feature and its keyframe (DESIGN.md "Stereo LocalMapping")
+struct TriFeatStereo { float ur, depth, bf, b; };
+
+// upstream's cos(2 atan2(mb / 2, mvDepth)) as (D^2 - h^2) / (D^2 + h^2), h = mb / 2, in fp64 (each
+// operation rounded once: no FMA), rounded once to fp32
+__device__ __forceinline__ float tri_stereo_cos(float b, float d) {
+    const double h = (double)b * 0.5, D = (double)d;
+    const double DD = D * D, hh = h * h;
+    return (float)((DD - hh) / (DD + hh));
+}
+
+// KeyFrame::UnprojectStereo of a feature with depth z > 0
+__device__ __forceinline__ void tri_unproject(const TriCam& c, const orbhip_kp& kp, float z, float X[3]) {
+    const float x = ((kp.x - c.cx) * z) * (1.0f / c.fx), y = ((kp.y - c.cy) * z) * (1.0f / c.fy);
+#pragma unroll
+    for (int j = 0; j < 3; j++) X[j] = ((c.R[j] * x + c.R[3 + j] * y) + c.R[6 + j] * z) + c.Ow[j];
+}
+
+// the reprojection test of a stereo feature: (eX, eY, eR) against 7.8 sigma2
+__device__ __forceinline__ bool tri_reproj_stereo_fails(const TriCam& c, const orbhip_kp& kp, const TriFeatStereo& f,
+                                                        float px, float py, float z, float sigma2) {
+    const float invz = 1.0f / z;
+    const float u = ((c.fx * px) * invz) + c.cx, v = ((c.fy * py) * invz) + c.cy;
+    const float u_r = u - f.bf * invz;
+    const float eX = u - kp.x, eY = v - kp.y, eR = u_r - f.ur;
+    return (double)((eX * eX + eY * eY) + eR * eR) > 7.8 * (double)sigma2;
+}
+
+// status of one matched pair (include/orbhip.h); X receives the point once it exists. STEREO: f1 / f2
+// are the features' stereo members, source receives the branch that made the point (0 none, 1
+// triangulated, 2 / 3 unprojected from KF1 / KF2)
+template <bool STEREO>
 __device__ __forceinline__ int tri_point(const TriCam& c1, const TriCam& c2, const orbhip_kp& kp1, const orbhip_kp& kp2,
                                          const float* __restrict__ scale_factors,
                                          const float* __restrict__ level_sigma2, double cos_max, float ratio_factor,
-                                         float far, float X[3]) {
+                                         float far, float X[3], const TriFeatStereo& f1, const TriFeatStereo& f2,
+                                         int& source) {
     const float xn1x = (kp1.x - c1.cx) / c1.fx, xn1y = (kp1.y - c1.cy) / c1.fy;
     const float xn2x = (kp2.x - c2.cx) / c2.fx, xn2y = (kp2.y - c2.cy) / c2.fy;
     float r1[3], r2[3];
@@ -438,8 +515,28 @@ __device__ __forceinline__ int tri_point(const TriCam& c1, const TriCam& c2, con
     const float nn1 = (r1[0] * r1[0] + r1[1] * r1[1]) + r1[2] * r1[2];
     const float nn2 = (r2[0] * r2[0] + r2[1] * r2[1]) + r2[2] * r2[2];
     const float cosP = dot / (sqrtf(nn1) * sqrtf(nn2));
-    if (!(cosP > 0.0f)) return 2;
-    if (!((double)cosP < cos_max)) return 3;
+    const bool st1 = STEREO && f1.ur >= 0.0f, st2 = STEREO && f2.ur >= 0.0f;
+    int branch = 1;
+    if (!STEREO) {
+        if (!(cosP > 0.0f)) return 2;
+        if (!((double)cosP < cos_max)) return 3;
+    } else {
+        float cosS1 = cosP + 1.0f, cosS2 = cosP + 1.0f;
+        if (st1) cosS1 = tri_stereo_cos(f1.b, f1.depth);
+        else if (st2) cosS2 = tri_stereo_cos(f2.b, f2.depth);
+        const float cosS = cosS2 < cosS1 ? cosS2 : cosS1;
+        if (cosP < cosS && cosP > 0.0f && (st1 || st2 || (double)cosP < cos_max)) branch = 1;
+        else if (st1 && cosS1 < cosS2) branch = 2;
+        else if (st2 && cosS2 < cosS1) branch = 3;
+        else return !(cosP > 0.0f) ? 2 : 3;
+        source = branch;
+        if (branch != 1) {
+            const float zs = branch == 2 ? f1.depth : f2.depth;
+            if (!(zs > 0.0f)) return 12;
+            tri_unproject(branch == 2 ? c1 : c2, branch == 2 ? kp1 : kp2, zs, X);
+        }
+    }
+    if (!STEREO || branch == 1) {
     double U[16], V[16];
 #pragma unroll
     for (int j = 0; j < 4; j++) {   // T = [R | t]
@@ -469,8 +566,9 @@ __device__ __forceinline__ int tri_point(const TriCam& c1, const TriCam& c2, con
         if (nk < best) { best = nk; v0 = V[k]; v1 = V[4 + k]; v2 = V[8 + k]; v3 = V[12 + k]; }
     }
     if (v3 == 0.0) return 4;
-    const float x = (float)(v0 / v3), y = (float)(v1 / v3), z = (float)(v2 / v3);
-    X[0] = x; X[1] = y; X[2] = z;
+    X[0] = (float)(v0 / v3); X[1] = (float)(v1 / v3); X[2] = (float)(v2 / v3);
+    }
+    const float x = X[0], y = X[1], z = X[2];
     const float z1 = ((c1.R[6] * x + c1.R[7] * y) + c1.R[8] * z) + c1.t[2];
     if (z1 <= 0.0f) return 5;
     const float z2 = ((c2.R[6] * x + c2.R[7] * y) + c2.R[8] * z) + c2.t[2];
@@ -478,16 +576,24 @@ __device__ __forceinline__ int tri_point(const TriCam& c1, const TriCam& c2, con
     {
         const float px = ((c1.R[0] * x + c1.R[1] * y) + c1.R[2] * z) + c1.t[0];
         const float py = ((c1.R[3] * x + c1.R[4] * y) + c1.R[5] * z) + c1.t[1];
+        if (st1) {
+            if (tri_reproj_stereo_fails(c1, kp1, f1, px, py, z1, level_sigma2[kp1.octave])) return 7;
+        } else {
         const float e = ((c1.fx * px) / z1 + c1.cx) - kp1.x;
         const float f = ((c1.fy * py) / z1 + c1.cy) - kp1.y;
         if ((double)(e * e + f * f) > 5.991 * (double)level_sigma2[kp1.octave]) return 7;
+        }
     }
     {
         const float px = ((c2.R[0] * x + c2.R[1] * y) + c2.R[2] * z) + c2.t[0];
         const float py = ((c2.R[3] * x + c2.R[4] * y) + c2.R[5] * z) + c2.t[1];
+        if (st2) {
+            if (tri_reproj_stereo_fails(c2, kp2, f2, px, py, z2, level_sigma2[kp2.octave])) return 8;
+        } else {
         const float e = ((c2.fx * px) / z2 + c2.cx) - kp2.x;
         const float f = ((c2.fy * py) / z2 + c2.cy) - kp2.y;
         if ((double)(e * e + f * f) > 5.991 * (double)level_sigma2[kp2.octave]) return 8;
+        }
     }
     const float d1x = x - c1.Ow[0], d1y = y - c1.Ow[1], d1z = z - c1.Ow[2];
     const float d2x = x - c2.Ow[0], d2y = y - c2.Ow[1], d2z = z - c2.Ow[2];
@@ -503,19 +609,31 @@ __device__ __forceinline__ int tri_point(const TriCam& c1, const TriCam& c2, con
 
 constexpr int kTriPointsThreads = 256;
 // pair = b * n1 + idx1 over the npairs = B x n1 pairs of the call; cams[0] = KF1, cams[1 + b] = neighbour b
+// STEREO: sx = every keyframe's [mvuRight | mvDepth] (TriSide::pad), sb = (mbf, mb) per keyframe, source per pair
+template <bool STEREO>
 __global__ __launch_bounds__(kTriPointsThreads) void k_tri_points(
     const TriSide* __restrict__ sides, const TriCam* __restrict__ cams, const float* __restrict__ scale_factors,
     const float* __restrict__ level_sigma2, const int32_t* __restrict__ match12, int n1, int npairs, double cos_max,
-    float ratio_factor, float far, uint8_t* __restrict__ status, float* __restrict__ x3d_all) {
+    float ratio_factor, float far, uint8_t* __restrict__ status, float* __restrict__ x3d_all,
+    const float* __restrict__ sx, const float* __restrict__ sb, uint8_t* __restrict__ source) {
     const int pair = blockIdx.x * kTriPointsThreads + threadIdx.x;
     if (pair >= npairs) return;
     const int b = pair / n1, idx1 = pair - b * n1;
     const int idx2 = match12[pair];
     int st = 0;
     float X[3] = {0.f, 0.f, 0.f};
-    if (idx2 >= 0)
-        st = tri_point(cams[0], cams[1 + b], sides[0].kps[idx1], sides[1 + b].kps[idx2], scale_factors, level_sigma2,
-                       cos_max, ratio_factor, far, X);
+    int src = 0;
+    if (idx2 >= 0) {
+        TriFeatStereo f1{-1.f, 0.f, 0.f, 0.f}, f2{-1.f, 0.f, 0.f, 0.f};
+        if (STEREO) {
+            const TriSide A = sides[0], N = sides[1 + b];
+            f1 = TriFeatStereo{sx[A.pad + idx1], sx[A.pad + A.n + idx1], sb[0], sb[1]};
+            f2 = TriFeatStereo{sx[N.pad + idx2], sx[N.pad + N.n + idx2], sb[2 * (1 + b)], sb[2 * (1 + b) + 1]};
+        }
+        st = tri_point<STEREO>(cams[0], cams[1 + b], sides[0].kps[idx1], sides[1 + b].kps[idx2], scale_factors,
+                               level_sigma2, cos_max, ratio_factor, far, X, f1, f2, src);
+    }
+    if (STEREO) source[pair] = (uint8_t)src;
     status[pair] = (uint8_t)st;
     x3d_all[3 * (int64_t)pair] = X[0];
     x3d_all[3 * (int64_t)pair + 1] = X[1];
@@ -588,7 +706,7 @@ static int tri_check_kps(const orbhip_tri_keyframe& k, int n_levels) {
 int tri_new_points(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_tri_keyframe* kf1,
                    const orbhip_tri_keyframe* nbrs, int B, const int32_t* match12_in, const float* median_depth,
                    const float* scale_factors, const float* level_sigma2, int n_levels, int check_orientation,
-                   const orbhip_tri_params* params, orbhip_new_points* out) {
+                   const orbhip_tri_params* params, orbhip_new_points* out, const TriStereo* sx, uint8_t* source) {
     const bool search = match12_in == nullptr;
     if (!kf1 || B < 0 || !params || !out) return ORBHIP_ERR_ARG;
     if (B > kTriMaxPairs) return ORBHIP_ERR_UNSUPPORTED;
@@ -615,6 +733,7 @@ int tri_new_points(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhi
     if (out->match12) for (size_t i = 0; i < pairs_all; i++) out->match12[i] = -1;
     if (out->status && pairs_all) std::memset(out->status, 0, pairs_all);
     if (out->x3d_all && pairs_all) std::memset(out->x3d_all, 0, pairs_all * 12);
+    if (source && pairs_all) std::memset(source, 0, pairs_all);
     if (B == 0 || n1 == 0) return 0;
     // the cameras, and the neighbours the baseline gate leaves (act): B scalar evaluations on the host
     std::vector<TriCam> cam(1 + B);
@@ -622,12 +741,16 @@ int tri_new_points(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhi
     int act[kTriMaxPairs], Ba = 0;
     for (int b = 0; b < B; b++) {
         tri_camera(nbrs[b], cam[1 + b]);
-        if (search && median_depth) {
+        if (search && (median_depth || sx)) {
             const float dx = cam[1 + b].Ow[0] - cam[0].Ow[0], dy = cam[1 + b].Ow[1] - cam[0].Ow[1],
                         dz = cam[1 + b].Ow[2] - cam[0].Ow[2];
             const float baseline = sqrtf((dx * dx + dy * dy) + dz * dz);
-            const float r = baseline / median_depth[b];
-            if ((double)r < 0.01) { out->gated[b] = 1; continue; }
+            if (sx) {   // the stereo gate: the neighbour's own stereo baseline mb
+                if (baseline < sx->b[1 + b]) { out->gated[b] = 1; continue; }
+            } else {
+                const float r = baseline / median_depth[b];
+                if ((double)r < 0.01) { out->gated[b] = 1; continue; }
+            }
         }
         act[Ba++] = b;
     }
@@ -645,6 +768,11 @@ int tri_new_points(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhi
     std::vector<TriSideOff> so(1 + Ba);
     for (int s = 0; s <= Ba; s++) so[s] = tri_take_side(lay, (size_t)(s ? nbrs[act[s - 1]].n : n1), search);
     const size_t o_min = lay.take(search ? 0 : npairs * 4);
+    const orbhip_tri_keyframe* ks[1 + kTriMaxPairs];
+    int which[1 + kTriMaxPairs];
+    for (int s = 0; s <= Ba; s++) { ks[s] = s ? &nbrs[act[s - 1]] : kf1; which[s] = s ? 1 + act[s - 1] : 0; }
+    const size_t o_sx = lay.take(sx ? tri_stereo_floats(ks, 1 + Ba) * 4 : 0);   // stereo: [mvuRight | mvDepth] per keyframe
+    const size_t o_sb = lay.take(sx ? (size_t)(1 + Ba) * 8 : 0);                // and (mbf, mb)
     const size_t up_bytes = lay.total();
     const size_t o_keys = lay.take(search ? (size_t)kTriMax * 8 : 0), o_m1 = lay.take(search ? 4 : 0);
     const size_t o_head = lay.take((size_t)(n1 + Ba + 1) * 4);
@@ -658,6 +786,8 @@ int tri_new_points(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhi
     if (out->status) back_end = lay.off;
     const size_t o_x3d = lay.take(npairs * 12);
     if (out->x3d_all) back_end = lay.off;
+    const size_t o_src = lay.take(sx ? npairs : 0);
+    if (sx && source) back_end = lay.off;
     const size_t back_bytes = back_end - o_head;
     HIPOK(S.ensure(lay.total(), up_bytes + back_bytes + 16));
     uint8_t* const d = S.d;
@@ -674,6 +804,7 @@ int tri_new_points(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhi
             tri_geometry(*kf1, k, geom[s - 1].F, geom[s - 1].ep);
         }
     }
+    if (sx) tri_put_stereo(S, o_sx, o_sb, *sx, which, 1 + Ba, sides);
     S.put(o_sf, scale_factors, (size_t)n_levels * 4);
     S.put(o_s2, level_sigma2, (size_t)n_levels * 4);
     if (!search) S.put(o_min, match12_in, npairs * 4);   // no neighbour is gated: the rows are the caller's
@@ -687,15 +818,23 @@ int tri_new_points(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhi
             launch_tri_search((const TriSide*)(d + o_sides), (const TriGeom*)(d + o_geom), n1, Ba,
                               (const float*)(d + o_sf), (const float*)(d + o_s2), (unsigned long long*)(d + o_keys),
                               (int32_t*)(d + o_m1), check_orientation, (int32_t*)(d + o_match), (int32_t*)(d + o_nm),
-                              st);
+                              st, sx ? (const float*)(d + o_sx) : nullptr);
             timer.end(7, st);
         }
         timer.begin(10, st);
         const unsigned wgs = (unsigned)((npairs + kTriPointsThreads - 1) / kTriPointsThreads);
-        ORBHIP_LAUNCH(k_tri_points, dim3(wgs), dim3(kTriPointsThreads), 0, st, (const TriSide*)(d + o_sides),
-                      (const TriCam*)(d + o_cams), (const float*)(d + o_sf), (const float*)(d + o_s2),
-                      (const int32_t*)(d + o_match), n1, (int)npairs, params->cos_parallax_max, params->ratio_factor,
-                      params->far_threshold, d + o_status, (float*)(d + o_x3d));
+        if (sx)
+            ORBHIP_LAUNCH(k_tri_points<true>, dim3(wgs), dim3(kTriPointsThreads), 0, st, (const TriSide*)(d + o_sides),
+                          (const TriCam*)(d + o_cams), (const float*)(d + o_sf), (const float*)(d + o_s2),
+                          (const int32_t*)(d + o_match), n1, (int)npairs, params->cos_parallax_max,
+                          params->ratio_factor, params->far_threshold, d + o_status, (float*)(d + o_x3d),
+                          (const float*)(d + o_sx), (const float*)(d + o_sb), d + o_src);
+        else
+            ORBHIP_LAUNCH(k_tri_points<false>, dim3(wgs), dim3(kTriPointsThreads), 0, st, (const TriSide*)(d + o_sides),
+                          (const TriCam*)(d + o_cams), (const float*)(d + o_sf), (const float*)(d + o_s2),
+                          (const int32_t*)(d + o_match), n1, (int)npairs, params->cos_parallax_max,
+                          params->ratio_factor, params->far_threshold, d + o_status, (float*)(d + o_x3d),
+                          (const float*)nullptr, (const float*)nullptr, (uint8_t*)nullptr);
         ORBHIP_LAUNCH(k_tri_claim, dim3(1), dim3(kTriThreads), 0, st, (const uint8_t*)(d + o_status),
                       (const int32_t*)(d + o_match), (const float*)(d + o_x3d), n1, Ba, d_head, d_head + n1,
                       d_head + n1 + Ba, (int32_t*)(d + o_nbr), (int32_t*)(d + o_i1), (int32_t*)(d + o_i2),
@@ -727,6 +866,7 @@ int tri_new_points(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhi
                                                                : (const void*)(match12_in + (size_t)b * n1),
                         (size_t)n1 * 4);
         if (out->status) std::memcpy(out->status + (size_t)b * n1, back(o_status) + (size_t)a * n1, (size_t)n1);
+        if (sx && source) std::memcpy(source + (size_t)b * n1, back(o_src) + (size_t)a * n1, (size_t)n1);
         if (out->x3d_all)
             std::memcpy(out->x3d_all + (size_t)b * n1 * 3, back(o_x3d) + (size_t)a * n1 * 12, (size_t)n1 * 12);
     }

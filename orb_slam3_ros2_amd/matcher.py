@@ -14,7 +14,7 @@ import ctypes
 import numpy as np
 
 from ._lib import (KP_DTYPE, FrameC, InitFrameC, LocalPointsC, NewPointsC, ProjLastC, StereoViewC, TriKeyFrameC,
-                   TriParamsC, torch_stream, Context, check, lib, ptr)
+                   TriParamsC, TriStereoKeyFrameC, torch_stream, Context, check, lib, ptr)
 
 
 class ORBmatcher:
@@ -200,9 +200,11 @@ class ORBmatcher:
         kf1 against every keyframe of `neighbours` (at most 64) in one call, with this matcher's
         mbCheckOrientation (CreateNewMapPoints uses ORBmatcher(0.6, false); there is no ratio test).
         Returns (nmatches[B], match12[B, n1]) with match12[b, i] = the feature of neighbour b
-        matched to kf1's feature i, or -1."""
+        matched to kf1's feature i, or -1. Keyframes that carry u_right take the stereo branch (no
+        epipole exclusion for a pair with a stereo feature); all keyframes of a call must agree."""
         nb = list(neighbours)
         B, n1 = len(nb), kf1.n
+        stereo = _tri_stereo("SearchForTriangulation", kf1, nb)
         sf = np.ascontiguousarray(scale_factors, np.float32)
         s2 = np.ascontiguousarray(level_sigma2, np.float32)
         if sf.shape[0] != s2.shape[0]:
@@ -210,6 +212,14 @@ class ORBmatcher:
         nm = np.zeros(B, np.int32)
         m = np.full((B, n1), -1, np.int32)
         if B == 0:
+            return nm, m
+        if stereo:
+            arr = (TriStereoKeyFrameC * B)(*[k.to_c_stereo() for k in nb])
+            c1 = kf1.to_c_stereo()
+            check(lib().orbhip_search_for_triangulation_stereo(self.ctx.handle, ctypes.byref(c1), arr, B, ptr(sf),
+                                                               ptr(s2), sf.shape[0], int(self.mbCheckOrientation),
+                                                               ptr(m), ptr(nm)),
+                  "orbhip_search_for_triangulation_stereo")
             return nm, m
         arr = (TriKeyFrameC * B)(*[k.to_c() for k in nb])
         c1 = kf1.to_c()
@@ -225,7 +235,9 @@ class ORBmatcher:
         U:src/LocalMapping.cc::CreateNewMapPoints on its matches, in one call (orbhip_create_new_map_points).
         median_depth: per neighbour its ComputeSceneMedianDepth(2), or None (no neighbour is gated);
         ratio_factor: None = 1.5f * mvScaleFactors[1]; far_threshold <= 0: off. diagnostics: also
-        return match12, status and x3d_all (B x n1)."""
+        return match12, status and x3d_all (B x n1). Keyframes that carry u_right (all of a call or
+        none) take the stereo branch (orbhip_create_new_map_points_stereo): a neighbour is gated when
+        the baseline is below its b, median_depth must be None, and diagnostics include `source`."""
         return self._new_points("orbhip_create_new_map_points", kf1, neighbours, scale_factors, level_sigma2, None,
                                 median_depth, cos_parallax_max, ratio_factor, far_threshold, diagnostics)
 
@@ -241,6 +253,9 @@ class ORBmatcher:
                     ratio_factor, far_threshold, diagnostics):
         nb = list(neighbours)
         B, n1 = len(nb), kf1.n
+        stereo = _tri_stereo(what, kf1, nb)
+        if stereo and median_depth is not None:
+            raise ValueError(f"{what}: stereo keyframes are gated on their b, not on median_depth")
         sf = np.ascontiguousarray(scale_factors, np.float32)
         s2 = np.ascontiguousarray(level_sigma2, np.float32)
         if sf.shape[0] != s2.shape[0]:
@@ -248,9 +263,25 @@ class ORBmatcher:
         if ratio_factor is None:
             ratio_factor = np.float32(1.5) * sf[1]
         prm = TriParamsC(float(cos_parallax_max), float(np.float32(ratio_factor)), float(np.float32(far_threshold)))
-        r = NewPoints(B, n1, diagnostics)
+        r = NewPoints(B, n1, diagnostics, stereo)
         out = NewPointsC(ptr(r.match12), ptr(r.nmatches), ptr(r.gated), ptr(r.status), ptr(r.x3d_all), ptr(r.first),
                          ptr(r.nnew), ptr(r._nbr), ptr(r._idx1), ptr(r._idx2), ptr(r._x3d))
+        if stereo:
+            arr = (TriStereoKeyFrameC * max(B, 1))(*[k.to_c_stereo() for k in nb])
+            c1 = kf1.to_c_stereo()
+            if match12 is None:
+                n = lib().orbhip_create_new_map_points_stereo(self.ctx.handle, ctypes.byref(c1), arr, B, ptr(sf), ptr(s2),
+                                                              sf.shape[0], int(self.mbCheckOrientation),
+                                                              ctypes.byref(prm), ctypes.byref(out), ptr(r.source))
+            else:
+                m = np.ascontiguousarray(match12, np.int32)
+                if m.shape != (B, n1):
+                    raise ValueError(f"{what}: match12 must be B x n1")
+                n = lib().orbhip_triangulate_matches_stereo(self.ctx.handle, ctypes.byref(c1), arr, B, ptr(m), ptr(sf),
+                                                            ptr(s2), sf.shape[0], ctypes.byref(prm), ctypes.byref(out),
+                                                            ptr(r.source))
+            r.n = check(n, what + "_stereo")
+            return r
         arr = (TriKeyFrameC * max(B, 1))(*[k.to_c() for k in nb])
         c1 = kf1.to_c()
         if match12 is None:
@@ -280,9 +311,15 @@ class ORBmatcher:
         it is at call time; the caller applies Replace / AddObservation / AddMapPoint in upstream
         order (INTEGRATION.md). Returns (nfused[B], best_idx[B, n], best_dist[B, n], level[B, n]):
         best_idx = the keypoint of kfs[b] the point fuses into or -1, best_dist = the least distance
-        over the gated candidates (256: none), level = nPredictedLevel (-1: rejected before it)."""
+        over the gated candidates (256: none), level = nPredictedLevel (-1: rejected before it).
+        Keyframes that carry u_right take the stereo branch (orbhip_fuse_stereo: a candidate with
+        u_right >= 0 is gated on its right coordinate too, at 7.8); all keyframes of a call must
+        agree, else ValueError."""
         kfs = list(kfs)
         B = len(kfs)
+        stereo = B > 0 and kfs[0].u_right is not None
+        if any((k.u_right is not None) != stereo for k in kfs):
+            raise ValueError("Fuse: stereo and monocular keyframes in one call")
         pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
         n = pts.shape[0]
         nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
@@ -303,8 +340,13 @@ class ORBmatcher:
             return nf, idx, dist, lvl
         if any(s2.shape[0] < len(k.scale_factors) for k in kfs):
             raise ValueError("Fuse: inv_level_sigma2 shorter than the keyframes' scale tables")
-        arr = (FrameC * B)(*[k.to_c() for k in kfs])
         lc = LocalPointsC(n, ptr(pts), ptr(nrm), ptr(mn), ptr(mx), ptr(d), ptr(sk))
+        if stereo:
+            views = (StereoViewC * B)(*[k.to_c_stereo() for k in kfs])
+            check(lib().orbhip_fuse_stereo(self.ctx.handle, views, B, ctypes.byref(lc), ptr(ps), ptr(s2), float(th),
+                                           ptr(idx), ptr(dist), ptr(lvl), ptr(nf)), "orbhip_fuse_stereo")
+            return nf, idx, dist, lvl
+        arr = (FrameC * B)(*[k.to_c() for k in kfs])
         check(lib().orbhip_fuse(self.ctx.handle, arr, B, ctypes.byref(lc), ptr(ps), ptr(s2), float(th), ptr(idx),
                                 ptr(dist), ptr(lvl), ptr(nf)), "orbhip_fuse")
         return nf, idx, dist, lvl
@@ -365,14 +407,23 @@ class ORBmatcher:
         return nm, match, dist, lvl
 
 
+def _tri_stereo(what, kf1, nb) -> bool:
+    """Whether the keyframes of a triangulation call are stereo (all or none, else ValueError)."""
+    stereo = kf1.u_right is not None
+    if any((k.u_right is not None) != stereo for k in nb):
+        raise ValueError(f"{what}: stereo and monocular keyframes in one call")
+    return stereo
+
+
 class NewPoints:
     """What CreateNewMapPoints / TriangulateMatches return. n new points, in upstream's creation
     order (ascending neighbour, then ascending idx1): new_nbr, new_idx1, new_idx2, new_x3d (views of
     the first n entries). first[idx1] = the neighbour whose point the feature became or -1;
     nnew[b], nmatches[b], gated[b] per neighbour. With diagnostics: match12, status and x3d_all
-    (B x n1; status codes in include/orbhip.h), else None."""
+    (B x n1; status codes in include/orbhip.h), else None; a stereo call's diagnostics also hold
+    source (B x n1: 0 no point, 1 triangulated, 2 / 3 unprojected from KF1 / the neighbour)."""
 
-    def __init__(self, B: int, n1: int, diagnostics: bool):
+    def __init__(self, B: int, n1: int, diagnostics: bool, stereo: bool = False):
         self.n = 0
         self.nmatches = np.zeros(B, np.int32)
         self.gated = np.zeros(B, np.uint8)
@@ -385,6 +436,7 @@ class NewPoints:
         self.match12 = np.full((B, n1), -1, np.int32) if diagnostics else None
         self.status = np.zeros((B, n1), np.uint8) if diagnostics else None
         self.x3d_all = np.zeros((B, n1, 3), np.float32) if diagnostics else None
+        self.source = np.zeros((B, n1), np.uint8) if diagnostics and stereo else None
 
     new_nbr = property(lambda self: self._nbr[:self.n])
     new_idx1 = property(lambda self: self._idx1[:self.n])
@@ -396,9 +448,11 @@ class TriKeyFrame:
     """A KeyFrame as SearchForTriangulation reads it: mvKeysUn (orbhip_kp records), descriptors, the
     FeatureVector as per-feature (node, weight) from ORBVocabulary.transform_features (levelsup 4;
     weight > 0 and node >= 0: in the vector), has_mp[i] = GetMapPoint(i) is set, the pinhole
-    intrinsics and Tcw."""
+    intrinsics and Tcw. A rectified-stereo keyframe also carries u_right (mvuRight) and depth (mvDepth),
+    one per feature, bf (mbf) and b (mb); the calls then take their stereo branches."""
 
-    def __init__(self, kps, desc, node, weight, has_mp, pose_q, pose_t, fx, fy, cx, cy):
+    def __init__(self, kps, desc, node, weight, has_mp, pose_q, pose_t, fx, fy, cx, cy, u_right=None, depth=None,
+                 bf=0.0, b=0.0):
         self.kps = np.ascontiguousarray(kps, KP_DTYPE)
         self.n = self.kps.shape[0]
         self.desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
@@ -412,6 +466,22 @@ class TriKeyFrame:
         self.pose_t = np.array(pose_t, np.float32).reshape(3)
         self.fx, self.fy, self.cx, self.cy = float(fx), float(fy), float(cx), float(cy)
         self._c = None
+        if (u_right is None) != (depth is None):
+            raise ValueError("TriKeyFrame: u_right and depth come together")
+        self.u_right = None if u_right is None else np.ascontiguousarray(u_right, np.float32).reshape(-1)
+        self.depth = None if depth is None else np.ascontiguousarray(depth, np.float32).reshape(-1)
+        self.bf, self.b = float(bf), float(b)
+
+    def to_c_stereo(self) -> TriStereoKeyFrameC:
+        """The stereo view: to_c() plus u_right / depth / bf / b (it points into this object's arrays)."""
+        self.u_right = np.ascontiguousarray(self.u_right, np.float32).reshape(-1)
+        self.depth = np.ascontiguousarray(self.depth, np.float32).reshape(-1)
+        c = TriStereoKeyFrameC()
+        c.kf = self.to_c()
+        if self.u_right.shape[0] != self.n or self.depth.shape[0] != self.n:
+            raise ValueError("TriKeyFrame: u_right and depth need one entry per feature")
+        c.u_right, c.depth, c.bf, c.b = ptr(self.u_right), ptr(self.depth), self.bf, self.b
+        return c
 
     def to_c(self) -> TriKeyFrameC:
         """The C view (it points into this object's arrays: keep the object alive while it is used).

@@ -1124,6 +1124,155 @@ def synthetic_stereo_projection_scene(n_kp=1000, n_mp=900, seed=5, motion="forwa
                 direction=dict(forward=1, backward=-1, neutral=0)[motion])
 
 
+def synthetic_stereo_new_points_scene(n=300, B=3, seed=0, b=STEREO_B, scale=0.3, mono_frac=0.3, off_frac=0.06,
+                                      zero_depth_frac=0.015, gated_at=1, **scene_args):
+    """synthetic_new_points_scene(n, B, seed, scale=scale, ...) seen by rectified-stereo keyframes, for
+    the stereo branches of SearchForTriangulation / CreateNewMapPoints. scale = 0.3 puts the
+    neighbours 0.09-0.14 m from KF1 and the points 0.6-2.4 m away, so that against a stereo baseline
+    b = 0.08 m the ray parallax wins for the sideways neighbour (triangulated), loses for most of the
+    forward one (unprojected) and the diagonal one has both. A KF1 feature's depth is that of the
+    float64 triangulation with its twin in the first (sideways) neighbour (1-8 scaled metres at
+    random without one), a twin's depth that of the same point in its own camera; u_right = x - bf /
+    depth (bf = fx * b) + 0.15 level sigma of noise. Then, per feature of every keyframe:
+      mono_frac        lose the stereo members (u_right = depth = -1; also where u_right < 0.5)
+      off_frac         of the stereo features get a right coordinate 4-8 level sigma off (depth kept):
+                       the three-term reprojection test fails where the monocular one passes
+      zero_depth_frac  of the stereo features get depth 0 (UnprojectStereo refuses them)
+    The neighbour inserted at gated_at lies 1 mm * scale from KF1: below every b, gated. Draws come
+    from a generator of their own. Returns the base dict with kf1 / neighbours carrying u_right, depth,
+    bf, b, plus b, bf, mono_kf1 / mono_neighbours (the same keyframes without them); median_depth is
+    None (the stereo call has no such gate)."""
+    from .matcher import TriKeyFrame
+    cam = dict(scene_args.pop("cam", None) or WIDE_CAM)
+    s = synthetic_new_points_scene(n, B, seed, cam=cam, scale=scale, gated_at=gated_at, **scene_args)
+    twins = synthetic_triangulation_scene(n, B, seed, cam=cam, **scene_args)["twin"]
+    rng = np.random.Generator(np.random.PCG64(32452843 * (seed + 1) + 7))
+    m = float(scale)
+    sf = s["scale_factors"].astype(np.float64)
+    k1, nbrs = s["kf1"], s["neighbours"]
+    bf = float(np.float32(np.float32(cam["fx"]) * np.float32(b)))
+    R1, t1 = _pose64(k1)
+
+    def tri_depth(k2, p1, p2):   # depth in KF1 of the float64 triangulation of two pixels
+        rows = []
+        for k, p in ((k1, p1), (k2, p2)):
+            R, t = _pose64(k)
+            T = np.concatenate([R, t[:, None]], 1)
+            xn = ((p[0] - k.cx) / k.fx, (p[1] - k.cy) / k.fy)
+            rows += [xn[0] * T[2] - T[0], xn[1] * T[2] - T[1]]
+        v = np.linalg.svd(np.array(rows))[2][3]
+        if v[3] == 0:
+            return -1.0
+        return float((R1 @ (v[:3] / v[3]) + t1)[2])
+
+    def new_index(bb):           # a base neighbour's place in the list with the gated one
+        return bb + (gated_at is not None and B > 0 and bb >= gated_at)
+
+    z1 = rng.uniform(1.0, 8.0, k1.n) * m
+    if B > 0:
+        k2 = nbrs[new_index(0)]
+        for i in np.nonzero(twins[0] >= 0)[0]:
+            j = int(twins[0][i])
+            z = tri_depth(k2, (k1.kps["x"][i], k1.kps["y"][i]), (k2.kps["x"][j], k2.kps["y"][j]))
+            if 0.3 * m < z < 30.0 * m:
+                z1[i] = z
+    Xw = (np.stack([(k1.kps["x"] - cam["cx"]) / cam["fx"] * z1, (k1.kps["y"] - cam["cy"]) / cam["fy"] * z1, z1], 1)
+          - t1) @ R1
+    depths = [z1]
+    for a, k in enumerate(nbrs):
+        z = rng.uniform(1.0, 8.0, k.n) * m
+        base_b = [bb for bb in range(B) if new_index(bb) == a]
+        if base_b:
+            R, t = _pose64(k)
+            zc = (Xw @ R.T + t)[:, 2]
+            tw = twins[base_b[0]]
+            for i in np.nonzero(tw >= 0)[0]:
+                if tw[i] < k.n and zc[i] > 0.1 * m:
+                    z[int(tw[i])] = zc[i]
+        depths.append(z)
+
+    def dress(k, z):
+        nk = k.n
+        sig = sf[k.kps["octave"]]
+        ur = k.kps["x"].astype(np.float64) - bf / z + rng.normal(size=nk) * 0.15 * sig
+        mono = rng.random(nk) < mono_frac
+        kind = rng.random(nk)
+        off = kind < off_frac
+        ur[off] += rng.choice([-1.0, 1.0], int(off.sum())) * rng.uniform(4.0, 8.0, int(off.sum())) * sig[off]
+        mono |= ur < 0.5
+        z = np.where((kind >= off_frac) & (kind < off_frac + zero_depth_frac), 0.0, z)
+        u_right = np.where(mono, -1.0, ur).astype(np.float32)
+        depth = np.where(mono, -1.0, z).astype(np.float32)
+        return TriKeyFrame(k.kps, k.desc, k.node, k.weight, k.has_mp, k.pose_q, k.pose_t, k.fx, k.fy, k.cx, k.cy,
+                           u_right=u_right, depth=depth, bf=bf, b=float(np.float32(b)))
+
+    stereo = [dress(k, z) for k, z in zip([k1] + nbrs, depths)]
+    return dict(s, kf1=stereo[0], neighbours=stereo[1:], mono_kf1=k1, mono_neighbours=nbrs, median_depth=None,
+                b=float(np.float32(b)), bf=bf)
+
+
+def synthetic_stereo_fuse_scene(n_kp=300, n_mp=300, B=3, seed=0, b=STEREO_B, mono_frac=0.25, off_frac=0.12,
+                                ring_frac=0.1, **fuse_args):
+    """synthetic_fuse_scene(n_kp, n_mp, B, seed, ...) seen by rectified-stereo keyframes, for the
+    stereo branch of ORBmatcher.Fuse. A keypoint is tied to the MapPoint whose projection into its
+    keyframe lies nearest, when that is within 4 level sigma (sigma = mvScaleFactors[octave]); tied
+    keypoints get u_right = that point's right projection u - bf / z (bf = fx * b) + 0.15 sigma of
+    noise, the others one for a depth of 1-8 m. Then, independently per keypoint:
+      mono_frac   lose the right coordinate (-1: a monocular keypoint; also where it would be < 0)
+      off_frac    of the tied stereo keypoints get a right coordinate 3-6 sigma off: with a small
+                  (u, v) error the three-term chi-square rejects what the monocular test accepts
+      ring_frac   of the tied stereo keypoints are moved onto a ring 2.5-2.7 sigma from the
+                  projection, the right coordinate kept: rejected at 5.99, accepted at 7.8
+    The draws come from a generator of their own and the points are the base scene's, so its level
+    margin holds. Returns the base scene's dict with kfs replaced by ProjFrames that carry u_right /
+    bf / b, plus bf, b and mono_kfs (the same keyframes, moved keypoints included, without them)."""
+    from .matcher import ProjFrame
+    s = synthetic_fuse_scene(n_kp, n_mp, B, seed, **fuse_args)
+    rng = np.random.Generator(np.random.PCG64(15485863 * (seed + 1) + 11))
+    sf = s["scale_factors"].astype(np.float64)
+    P64 = s["points"].astype(np.float64)
+    kfs, mono_kfs = [], []
+    bf = 0.0
+    for k in s["kfs"]:
+        cam = dict(fx=k.fx, fy=k.fy, cx=k.cx, cy=k.cy)
+        bf = float(np.float32(np.float32(k.fx) * np.float32(b)))
+        nk = k.kps.shape[0]
+        kps = k.kps.copy()
+        x, y = kps["x"].astype(np.float64), kps["y"].astype(np.float64)
+        sig = sf[kps["octave"]]
+        tied = np.zeros(nk, bool)
+        pu, pv, pz = np.zeros(nk), np.zeros(nk), rng.uniform(1.0, 8.0, nk)
+        if n_mp:
+            with np.errstate(all="ignore"):
+                uv, z = pinhole_project(k.pose_q, k.pose_t, cam, P64)
+            front = z > 0.1
+            for i0 in range(0, nk, 256):
+                i1 = min(nk, i0 + 256)
+                d2 = (x[i0:i1, None] - uv[None, :, 0]) ** 2 + (y[i0:i1, None] - uv[None, :, 1]) ** 2
+                d2[:, ~front] = np.inf
+                m = np.argmin(d2, axis=1)
+                near = np.sqrt(d2[np.arange(i1 - i0), m]) < 4.0 * sig[i0:i1]
+                tied[i0:i1] = near
+                pu[i0:i1], pv[i0:i1] = uv[m, 0], uv[m, 1]
+                pz[i0:i1] = np.where(near, z[m], pz[i0:i1])
+        ur = np.where(tied, pu, x) - bf / pz + rng.normal(size=nk) * 0.15 * sig
+        mono = (rng.random(nk) < mono_frac) | (ur < 0.5)
+        kind = rng.random(nk)
+        off = tied & ~mono & (kind < off_frac)
+        ring = tied & ~mono & (kind >= off_frac) & (kind < off_frac + ring_frac)
+        ur[off] += rng.choice([-1.0, 1.0], int(off.sum())) * rng.uniform(3.0, 6.0, int(off.sum())) * sig[off]
+        mono |= ur < 0.5
+        a, rho = rng.uniform(0, 2 * np.pi, nk), rng.uniform(2.5, 2.7, nk) * sig
+        kps["x"] = np.where(ring, pu + rho * np.cos(a), x).astype(np.float32)
+        kps["y"] = np.where(ring, pv + rho * np.sin(a), y).astype(np.float32)
+        u_right = np.where(mono, -1.0, ur).astype(np.float32)
+        for out, extra in ((kfs, dict(u_right=u_right, bf=bf, b=float(np.float32(b)))), (mono_kfs, {})):
+            f = ProjFrame(kps, k.desc, k.pose_q, k.pose_t, k.fx, k.fy, k.cx, k.cy, bounds=k.bounds, **extra)
+            f.scale_factors, f.log_scale_factor = k.scale_factors, k.log_scale_factor
+            out.append(f)
+    return dict(s, kfs=kfs, mono_kfs=mono_kfs, bf=bf, b=float(np.float32(b)))
+
+
 def synthetic_stereo_ba_problem(n_kf=50, n_pts=2000, stereo_frac=0.7, seed=7, ur_noise=1.0, b=0.05, **ba_args):
     """synthetic_ba_problem(n_kf, n_pts, seed=seed, ...) seen by rectified-stereo keyframes: about
     stereo_frac of the observations carry edge_ur = the ground-truth point's projection into the
