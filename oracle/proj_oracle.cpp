@@ -341,6 +341,21 @@ int orc_search_for_initialization(int n1, const void* kps1, const uint8_t* desc1
     return nmatches;
 }
 
+// MapPoint::PredictScale as orc_search_local_points computes it, for every float `ratio` whose bit
+// pattern lies in [lo_bits, hi_bits]: out[bits - lo_bits] = the level (n_levels <= 127).
+int orc_predict_scale_range(uint32_t lo_bits, uint32_t hi_bits, float log_sf, int n_levels, int8_t* out) {
+    for (uint64_t u = lo_bits; u <= hi_bits; u++) {
+        const uint32_t b = (uint32_t)u;
+        float ratio;
+        std::memcpy(&ratio, &b, 4);
+        int nScale = (int)std::ceil(std::log(ratio) / log_sf);
+        if (nScale < 0) nScale = 0;
+        else if (nScale >= n_levels) nScale = n_levels - 1;
+        out[u - lo_bits] = (int8_t)nScale;
+    }
+    return 0;
+}
+
 // ---- distorted pinhole cameras (UndistortKeyPoints + image bounds) ----
 // U:src/Frame.cc::Frame::UndistortKeyPoints: if mDistCoef.at<float>(0) == 0, mvKeysUn = mvKeys;
 // else cv::undistortPoints(mat(N x 1, CV_32FC2), mat, K (float), mDistCoef (float k1 k2 p1 p2

@@ -83,6 +83,8 @@ def lib():
                                        _f32p]
         L.orc_bgr2gray.argtypes = [_u8p, c_int, c_int, c_int, _u8p, c_int]
         L.orc_glibc_sincosf_range.argtypes = [ctypes.c_uint32, ctypes.c_uint32, _f32p, _f32p]
+        L.orc_predict_scale_range.argtypes = [ctypes.c_uint32, ctypes.c_uint32, c_float, c_int,
+                                              np.ctypeslib.ndpointer(dtype=np.int8, flags="C_CONTIGUOUS")]
         _lib = L
     return _lib
 
@@ -209,6 +211,14 @@ def glibc_sincosf_range(lo_bits: int, hi_bits: int):
     c = np.empty(n, np.float32); s = np.empty(n, np.float32)
     lib().orc_glibc_sincosf_range(lo_bits, hi_bits, c, s)
     return c, s
+
+
+def predict_scale_range(lo_bits: int, hi_bits: int, log_sf: float, n_levels: int):
+    """MapPoint::PredictScale (as search_local_points computes it) of every float whose bit pattern
+    lies in [lo_bits, hi_bits] -> int8 levels."""
+    out = np.empty(hi_bits - lo_bits + 1, np.int8)
+    lib().orc_predict_scale_range(lo_bits, hi_bits, log_sf, n_levels, out)
+    return out
 
 
 def ba_solve(prob):

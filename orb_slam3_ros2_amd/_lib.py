@@ -298,6 +298,14 @@ def lib():
     L.orbhip_test_kfdb_members.argtypes = [vp, i32, vp, vp, vp]
     # the stored list capacity of the Sim3 projection search (tests build a chain deeper than it)
     L.orbhip_test_sim3_list_cap.argtypes = []
+    # host only: the projection searches' route for a call's sizes; the last search on a context
+    L.orbhip_test_proj_route.argtypes = [i32, i32, i32, vp]
+    L.orbhip_test_proj_stats.argtypes = [vp, vp]
+    # the device's PredictScale against host levels over a range of float bit patterns
+    L.orbhip_test_predict_scale_sweep.argtypes = [ctypes.c_uint32, ctypes.c_uint32, f32, i32, vp]
+    L.orbhip_test_predict_scale_sweep.restype = ctypes.c_int64
+    # host only: the steps the device compares a ratio against (one per level, from the host's log)
+    L.orbhip_test_level_thresholds.argtypes = [f32, i32, vp]
     _lib = L
     return L
 

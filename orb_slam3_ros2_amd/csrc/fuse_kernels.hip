@@ -152,8 +152,8 @@ constexpr int kFuseSplit = 4;
 // z = Pc.z, read by the stereo form only (set from step 2 on).
 struct FuseWin { float u, v, r; int lvl, x0, x1, y0, y1; float z; };
 __device__ __forceinline__ bool fuse_gates(const FuseKf& f, const DevPoints& mp, int m,
-                                           const float* __restrict__ scale_factors, int n_levels, float log_sf,
-                                           float th, FuseWin& w) {
+                                           const float* __restrict__ scale_factors, int n_levels,
+                                           const LevelSteps& steps, float th, FuseWin& w) {
     w.lvl = -1;
     const float P[3] = {mp.pts[3 * m], mp.pts[3 * m + 1], mp.pts[3 * m + 2]};
     // 1. Sophus SE3f * p
@@ -173,9 +173,8 @@ __device__ __forceinline__ bool fuse_gates(const FuseKf& f, const DevPoints& mp,
     // 5. viewing angle
     const float* Pn = mp.nrm + 3 * m;
     if ((PO[0] * Pn[0] + PO[1] * Pn[1]) + PO[2] * Pn[2] < 0.5f * dist3D) return false;
-    // 6. MapPoint::PredictScale (clamped before the conversion: the same for every finite value)
-    const float fl = ceilf(logf(maxd / dist3D) / log_sf);
-    const int lvl = !(fl > 0.0f) ? 0 : (fl >= (float)n_levels ? n_levels - 1 : (int)fl);
+    // 6. MapPoint::PredictScale
+    const int lvl = predict_scale(maxd / dist3D, steps, scale_factors + n_levels, n_levels);
     w.lvl = lvl;
     // 7. radius
     const float r = th * scale_factors[lvl];
@@ -210,7 +209,7 @@ __global__ __launch_bounds__(kFuseThreads) void k_fuse_search(const FuseKf* __re
                                                               const uint8_t* __restrict__ pair_skip,
                                                               const float* __restrict__ scale_factors,
                                                               const float* __restrict__ inv_level_sigma2,
-                                                              int n_levels, float log_sf, float th,
+                                                              int n_levels, LevelSteps steps, float th,
                                                               const int32_t* __restrict__ cell_start,
                                                               const FuseRec* __restrict__ recs,
                                                               const uint8_t* __restrict__ kf_desc,
@@ -234,7 +233,7 @@ __global__ __launch_bounds__(kFuseThreads) void k_fuse_search(const FuseKf* __re
         if (mp.skip[m]) break;
         if (pair_skip && pair_skip[(int64_t)b * mp.n + m]) break;
         FuseWin w;
-        const bool in = fuse_gates(f, mp, m, scale_factors, n_levels, log_sf, th, w);
+        const bool in = fuse_gates(f, mp, m, scale_factors, n_levels, steps, th, w);
         outLvl = w.lvl;
         if (!in) break;
         const float u = w.u, v = w.v, r = w.r;
@@ -325,7 +324,7 @@ template <int S>
 __global__ __launch_bounds__(kFuseThreads) void k_sim3_search(const FuseKf* __restrict__ kfs, DevPoints mp,
                                                               const uint8_t* __restrict__ claimed,
                                                               const float* __restrict__ scale_factors, int n_levels,
-                                                              float log_sf, float th, float thr,
+                                                              LevelSteps steps, float th, float thr,
                                                               const int32_t* __restrict__ cell_start,
                                                               const FuseRec* __restrict__ recs,
                                                               const uint8_t* __restrict__ kf_desc, Sim3Work wk,
@@ -341,7 +340,7 @@ __global__ __launch_bounds__(kFuseThreads) void k_sim3_search(const FuseKf* __re
     FuseWin w;
     w.lvl = -1; w.u = w.v = w.r = w.z = 0.0f; w.x0 = w.x1 = w.y0 = w.y1 = 0;
     bool in = false;
-    if (m < mp.n && !mp.skip[m]) in = fuse_gates(f, mp, m, scale_factors, n_levels, log_sf, th, w);
+    if (m < mp.n && !mp.skip[m]) in = fuse_gates(f, mp, m, scale_factors, n_levels, steps, th, w);
     if (in) {
         const uint4* dm = (const uint4*)(mp.desc + (int64_t)m * 32);
         const uint4 da = dm[0], db = dm[1];
@@ -508,11 +507,12 @@ static void launch_sim3_search(const FuseKf* kf, const DevPoints& mp, const uint
                                const orbhip_kp* kps, const uint8_t* kf_desc, int nk, int32_t* cell_start,
                                FuseRec* recs, const Sim3Work& w, int32_t* match, int32_t* match_dist, int32_t* level,
                                int32_t* nmatches, hipStream_t st) {
+    const LevelSteps steps = level_steps(log_sf, n_levels);
     ORBHIP_LAUNCH(k_fuse_grid<false>, dim3(1), dim3(kFuseGridThreads), 0, st, kf, kps, cell_start, recs, nmatches,
                   (const float*)nullptr, (float*)nullptr);
     const unsigned tiles = (unsigned)(((int64_t)mp.n * kFuseSplit + kFuseThreads - 1) / kFuseThreads);
     ORBHIP_LAUNCH(k_sim3_search<kFuseSplit>, dim3(tiles), dim3(kFuseThreads), 0, st, kf, mp, claimed, scale_factors,
-                  n_levels, log_sf, th, thr, (const int32_t*)cell_start, (const FuseRec*)recs, kf_desc, w, level);
+                  n_levels, steps, th, thr, (const int32_t*)cell_start, (const FuseRec*)recs, kf_desc, w, level);
     ORBHIP_LAUNCH(k_sim3_resolve, dim3(1), dim3(kSim3ResolveThreads), 0, st, mp, claimed, thr, nk,
                   (const int32_t*)cell_start, (const FuseRec*)recs, kf_desc, w, match, match_dist, nmatches);
 }
@@ -527,11 +527,12 @@ static void launch_fuse(const FuseKf* kfs, int B, const DevPoints& mp, const uin
                         int32_t* best_idx, int32_t* best_dist, int32_t* level, int32_t* nfused, hipStream_t st,
                         const float* ur = nullptr, float* ur_cell = nullptr, const float* kf_bf = nullptr) {
     const unsigned tiles = (unsigned)(((int64_t)mp.n * kFuseSplit + kFuseThreads - 1) / kFuseThreads);
+    const LevelSteps steps = level_steps(log_sf, n_levels);
     if (ur) {   // the stereo form: ur / ur_cell one per keypoint of the call, kf_bf B
         ORBHIP_LAUNCH(k_fuse_grid<true>, dim3((unsigned)B), dim3(kFuseGridThreads), 0, st, kfs, kps, cell_start, recs,
                       nfused, ur, ur_cell);
         ORBHIP_LAUNCH((k_fuse_search<kFuseSplit, true, true>), dim3(tiles, (unsigned)B), dim3(kFuseThreads), 0, st, kfs,
-                      mp, pair_skip, scale_factors, inv_level_sigma2, n_levels, log_sf, th, (const int32_t*)cell_start,
+                      mp, pair_skip, scale_factors, inv_level_sigma2, n_levels, steps, th, (const int32_t*)cell_start,
                       (const FuseRec*)recs, kf_desc, best_idx, best_dist, level, nfused, (const float*)ur_cell, kf_bf);
         return;
     }
@@ -539,12 +540,12 @@ static void launch_fuse(const FuseKf* kfs, int B, const DevPoints& mp, const uin
                   nfused, (const float*)nullptr, (float*)nullptr);
     if (inv_level_sigma2)
         ORBHIP_LAUNCH((k_fuse_search<kFuseSplit, true>), dim3(tiles, (unsigned)B), dim3(kFuseThreads), 0, st, kfs, mp,
-                      pair_skip, scale_factors, inv_level_sigma2, n_levels, log_sf, th, (const int32_t*)cell_start,
+                      pair_skip, scale_factors, inv_level_sigma2, n_levels, steps, th, (const int32_t*)cell_start,
                       (const FuseRec*)recs, kf_desc, best_idx, best_dist, level, nfused, (const float*)nullptr,
                       (const float*)nullptr);
     else
         ORBHIP_LAUNCH((k_fuse_search<kFuseSplit, false>), dim3(tiles, (unsigned)B), dim3(kFuseThreads), 0, st, kfs, mp,
-                      pair_skip, scale_factors, inv_level_sigma2, n_levels, log_sf, th, (const int32_t*)cell_start,
+                      pair_skip, scale_factors, inv_level_sigma2, n_levels, steps, th, (const int32_t*)cell_start,
                       (const FuseRec*)recs, kf_desc, best_idx, best_dist, level, nfused, (const float*)nullptr,
                       (const float*)nullptr);
 }
@@ -589,14 +590,14 @@ int fuse_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_f
     if (!best_idx || !mps->points || !mps->normals || !mps->min_dist || !mps->max_dist || !mps->desc)
         return ORBHIP_ERR_ARG;
     // one block, the same layout on the host (pinned) and the device:
-    // [keyframes B | scale factors | inv sigma2 | points normals min max desc skip | pair_skip B x n |
+    // [keyframes B | scale factors, level steps | inv sigma2 | points normals min max desc skip | pair_skip B x n |
     //  keypoints | keyframe descriptors | stereo: mvuRight, mbf B], then device only [cell_start B x 3073 |
     //  records | stereo: mvuRight in cell order | nfused B, best_idx B x n, best_dist B x n, level B x n];
     //  the last segment is read back
     StageLayout lay(16);
     const size_t bn = (size_t)B * (size_t)n;
     const size_t o_kf = lay.take((size_t)B * sizeof(FuseKf));
-    const size_t o_sf = lay.take((size_t)L * 4), o_s2 = lay.take(chi2 ? (size_t)L * 4 : 0);
+    const size_t o_sf = lay.take((size_t)L * 8), o_s2 = lay.take(chi2 ? (size_t)L * 4 : 0);   // + PredictScale's steps
     const PointsLayout o_mp(lay, (size_t)n);
     const size_t o_pskip = lay.take(pair_skip ? bn : 0);
     const size_t o_kps = lay.take(nk_total * sizeof(orbhip_kp)), o_kdesc = lay.take(nk_total * 32);
@@ -622,6 +623,7 @@ int fuse_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_f
     }
     if (sx) S.put(o_bf, sx->bf, (size_t)B * 4);
     S.put(o_sf, kfs[0].scale_factors, (size_t)L * 4);
+    S.put(o_sf + (size_t)L * 4, level_thresholds(kfs[0].log_scale_factor, L), (size_t)L * 4);
     if (chi2) S.put(o_s2, inv_level_sigma2, (size_t)L * 4);
     const DevPoints mp = o_mp.put(S, *mps, true);   // the kernels read skip unconditionally
     if (pair_skip) S.put(o_pskip, pair_skip, bn);
@@ -666,11 +668,11 @@ int sim3_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_f
     if (!match || !mps->points || !mps->normals || !mps->min_dist || !mps->max_dist || !mps->desc) return ORBHIP_ERR_ARG;
     const float thr = 50.0f * ratio_hamming;
     // one block, the same layout on the host (pinned) and the device:
-    // [keyframe | scale factors | points normals min max desc skip | claimed | keypoints | descriptors],
+    // [keyframe | scale factors, level steps | points normals min max desc skip | claimed | keypoints | descriptors],
     // then device only [cell_start 3073 | records | windows n | lists n x 8 | counts n | picks 2 x n |
     //  owners | nmatches, match n, match_dist n, level n]; the last segment is read back
     StageLayout lay(16);
-    const size_t o_kf = lay.take(sizeof(FuseKf)), o_sf = lay.take((size_t)L * 4);
+    const size_t o_kf = lay.take(sizeof(FuseKf)), o_sf = lay.take((size_t)L * 8);   // + PredictScale's steps
     const PointsLayout o_mp(lay, (size_t)n);
     const size_t o_claimed = lay.take(nk), o_kps = lay.take(nk * sizeof(orbhip_kp)), o_kdesc = lay.take(nk * 32);
     const size_t up_bytes = lay.total();
@@ -686,6 +688,7 @@ int sim3_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_f
     uint8_t* const h = S.h;
     fuse_kf_params(*kf, 0, (FuseKf*)(h + o_kf));
     S.put(o_sf, kf->scale_factors, (size_t)L * 4);
+    S.put(o_sf + (size_t)L * 4, level_thresholds(kf->log_scale_factor, L), (size_t)L * 4);
     const DevPoints mp = o_mp.put(S, *mps, true);   // the kernels read skip unconditionally
     S.put_or_zero(o_claimed, kf->claimed, nk);
     put_keyframe(S, o_kps, o_kdesc, 0, kf->kps, kf->desc, nk);

@@ -40,6 +40,28 @@ __device__ __forceinline__ int grid_cell(float minx, float miny, float invw, flo
     return (px < 0 || px >= kGridCols || py < 0 || py >= kGridRows) ? outside : px * kGridRows + py;
 }
 
+// MapPoint::PredictScale: ceil(log(ratio) / mfLogScaleFactor) clamped to [0, n_levels - 1], the one
+// definition of isInFrustum's and Fuse's level. The reference takes the logarithm from the host's
+// libm, and the device's logf differs from it in the last bit often enough to move the ceiling at a
+// few ratios next to a step (1 of the 33 554 432 floats in [0.5, 8) at 1.2 / 8 levels, 3 next to the
+// powers of two at 2.0 / 8 levels), so the device takes no logarithm: the level is monotone in the
+// ratio, the host finds the smallest float ratio of every level with its own log (level_thresholds,
+// stage.h) and the device counts the steps at or below the ratio. The first kStepArgs steps travel in
+// the kernel arguments (LevelSteps: scalar registers, no memory round trip before the level is
+// known; NaN beyond n_levels, which no ratio reaches), the steps of a deeper pyramid are read from
+// thr: n_levels floats behind the scale factors of the call's block, thr[0] unused.
+// orbhip_test_predict_scale_sweep compares this function with the host's level over float ranges.
+constexpr int kStepArgs = 16;
+struct LevelSteps { float thr[kStepArgs]; };
+__device__ __forceinline__ int predict_scale(float ratio, const LevelSteps& steps, const float* __restrict__ thr,
+                                             int n_levels) {
+    int lvl = 0;
+#pragma unroll
+    for (int k = 1; k < kStepArgs; k++) lvl += ratio >= steps.thr[k] ? 1 : 0;
+    for (int k = kStepArgs; k < n_levels; k++) lvl += ratio >= thr[k] ? 1 : 0;
+    return lvl;
+}
+
 // Hamming distance of the 256-bit descriptors (a, b) and (c, d)
 __device__ __forceinline__ int hamming256(uint4 a, uint4 b, uint4 c, uint4 d) {
     return __popc(a.x ^ c.x) + __popc(a.y ^ c.y) + __popc(a.z ^ c.z) + __popc(a.w ^ c.w) + __popc(b.x ^ d.x) +

@@ -810,6 +810,21 @@ int orbhip_test_match_route(int npairs, int max_q, int max_t, int fused_allowed,
     return ORBHIP_OK;
 }
 
+// host only (no device): the projection searches' decisions for a call's sizes (the functions
+// proj_search_last / proj_search_local call, under the current ORBHIP_PROJ_* switches). out4 =
+// {1 = the list form applies, ent_cap, list capacity, 1 = one launch}; max_octave stands for the
+// largest octave among the frame's keypoints
+int orbhip_test_proj_route(int n, int nq, int max_octave, int32_t* out4) {
+    return proj_test_route(n, nq, max_octave, out4);
+}
+// the last projection search on this context: out4 = {form (0 lists + resolve, 1 a list overflowed
+// and the rounds produced the result, 2 rounds only, -1 none yet or no queries), rounds, list
+// entries the resolve saw (form 0), that call's ent_cap}
+int orbhip_test_proj_stats(orbhip_ctx* c, int32_t* out4) {
+    if (!c) return ORBHIP_ERR_ARG;
+    return proj_test_stats(c->proj, out4);
+}
+
 // the persistent KeyFrame members of a KeyFrameDatabase (mode 0: mnRelocQuery / mnRelocWords /
 // mRelocScore, mode 1: the mnPlaceRecognition* ones), max_kf entries each, after a stream sync
 int orbhip_test_kfdb_members(orbhip_kfdb* db, int mode, int64_t* query, int32_t* words, float* score) {
@@ -851,6 +866,40 @@ int64_t orbhip_test_sincosf_sweep(uint32_t lo, uint32_t hi, const float* ref_c, 
     (void)hipMemcpy(&hm, dm, 8, hipMemcpyDeviceToHost);
     (void)hipFree(dc); (void)hipFree(ds); (void)hipFree(dm);
     return (int64_t)hm;
+}
+
+// host only (no device): PredictScale's steps as the searches hand them to the device
+// (level_thresholds, stage.h): n_levels floats, out[0] unused
+int orbhip_test_level_thresholds(float log_sf, int n_levels, float* out) {
+    if (!out || n_levels < 1 || n_levels > 127) return ORBHIP_ERR_ARG;
+    std::memcpy(out, level_thresholds(log_sf, n_levels), 4 * (size_t)n_levels);
+    return ORBHIP_OK;
+}
+
+// Compare the device's predict_scale (geom.h) with host levels (int8, one per float) over the
+// float bit range [lo, hi]; returns the number of ratios whose level differs.
+int64_t orbhip_test_predict_scale_sweep(uint32_t lo, uint32_t hi, float log_sf, int n_levels, const int8_t* ref) {
+    if (hi < lo || !ref || n_levels < 1 || n_levels > 127) return ORBHIP_ERR_ARG;
+    const size_t n = (size_t)hi - lo + 1;
+    int8_t* dr = nullptr;
+    float* dt = nullptr;
+    unsigned long long* dm = nullptr;
+    unsigned long long hm = 0;
+    if (hipMalloc((void**)&dr, n) != hipSuccess) return ORBHIP_ERR_DEVICE;
+    if (hipMalloc((void**)&dm, 8) != hipSuccess) { (void)hipFree(dr); return ORBHIP_ERR_DEVICE; }
+    if (hipMalloc((void**)&dt, 4 * (size_t)n_levels) != hipSuccess) {
+        (void)hipFree(dr); (void)hipFree(dm);
+        return ORBHIP_ERR_DEVICE;
+    }
+    const float* thr = level_thresholds(log_sf, n_levels);
+    bool ok = hipMemset(dm, 0, 8) == hipSuccess && hipMemcpy(dr, ref, n, hipMemcpyHostToDevice) == hipSuccess &&
+              hipMemcpy(dt, thr, 4 * (size_t)n_levels, hipMemcpyHostToDevice) == hipSuccess;
+    if (ok) {
+        launch_predict_scale_sweep(lo, hi, log_sf, dt, n_levels, dr, dm, nullptr);
+        ok = hipDeviceSynchronize() == hipSuccess && hipMemcpy(&hm, dm, 8, hipMemcpyDeviceToHost) == hipSuccess;
+    }
+    (void)hipFree(dr); (void)hipFree(dm); (void)hipFree(dt);
+    return ok ? (int64_t)hm : (int64_t)ORBHIP_ERR_DEVICE;
 }
 
 // the extractor's hooks (extract.cpp): one frame's intermediates, its FAST candidate count, a

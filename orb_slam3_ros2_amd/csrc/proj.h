@@ -25,6 +25,12 @@ int proj_search_last(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_proj
 int proj_search_local(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_local_points* M, float view_cos_limit,
                       float th, float nnratio, int far_points, float th_far, uint8_t* in_view, int32_t* level,
                       int32_t* match, int* rounds_out, hipStream_t st, const ProjStereo* sx = nullptr);
+// test hooks (orbhip_test_proj_route, _proj_stats, _predict_scale_sweep)
+int proj_test_route(int n, int nq, int max_octave, int32_t* out4);
+int proj_test_stats(const ProjWorkspace* ws, int32_t* out4);
+// (thr: level_thresholds(log_sf, n_levels) in device memory)
+void launch_predict_scale_sweep(uint32_t lo_bits, uint32_t hi_bits, float log_sf, const float* thr, int n_levels,
+                                const int8_t* ref, unsigned long long* mismatches, hipStream_t st);
 int init_search(ProjWorkspace* ws, const orbhip_init_frame* F1, const orbhip_init_frame* F2, float* prev_matched,
                 int window_size, float nnratio, int check_orientation, int32_t* matches12, hipStream_t st);
 }  // namespace orbhip

@@ -113,11 +113,12 @@ __global__ void k_proj_prep_last(ProjFrame f, int nq, PrepLast a, Query* __restr
 struct PrepLocal {
     const float *pts, *nrm, *mind, *maxd;
     const uint8_t* skip;
-    const float* scale;
+    const float* scale;   // the scale factors, then PredictScale's steps (level_thresholds)
     int n_levels;
-    float log_sf, view_cos_limit, th;
+    float view_cos_limit, th;
     int far_points;
     float th_far;
+    LevelSteps steps;     // the first of them, in the kernel arguments
 };
 __device__ __forceinline__ Query prep_local(const ProjFrame& f, const PrepLocal& a, int m, uint8_t* iv_out,
                                             int* lvl_out, float* xr_out) {
@@ -145,9 +146,7 @@ __device__ __forceinline__ Query prep_local(const ProjFrame& f, const PrepLocal&
         const float viewCos = (PO[0] * Pn[0] + PO[1] * Pn[1] + PO[2] * Pn[2]) / dist;
         if (viewCos < a.view_cos_limit) break;
         const float ratio = a.maxd[m] / dist;
-        int nScale = (int)ceilf(logf(ratio) / a.log_sf);   // MapPoint::PredictScale
-        if (nScale < 0) nScale = 0;
-        else if (nScale >= a.n_levels) nScale = a.n_levels - 1;
+        const int nScale = predict_scale(ratio, a.steps, a.scale + a.n_levels, a.n_levels);
         iv = 1;
         lvl = nScale;
         const float invz = 1.0f / Pc[2];
@@ -573,7 +572,8 @@ __global__ __launch_bounds__(1024) void k_proj_lists(ProjFrame f, int nq, PrepLa
     TR_END(7)
 }
 
-// res[0] = matches, res[1] = status (1: a list overflowed, nothing else written), res[2] = rounds.
+// res[0] = matches, res[1] = status (1: a list overflowed, nothing else written), res[2] = rounds,
+// res[3] = the list entries in all (orbhip_test_proj_stats).
 // LDS rsm: 3 owner tables (n ints), the list offsets (nq ints), then the lists themselves when
 // they fit the rest (`ent_cap` entries; else the rounds read them from global memory). The lists,
 // their counts and pick0 are read with agent-scope (sc1) loads: in the one-launch form they were
@@ -719,6 +719,7 @@ __device__ void resolve_body(unsigned char* rsm, int n, int nq, float nnratio, i
         res[0] = cnt;
         res[1] = 0;
         res[2] = r + 1;
+        res[3] = run;
     }
     mark(5);
 }
@@ -1265,6 +1266,10 @@ struct ProjWorkspace {
     int* arrive = nullptr;   // the one-launch search's arrival counter (0 between launches)
     int ahead = 4;   // rounds launched per host sync (adapts to the last search)
     int init_ahead = 6;   // the same for SearchForInitialization's rounds
+    // the last projection search (orbhip_test_proj_stats): the form that produced the result (0 lists
+    // + resolve, 1 a list overflowed and the rounds produced it, 2 rounds only, -1 none yet or no
+    // queries), its rounds, the list entries the resolve saw (form 0) and the call's ent_cap
+    int st_form = -1, st_rounds = 0, st_entries = 0, st_ent_cap = 0;
     ~ProjWorkspace() {
         if (arrive) (void)hipFree(arrive);
     }
@@ -1342,12 +1347,16 @@ int run_rounds(ProjWorkspace* ws, const ProjFrame& f, int nq, int mode, float nn
 
 // the two-launch form applies: every octave fits the list entry's 4 bits, the owner tables fit LDS
 constexpr size_t kResolveLds = 150 * 1024;   // k_proj_resolve's dynamic LDS
-bool onepass_ok(const orbhip_frame* F, int nq) {
+// (the sizes and the switch alone: orbhip_test_proj_route asks this with the largest octave given)
+bool onepass_sizes_ok(int n, int nq) {
     const char* e = std::getenv("ORBHIP_PROJ_ROUNDS");   // A/B switch (read per call: tests flip it)
-    if ((e && e[0] == '1') || F->n > kProjMaxN || nq > kProjMaxQ || resolve_head_bytes(F->n, nq) > kResolveLds)
-        return false;
+    return !((e && e[0] == '1') || n > kProjMaxN || nq > kProjMaxQ || resolve_head_bytes(n, nq) > kResolveLds);
+}
+bool octave_fits(int octave) { return octave >= 0 && octave <= 15; }
+bool onepass_ok(const orbhip_frame* F, int nq) {
+    if (!onepass_sizes_ok(F->n, nq)) return false;
     for (int k = 0; k < F->n; k++)
-        if (F->kps[k].octave < 0 || F->kps[k].octave > 15) return false;
+        if (!octave_fits(F->kps[k].octave)) return false;
     return true;
 }
 // k_proj_lists' LDS: keypoint records, cells (padded to 256), the waves' index lists
@@ -1388,6 +1397,42 @@ struct OutBlock {
 
 }  // namespace
 
+// orbhip_test_proj_route: the decisions both searches take from a call's sizes, from the functions
+// they call. out4 = {list form applies, ent_cap, list capacity, one launch}
+int proj_test_route(int n, int nq, int max_octave, int32_t* out4) {
+    if (!out4 || n < 0 || nq < 0 || n > 65535 || max_octave < 0) return ORBHIP_ERR_ARG;
+    out4[0] = onepass_sizes_ok(n, nq) && octave_fits(max_octave) ? 1 : 0;
+    out4[1] = resolve_ent_cap(n, nq);
+    out4[2] = proj_cap();
+    out4[3] = proj_fused() ? 1 : 0;
+    return ORBHIP_OK;
+}
+// orbhip_test_proj_stats: the last projection search on this workspace (ProjWorkspace::st_*)
+int proj_test_stats(const ProjWorkspace* ws, int32_t* out4) {
+    if (!out4) return ORBHIP_ERR_ARG;
+    out4[0] = ws ? ws->st_form : -1;
+    out4[1] = ws ? ws->st_rounds : 0;
+    out4[2] = ws ? ws->st_entries : 0;
+    out4[3] = ws ? ws->st_ent_cap : 0;
+    return ORBHIP_OK;
+}
+
+namespace {
+// predict_scale over the floats of bit patterns [lo, hi] against the host's levels
+__global__ void k_predict_scale_sweep(uint32_t lo, uint32_t hi, LevelSteps steps, const float* __restrict__ thr,
+                                      int n_levels, const int8_t* __restrict__ ref, unsigned long long* mism) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > hi - lo) return;
+    if (predict_scale(__uint_as_float(lo + i), steps, thr, n_levels) != (int)ref[i]) atomicAdd(mism, 1ull);
+}
+}  // namespace
+void launch_predict_scale_sweep(uint32_t lo_bits, uint32_t hi_bits, float log_sf, const float* thr, int n_levels,
+                                const int8_t* ref, unsigned long long* mismatches, hipStream_t st) {
+    const uint64_t n = (uint64_t)hi_bits - lo_bits + 1;
+    hipLaunchKernelGGL(k_predict_scale_sweep, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, lo_bits, hi_bits,
+                       level_steps(log_sf, n_levels), thr, n_levels, ref, mismatches);
+}
+
 // twc = -Rcw^T tcw, tlc = Rlw twc + tlw (float, in the order written); forward: tlc.z > b,
 // backward: -tlc.z > b. Decided on the host and passed to the kernels as a uniform.
 int proj_direction(const float cur_q[4], const float cur_t[3], const float last_q[4], const float last_t[3], float b) {
@@ -1409,6 +1454,8 @@ int proj_search_last(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_proj
     for (int i = 0; i < L->n; i++)
         if (L->octave[i] < 0 || L->octave[i] >= F->n_levels) return ORBHIP_ERR_ARG;
     const int n = F->n, nq = L->n;
+    ws->st_form = -1;
+    ws->st_rounds = ws->st_entries = ws->st_ent_cap = 0;
     if (nq == 0) return 0;
     const bool onepass = onepass_ok(F, nq);
     const int cap = proj_cap();
@@ -1464,9 +1511,11 @@ int proj_search_last(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_proj
                                (const int*)(D + o_lcnt), (const int*)(D + o_pick0), ra.match, ra.res);
         HIPOK(hipGetLastError());
         HIPOK(hipStreamSynchronize(st));
+        ws->st_ent_cap = ra.ent_cap;
         if (hres[1] == 0) {
             std::memcpy(match, H + o_out + ob.match, 4 * (size_t)nq);
             if (rounds_out) *rounds_out = hres[2];
+            ws->st_form = 0; ws->st_rounds = hres[2]; ws->st_entries = hres[3];
             return hres[0];
         }
     }
@@ -1487,6 +1536,7 @@ int proj_search_last(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_proj
     if (rounds < 0) return rounds;
     std::memcpy(match, H + o_out + ob.match, 4 * (size_t)nq);
     if (rounds_out) *rounds_out = rounds;
+    ws->st_form = onepass ? 1 : 2; ws->st_rounds = rounds;
     return hres[0];
 }
 
@@ -1499,16 +1549,18 @@ int proj_search_local(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_loc
         return ORBHIP_ERR_ARG;
     if (sx && ((F->n && !sx->u_right) || !(sx->bf > 0.0f))) return ORBHIP_ERR_ARG;
     const int n = F->n, nq = M->n;
+    ws->st_form = -1;
+    ws->st_rounds = ws->st_entries = ws->st_ent_cap = 0;
     if (nq == 0) return 0;
     const bool onepass = onepass_ok(F, nq);
     const int cap = proj_cap();
     if (onepass) HIPOK(proj_lds_attr());
     const OutBlock ob(nq);
-    // uploaded: [keypoints | descriptors | claimed | scale factors | points normals min max desc skip],
+    // uploaded: [keypoints | descriptors | claimed | scale factors, level steps | points normals min max desc skip],
     // then device only as proj_search_last
     StageLayout lay(256);
     const size_t o_kps = lay.take(sizeof(orbhip_kp) * n), o_kd = lay.take(32 * (size_t)n), o_cl = lay.take(n);
-    const size_t o_scale = lay.take(sizeof(float) * F->n_levels);
+    const size_t o_scale = lay.take(sizeof(float) * 2 * F->n_levels);   // + PredictScale's steps
     const PointsLayout o_mp(lay, (size_t)nq);
     const size_t o_qd = o_mp.desc;
     const size_t o_ur = lay.take(sx ? 4 * (size_t)n : 0);
@@ -1528,6 +1580,8 @@ int proj_search_local(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_loc
     put_keyframe(S, o_kps, o_kd, 0, F->kps, F->desc, n);
     if (F->claimed) S.put(o_cl, F->claimed, n);
     S.put(o_scale, F->scale_factors, sizeof(float) * F->n_levels);
+    S.put(o_scale + sizeof(float) * F->n_levels, level_thresholds(F->log_scale_factor, F->n_levels),
+          sizeof(float) * F->n_levels);
     const DevPoints mp = o_mp.put(S, *M, false);   // no skip array: a null pointer
     if (sx) S.put(o_ur, sx->u_right, 4 * (size_t)n);
     HIPOK(upload_inputs(S.hd, D, H, o_in_end, st));
@@ -1535,8 +1589,8 @@ int proj_search_local(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_loc
     if (sx) f.bf = sx->bf;
     const float* dur = sx ? (const float*)(D + o_ur) : nullptr;
     const PrepLocal pc{mp.pts, mp.nrm, mp.mind, mp.maxd, mp.skip,
-                       (const float*)(D + o_scale), F->n_levels, F->log_scale_factor, view_cos_limit, th, far_points,
-                       th_far};
+                       (const float*)(D + o_scale), F->n_levels, view_cos_limit, th, far_points, th_far,
+                       level_steps(F->log_scale_factor, F->n_levels)};
     const uint8_t* dcl = F->claimed ? (const uint8_t*)(D + o_cl) : nullptr;
     uint8_t* d_iv = (uint8_t*)(D + o_out + ob.iv);
     int* d_lvl = (int*)(D + o_out + ob.lvl);
@@ -1568,9 +1622,11 @@ int proj_search_local(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_loc
                                ra.match, ra.res);
         HIPOK(hipGetLastError());
         HIPOK(hipStreamSynchronize(st));
+        ws->st_ent_cap = ra.ent_cap;
         if (hres[1] == 0) {
             outputs();
             if (rounds_out) *rounds_out = hres[2];
+            ws->st_form = 0; ws->st_rounds = hres[2]; ws->st_entries = hres[3];
             return hres[0];
         }
     }
@@ -1592,6 +1648,7 @@ int proj_search_local(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_loc
     if (rounds < 0) return rounds;
     outputs();
     if (rounds_out) *rounds_out = rounds;
+    ws->st_form = onepass ? 1 : 2; ws->st_rounds = rounds;
     return hres[0];
 }
 

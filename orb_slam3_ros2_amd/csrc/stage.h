@@ -31,6 +31,7 @@ struct StageLayout {
 #include <cstring>
 
 #include "../../include/orbhip.h"
+#include "geom.h"
 
 // `return ORBHIP_ERR_DEVICE` from the calling function, with a line on stderr, when a HIP call fails
 #define ORBHIP_HIPOK(unit, x)                                                                      \
@@ -71,6 +72,15 @@ struct StageBlock {
 // Staged host inputs (pinned block h, its device alias hd) to device memory d by a shader copy
 // (small blocks: no DMA-engine start-up); ORBHIP_PROJ_DMA=1 uses hipMemcpyAsync.
 hipError_t upload_inputs(const void* hd, void* d, const void* h, size_t bytes, hipStream_t st);
+
+// PredictScale's steps for a scale pyramid (geom.h predict_scale): n_levels floats, thr[k] = the
+// smallest float ratio whose level ceil(log(ratio) / log_sf), clamped to [0, n_levels - 1], is >= k
+// with the host's own log (a bisection over the float bit patterns: the level is monotone in the
+// ratio), +inf where no ratio reaches k; thr[0] = 0, unused. Computed once per (log_sf, n_levels)
+// and kept for the process; the pointer stays valid.
+const float* level_thresholds(float log_sf, int n_levels);
+// their first kStepArgs as a kernel argument (NaN from n_levels on)
+LevelSteps level_steps(float log_sf, int n_levels);
 
 // An orbhip_local_points in a block. The segments are taken in the order points, normals,
 // min_dist, max_dist, desc, skip; put() copies the arrays in and returns them as the kernels see them.

@@ -2,7 +2,13 @@
 #include "stage.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
+#include <limits>
+#include <map>
+#include <mutex>
+#include <utility>
+#include <vector>
 
 namespace orbhip {
 
@@ -54,6 +60,53 @@ hipError_t upload_inputs(const void* hd, void* d, const void* h, size_t bytes, h
     hipLaunchKernelGGL(k_upload, dim3((unsigned)((n16 + 511) / 512)), dim3(256), 0, st, (const uint4*)hd, (uint4*)d,
                        n16);
     return hipGetLastError();
+}
+
+namespace {
+// MapPoint::PredictScale on the host (clamped before the conversion: the same for every finite value)
+int host_predict_scale(float ratio, float log_sf, int n_levels) {
+    const float fl = std::ceil(std::log(ratio) / log_sf);
+    return !(fl > 0.0f) ? 0 : (fl >= (float)n_levels ? n_levels - 1 : (int)fl);
+}
+float float_of_bits(uint32_t b) {
+    float f;
+    std::memcpy(&f, &b, 4);
+    return f;
+}
+}  // namespace
+
+const float* level_thresholds(float log_sf, int n_levels) {
+    static std::mutex mu;
+    static std::map<std::pair<uint32_t, int>, std::vector<float>> cache;
+    uint32_t key;
+    std::memcpy(&key, &log_sf, 4);
+    const std::lock_guard<std::mutex> lock(mu);
+    std::vector<float>& thr = cache[{key, n_levels}];
+    if (thr.empty()) {
+        thr.assign((size_t)std::max(n_levels, 1), 0.0f);
+        const uint32_t inf = 0x7F800000u;   // the positive floats in bit order: 1 (the least subnormal) .. +inf
+        for (int k = 1; k < n_levels; k++) {
+            if (host_predict_scale(float_of_bits(inf), log_sf, n_levels) < k) {
+                thr[k] = std::numeric_limits<float>::infinity();
+                continue;
+            }
+            uint32_t lo = 1u, hi = inf;   // the least bit pattern whose level is >= k lies in [lo, hi]
+            while (lo < hi) {
+                const uint32_t mid = lo + (hi - lo) / 2;
+                if (host_predict_scale(float_of_bits(mid), log_sf, n_levels) >= k) hi = mid;
+                else lo = mid + 1;
+            }
+            thr[k] = float_of_bits(lo);
+        }
+    }
+    return thr.data();
+}
+
+LevelSteps level_steps(float log_sf, int n_levels) {
+    const float* thr = level_thresholds(log_sf, n_levels);
+    LevelSteps s;
+    for (int k = 0; k < kStepArgs; k++) s.thr[k] = k < n_levels ? thr[k] : std::numeric_limits<float>::quiet_NaN();
+    return s;
 }
 
 }  // namespace orbhip

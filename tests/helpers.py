@@ -166,6 +166,29 @@ def match_route(npairs: int, max_q: int, max_t: int, fused_allowed: bool = True)
     return {"kernel": "fused" if out[0] == 0 else f"tc{out[0]}", "nch": out[1], "xrun": out[2], "pk": out[3]}
 
 
+def proj_route(n: int, nq: int, max_octave: int = 0) -> dict:
+    """The projection searches' decisions for a call's sizes (the functions both searches call),
+    under the current ORBHIP_PROJ_* switches: lists = the list/resolve form applies (max_octave
+    stands for the keypoints' largest octave), ent_cap = list entries the resolve holds in LDS,
+    cap = entries per list, fused = one launch."""
+    import ctypes
+    from orb_slam3_ros2_amd._lib import lib
+    out = (ctypes.c_int32 * 4)()
+    assert lib().orbhip_test_proj_route(n, nq, max_octave, out) == 0
+    return {"lists": bool(out[0]), "ent_cap": out[1], "cap": out[2], "fused": bool(out[3])}
+
+
+def proj_stats(ctx) -> dict:
+    """The last projection search on this context: form 0 = lists + resolve, 1 = a list overflowed
+    and the rounds produced the result, 2 = rounds only, -1 = none yet or no queries; its rounds;
+    the list entries the resolve saw (form 0) and that call's ent_cap."""
+    import ctypes
+    from orb_slam3_ros2_amd._lib import lib
+    out = (ctypes.c_int32 * 4)()
+    assert lib().orbhip_test_proj_stats(ctx.handle, out) == 0
+    return {"form": out[0], "rounds": out[1], "entries": out[2], "ent_cap": out[3]}
+
+
 class PlantedSet:
     """q (nq, 32) / qa (nq,), t (nt, 32) / ta (nt,); per query: train (the train it was planted
     from, -1 = random query), bin (its rotation bin), flips (its distance to that train)."""

@@ -15,9 +15,10 @@ from orb_slam3_ros2_amd.synthetic import synthetic_projection_scene
 
 
 # the device forms: the one-launch list/resolve path (default), the same as two launches, the list
-# path overflowing into the round kernels (list capacity 2), and the round kernels alone
+# path overflowing into the round kernels (list capacity 2), the round kernels alone, and the
+# default form with the inputs uploaded by hipMemcpyAsync
 PROJ_MODES = {"lists": {}, "two": {"ORBHIP_PROJ_TWO": "1"}, "overflow": {"ORBHIP_PROJ_CAP": "2"},
-              "rounds": {"ORBHIP_PROJ_ROUNDS": "1"}}
+              "rounds": {"ORBHIP_PROJ_ROUNDS": "1"}, "dma": {"ORBHIP_PROJ_DMA": "1"}}
 
 
 @pytest.fixture(params=list(PROJ_MODES))
