@@ -70,7 +70,7 @@ struct BaArgs {
     const int* items; int nitems;
     const int* fin; int nfin;
     const int* ifin;
-    LmCtl* ctl;        // device-driven solve: this problem's LM state (nullptr: host-driven rounds)
+    LmCtl* ctl;        // this problem's LM state (every solve has one; null only in the Cholesky test hooks)
     double* part;      // workgroup partial sums of a trial: chi2 (npart_e = ceil(E / 256)), then the
     int npart_e, npart_m;   // landmark scale terms (npart_m = ceil(M / 256)); in the build phase
                             // k_ba_lin's per-workgroup max diagonal (ceil(M / 256) + ceil(np / 4))

@@ -4,15 +4,15 @@
 //
 // Batched: every kernel runs over grid.y = the problems (problem index from act[]), so B
 // independent problems (SURVEY.md §8e "replicas": concurrent maps / agents, or a batch of local
-// windows) share each launch. The device-driven solve advances every problem by one LM trial per
-// slot with no host round trip (the g2o control flow on the device, LmCtl); the host-driven
-// rounds of r01 remain for the sharded solves. fp64 throughout:
+// windows) share each launch. Every solve is device-driven: a slot advances every problem by one LM
+// trial with no host round trip (the g2o control flow on the device, LmCtl). The sharded solves run
+// the same slots with their collectives between the kernels and the controller's sums split from
+// its decisions (BaArgs::sync). fp64 throughout:
 //   k_ba_errors        EdgeSE3ProjectXYZ::computeError + RobustKernelHuber::robustify; in a trial
 //                      its last workgroup per problem runs the LM controller step (ctl_end_body)
 //   k_ba_lin           linearizeOplus + constructQuadraticForm: landmark side (Hll, b_l, the
 //                      edge records) and pose side (Hpp, b_p, one wave per pose) in one launch;
 //                      its last workgroup per problem starts the trial (ctl_begin_body)
-//                      (k_ba_lin_points / k_ba_lin_poses: the same bodies for host-driven rounds)
 //   k_ba_schur_points  setLambda on Hll, Dinv (Eigen 3x3 cofactor inverse), db
 //   k_ba_schur_items   S_ij = [i==j](Hpp_i + lambda I) - sum W_a Hpl_b^T over shared landmarks,
 //                      matrix-free; its trailing workgroups compute b_schur = b_p - sum Hpl db
@@ -20,8 +20,10 @@
 //   k_chol_dag / k_ba_chol_reg / k_ba_cholesky / k_cb_*   the reduced camera system (ba_chol_*)
 //   k_ba_backsub       xl = Dinv (b_l - Hpl^T xp), X += xl (push: old X saved)
 //                      and T <- exp(xp) * T (SE3Quat::exp, operator*)   (push: old T saved)
-//   k_ba_reduce        activeRobustChi2, computeScale, max diag (host-driven rounds)
+//   k_ba_ctl_init / k_ba_reduce   the initial activeRobustChi2 (k_ba_reduce: a shard's part of it)
 //   k_ba_pop           restore the pushed state of problems whose trial was rejected
+// The host driver below the kernels is ba_solve_batch: a sequence of named steps over one per-call
+// context (BaCall); the host-only problem preparation is ba_prep.cpp.
 // The kernels that form an edge's error or Jacobians (k_ba_errors, k_ba_lin, k_ba_schur_items,
 // k_ba_backsub, k_ba_backsub_errs) are templates on Stereo: false is the monocular problem
 // (EdgeSE3ProjectXYZ alone, every entry point but the stereo ones), true adds the third row of
@@ -31,13 +33,10 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
-#include <atomic>
 #include <chrono>
-#include <condition_variable>
-#include <functional>
-#include <mutex>
 #include <cfloat>
 #include <cmath>
+#include <cstdint>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
@@ -52,6 +51,7 @@
 #include "ba_chol_dag.h"
 #include "ba_nd.h"
 #include "ba_args.h"
+#include "ba_prep.h"
 #include "ba_chol_reg.h"
 #include "ba_se3.h"
 
@@ -84,10 +84,9 @@ __device__ __forceinline__ void ba_xcd_map(int& bx, int& by) {
     ba_xcd_map(bx_, by_);                           \
     const BaArgs& a = args[act[by_]];
 
-// Device-driven rounds: a kernel runs for a problem only in the phase it belongs to (build:
-// linearisation; trial: Schur / solve / update / errors). Host-driven rounds (a.ctl == nullptr)
-// select problems through act[] alone.
-__device__ __forceinline__ bool in_phase(const BaArgs& a, int ph) { return !a.ctl || a.ctl->phase == ph; }
+// A kernel runs for a problem only in the phase it belongs to (build: linearisation; trial: Schur /
+// solve / update / errors); every problem has its controller (a.ctl).
+__device__ __forceinline__ bool in_phase(const BaArgs& a, int ph) { return a.ctl->phase == ph; }
 #define BA_PHASE(ph) \
     if (!in_phase(a, ph)) return;
 
@@ -236,10 +235,7 @@ __device__ __forceinline__ int* done_of(int* const* donep) { return donep ? done
 __device__ __forceinline__ void relay_host_stop(const BaArgs* args, const int* act, int* const* donep) {
     const int* hstop = donep ? donep[1] : nullptr;
     if (!hstop || __hip_atomic_load(hstop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) == 0) return;
-    for (int b = 0; b < (int)gridDim.y; b++) {
-        LmCtl* c = args[act[b]].ctl;
-        if (c) c->stop = 1;
-    }
+    for (int b = 0; b < (int)gridDim.y; b++) args[act[b]].ctl->stop = 1;
 }
 
 template <bool Stereo>
@@ -249,15 +245,15 @@ __global__ __launch_bounds__(256) void k_ba_errors(const BaArgs* __restrict__ ar
     int* const done = done_of(donep);
     if (when == 1) {
         LmCtl* c = a.ctl;
-        const bool ends = c && c->phase == kPhBuild && (c->stop || c->it >= c->iterations);
-        if (c && bx_ == 0 && threadIdx.x == 0) {
+        const bool ends = c->phase == kPhBuild && (c->stop || c->it >= c->iterations);
+        if (bx_ == 0 && threadIdx.x == 0) {
             c->pop = 0;
             if (ends) {
                 c->phase = kPhDone;
                 post_done(done, act[by_]);
             }
         }
-        if (ends || !(in_phase(a, kPhBuild) && (!c || !c->errors_valid))) return;
+        if (ends || !(in_phase(a, kPhBuild) && !c->errors_valid)) return;
     }
     if (when == 2 && !in_phase(a, kPhTrial)) return;
     const bool has = bx_ * (int)blockDim.x < a.E;   // uniform
@@ -270,7 +266,7 @@ __global__ __launch_bounds__(256) void k_ba_errors(const BaArgs* __restrict__ ar
         const double t = block_sum(r0, sh);
         if (threadIdx.x == 0 && has) st_agent(a.part + bx_, t);
         // the row's last workgroup runs the trial's controller step (the former k_ba_ctl_end)
-        if (a.ctl && !a.sync && last_arrival(&a.ctl->arrive_t, gridDim.x, &lastf)) ctl_end_body(a, act[by_], done, sh);
+        if (!a.sync && last_arrival(&a.ctl->arrive_t, gridDim.x, &lastf)) ctl_end_body(a, act[by_], done, sh);
     }
 }
 
@@ -350,54 +346,12 @@ __device__ __forceinline__ double lin_ab(const BaArgs& a, int e, int oi, double*
 // ---------------------------------------------------------------------------
 // buildSystem
 // ---------------------------------------------------------------------------
-// one thread per landmark: Hll, b_l over all its edges; stores each edge's linearisation (Pc, w)
-// returns the largest |diagonal| of Hll (0 for m >= M)
+// four lanes per landmark: Hll, b_l over all its edges (lane sub takes edges sub, sub + 4, ...; the 12
+// sums are added over the quad, a butterfly: the same bits in its lanes, and lane 0 stores them);
+// stores each edge's linearisation (Pc, w); returns the largest |diagonal| of Hll in every lane of
+// the quad (0 for m >= M)
 // fresh: the stored errors belong to a rejected trial (an unsharded problem whose iteration ended
 // on one): each edge's terms are taken from the restored state here, and stored, instead of read
-template <bool Stereo>
-__device__ __forceinline__ double lin_point(const BaArgs& a, int m, bool fresh = false) {
-    if (m >= a.M) return 0.0;
-    double H[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, bl[3] = {0, 0, 0};
-    for (int k = a.pt_ptr[m]; k < a.pt_ptr[m + 1]; k++) {
-        const int e = a.pt_edges[k];
-        double x, y, z, R[9], j[4], js[2] = {0.0, 0.0}, A[JacDim<Stereo>::kA], B[JacDim<Stereo>::kB];
-        edge_pc(a, e, x, y, z, R);
-        proj_jac(a.fx, a.fy, x, y, z, j);
-        if constexpr (Stereo) stereo_jac(a.bf, a.e_ur[e], j, z, js);
-        jac_ab<Stereo>(j, js, x, y, z, R, A, B);
-        double r1, er0, er1, er2 = 0.0;
-        if (fresh) {   // uniform
-            double chi2, r0;
-            edge_terms<Stereo>(a, e, x, y, z, er0, er1, er2, chi2, r0, r1);
-            store_terms<Stereo>(a, e, er0, er1, er2, chi2, r0, r1);
-        } else {
-            r1 = a.e_rho1[e];
-            er0 = a.e_err[2 * e];
-            er1 = a.e_err[2 * e + 1];
-            if constexpr (Stereo) er2 = a.e_err2[e];
-        }
-        const double info = a.e_info[e];
-        const double w = r1 * info;
-        const double om0 = -info * er0 * r1, om1 = -info * er1 * r1;
-        const double om2 = Stereo ? -info * er2 * r1 : 0.0;
-        [[maybe_unused]] constexpr int a2 = Stereo ? 6 : 0, b2 = Stereo ? 12 : 0;   // the third rows of A and B (unused unless Stereo)
-#pragma unroll
-        for (int r = 0; r < 3; r++) {
-            bl[r] += rows_dot<Stereo>(A[r], om0, A[3 + r], om1, A[a2 + r], om2);
-#pragma unroll
-            for (int c = 0; c < 3; c++) H[3 * r + c] += w * rows_dot<Stereo>(A[r], A[c], A[3 + r], A[3 + c], A[a2 + r], A[a2 + c]);
-        }
-        ((double4*)a.e_lin)[e] = make_double4(x, y, z, w);
-    }
-#pragma unroll
-    for (int i = 0; i < 9; i++) a.Hll[9 * m + i] = H[i];
-#pragma unroll
-    for (int r = 0; r < 3; r++) a.b[a.n + 3 * m + r] = bl[r];
-    return fmax(fmax(fabs(H[0]), fabs(H[4])), fabs(H[8]));
-}
-// the same with four lanes per landmark (k_ba_lin, r06): lane sub takes edges sub, sub + 4, ...
-// of landmark m, the 12 sums are added over the quad (butterfly: the same bits in its lanes) and
-// lane 0 stores them; returns the largest |diagonal| of Hll in every lane of the quad
 constexpr int kLinL = 64;   // landmarks per workgroup of k_ba_lin
 template <bool Stereo>
 __device__ __forceinline__ double lin_point_quad(const BaArgs& a, int m, int sub, bool fresh) {
@@ -448,11 +402,6 @@ __device__ __forceinline__ double lin_point_quad(const BaArgs& a, int m, int sub
         for (int r = 0; r < 3; r++) a.b[a.n + 3 * m + r] = bl[r];
     }
     return fmax(fmax(fabs(H[0]), fabs(H[4])), fabs(H[8]));
-}
-__global__ __launch_bounds__(256) void k_ba_lin_points(const BaArgs* __restrict__ args, const int* __restrict__ act) {
-    BA_PROLOGUE
-    BA_PHASE(kPhBuild)
-    (void)lin_point<false>(a, bx_ * blockDim.x + threadIdx.x);
 }
 
 // one wave per optimised pose: 21 upper Hpp terms + 6 b terms, lanes over the pose's edges; lane 0
@@ -627,11 +576,6 @@ __device__ __forceinline__ double lin_pose_wg(const BaArgs& a, int i, bool fresh
     }
     return dmax;
 }
-__global__ __launch_bounds__(256) void k_ba_lin_poses(const BaArgs* __restrict__ args, const int* __restrict__ act) {
-    BA_PROLOGUE
-    BA_PHASE(kPhBuild)
-    (void)lin_pose<false>(a, bx_ * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
-}
 
 // the device-driven build in one launch: workgroups [0, nbp) linearise landmarks (kLinL each,
 // four lanes per landmark), the rest poses (one per wave); each stores its largest |diagonal| (sc1), and the
@@ -651,7 +595,7 @@ __global__ __launch_bounds__(256) void k_ba_lin(const BaArgs* __restrict__ args,
     // build takes them from the restored state (a small problem's restored in the trial's launch, a
     // larger one's by k_ba_pop). r06 (late): every unsharded problem, so the larger ones' slots lost
     // their k_ba_errors(1) launch (C5: one launch less per trial); the shards keep it
-    const bool fresh = (a.small || !a.sync) && a.ctl && !a.ctl->errors_valid;
+    const bool fresh = (a.small || !a.sync) && !a.ctl->errors_valid;
     double d;
     int slot;
     if (bx_ < nbp) {
@@ -741,11 +685,11 @@ __global__ __launch_bounds__(256) void k_ba_zero_s(const BaArgs* __restrict__ ar
 //   W_a Hpl_b^T = Hpl_a Dinv_m Hpl_b^T = w_a w_b B_a^T (A_a Dinv_m A_b^T) B_b
 // with A, B rebuilt from the edges' stored (Pc, w) and the poses' R_lin: 17 doubles read per pair
 // (edge records + Dinv) instead of the 36 of stored W / Hpl blocks, and no W written per trial.
-constexpr int kItemsWg = 128;   // Schur work items per k_ba_schur_items work-group (two lanes each)
+// (kItemsWg Schur work items per work-group: ba_prep.h, whose prepare() lays the items out for it)
 template <bool Stereo>
 __device__ __forceinline__ void schur_b_pose(const BaArgs& a, int i, int lane);
-// work-groups [nbi, gridDim.x) run k_ba_schur_b's poses instead (it reads only k_ba_schur_points'
-// db and the linearisation: no dependence on the items, one launch less per trial)
+// work-groups [nbi, gridDim.x - 1) run schur_b_pose on the poses instead (it reads only
+// k_ba_schur_points' db and the linearisation: no dependence on the items, one launch less per trial)
 // Stereo: A_a, A_b get their third rows (sa, sb: the stereo_jac pairs), so T = A_a Dinv and
 // C = w_a w_b A_a Dinv A_b^T are 3x3, and B_b, B_a^T get a third row / column; the same two lanes
 // per item and the same 18 sums per lane
@@ -944,11 +888,6 @@ __device__ __forceinline__ void schur_b_pose(const BaArgs& a, int i, int lane) {
         if (lane == 0) a.bs[6 * i + r] = a.b[6 * i + r] - v;
     }
 }
-__global__ __launch_bounds__(256) void k_ba_schur_b(const BaArgs* __restrict__ args, const int* __restrict__ act) {
-    BA_PROLOGUE
-    BA_PHASE(kPhTrial)
-    schur_b_pose<false>(a, bx_ * 4 + (threadIdx.x >> 6), threadIdx.x & 63);
-}
 
 // ---------------------------------------------------------------------------
 // dense Cholesky of S (n x n, lower, in place) + solve S xp = bs; one workgroup (8 waves).
@@ -965,7 +904,6 @@ __global__ __launch_bounds__(256) void k_ba_schur_b(const BaArgs* __restrict__ a
 //  (c) backward solve panel by panel: x_p = Linv^T (y_p - L21^T x_below) (Linv saved per panel).
 // ---------------------------------------------------------------------------
 constexpr int kNB = 32;
-constexpr int kSchurChunk = 16;    // pairs per Schur work item (one lane)
 constexpr int kCholSmallN = 480;   // largest n of the single-workgroup solver (LDS envelope)
 constexpr int kPS = 34;   // panel row stride in doubles
 
@@ -1378,46 +1316,15 @@ __global__ __launch_bounds__(256) void k_ba_backsub_errs(const BaArgs* __restric
     if (last_arrival(&a.ctl->arrive_t, gridDim.x, &lastf)) ctl_end_body(a, act[by_], done, sh);
 }
 
-// restore the pushed state: host-driven rounds list the rejected problems in act[]; device-driven
-// rounds restore every problem whose controller flagged its trial rejected (ctl->pop)
+// restore the pushed state of every problem whose controller flagged its trial rejected (ctl->pop);
+// launched once per slot unless every problem of the call is small (those restore in ctl_end_body)
 __global__ __launch_bounds__(256) void k_ba_pop(const BaArgs* __restrict__ args, const int* __restrict__ act) {
     BA_PROLOGUE
-    if (a.ctl && !a.ctl->pop) return;
+    if (!a.ctl->pop) return;
     const int i = bx_ * blockDim.x + threadIdx.x;
     // (a fused trial left the poses unmoved: pose_bak holds the rejected trial's)
     if (i < 8 * a.P && !a.fused) a.pose[i] = a.pose_bak[i];
     if (i < 3 * a.M) a.pts[i] = a.pts_bak[i];
-}
-
-// red[0..3] + flag of the active problems packed contiguously for ONE device->host copy
-__global__ void k_ba_gather_red(const BaArgs* __restrict__ args, const int* __restrict__ act, int nact,
-                                double* __restrict__ out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nact) return;
-    const BaArgs& a = args[act[i]];
-    for (int k = 0; k < 4; k++) out[5 * i + k] = a.red[k];
-    out[5 * i + 4] = (double)a.flag[0];
-}
-
-// ---------------------------------------------------------------------------
-// reductions (one workgroup per problem, fixed order): [0] sum rho0, [1] scale, [2] max diag
-// ---------------------------------------------------------------------------
-// In-batch model of the sharded solve: problems 0..B-1 are shards of one problem (same poses,
-// disjoint landmarks); every shard's field[off .. off+count) becomes the sum (op 0) or max
-// (op 1) over the shards, in shard order (deterministic). field: 0 Hpp, 1 S, 2 bs, 3 red.
-__device__ __forceinline__ double* shard_field(const BaArgs& a, int field) {
-    return field == 0 ? a.Hpp : (field == 1 ? a.S : (field == 2 ? a.bs : a.red));
-}
-__global__ __launch_bounds__(256) void k_ba_shard_reduce(const BaArgs* __restrict__ args, int B, int field, int off,
-                                                         size_t count, int op) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x) {
-        double acc = op ? -1.0e300 : 0.0;
-        for (int b = 0; b < B; b++) {
-            const double v = shard_field(args[b], field)[off + i];
-            acc = op ? fmax(acc, v) : acc + v;
-        }
-        for (int b = 0; b < B; b++) shard_field(args[b], field)[off + i] = acc;
-    }
 }
 
 // Envelope packing of S for the sharded all-reduce: 32-row tile R keeps columns [32 rf[R],
@@ -1438,57 +1345,33 @@ __global__ __launch_bounds__(256) void k_ba_env_pack(double* __restrict__ S, int
     }
 }
 
-__device__ void ba_reduce_body(const BaArgs& a, int what, double* sh) {
+// red[0] = the sum of the robust chi2 terms over the problem's edges (one workgroup, fixed order)
+__device__ void ba_reduce_body(const BaArgs& a, double* sh) {
     double v = 0;
-    if (what & 1) {
-        for (int e = threadIdx.x; e < a.E; e += blockDim.x) v += a.e_rho0[e];
-        v = block_sum(v, sh);
-        if (threadIdx.x == 0) a.red[0] = v;
-    }
-    if (what & 2) {
-        const double lambda = *a.lambda;
-        const double lam_pose = a.lead ? lambda : 0.0;   // pose x is replicated across shards
-        v = 0;
-        const int N = a.n + 3 * a.M;
-        for (int j = threadIdx.x; j < N; j += blockDim.x) v += a.x[j] * ((j < a.n ? lam_pose : lambda) * a.x[j] + a.b[j]);
-        v = block_sum(v, sh);
-        if (threadIdx.x == 0) a.red[1] = v;
-    }
-    if (what & 4) {
-        v = 0;
-        for (int i = threadIdx.x; i < a.np * 6; i += blockDim.x) v = fmax(v, fabs(a.Hpp[36 * (i / 6) + 7 * (i % 6)]));
-        for (int i = threadIdx.x; i < a.M * 3; i += blockDim.x) v = fmax(v, fabs(a.Hll[9 * (i / 3) + 4 * (i % 3)]));
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            double m = 0;
-            for (int i = 0; i < (int)(blockDim.x >> 6); i++) m = fmax(m, sh[i]);
-            a.red[2] = m;
-        }
-    }
-    if ((what & 8) && threadIdx.x == 0) a.red[3] = a.flag[0] ? 0.0 : 1.0;   // the solve failed (summed over ranks)
+    for (int e = threadIdx.x; e < a.E; e += blockDim.x) v += a.e_rho0[e];
+    v = block_sum(v, sh);
+    if (threadIdx.x == 0) a.red[0] = v;
 }
 
-__global__ __launch_bounds__(1024) void k_ba_reduce(const BaArgs* __restrict__ args, const int* __restrict__ act,
-                                                    int what) {
+// a shard's part of the initial activeRobustChi2 (summed over the shards before k_ba_sh_init)
+__global__ __launch_bounds__(1024) void k_ba_reduce(const BaArgs* __restrict__ args, const int* __restrict__ act) {
     __shared__ double sh[16];
-    ba_reduce_body(args[act[blockIdx.x]], what, sh);
+    ba_reduce_body(args[act[blockIdx.x]], sh);
 }
 
 // ---------------------------------------------------------------------------
-// device-driven Levenberg-Marquardt control: one slot = [pre] build kernels [begin] trial kernels
-// [end] pop. The rules are those of the host-driven rounds in ba_solve_batch (g2o
-// OptimizationAlgorithmLevenberg::solve + SparseOptimizer::optimize, U:Thirdparty/g2o), applied
-// per problem on the device so that a whole solve needs no host round trip per trial.
+// Levenberg-Marquardt control on the device: one slot = the build kernels, the trial start
+// (ctl_begin_*), the trial kernels, the trial end (ctl_end_*), pop. The rules are g2o's
+// (OptimizationAlgorithmLevenberg::solve + SparseOptimizer::optimize, U:Thirdparty/g2o), applied
+// per problem on the device so that a whole solve needs no host round trip per trial: unsharded,
+// in the last workgroup of k_ba_lin and of the trial's error kernel; sharded, in the k_ba_sh_*
+// launches around the collectives.
 // ---------------------------------------------------------------------------
 // initial activeRobustChi2 (errors computed by the preceding k_ba_errors)
 __global__ __launch_bounds__(1024) void k_ba_ctl_init(const BaArgs* __restrict__ args, const int* __restrict__ act) {
     __shared__ double sh[16];
     const BaArgs& a = args[act[blockIdx.x]];
-    ba_reduce_body(a, 1, sh);
+    ba_reduce_body(a, sh);
     if (threadIdx.x == 0) {
         LmCtl& c = *a.ctl;
         c.currentChi = a.red[0];
@@ -1698,450 +1581,12 @@ __global__ __launch_bounds__(256) void k_ba_multi_reduce(const double* const* __
 
 namespace {
 
-// per-problem host preparation (O(E)): index mapping, CSRs, Schur pair lists by counting sort
-struct Prep {
-    int rc = 0;
-    int P = 0, M = 0, E = 0, np = 0, n = 0, nblk = 0;
-    std::vector<int> opt, pt_ptr, pt_edges, ps_ptr, ps_edges, blk_i, blk_j, blk_ptr, blk_pairs;
-    std::vector<int> row_first;   // blocked Cholesky structure: first 32-col tile per 32-row tile
-    std::vector<int> cb_tiles, cb_off;   // blocked Cholesky: envelope tiles per panel (cb_envelope_tiles)
-    std::vector<int> items, fin;  // Schur work items {k0, k1, blk, slot} and finisher blocks {blk, slot0, n}
-    std::vector<int> ifin;        // each item's finisher entry (-1: the block's only item)
-    int nslot = 0;
-    bool use_dag = false;         // the persistent tiled-DAG Cholesky (ba_chol_dag.hip)
-    DagPlan dag;                  // its helper task lists
-    bool use_nd = false;          // nested dissection over the DAG solver (ba_nd.hip): a lone banded GBA
-    NdPlan nd;
-    bool use_nd_sh = false;       // a shard of a sharded solve by keyframe segments (segment = shard)
-    std::vector<unsigned char> own;   // ... the poses whose pose-side terms it adds
-    size_t dag_task_cap = 0;      // ints reserved for the lists (RCCL shards: planned after the union envelope)
-    size_t o_dag = 0, o_dagi = 0;
-    size_t o_red2 = 0;            // workgroup partials of a trial's chi2 / scale (BaArgs::part)
-    // offsets (elements) into the packed buffers; see the segment map in ba_solve_batch
-    size_t o_chi2 = 0, o_state = 0, o_obs = 0, o_scr = 0, o_lin = 0, o_S = 0, o_L = 0, o_int = 0;
-};
-
-// fn(i) for i in [0, n) on up to `threads` host threads (problems are independent)
-template <typename F>
-void parallel_for(int n, int threads, F fn) {
-    threads = std::max(1, std::min(threads, n));
-    if (threads == 1) {
-        for (int i = 0; i < n; i++) fn(i);
-        return;
-    }
-    std::atomic<int> next{0};
-    auto work = [&] {
-        for (int i; (i = next.fetch_add(1)) < n;) fn(i);
-    };
-    std::vector<std::thread> pool;
-    for (int t = 1; t < threads; t++) pool.emplace_back(work);
-    work();
-    for (auto& th : pool) th.join();
-}
-
-int host_threads() {
-    static const int n = [] {
-        const char* s = std::getenv("ORBHIP_BA_THREADS");
-        if (s && std::atoi(s) > 0) return std::atoi(s);
-        const unsigned hw = std::thread::hardware_concurrency();
-        return (int)std::min<unsigned>(16, hw ? hw : 1);
-    }();
-    return n;
-}
-
-constexpr int kPrepParallelE = 20000;   // edges from which one problem's pair lists use host threads
-
-// A persistent host worker pool for the preparation of one large problem: run(n, fn) calls fn(i)
-// for i in [0, n) on the caller and the idle workers (indices claimed dynamically, so it completes
-// on the caller alone if no worker is free), and returns when every call has returned. One run at a
-// time: a concurrent caller (another context's thread) runs its loop alone.
-// Created lazily, on the first large problem prepared with ORBHIP_PREP_THREADS > 1 (never
-// otherwise), and deliberately leaked with detached workers: no destructor runs at process exit
-// or library unload, so no join can meet a worker inside run() or a destroyed mutex.
-class HostPool {
-  public:
-    static HostPool& get(int workers) {
-        static HostPool* pool = new HostPool(workers);
-        return *pool;
-    }
-    template <typename F>
-    void run(int n, F&& fn) {
-        std::unique_lock<std::mutex> busy(run_m_, std::try_to_lock);
-        if (!busy.owns_lock() || workers_.empty()) {
-            for (int i = 0; i < n; i++) fn(i);
-            return;
-        }
-        std::function<void(int)> job(fn);
-        {
-            std::lock_guard<std::mutex> g(m_);
-            job_ = &job;
-            n_ = n;
-            next_.store(0, std::memory_order_relaxed);
-            active_ = (int)workers_.size();
-            gen_++;
-        }
-        cv_.notify_all();
-        for (int i; (i = next_.fetch_add(1)) < n;) job(i);
-        std::unique_lock<std::mutex> g(m_);
-        done_cv_.wait(g, [&] { return active_ == 0; });   // every worker has left this job
-        job_ = nullptr;
-    }
-
-  private:
-    explicit HostPool(int workers) {
-        for (int w = 0; w < workers; w++) {
-            std::thread t([this] { loop(); });
-            t.detach();
-            workers_.push_back(w);
-        }
-    }
-    ~HostPool() = delete;   // leaked (see above)
-    void loop() {
-        unsigned long long seen = 0;
-        for (;;) {
-            std::function<void(int)>* job;
-            int n;
-            {
-                std::unique_lock<std::mutex> g(m_);
-                cv_.wait(g, [&] { return gen_ != seen; });
-                seen = gen_;
-                job = job_;
-                n = n_;
-            }
-            if (job)
-                for (int i; (i = next_.fetch_add(1)) < n;) (*job)(i);
-            std::lock_guard<std::mutex> g(m_);
-            if (--active_ == 0) done_cv_.notify_one();
-        }
-    }
-    std::vector<int> workers_;   // the detached workers' indices (their count is what run() uses)
-    std::mutex run_m_, m_;
-    std::condition_variable cv_, done_cv_;
-    std::function<void(int)>* job_ = nullptr;
-    int n_ = 0, active_ = 0;
-    std::atomic<int> next_{0};
-    unsigned long long gen_ = 0;
-};
-
-// r06 (late): one large problem (E >= kPrepParallelE, a GBA) writes its outputs on the pool (C5
-// 0.146 -> 0.05 ms; its pair lists and packing measured slower there, tools/r06/gpu_hostpool_ab.sh);
-// ORBHIP_HOST_POOL=0 keeps every host loop on the calling thread
-bool host_pool_on() {
-    static const bool on = [] {
-        const char* s = std::getenv("ORBHIP_HOST_POOL");
-        return !(s && s[0] == '0') && host_threads() > 1;
-    }();
-    return on;
-}
-
-// The Schur pair lists of prepare() on host threads, identical to the serial build:
-//   1. landmark chunk t (contiguous): its pairs counted per pose row ia;
-//   2. the same chunk writes its pairs (ib, ea, eb) at its per-row cursors (rows in order, chunks
-//      in order within a row: landmark order within a row);
-//   3. rows in parallel: a stable counting sort by ib gives the row's blocks (j = i always, others
-//      with pairs) and their pairs at the row's offset; then the blocks are listed row by row.
-void schur_pairs_parallel(Prep& o, const int* eopt, int threads) {
-    const int M = o.M, np = o.np;
-    const int T = std::max(1, std::min(threads, M / 512 + 1));
-    // scratch kept per calling thread across calls; the lambdas below run on the pool's threads, so
-    // they must reach it through these references (a thread_local named inside them would be the
-    // worker's own, empty instance)
-    static thread_local std::vector<size_t> rc_s, roff_s;
-    static thread_local std::vector<int> tj_s, tab_s;
-    static thread_local std::vector<std::vector<int>> rb_s;
-    std::vector<size_t>& rc = rc_s;
-    std::vector<size_t>& roff = roff_s;
-    std::vector<int>& tj = tj_s;
-    std::vector<int>& tab = tab_s;
-    std::vector<std::vector<int>>& rb = rb_s;
-    std::vector<int> m0(T + 1);
-    for (int t = 0; t <= T; t++) m0[t] = (int)((long long)M * t / T);
-    rc.assign((size_t)T * np, 0);
-    roff.assign(np + 1, 0);
-    rb.resize(np);
-    for (auto& v : rb) v.clear();
-    HostPool& pool = HostPool::get(host_threads() - 1);
-    pool.run(T, [&](int t) {
-        size_t* c = rc.data() + (size_t)t * np;
-        for (int m = m0[t]; m < m0[t + 1]; m++) {
-            const int k0 = o.pt_ptr[m], k1 = o.pt_ptr[m + 1];
-            for (int ka = k0; ka < k1; ka++) {
-                const int ia = eopt[ka];
-                if (ia < 0) continue;
-                for (int kb = k0; kb < k1; kb++) c[ia] += eopt[kb] >= ia;
-            }
-        }
-    });
-    size_t total = 0;
-    for (int i = 0; i < np; i++) {
-        roff[i] = total;
-        for (int t = 0; t < T; t++) {
-            const size_t v = rc[(size_t)t * np + i];
-            rc[(size_t)t * np + i] = total;
-            total += v;
-        }
-    }
-    roff[np] = total;
-    tj.resize(total);
-    tab.resize(2 * total);
-    o.blk_pairs.resize(2 * total);
-    pool.run(T, [&](int t) {
-        size_t* c = rc.data() + (size_t)t * np;
-        for (int m = m0[t]; m < m0[t + 1]; m++) {
-            const int k0 = o.pt_ptr[m], k1 = o.pt_ptr[m + 1];
-            for (int ka = k0; ka < k1; ka++) {
-                const int ia = eopt[ka];
-                if (ia < 0) continue;
-                const int ea = o.pt_edges[ka];
-                for (int kb = k0; kb < k1; kb++) {
-                    const int ib = eopt[kb];
-                    if (ib < ia) continue;
-                    const size_t slot = c[ia]++;
-                    tj[slot] = ib;
-                    tab[2 * slot] = ea;
-                    tab[2 * slot + 1] = o.pt_edges[kb];
-                }
-            }
-        }
-    });
-    const int RB = 8;   // rows per task
-    pool.run((np + RB - 1) / RB, [&](int task) {
-        static thread_local std::vector<int> cj;
-        cj.assign(np, 0);
-        for (int i = task * RB; i < std::min(np, task * RB + RB); i++) {
-            const size_t a = roff[i], b = roff[i + 1];
-            for (size_t k = a; k < b; k++) cj[tj[k]]++;
-            int s = 0;
-            for (int j = i; j < np; j++) {
-                const int cnt = cj[j];
-                if (j == i || cnt > 0) { rb[i].push_back(j); rb[i].push_back(cnt); }
-                cj[j] = s;   // from here on: the block's cursor within the row
-                s += cnt;
-            }
-            for (size_t k = a; k < b; k++) {
-                const size_t slot = a + (size_t)cj[tj[k]]++;
-                o.blk_pairs[2 * slot] = tab[2 * k];
-                o.blk_pairs[2 * slot + 1] = tab[2 * k + 1];
-            }
-            for (int j = i; j < np; j++) cj[j] = 0;
-        }
-    });
-    o.blk_ptr.assign(1, 0);
-    size_t s = 0;
-    for (int i = 0; i < np; i++)
-        for (size_t q = 0; q < rb[i].size(); q += 2) {
-            o.blk_i.push_back(i);
-            o.blk_j.push_back(rb[i][q]);
-            s += (size_t)rb[i][q + 1];
-            o.blk_ptr.push_back((int)s);
-        }
-}
-
-// a Prep for the next call with its vectors' capacity kept (no allocation / first-touch page
-// faults on the hot path: the C5 lists are a few MB)
-void prep_reset(Prep& o) {
-    o.rc = 0;
-    o.P = o.M = o.E = o.np = o.n = o.nblk = 0;
-    for (auto* v : {&o.opt, &o.pt_ptr, &o.pt_edges, &o.ps_ptr, &o.ps_edges, &o.blk_i, &o.blk_j, &o.blk_ptr,
-                    &o.blk_pairs, &o.row_first, &o.cb_tiles, &o.cb_off, &o.items, &o.fin, &o.ifin})
-        v->clear();
-    o.own.clear();
-    o.nslot = 0;
-    o.use_dag = o.use_nd = o.use_nd_sh = false;
-    o.dag = DagPlan{};
-    o.nd = NdPlan{};
-    o.dag_task_cap = 0;
-    o.o_dag = o.o_dagi = o.o_red2 = 0;
-    o.o_chi2 = o.o_state = o.o_obs = o.o_scr = o.o_lin = o.o_S = o.o_L = o.o_int = 0;
-}
-
 inline void se3_from_float(const float* q, const float* t, double* out) {
     double x = q[0], y = q[1], z = q[2], w = q[3];
     if (w < 0) { x = -x; y = -y; z = -z; w = -w; }
     const double nn = std::sqrt(x * x + y * y + z * z + w * w);
     out[0] = x / nn; out[1] = y / nn; out[2] = z / nn; out[3] = w / nn;
     out[4] = t[0]; out[5] = t[1]; out[6] = t[2]; out[7] = 0;
-}
-
-int prepare(const orbhip_ba_problem* pr, Prep& o, int chunk, int threads) {
-    const int P = pr->n_poses, M = pr->n_points, E = pr->n_edges;
-    if (P < 0 || M < 0 || E < 0 || (P && (!pr->pose_q || !pr->pose_t || !pr->pose_fixed)) || (M && !pr->points) ||
-        (E && (!pr->edge_pose || !pr->edge_point || !pr->edge_uv || !pr->edge_octave || !pr->inv_sigma2)))
-        return ORBHIP_ERR_ARG;
-    for (int e = 0; e < E; e++)
-        if (pr->edge_pose[e] < 0 || pr->edge_pose[e] >= P || pr->edge_point[e] < 0 || pr->edge_point[e] >= M ||
-            pr->edge_octave[e] < 0 || pr->edge_octave[e] >= pr->n_octaves)
-            return ORBHIP_ERR_ARG;
-    static const bool pdbg = std::getenv("ORBHIP_PREP_DBG") != nullptr;
-    auto tus = [] { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    double tp[8] = {tus()};
-    o.P = P; o.M = M; o.E = E;
-    o.opt.assign(P, -1);
-    int np = 0;
-    for (int i = 0; i < P; i++)
-        if (!pr->pose_fixed[i]) o.opt[i] = np++;
-    o.np = np;
-    o.n = 6 * np;
-    // n <= kCholSmallN: single-workgroup Cholesky (LDS-resident panel); larger: blocked solver
-    if (o.n > kCbMaxN) return ORBHIP_ERR_UNSUPPORTED;
-    const int* e_pose = pr->edge_pose;
-    const int* e_pt = pr->edge_point;
-    o.pt_ptr.assign(M + 1, 0);
-    o.ps_ptr.assign(np + 1, 0);
-    for (int e = 0; e < E; e++) {
-        o.pt_ptr[e_pt[e] + 1]++;
-        if (o.opt[e_pose[e]] >= 0) o.ps_ptr[o.opt[e_pose[e]] + 1]++;
-    }
-    for (int m = 0; m < M; m++) o.pt_ptr[m + 1] += o.pt_ptr[m];
-    for (int i = 0; i < np; i++) o.ps_ptr[i + 1] += o.ps_ptr[i];
-    o.pt_edges.resize(E);
-    o.ps_edges.resize(o.ps_ptr[np]);
-    // scratch kept per host thread across calls (no page faults on the hot path): eopt[k] = the opt
-    // index of the pose of landmark-CSR slot k (one load per pair endpoint below), cnt = the dense
-    // (i, j) pair counts, then the blocks' fill cursors
-    static thread_local std::vector<int> eopt, cnt, fp, fq;   // (fp / fq: the fill cursors, no allocation per call)
-    eopt.resize(E);
-    {
-        fp.assign(o.pt_ptr.begin(), o.pt_ptr.end() - 1);
-        fq.assign(o.ps_ptr.begin(), o.ps_ptr.end() - 1);
-        for (int e = 0; e < E; e++) {
-            const int oi = o.opt[e_pose[e]];
-            const int k = fp[e_pt[e]]++;
-            o.pt_edges[k] = e;
-            eopt[k] = oi;
-            if (oi >= 0) o.ps_edges[fq[oi]++] = e;
-        }
-    }
-    tp[1] = tus();
-    // Schur pairs (a, b) of one landmark with opt(a) <= opt(b), grouped by block (i, j) (row-major
-    // over i <= j, every diagonal block listed); within a block: landmark order (deterministic).
-    // Large problems: schur_pairs_parallel (the same lists, built on host threads)
-    if (threads > 1 && E >= kPrepParallelE) {
-        schur_pairs_parallel(o, eopt.data(), threads);
-    } else {
-        // a counting sort on the dense block id i*np + j
-        cnt.assign((size_t)np * np, 0);
-        size_t npairs = 0;
-        for (int m = 0; m < M; m++) {
-            const int k0 = o.pt_ptr[m], k1 = o.pt_ptr[m + 1];
-            for (int ka = k0; ka < k1; ka++) {
-                const int ia = eopt[ka];
-                if (ia < 0) continue;
-                int* row = cnt.data() + (size_t)ia * np;
-                for (int kb = k0; kb < k1; kb++) {
-                    const int ib = eopt[kb];
-                    if (ib < ia) continue;   // also drops the fixed poses (-1)
-                    row[ib]++;
-                    npairs++;
-                }
-            }
-        }
-        o.blk_ptr.assign(1, 0);
-        {
-            int s = 0;
-            for (int i = 0; i < np; i++) {
-                int* row = cnt.data() + (size_t)i * np;
-                for (int j = i; j < np; j++) {
-                    const int c = row[j];
-                    if (i == j || c > 0) {
-                        o.blk_i.push_back(i);
-                        o.blk_j.push_back(j);
-                        row[j] = s;   // from here on: the block's fill cursor
-                        s += c;
-                        o.blk_ptr.push_back(s);
-                    }
-                }
-            }
-        }
-        o.blk_pairs.resize(2 * npairs);
-        int* bp = o.blk_pairs.data();
-        for (int m = 0; m < M; m++) {
-            const int k0 = o.pt_ptr[m], k1 = o.pt_ptr[m + 1];
-            for (int ka = k0; ka < k1; ka++) {
-                const int ia = eopt[ka];
-                if (ia < 0) continue;
-                const int ea = o.pt_edges[ka];
-                int* row = cnt.data() + (size_t)ia * np;
-                for (int kb = k0; kb < k1; kb++) {
-                    const int ib = eopt[kb];
-                    if (ib < ia) continue;
-                    const int slot = row[ib]++;
-                    bp[2 * (size_t)slot] = ea;
-                    bp[2 * (size_t)slot + 1] = o.pt_edges[kb];
-                }
-            }
-        }
-    }
-    tp[2] = tus();
-    o.nblk = (int)o.blk_i.size();
-    {   // envelope of S: first pose column coupled to each pose row (blocks are stored i <= j)
-        std::vector<int> fp(np);
-        for (int i = 0; i < np; i++) fp[i] = i;
-        for (int b = 0; b < o.nblk; b++) fp[o.blk_j[b]] = std::min(fp[o.blk_j[b]], o.blk_i[b]);
-        const int nt = (o.n + 31) / 32;
-        o.row_first.assign(nt, 0);
-        for (int R = 0; R < nt; R++) {
-            int f = R;
-            for (int r = 32 * R; r < std::min(o.n, 32 * R + 32); r++) f = std::min(f, (6 * fp[r / 6]) / 32);
-            o.row_first[R] = f;
-        }
-    }
-    // Schur work items: chunks of at most `chunk` pairs; a block with one off-diagonal chunk is
-    // written by its item, the others (and every diagonal block) are summed inside one work-group
-    // of k_ba_schur_items (r06): at most kItemsWg chunks per block (a longer block takes longer
-    // chunks), and a block that would straddle a work-group boundary starts the next work-group
-    // (empty items, blk -1, pad the one before)
-    // (two passes: the count, then direct stores into the sized arrays; per-item vector inserts
-    // cost ~6 ns each, 0.3 ms at C5)
-    size_t nit = 0, nfin = 0;
-    for (int b = 0; b < o.nblk; b++) {
-        const int k0 = o.blk_ptr[b], k1 = o.blk_ptr[b + 1];
-        if (o.blk_i[b] != o.blk_j[b] && k1 - k0 <= chunk) { nit++; continue; }
-        const int cb = std::max(chunk, (k1 - k0 + kItemsWg - 1) / kItemsWg);
-        const int nch = std::max(1, (k1 - k0 + cb - 1) / cb);
-        const int at = (int)(nit % kItemsWg);
-        if (at + nch > kItemsWg) nit += kItemsWg - at;
-        nit += nch;
-        nfin++;
-    }
-    o.items.resize(4 * nit);
-    o.ifin.resize(nit);
-    o.fin.resize(3 * nfin);
-    int* itp = o.items.data();
-    int* ifp = o.ifin.data();
-    int* fnp = o.fin.data();
-    size_t it = 0;
-    int f = 0;
-    for (int b = 0; b < o.nblk; b++) {
-        const int k0 = o.blk_ptr[b], k1 = o.blk_ptr[b + 1];
-        const bool diag = o.blk_i[b] == o.blk_j[b];
-        if (!diag && k1 - k0 <= chunk) {
-            int* q = itp + 4 * it;
-            q[0] = k0; q[1] = k1; q[2] = b; q[3] = -1;
-            ifp[it++] = -1;
-            continue;
-        }
-        const int cb = std::max(chunk, (k1 - k0 + kItemsWg - 1) / kItemsWg);
-        const int nch = std::max(1, (k1 - k0 + cb - 1) / cb);
-        const int at = (int)(it % kItemsWg);
-        if (at + nch > kItemsWg)
-            for (int q = at; q < kItemsWg; q++) {
-                int* r = itp + 4 * it;
-                r[0] = 0; r[1] = 0; r[2] = -1; r[3] = -1;
-                ifp[it++] = -1;
-            }
-        fnp[3 * f] = b; fnp[3 * f + 1] = o.nslot; fnp[3 * f + 2] = nch;
-        for (int c = 0; c < nch; c++) {
-            int* r = itp + 4 * it;
-            r[0] = k0 + c * cb; r[1] = std::min(k1, k0 + (c + 1) * cb); r[2] = b; r[3] = o.nslot + c;
-            ifp[it++] = f;
-        }
-        o.nslot += nch;
-        f++;
-    }
-    tp[3] = tus();
-    if (pdbg) std::fprintf(stderr, "prepare E=%d: csr %.0f us, pairs %.0f us, envelope+items %.0f us\n", E, tp[1] - tp[0], tp[2] - tp[1], tp[3] - tp[2]);
-    return ORBHIP_OK;
 }
 
 template <typename T>
@@ -2176,25 +1621,20 @@ struct HBuf {   // pinned host staging
 }  // namespace
 
 struct BaWorkspace {
-    DBuf<double> dbl;      // all fp64 per-problem arrays, packed (segment map in ba_solve_batch)
+    DBuf<double> dbl;      // all fp64 per-problem arrays, packed (segment map at place_problem)
     DBuf<int> act;         // active problem lists (several slots)
     DBuf<double> lam;      // per-problem lambda
-    DBuf<double> gath;     // gathered red/flag of the active problems
-    DBuf<LmCtl> ctl;       // device-driven rounds: per-problem LM state
+    DBuf<LmCtl> ctl;       // per-problem LM state
     HBuf<LmCtl> hctl;      // its pinned staging (initial state up, final state down)
     HBuf<double> hdbl;     // staging: [e_chi2 | pose,pts | obs,info | the int arrays | BaArgs] of every problem
-    double* h_gath = nullptr;  // pinned
-    double* h_lam = nullptr;   // pinned
-    double* h_red = nullptr;   // pinned: per problem red[4] + flag
-    int* h_act = nullptr;      // pinned
-    size_t h_cap = 0;
+    HBuf<int> h_act;       // pinned: the active lists' staging
     // sharded solve over RCCL (orbhip_comm_init): landmarks partitioned, poses replicated
     ncclComm_t comm = nullptr;
     int nranks = 1, rank = 0;
     DBuf<int> dstop;           // stop-flag consensus (all-reduce max)
     DBuf<double> envbuf;       // S's union envelope, packed for the all-reduce (k_ba_env_pack)
     DBuf<long long> envoff;    // its per-32-row-tile offsets
-    int* h_stop = nullptr;     // pinned
+    HBuf<int> h_stop;          // pinned
     int* h_done = nullptr;     // pinned, mapped: per problem, set by the device when its LM run ends
     int* d_done = nullptr;     // its device address
     DBuf<int*> d_donep;        // ... stored in device memory: what the kernels get
@@ -2207,7 +1647,7 @@ struct BaWorkspace {
     DBuf<double*> ptab;        // in-process shards: the collectives' pointer tables
     DBuf<int> dint4;           // RCCL: small consensus all-reduces (plan, stop)
     DBuf<unsigned char> uadj;  // RCCL, replicated form: the union pose adjacency (all-reduce max)
-    int* h_int4 = nullptr;     // pinned
+    HBuf<int> h_int4;          // pinned
 };
 
 BaWorkspace* ba_create() { return new BaWorkspace(); }
@@ -2217,25 +1657,134 @@ void ba_destroy(BaWorkspace* w) {
     if (w->comm) (void)ncclCommDestroy(w->comm);
     if (w->nd) nd_destroy(w->nd);
     for (NdWorkspace* q : w->nds) nd_destroy(q);
-    if (w->h_int4) (void)hipHostFree(w->h_int4);
-    if (w->h_stop) (void)hipHostFree(w->h_stop);
     if (w->h_done) (void)hipHostFree(w->h_done);
-    if (w->h_lam) (void)hipHostFree(w->h_lam);
-    if (w->h_red) (void)hipHostFree(w->h_red);
-    if (w->h_act) (void)hipHostFree(w->h_act);
-    if (w->h_gath) (void)hipHostFree(w->h_gath);
     delete w;
 }
 
-struct LmState {
-    double lambda = 0, ni = 2, currentChi = 0, rho = 0;
-    int nBad = 0, it = 0, trials = 0, qmax = 0;
-    bool done = false, errors_valid = true;
+// ---------------------------------------------------------------------------
+// ba_solve_batch: the steps below, in the order they run, over one BaCall on its stack
+// ---------------------------------------------------------------------------
+namespace {
+
+// Every environment switch of a call, read in one place at its top (read_switches).
+struct BaSwitches {
+    // read once per process
+    bool timing;          // ORBHIP_BA_TIMING: one line of host phase times per call
+    int chunk;            // ORBHIP_SCHUR_CHUNK: pairs per Schur work item (0: chosen per call)
+    int prep_threads;     // ORBHIP_PREP_THREADS=k: one large problem's pair lists on k host threads (1)
+    bool force_blocked;   // ORBHIP_CHOL_BLOCKED: the one-launch-per-panel blocked solver for the large problems
+    int dag_min;          // ORBHIP_CHOL_DAG_MIN: the smallest n a lone problem takes the DAG solver at (128)
+    // read on every call (the tests flip them)
+    long small_words;     // ORBHIP_BA_SMALL_WORDS: see BaArgs::small (32768)
+    bool nd;              // ORBHIP_ND=0: no nested dissection
+    int nd_k;             // ORBHIP_ND_K=k: k segments (0: the planner's choice)
+    int nd_min;           // ORBHIP_ND_MIN: the smallest n considered for dissection (960)
+    bool shard_nd;        // ORBHIP_SHARD_ND=0: sharded solves take the replicated form
+    bool shard_full_s;    // ORBHIP_SHARD_FULL_S: RCCL all-reduces the whole S, not its packed envelope
+    int lin_ppw;          // ORBHIP_LIN_PPW=1/4: poses per pose work-group of k_ba_lin (0: by batch size)
+    bool fused;           // ORBHIP_BA_FUSED=0: separate k_ba_backsub + k_ba_errors(2) trials
+    bool dag_rerun;       // ORBHIP_DAG_RERUN=0: a DAG hand-off timeout is reported, not re-run
 };
 
-int ba_solve_batch(BaWorkspace* ws, const orbhip_ba_problem* const* probs, int B, orbhip_ba_result* const* res,
-                   const volatile int* stop, hipStream_t st, int shard_mode, bool no_dag, bool no_nd,
-                   const BaStereoExt* sx) {
+BaSwitches read_switches() {
+    auto set = [](const char* name) { return std::getenv(name) != nullptr; };
+    auto off = [](const char* name) { const char* s = std::getenv(name); return s && s[0] == '0'; };
+    auto num = [](const char* name, int dflt) { const char* s = std::getenv(name); return s ? std::atoi(s) : dflt; };
+    static const BaSwitches once = {set("ORBHIP_BA_TIMING"), num("ORBHIP_SCHUR_CHUNK", 0), num("ORBHIP_PREP_THREADS", 1),
+                                    set("ORBHIP_CHOL_BLOCKED"), num("ORBHIP_CHOL_DAG_MIN", 128)};
+    BaSwitches s = once;
+    const char* sw = std::getenv("ORBHIP_BA_SMALL_WORDS");
+    s.small_words = sw ? std::atol(sw) : 32768;
+    s.nd = !off("ORBHIP_ND");
+    s.nd_k = num("ORBHIP_ND_K", 0);
+    s.nd_min = num("ORBHIP_ND_MIN", 960);
+    s.shard_nd = !off("ORBHIP_SHARD_ND");
+    s.shard_full_s = set("ORBHIP_SHARD_FULL_S");
+    const char* ppw = std::getenv("ORBHIP_LIN_PPW");
+    s.lin_ppw = ppw ? (std::atoi(ppw) == 1 ? 1 : 4) : 0;
+    s.fused = !off("ORBHIP_BA_FUSED");
+    s.dag_rerun = !off("ORBHIP_DAG_RERUN");
+    return s;
+}
+
+double now_ms() {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
+}
+unsigned gx(int n_, int b_) { return (unsigned)std::max(1, (n_ + b_ - 1) / b_); }
+
+// The collectives of a sharded slot: site s sums (or maxes) src[b] into dst[b] over the shards
+enum { kHpp, kRed0, kRed2, kRed01, kRepS, kRepBs, kNdPack, kNdBz, kNdX, kSites };
+struct Site { std::vector<double*> src, dst; size_t count = 0; int op = 0; size_t tab = 0; };
+
+// A step's request to run the call again (ba_solve_batch re-enters itself, after its last use of
+// this frame's preparations: the re-entered call reuses the workspace)
+enum { kRerunNoNd = -1001, kRerunNoDag = -1002 };
+
+// What one call's steps share; lives on the stack of ba_solve_batch
+struct BaCall {
+    // the call's arguments
+    BaWorkspace* ws; const orbhip_ba_problem* const* probs; int B; orbhip_ba_result* const* res;
+    const volatile int* stop; hipStream_t st; int shard_mode; bool no_dag, no_nd; const BaStereoExt* sx;
+    BaSwitches sw;
+    bool stereo = false;    // some edge is a stereo edge: the Stereo = true kernels on every problem
+    bool sharded = false, rccl = false;
+    int nth = 1;            // host threads
+    double t_start = 0, t_prepare = 0, t_prep = 0, t_pack = 0, t_solve = 0;
+    Prep* pp = nullptr;     // ws->prep: the per-problem preparations
+    int local_bad = 0;      // RCCL: this rank's shards are invalid (its verdict travels in the first collective)
+    int dag_helpers = 0;
+    // the sharded plan
+    int seg0 = 0;           // segment of problem 0
+    NdPlan ndp;             // the segments of a solve by keyframe segments (nd_sh)
+    bool nd_sh = false;
+    std::vector<int> ubi, ubj;   // the replicated form's union block structure (when dissected)
+    // the packed buffers: sizes and starts (doubles) of the segments, device and staging bases
+    size_t nC = 0, nA = 0, nR = 0, sC = 0, sA = 0, sU = 0, sI = 0, sG = 0, sR = 0;
+    double* D = nullptr; int* I = nullptr; double* hd = nullptr; int* hi = nullptr;
+    BaArgs* ha = nullptr; BaArgs* dArgs = nullptr;
+    std::vector<DagDev> dd;
+    size_t env_total = 0;   // RCCL, replicated, B == 1: doubles of S's packed union envelope (0: the whole S)
+    // launch widths and forms
+    int maxM = 0, maxE = 0, maxP = 0, maxNp = 0, maxN = 0, maxItems = 0, maxPM = 0;
+    bool s_readonly = false;   // S is zeroed once, not per trial
+    size_t chol_lds = 0;
+    int ns = 0;             // problems on the single-workgroup solvers (act slot 3)
+    bool all_small = true;  // every problem restores / refreshes in its trial's last workgroup
+    bool fused = false;     // the fused trial (k_ba_backsub_errs)
+    unsigned gbs = 1;       // ... its work-groups
+    int lin_ppw = 4;        // poses per pose work-group of k_ba_lin
+    int* d_act = nullptr; int* h_act = nullptr; LmCtl* dctl = nullptr;
+    std::vector<const int*> tw;   // the timeout words of every persistent solve of this call (ndag of them)
+    int ndag = 0;
+    std::vector<Site> sites;
+    int* const* donep = nullptr;  // {done, stop} of post_done / relay_host_stop, on the device
+    int* h_stopw = nullptr;       // the host's side of the relayed stop word (null: nothing to relay)
+    bool stop_sent = false;
+    bool outputs_in = false;      // the speculative copies behind the last slots brought the outputs
+
+    // "large": solved on its own (dissection, DAG or blocked); the rest share one single-workgroup launch
+    bool large(int b) const { return pp[b].use_nd || pp[b].use_nd_sh || pp[b].use_dag || pp[b].n > kCholSmallN; }
+    NdWorkspace* nd_of(int b) const { return B == 1 ? ws->nd : ws->nds[b]; }
+};
+
+// n values of `host` up to `dev`, all-reduced (max or min) over the ranks, back into `host`; the
+// stream is synchronised. ORBHIP_ERR_DEVICE on any failure.
+template <typename T>
+int rccl_consensus(const BaCall& c, T* host, T* dev, size_t n, ncclRedOp_t op) {
+    static_assert(sizeof(T) == 4 || sizeof(T) == 1, "ints or bytes");
+    const ncclDataType_t ty = sizeof(T) == 1 ? ncclUint8 : ncclInt32;
+    if (hipMemcpyAsync(dev, host, n * sizeof(T), hipMemcpyHostToDevice, c.st) != hipSuccess ||
+        ncclAllReduce(dev, dev, n, ty, op, c.ws->comm, c.st) != ncclSuccess ||
+        hipMemcpyAsync(host, dev, n * sizeof(T), hipMemcpyDeviceToHost, c.st) != hipSuccess ||
+        hipStreamSynchronize(c.st) != hipSuccess)
+        return ORBHIP_ERR_DEVICE;
+    return ORBHIP_OK;
+}
+
+// ---- step 1: arguments; a call with stereo edges (orbhip_ba_solve_stereo*: some edge_ur >= 0) runs
+// the Stereo = true kernels on every problem of it, every other call the monocular kernels ----
+int ba_validate(const BaWorkspace* ws, const orbhip_ba_problem* const* probs, int B, orbhip_ba_result* const* res,
+                int shard_mode, const BaStereoExt* sx, bool& stereo) {
     if (B <= 0 || !probs || !res) return ORBHIP_ERR_ARG;
     if (sx && shard_mode != kShardNone) return ORBHIP_ERR_ARG;   // the sharded forms have no stereo edges
     // RCCL: this rank holds B consecutive shards (segments rank*B .. rank*B+B-1 of nranks*B), the
@@ -2243,9 +1792,7 @@ int ba_solve_batch(BaWorkspace* ws, const orbhip_ba_problem* const* probs, int B
     if (shard_mode == kShardRccl && !ws->comm) return ORBHIP_ERR_ARG;
     for (int b = 0; b < B; b++)
         if (!probs[b] || !res[b]) return ORBHIP_ERR_ARG;
-    // a call with stereo edges (orbhip_ba_solve_stereo*: some edge_ur >= 0) runs the Stereo = true
-    // kernels on every problem of it; every other call runs today's monocular kernels
-    bool stereo = false;
+    stereo = false;
     if (sx) {
         for (int b = 0; b < B; b++) {
             const int E = probs[b]->n_edges;
@@ -2256,912 +1803,947 @@ int ba_solve_batch(BaWorkspace* ws, const orbhip_ba_problem* const* probs, int B
             stereo = stereo || any;
         }
     }
-    static const bool timing = std::getenv("ORBHIP_BA_TIMING") != nullptr;
-    // the state words (8 P + 3 M) up to which the trial's last work-group restores a rejected
-    // trial itself ("small"); larger problems restore in k_ba_pop. ORBHIP_BA_SMALL_WORDS (read per
-    // call) lowers it: the tests run the large-problem path on problems that reject trials
-    const char* e_sw = std::getenv("ORBHIP_BA_SMALL_WORDS");
-    const long small_words = e_sw ? std::atol(e_sw) : 32768;
-    auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_start = now();
-    const int nth = host_threads();
-    // the per-problem preparations, kept in the workspace across calls (their vectors' capacity:
-    // no allocation on the hot path). A DAG-timeout re-run re-enters with the same workspace as a
-    // tail call, after this frame's last use of them.
-    if (ws->prep.size() < (size_t)B) ws->prep.resize(B);
-    std::vector<Prep>& pp = ws->prep;
+    return ORBHIP_OK;
+}
+
+// ---- step 2: the per-problem preparations, kept in the workspace across calls (their vectors'
+// capacity: no allocation on the hot path); the shards of one problem must agree in shape and
+// share the union envelope ----
+int ba_prepare_all(BaCall& c) {
+    const int B = c.B;
+    if (c.ws->prep.size() < (size_t)B) c.ws->prep.resize(B);
+    Prep* pp = c.pp = c.ws->prep.data();
     for (int b = 0; b < B; b++) prep_reset(pp[b]);
     // Schur work-item size: a batch fills the chip with 16 pairs per lane; a few problems alone
     // would leave it mostly idle, so their items are cut to 4 pairs (4x the lanes), 3 for the
-    // LBA sizes (r06, alternating runs, tools/r06/gpu_chunk.sh: C4 1.323 -> 1.309 ms with 3, 1.31-1.33 with 2, 1.34-1.35
+    // LBA sizes (r06, alternating runs: C4 1.323 -> 1.309 ms with 3, 1.31-1.33 with 2, 1.34-1.35
     // with 1; the C5 GBA 5.18 -> 5.58 ms with 2)
-    static const int chunk_env = std::getenv("ORBHIP_SCHUR_CHUNK") ? std::atoi(std::getenv("ORBHIP_SCHUR_CHUNK")) : 0;
     int maxE_in = 0;
-    for (int b = 0; b < B; b++) maxE_in = std::max(maxE_in, probs[b]->n_edges);
-    const int chunk = chunk_env > 0 ? chunk_env : (B >= 32 ? kSchurChunk : (maxE_in <= 32768 ? 3 : 4));
-    // one problem: its Schur pair lists on the host threads; a batch: one problem per thread
-    // (ORBHIP_PREP_THREADS=k: one large problem's pair lists on k host threads; off by default: on
-    // the MI355X box's EPYC the C5 build went 0.62 -> 0.55 ms at 16 threads, 0.71 at 4 in r05, and
-    // 0.63 -> 1.09-1.26 ms on the r06 tree (tools/r06/gpu_hostpool_ab.sh): its scattered fill does
-    // not scale)
-    static const int prep_par = std::getenv("ORBHIP_PREP_THREADS") ? std::atoi(std::getenv("ORBHIP_PREP_THREADS"))
-                                                                   : 1;
-    parallel_for(B, nth, [&](int b) { pp[b].rc = prepare(probs[b], pp[b], chunk, B == 1 ? prep_par : 1); });
-    const double t_prepare = now();
+    for (int b = 0; b < B; b++) maxE_in = std::max(maxE_in, c.probs[b]->n_edges);
+    const int chunk = c.sw.chunk > 0 ? c.sw.chunk : (B >= 32 ? kSchurChunk : (maxE_in <= 32768 ? 3 : 4));
+    // one problem: its Schur pair lists on the host threads (off by default: on the MI355X box's
+    // EPYC the C5 build went 0.62 -> 0.55 ms at 16 threads, 0.71 at 4 in r05, and 0.63 -> 1.09-1.26 ms
+    // on the r06 tree: its scattered fill does not scale); a batch: one problem per thread
+    const int prep_par = B == 1 ? c.sw.prep_threads : 1;
+    parallel_for(B, c.nth, [&](int b) { pp[b].rc = prepare(c.probs[b], pp[b], chunk, prep_par); });
+    c.t_prepare = now_ms();
     // RCCL shards: a rank whose shards are invalid must not return before the first collective
     // (the other ranks would wait in it forever); its verdict travels in that all-reduce and every
     // rank returns together
-    int local_bad = 0;
-    for (int b = 0; b < B && !local_bad; b++)
+    for (int b = 0; b < B && !c.local_bad; b++)
         if (pp[b].rc) {
-            if (shard_mode != kShardRccl) return pp[b].rc;
-            local_bad = pp[b].rc;
+            if (!c.rccl) return pp[b].rc;
+            c.local_bad = pp[b].rc;
         }
-    if (shard_mode != kShardNone && B > 1 && !local_bad) {
-        for (int b = 1; b < B && !local_bad; b++)
-            if (pp[b].P != pp[0].P || pp[b].np != pp[0].np) {
-                if (shard_mode != kShardRccl) return ORBHIP_ERR_ARG;
-                local_bad = ORBHIP_ERR_ARG;
-            }
+    if (!c.sharded || B == 1 || c.local_bad) return ORBHIP_OK;
+    for (int b = 1; b < B; b++)
+        if (pp[b].P != pp[0].P || pp[b].np != pp[0].np) {
+            if (!c.rccl) return ORBHIP_ERR_ARG;
+            c.local_bad = ORBHIP_ERR_ARG;
+            return ORBHIP_OK;
+        }
+    // every shard factors the SUMMED S: the blocked Cholesky needs the union envelope
+    for (int b = 1; b < B; b++)
+        for (size_t R = 0; R < pp[0].row_first.size(); R++)
+            pp[0].row_first[R] = std::min(pp[0].row_first[R], pp[b].row_first[R]);
+    for (int b = 1; b < B; b++) pp[b].row_first = pp[0].row_first;
+    return ORBHIP_OK;
+}
+
+// ---- step 3: the Cholesky of each problem: the persistent DAG solver for the GBA sizes and for a
+// problem solved alone (one LBA), the register / LDS single-workgroup solvers for batches of
+// small problems, the blocked solver for the large ones when forced; a lone large problem whose S
+// is a narrow (cyclic) block band (a GBA's keyframe loop): nested dissection, when the plan's
+// chain is shorter ----
+void ba_choose_solvers(BaCall& c) {
+    Prep* pp = c.pp;
+    c.dag_helpers = dag_max_helpers();
+    for (int b = 0; b < c.B; b++)
+        pp[b].use_dag = !c.no_dag && !c.sw.force_blocked && pp[b].n > 0 &&
+                        (pp[b].n > kCholSmallN || (c.B == 1 && pp[b].n >= c.sw.dag_min));
+    if (!c.sharded && c.B == 1 && !c.no_nd && pp[0].use_dag && pp[0].n >= c.sw.nd_min && c.sw.nd) {
+        Prep& p = pp[0];
+        if (nd_plan(p.np, p.blk_i.data(), p.blk_j.data(), p.nblk, c.sw.nd_k, p.nd)) {
+            p.use_nd = true;
+            p.use_dag = false;
+        }
     }
-    if (shard_mode != kShardNone && B > 1 && !local_bad) {
-        // every shard factors the SUMMED S: the blocked Cholesky needs the union envelope
-        for (int b = 1; b < B; b++)
-            for (size_t R = 0; R < pp[0].row_first.size(); R++)
-                pp[0].row_first[R] = std::min(pp[0].row_first[R], pp[b].row_first[R]);
-        for (int b = 1; b < B; b++) pp[b].row_first = pp[0].row_first;
+}
+
+// ---- step 4: sharded solves by keyframe segments (the distributed form of the
+// dissection): shard r is segment r when every shard's landmarks lie inside its segment's matrix
+// (sharding.shard_problem_nd); then each shard eliminates its interior, the separator system is
+// summed over the shards, every shard solves it, and the shards' x are summed. Otherwise the
+// shards sum S itself and every shard solves it (replicated). The decision is agreed over the
+// ranks. Collectives of this step, in order (RCCL only): the band and shard count (5 ints, the
+// first collective of a call: an invalid rank reaches it), whether every rank's landmarks fit
+// (1 int), and, for a replicated form that may be dissected, the union pose adjacency (np^2 bytes) ----
+int ba_plan_replicated_nd(BaCall& c);
+int ba_plan_shards(BaCall& c) {
+    BaWorkspace* ws = c.ws;
+    Prep* pp = c.pp;
+    const int B = c.B;
+    c.seg0 = c.rccl ? ws->rank * B : 0;
+    const int K = c.shard_mode == kShardLocal ? B : ws->nranks * B;
+    int wl = 0, wc = 0;
+    for (int b = 0; b < B && !c.local_bad; b++) {
+        int l = 0, w = 0;
+        nd_bandwidth(pp[b].np, pp[b].blk_i.data(), pp[b].blk_j.data(), pp[b].nblk, l, w);
+        wl = std::max(wl, l);
+        wc = std::max(wc, w);
     }
-    // Cholesky per problem: the persistent DAG solver for the GBA sizes and for a problem solved
-    // alone (one LBA), the register / LDS single-workgroup solvers for batches of small problems;
-    // ORBHIP_CHOL_BLOCKED=1 restores the one-launch-per-panel blocked solver for the large ones,
-    // ORBHIP_CHOL_DAG_MIN sets the smallest n a lone problem takes the DAG solver at (default 128)
-    static const bool force_blocked = std::getenv("ORBHIP_CHOL_BLOCKED") != nullptr;
-    static const int dag_min = std::getenv("ORBHIP_CHOL_DAG_MIN") ? std::atoi(std::getenv("ORBHIP_CHOL_DAG_MIN")) : 128;
-    const int dag_helpers = dag_max_helpers();
+    const bool ok_base = !c.no_dag && !c.sw.force_blocked && pp[0].n >= c.sw.nd_min;
+    int ok = (ok_base && c.sw.shard_nd) ? 1 : 0;
+    if (c.rccl) {   // the band over every rank's landmarks; the same B everywhere
+        // words 3 / 4: the max of B and of -B agree only when every rank has the same B and
+        // valid shards (an invalid rank sends INT_MAX)
+        int* h = ws->h_int4.p;
+        h[0] = wl; h[1] = wc; h[2] = -ok;
+        h[3] = c.local_bad ? std::numeric_limits<int>::max() : B; h[4] = -B;
+        if (rccl_consensus(c, h, ws->dint4.p, 5, ncclMax)) return ORBHIP_ERR_DEVICE;
+        if (h[3] != B || -h[4] != B) return c.local_bad ? c.local_bad : ORBHIP_ERR_ARG;
+        wl = h[0]; wc = h[1]; ok = -h[2];
+    }
+    ok = ok && nd_plan_band(pp[0].np, wl, wc, K, c.ndp);
+    for (int b = 0; b < B && ok; b++)
+        ok = nd_blocks_fit(c.ndp, c.seg0 + b, pp[b].blk_i.data(), pp[b].blk_j.data(), pp[b].nblk);
+    if (c.rccl) {   // every rank's landmarks fit its segment
+        int* h = ws->h_int4.p;
+        h[0] = ok ? 0 : 1;
+        if (rccl_consensus(c, h, ws->dint4.p, 1, ncclMax)) return ORBHIP_ERR_DEVICE;
+        ok = h[0] == 0;
+    }
+    c.nd_sh = ok != 0;
+    if (c.nd_sh)
+        for (int b = 0; b < B; b++) {
+            Prep& p = pp[b];
+            p.use_nd_sh = true;
+            p.use_dag = false;
+            const int r = c.seg0 + b;
+            p.own.assign(p.np, 0);
+            for (int q = c.ndp.seg[r]; q < c.ndp.seg[r + 1]; q++) p.own[q] = 1;   // interior + own separator
+        }
+    if (!c.nd_sh && ok_base && !c.no_nd && c.sw.nd) return ba_plan_replicated_nd(c);
+    return ORBHIP_OK;
+}
+// r06: the replicated form (landmark shards, or segments whose landmarks cross) solves the summed S
+// by nested dissection too when that pays, planned on the union of the shards' pose adjacencies
+// (every rank derives the same plan from the same union); ORBHIP_ND=0 keeps the plain DAG solve on
+// the union envelope
+int ba_plan_replicated_nd(BaCall& c) {
+    Prep* pp = c.pp;
+    const int B = c.B, np = pp[0].np;
+    std::vector<unsigned char> adj((size_t)np * np, 0);   // [max(i, j)][min(i, j)]
     for (int b = 0; b < B; b++)
-        pp[b].use_dag = !no_dag && !force_blocked && pp[b].n > 0 && (pp[b].n > kCholSmallN || (B == 1 && pp[b].n >= dag_min));
-    // a lone large problem whose S is a narrow (cyclic) block band (a GBA's keyframe loop): nested
-    // dissection, when the plan's chain is shorter (ORBHIP_ND=0 disables it, ORBHIP_ND_K=k forces k
-    // segments, ORBHIP_ND_MIN sets the smallest n considered)
-    {
-        const char* e_nd = std::getenv("ORBHIP_ND");
-        const char* e_k = std::getenv("ORBHIP_ND_K");
-        const char* e_min = std::getenv("ORBHIP_ND_MIN");
-        const int nd_min = e_min ? std::atoi(e_min) : 960;
-        if (shard_mode == kShardNone && B == 1 && !no_nd && pp[0].use_dag && pp[0].n >= nd_min &&
-            !(e_nd && e_nd[0] == '0')) {
-            Prep& p = pp[0];
-            if (nd_plan(p.np, p.blk_i.data(), p.blk_j.data(), p.nblk, e_k ? std::atoi(e_k) : 0, p.nd)) {
-                p.use_nd = true;
-                p.use_dag = false;
-            }
+        for (int k = 0; k < pp[b].nblk; k++) {
+            const int i = pp[b].blk_i[k], j = pp[b].blk_j[k];
+            adj[(size_t)std::max(i, j) * np + std::min(i, j)] = 1;
         }
+    if (c.rccl) {
+        BAOK(c.ws->uadj.ensure(adj.size()));
+        if (rccl_consensus(c, adj.data(), c.ws->uadj.p, adj.size(), ncclMax)) return ORBHIP_ERR_DEVICE;
     }
-    // sharded solves by keyframe segments (the distributed form of the dissection):
-    // shard r is segment r when every shard's landmarks lie inside its segment's matrix
-    // (sharding.shard_problem_nd); then each shard eliminates its interior, the separator system is
-    // summed over the shards, every shard solves it, and the shards' x are summed. Otherwise the
-    // shards sum S itself and every shard solves it (replicated). The decision is agreed over the
-    // ranks; ORBHIP_SHARD_ND=0 forces the replicated form.
-    const int seg0 = shard_mode == kShardRccl ? ws->rank * B : 0;   // segment of problem 0
-    NdPlan ndp;
-    bool nd_sh = false;
-    std::vector<int> ubi, ubj;   // the replicated form's union block structure (when dissected)
-    if (shard_mode != kShardNone) {
-        const char* e_snd = std::getenv("ORBHIP_SHARD_ND");
-        const char* e_min = std::getenv("ORBHIP_ND_MIN");
-        const int nd_min = e_min ? std::atoi(e_min) : 960;
-        const int K = shard_mode == kShardLocal ? B : ws->nranks * B;
-        int wl = 0, wc = 0;
-        for (int b = 0; b < B && !local_bad; b++) {
-            int l = 0, c = 0;
-            nd_bandwidth(pp[b].np, pp[b].blk_i.data(), pp[b].blk_j.data(), pp[b].nblk, l, c);
-            wl = std::max(wl, l);
-            wc = std::max(wc, c);
+    for (int i = 0; i < np; i++)
+        for (int j = 0; j <= i; j++)
+            if (adj[(size_t)i * np + j]) { c.ubi.push_back(j); c.ubj.push_back(i); }
+    NdPlan up;
+    if (nd_plan(np, c.ubi.data(), c.ubj.data(), (int)c.ubi.size(), 0, up))
+        for (int b = 0; b < B; b++) {
+            pp[b].nd = up;
+            pp[b].use_nd = true;
+            pp[b].use_dag = false;
         }
-        const bool ok_base = !no_dag && !force_blocked && pp[0].n >= nd_min;
-        int ok = (ok_base && !(e_snd && e_snd[0] == '0')) ? 1 : 0;
-        if (shard_mode == kShardRccl) {   // the band over every rank's landmarks; the same B everywhere
-            // words 3 / 4: the max of B and of -B agree only when every rank has the same B and
-            // valid shards (an invalid rank sends INT_MAX)
-            ws->h_int4[0] = wl; ws->h_int4[1] = wc; ws->h_int4[2] = -ok;
-            ws->h_int4[3] = local_bad ? std::numeric_limits<int>::max() : B; ws->h_int4[4] = -B;
-            if (hipMemcpyAsync(ws->dint4.p, ws->h_int4, 5 * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess ||
-                ncclAllReduce(ws->dint4.p, ws->dint4.p, 5, ncclInt32, ncclMax, ws->comm, st) != ncclSuccess ||
-                hipMemcpyAsync(ws->h_int4, ws->dint4.p, 5 * sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipStreamSynchronize(st) != hipSuccess)
-                return ORBHIP_ERR_DEVICE;
-            if (ws->h_int4[3] != B || -ws->h_int4[4] != B) return local_bad ? local_bad : ORBHIP_ERR_ARG;
-            wl = ws->h_int4[0]; wc = ws->h_int4[1]; ok = -ws->h_int4[2];
-        }
-        ok = ok && nd_plan_band(pp[0].np, wl, wc, K, ndp);
-        for (int b = 0; b < B && ok; b++)
-            ok = nd_blocks_fit(ndp, seg0 + b, pp[b].blk_i.data(), pp[b].blk_j.data(), pp[b].nblk);
-        if (shard_mode == kShardRccl) {   // every rank's landmarks fit its segment
-            ws->h_int4[0] = ok ? 0 : 1;
-            if (hipMemcpyAsync(ws->dint4.p, ws->h_int4, sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess ||
-                ncclAllReduce(ws->dint4.p, ws->dint4.p, 1, ncclInt32, ncclMax, ws->comm, st) != ncclSuccess ||
-                hipMemcpyAsync(ws->h_int4, ws->dint4.p, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipStreamSynchronize(st) != hipSuccess)
-                return ORBHIP_ERR_DEVICE;
-            ok = ws->h_int4[0] == 0;
-        }
-        nd_sh = ok != 0;
-        if (nd_sh)
-            for (int b = 0; b < B; b++) {
-                Prep& p = pp[b];
-                p.use_nd_sh = true;
-                p.use_dag = false;
-                const int r = seg0 + b;
-                p.own.assign(p.np, 0);
-                for (int q = ndp.seg[r]; q < ndp.seg[r + 1]; q++) p.own[q] = 1;   // interior + own separator
-            }
-        // r06: the replicated form (landmark shards, or segments whose landmarks cross) solves the
-        // summed S by nested dissection too when that pays, planned on the union of the shards'
-        // pose adjacencies (every rank derives the same plan from the same union); ORBHIP_ND=0
-        // keeps the plain DAG solve on the union envelope
-        const char* e_nd = std::getenv("ORBHIP_ND");
-        if (!nd_sh && ok_base && !no_nd && !(e_nd && e_nd[0] == '0')) {
-            const int np = pp[0].np;
-            std::vector<unsigned char> adj((size_t)np * np, 0);   // [max(i, j)][min(i, j)]
-            for (int b = 0; b < B; b++)
-                for (int k = 0; k < pp[b].nblk; k++) {
-                    const int i = pp[b].blk_i[k], j = pp[b].blk_j[k];
-                    adj[(size_t)std::max(i, j) * np + std::min(i, j)] = 1;
-                }
-            if (shard_mode == kShardRccl) {
-                BAOK(ws->uadj.ensure(adj.size()));
-                if (hipMemcpyAsync(ws->uadj.p, adj.data(), adj.size(), hipMemcpyHostToDevice, st) != hipSuccess ||
-                    ncclAllReduce(ws->uadj.p, ws->uadj.p, adj.size(), ncclUint8, ncclMax, ws->comm, st) != ncclSuccess ||
-                    hipMemcpyAsync(adj.data(), ws->uadj.p, adj.size(), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                    hipStreamSynchronize(st) != hipSuccess)
-                    return ORBHIP_ERR_DEVICE;
-            }
-            for (int i = 0; i < np; i++)
-                for (int j = 0; j <= i; j++)
-                    if (adj[(size_t)i * np + j]) { ubi.push_back(j); ubj.push_back(i); }
-            NdPlan up;
-            if (nd_plan(np, ubi.data(), ubj.data(), (int)ubi.size(), 0, up))
-                for (int b = 0; b < B; b++) {
-                    pp[b].nd = up;
-                    pp[b].use_nd = true;
-                    pp[b].use_dag = false;
-                }
-            else
-                ubi.clear(), ubj.clear();
-        }
-    }
-    const bool sharded = shard_mode != kShardNone;
-    // the per-panel tile lists / the DAG plans (RCCL shards: the envelope is the union over the
-    // ranks, known after a collective; their DAG plan is made then, into reserved space)
-    parallel_for(B, nth, [&](int b) {
-        Prep& p = pp[b];
+    else
+        c.ubi.clear(), c.ubj.clear();
+    return ORBHIP_OK;
+}
+
+// the per-panel tile lists / the DAG plans (RCCL shards: the envelope is the union over the
+// ranks, known after a collective; their DAG plan is made then, into reserved space)
+void ba_plan_factors(BaCall& c) {
+    parallel_for(c.B, c.nth, [&](int b) {
+        Prep& p = c.pp[b];
         if (p.use_nd || p.use_nd_sh) {
             // planned above; its device data is set up with the problem's buffers (nd_setup)
         } else if (p.use_dag) {
-            if (shard_mode == kShardRccl) {
+            if (c.rccl) {
                 const size_t NT = (p.n + kDagTile - 1) / kDagTile;
-                p.dag_task_cap = (size_t)dag_helpers + 1 + NT * (NT + 1) / 2 + 2 * NT;   // + the copy tasks, the column counts
+                p.dag_task_cap = (size_t)c.dag_helpers + 1 + NT * (NT + 1) / 2 + 2 * NT;   // + the copy tasks, the column counts
             } else {
-                dag_plan(p.row_first.data(), p.n, dag_helpers, p.dag);
+                dag_plan(p.row_first.data(), p.n, c.dag_helpers, p.dag);
                 p.dag_task_cap = p.dag.toff.size() + p.dag.tasks.size();
             }
-        } else if (p.n > kCholSmallN && shard_mode != kShardRccl) {
+        } else if (p.n > kCholSmallN && !c.rccl) {
             cb_envelope_tiles(p.row_first.data(), p.n, p.cb_tiles, p.cb_off);
         }
     });
-    const double t_prep = now();
-    // ---- packed layout: fp64 segments, each contiguous over all problems ----
-    //   C  e_chi2 (E)                 downloaded with A in one transfer
-    //   A  pose (8P) + pts (3M)       uploaded, optimised in place, downloaded
-    //   U  obs (2E) + info (E)        uploaded (a call with stereo edges: + ur (E))
-    //   R  the rest (scratch), then the edge linearisations e_lin (32-byte aligned), S (n*n) and
-    //      the panel inverses Lsave, 16-byte aligned
-    size_t nC = 0, nA = 0, nU = 0, nR = 0, ni = 0;
-    for (int b = 0; b < B; b++) {
-        Prep& p = pp[b];
-        const size_t P = p.P, M = p.M, E = p.E, np_ = p.np, n = p.n;
-        p.o_chi2 = nC; nC += E;
-        p.o_state = nA; nA += 8 * P + 3 * M;
-        p.o_obs = nU; nU += (stereo ? 4 : 3) * E;
-        p.o_scr = nR;
-        nR += 8 * P + 3 * M                          // pose_bak, pts_bak
-              + 2 * E + 3 * E                        // e_err, e_rho0, e_rho1 (+ pad)
-              + (stereo ? E : 0)                     // e_err2
-              + 36 * np_ + 9 * np_ + 18 * M + 3 * M  // Hpp, R_lin, Hll, Dinv, db
-              + (sharded ? 36 * np_ : 0)             // Hpp_g: Hpp summed over the shards
-              + 2 * (n + 3 * M) + n + 4;             // b, x, bs, red
-        nR = (nR + 3) & ~size_t(3);
-        p.o_lin = nR; nR += 4 * E;
-        p.o_S = nR; nR += n * n;
-        nR = (nR + 1) & ~size_t(1);
-        p.o_L = nR; nR += 1024 * ((n + 31) / 32);
-        nR = (nR + 1) & ~size_t(1);
-        p.o_red2 = nR;
-        nR += std::max((E + 255) / 256 + (std::max(M, P) + kBsL - 1) / kBsL, (M + kLinL - 1) / kLinL + np_) + 2;
-        if (p.use_dag) {   // 128-byte aligned
-            nR = (nR + 15) & ~size_t(15);
-            p.o_dag = nR; nR += dag_doubles(p.n);
-        }
-        p.o_int = ni;
-        ni += (P + 4) + 2 * E + (M + 1) + E + (np_ + 1) + p.ps_edges.size() + 3 * p.nblk + 1 + p.blk_pairs.size() +
-              p.row_first.size() + p.items.size() + p.fin.size() + p.ifin.size() + p.cb_tiles.size() + 8 +
-              (p.use_dag ? dag_ints(p.n) + p.dag_task_cap + 4 : 0) + (p.own.size() + 3) / 4 + 1;
+}
+
+// A cursor over one packed segment: take(count, align) is the address of the segment's next
+// `count` elements, aligned to `align` elements from the segment's start. The sizing pass runs
+// over a zero base (only `at` matters there), the packing pass over the segment's device address.
+template <typename T>
+struct Carve {
+    uintptr_t base = 0;
+    size_t at = 0;
+    T* take(size_t count, size_t align = 1) {
+        at = (at + align - 1) & ~(align - 1);
+        T* p = reinterpret_cast<T*>(base + at * sizeof(T));
+        at += count;
+        return p;
+    }
+};
+// the int segment's cursor also fills the pinned staging copy (host: null in the sizing pass)
+struct CarveInt : Carve<int> {
+    int* host = nullptr;
+    size_t counted = 0;   // ints taken, without the alignment gaps
+    int* skip(size_t count, size_t align = 1) {   // taken, not filled
+        counted += count;
+        return take(count, align);
+    }
+    // src (null: zeros) copied into the staging; bytes: of src, when not whole ints
+    int* put(const void* src, size_t count, size_t align = 1, size_t bytes = ~size_t(0)) {
+        int* d = skip(count, align);
+        if (bytes == ~size_t(0)) bytes = count * sizeof(int);
+        if (host && src) std::memcpy(host + at - count, src, bytes);
+        if (host && !src) std::memset(host + at - count, 0, bytes);
+        return d;
+    }
+    int* put(const std::vector<int>& v, size_t align = 1) { return put(v.data(), v.size(), align); }
+};
+struct Segs {
+    Carve<double> C, A, U, R;
+    CarveInt I;
+};
+
+// ---- the packed layout: ONE device buffer (and its pinned staging twin) of doubles,
+//   [ C | A | U | I | G | R ],   every segment contiguous over all problems:
+//   C  e_chi2 (E)                 downloaded with A in one transfer (nC + nA doubles from 0)
+//   A  pose (8P) + pts (3M)       uploaded, optimised in place, downloaded
+//   U  obs (2E) + info (E)        uploaded (a call with stereo edges: + ur (E))
+//   I  the int arrays             uploaded; 16-byte aligned
+//   G  the BaArgs records         uploaded; 16-byte aligned (one copy uploads A .. G: sA to sR)
+//   R  the rest (scratch), 128-byte aligned: per problem the arrays below, then the edge
+//      linearisations e_lin (32-byte aligned), S (n*n), the panel inverses Lsave and the trial
+//      partials (16-byte aligned), and the DAG solver's buffer (128-byte aligned)
+// place_problem is the one description of a problem's arrays: each appears here once, with its
+// size and alignment, in the order it lies in memory. ba_layout runs it over zero bases to size
+// the segments and record where each problem starts; ba_pack_upload runs it again from those
+// starts over the real bases, which fills the problem's BaArgs / DagDev and the int staging. ----
+void place_problem(Segs& s, const Prep& p, const orbhip_ba_problem* pr, bool stereo, bool sharded, BaArgs& a,
+                   DagDev& dd) {
+    const size_t P = p.P, M = p.M, E = p.E, np = p.np, n = p.n;
+    a.e_chi2 = s.C.take(E);
+    a.pose = s.A.take(8 * P); a.pts = s.A.take(3 * M);
+    a.e_obs = s.U.take(2 * E); a.e_info = s.U.take(E);
+    a.e_ur = stereo ? s.U.take(E) : nullptr;
+    Carve<double>& r = s.R;
+    a.pose_bak = r.take(8 * P); a.pts_bak = r.take(3 * M);
+    a.e_err = r.take(2 * E); a.e_rho0 = r.take(E); a.e_rho1 = r.take(2 * E);   // (+ pad)
+    a.e_err2 = stereo ? r.take(E) : nullptr;
+    a.Hpp = r.take(36 * np); a.R_lin = r.take(9 * np);
+    a.Hll = r.take(9 * M); a.Dinv = r.take(9 * M); a.db = r.take(3 * M);
+    a.Hpp_g = sharded ? r.take(36 * np) : a.Hpp;   // Hpp summed over the shards
+    a.b = r.take(n + 3 * M); a.x = r.take(n + 3 * M); a.bs = r.take(n); a.red = r.take(4);
+    a.e_lin = r.take(4 * E, 4);
+    a.S = r.take(n * n);
+    a.Lsave = r.take(1024 * ((n + 31) / 32), 2);
+    const size_t npart_e = (E + 255) / 256, npart_m = (std::max(M, P) + kBsL - 1) / kBsL;   // k_ba_backsub_errs' workgroups
+    a.npart_e = (int)npart_e; a.npart_m = (int)npart_m;
+    a.part = r.take(std::max(npart_e + npart_m, (M + kLinL - 1) / kLinL + np) + 2, 2);
+    dd.buf = p.use_dag ? r.take(dag_doubles(p.n), 16) : nullptr;
+    CarveInt& q = s.I;
+    a.opt = q.put(p.opt);
+    a.flag = q.put(nullptr, 4);   // [0] Cholesky ok, [1] blocked backward arrival counter (zero between uses)
+    a.e_pose = q.put(pr->edge_pose, E); a.e_pt = q.put(pr->edge_point, E);
+    a.pt_ptr = q.put(p.pt_ptr); a.pt_edges = q.put(p.pt_edges);
+    a.ps_ptr = q.put(p.ps_ptr); a.ps_edges = q.put(p.ps_edges);
+    a.nblk = p.nblk; a.nitems = (int)(p.items.size() / 4); a.nfin = (int)(p.fin.size() / 3);
+    a.blk_i = q.put(p.blk_i); a.blk_j = q.put(p.blk_j); a.blk_ptr = q.put(p.blk_ptr);
+    a.blk_pairs = q.put(p.blk_pairs, 2);   // int2
+    a.items = q.put(p.items, 4);           // int4
+    a.fin = q.put(p.fin); a.ifin = q.put(p.ifin);
+    a.row_first = q.put(p.row_first);
+    a.cb_tiles = p.cb_tiles.empty() ? nullptr : q.put(p.cb_tiles);
+    a.own = p.own.empty() ? nullptr   // bytes, in the int staging
+                          : (const unsigned char*)q.put(p.own.data(), (p.own.size() + 3) / 4, 1, p.own.size());
+    if (p.use_dag) {   // flags + control words (zero), then the plan (or the space reserved for it)
+        dd.ints = q.put(nullptr, dag_ints(p.n), 4);
+        dd.toff = p.dag.toff.empty() ? q.skip(p.dag_task_cap) : q.put(p.dag.toff);
+        // (RCCL: planned after the union envelope, into the space skipped here)
+        dd.tasks = p.dag.toff.empty() ? dd.toff + kDagMaxHelpers + 1 : q.put(p.dag.tasks);
+        dd.G = p.dag.G; dd.pb = p.dag.pb;
+        dd.need_off = p.dag.toff.empty() ? 0 : p.dag.toff[p.dag.G];
+    }
+}
+
+// ---- step 5a: the sizing pass ----
+void ba_layout(BaCall& c) {
+    Segs s;
+    BaArgs a;
+    DagDev d;
+    for (int b = 0; b < c.B; b++) {
+        Prep& p = c.pp[b];
+        p.o_chi2 = s.C.at; p.o_state = s.A.at; p.o_obs = s.U.at; p.o_scr = s.R.at; p.o_int = s.I.at;
+        s.I.counted = 0;
+        place_problem(s, p, c.probs[b], c.stereo, c.sharded, a, d);
+        // the gaps in front of the aligned int arrays depend on where the problem starts (at most
+        // 1 + 3 ints in front of the pair list and the items, 3 in front of the DAG words): each
+        // problem gets a fixed room above them, so its start depends on the sizes alone
+        s.I.at = p.o_int + s.I.counted + 9 + (p.use_dag ? 4 : 0);
     }
     // r06: the int arrays and the BaArgs follow the uploaded doubles in the same device / pinned
     // buffers, so that ONE copy uploads all of it (three blit launches of ~4.4 us each before)
-    const size_t sC = 0, sA = nC, sU = sA + nA;
-    const size_t sI = (sU + nU + 1) & ~size_t(1);                            // 16-byte aligned
-    const size_t sG = (sI + (ni * sizeof(int) + 7) / 8 + 1) & ~size_t(1);  // the BaArgs
-    const size_t sR = (sG + (B * sizeof(BaArgs) + 7) / 8 + 15) & ~size_t(15);
-    const size_t nd = sR + nR;
-    BAOK(ws->dbl.ensure(nd));
+    c.nC = s.C.at; c.nA = s.A.at;
+    c.sC = 0; c.sA = c.nC; c.sU = c.sA + c.nA;
+    c.sI = (c.sU + s.U.at + 1) & ~size_t(1);                                    // 16-byte aligned
+    c.sG = (c.sI + (s.I.at * sizeof(int) + 7) / 8 + 1) & ~size_t(1);            // the BaArgs
+    c.sR = (c.sG + (c.B * sizeof(BaArgs) + 7) / 8 + 15) & ~size_t(15);
+    c.nR = s.R.at;
+}
+
+// ---- step 5b: the buffers, every problem's arrays and BaArgs into the staging, one upload ----
+int ba_pack_upload(BaCall& c) {
+    BaWorkspace* ws = c.ws;
+    const int B = c.B;
+    BAOK(ws->dbl.ensure(c.sR + c.nR));
     BAOK(ws->act.ensure(3 * (size_t)B));
     BAOK(ws->lam.ensure(B));
-    BAOK(ws->gath.ensure(5 * (size_t)B));
     BAOK(ws->ctl.ensure(B));
     BAOK(ws->hctl.ensure(B));
-    BAOK(ws->hdbl.ensure(sR));
-    if (ws->h_cap < (size_t)B) {
-        if (ws->h_lam) (void)hipHostFree(ws->h_lam);
-        if (ws->h_red) (void)hipHostFree(ws->h_red);
-        ws->h_red = nullptr;
-        if (ws->h_act) (void)hipHostFree(ws->h_act);
-        if (ws->h_gath) (void)hipHostFree(ws->h_gath);
-        BAOK(hipHostMalloc((void**)&ws->h_gath, sizeof(double) * 5 * B, hipHostMallocDefault));
-        BAOK(hipHostMalloc((void**)&ws->h_lam, sizeof(double) * B, hipHostMallocDefault));
-        BAOK(hipHostMalloc((void**)&ws->h_red, sizeof(double) * 5 * B, hipHostMallocDefault));
-        BAOK(hipHostMalloc((void**)&ws->h_act, sizeof(int) * 3 * B, hipHostMallocDefault));
-        ws->h_cap = B;
-    }
-    double* D = ws->dbl.p;
-    int* I = reinterpret_cast<int*>(D + sI);
-    double* hd = ws->hdbl.p;
-    int* hi = reinterpret_cast<int*>(hd + sI);
-    BaArgs* ha = reinterpret_cast<BaArgs*>(hd + sG);
-    BaArgs* const dArgs = reinterpret_cast<BaArgs*>(D + sG);
-    std::vector<DagDev> dd(B, DagDev{nullptr, nullptr, nullptr, nullptr, 0, 0, 0});
-    parallel_for(B, nth, [&](int b) {
-        const Prep& p = pp[b];
-        const orbhip_ba_problem* pr = probs[b];
+    BAOK(ws->hdbl.ensure(c.sR));
+    BAOK(ws->h_act.ensure(3 * (size_t)B));
+    double* const D = c.D = ws->dbl.p;
+    double* const hd = c.hd = ws->hdbl.p;
+    c.I = reinterpret_cast<int*>(D + c.sI);
+    c.hi = reinterpret_cast<int*>(hd + c.sI);
+    c.ha = reinterpret_cast<BaArgs*>(hd + c.sG);
+    c.dArgs = reinterpret_cast<BaArgs*>(D + c.sG);
+    c.dd.assign(B, DagDev{nullptr, nullptr, nullptr, nullptr, 0, 0, 0});
+    parallel_for(B, c.nth, [&](int b) {
+        const Prep& p = c.pp[b];
+        const orbhip_ba_problem* pr = c.probs[b];
         const size_t P = p.P, M = p.M, E = p.E;
-        double* st_ = hd + sA + p.o_state;
+        double* st_ = hd + c.sA + p.o_state;
         for (size_t i = 0; i < P; i++) se3_from_float(pr->pose_q + 4 * i, pr->pose_t + 3 * i, st_ + 8 * i);
         for (size_t k = 0; k < 3 * M; k++) st_[8 * P + k] = pr->points[k];
-        double* ob = hd + sU + p.o_obs;
+        double* ob = hd + c.sU + p.o_obs;
         // (on the host pool this loop measured slower: C5 pack + upload 0.11 -> 0.21 ms, r06 A/B)
         for (size_t e = 0; e < E; e++) {
             ob[2 * e] = pr->edge_uv[2 * e];
             ob[2 * e + 1] = pr->edge_uv[2 * e + 1];
             ob[2 * E + e] = (double)pr->inv_sigma2[pr->edge_octave[e]];
         }
-        if (stereo)
-            for (size_t e = 0; e < E; e++) ob[3 * E + e] = (double)sx[b].edge_ur[e];
-        int* q = hi + p.o_int;
-        auto put = [&](const int* src, size_t cnt) { int* at = q; std::memcpy(q, src, cnt * sizeof(int)); q += cnt; return at; };
-        BaArgs& a = ha[b];
-        int* d0 = I + p.o_int;
-        auto dev = [&](const int* host_at) { return d0 + (host_at - (hi + p.o_int)); };
-        a.opt = dev(put(p.opt.data(), P));
-        a.flag = dev(q);   // [0] Cholesky ok, [1] blocked backward arrival counter (zero between uses)
-        std::memset(q, 0, 4 * sizeof(int));
-        q += 4;
-        a.e_pose = dev(put(pr->edge_pose, E));
-        a.e_pt = dev(put(pr->edge_point, E));
-        a.pt_ptr = dev(put(p.pt_ptr.data(), M + 1));
-        a.pt_edges = dev(put(p.pt_edges.data(), E));
-        a.ps_ptr = dev(put(p.ps_ptr.data(), p.np + 1));
-        a.ps_edges = dev(put(p.ps_edges.data(), p.ps_edges.size()));
-        a.blk_i = dev(put(p.blk_i.data(), p.nblk));
-        a.blk_j = dev(put(p.blk_j.data(), p.nblk));
-        a.blk_ptr = dev(put(p.blk_ptr.data(), p.nblk + 1));
-        if ((q - hi) & 1) q++;   // int2 alignment of the pair list
-        a.blk_pairs = dev(put(p.blk_pairs.data(), p.blk_pairs.size()));
-        while ((q - hi) & 3) q++;   // int4 alignment of the items
-        a.items = dev(put(p.items.data(), p.items.size()));
-        a.nitems = (int)(p.items.size() / 4);
-        a.fin = dev(put(p.fin.data(), p.fin.size()));
-        a.nfin = (int)(p.fin.size() / 3);
-        a.ifin = dev(put(p.ifin.data(), p.ifin.size()));
-        a.row_first = dev(put(p.row_first.data(), p.row_first.size()));
-        a.cb_tiles = p.cb_tiles.empty() ? nullptr : dev(put(p.cb_tiles.data(), p.cb_tiles.size()));
-        a.own = nullptr;
-        if (!p.own.empty()) {   // bytes, in the int staging
-            std::memcpy(q, p.own.data(), p.own.size());
-            a.own = reinterpret_cast<const unsigned char*>(dev(q));
-            q += (p.own.size() + 3) / 4;
-        }
-        if (p.use_dag) {   // flags + control words (zero), then the plan (or the space reserved for it)
-            while ((q - hi) & 3) q++;
-            dd[b].ints = dev(q);
-            std::memset(q, 0, dag_ints(p.n) * sizeof(int));
-            q += dag_ints(p.n);
-            dd[b].toff = dev(q);
-            if (!p.dag.toff.empty()) {
-                put(p.dag.toff.data(), p.dag.toff.size());
-                dd[b].tasks = dev(q);
-                put(p.dag.tasks.data(), p.dag.tasks.size());
-            } else {
-                dd[b].tasks = dev(q + kDagMaxHelpers + 1);   // RCCL: planned after the union envelope
-                q += p.dag_task_cap;
-            }
-            dd[b].G = p.dag.G;
-            dd[b].pb = p.dag.pb;
-            dd[b].need_off = p.dag.toff.empty() ? 0 : p.dag.toff[p.dag.G];
-        }
-        a.nblk = p.nblk;
+        if (c.stereo)
+            for (size_t e = 0; e < E; e++) ob[3 * E + e] = (double)c.sx[b].edge_ur[e];
+        Segs s;
+        s.C.base = (uintptr_t)(D + c.sC); s.C.at = p.o_chi2;
+        s.A.base = (uintptr_t)(D + c.sA); s.A.at = p.o_state;
+        s.U.base = (uintptr_t)(D + c.sU); s.U.at = p.o_obs;
+        s.R.base = (uintptr_t)(D + c.sR); s.R.at = p.o_scr;
+        s.I.base = (uintptr_t)c.I; s.I.host = c.hi; s.I.at = p.o_int;
+        BaArgs& a = c.ha[b];
+        place_problem(s, p, pr, c.stereo, c.sharded, a, c.dd[b]);
         a.P = p.P; a.M = p.M; a.E = p.E; a.np = p.np; a.n = p.n;
         a.fx = pr->fx; a.fy = pr->fy; a.cx = pr->cx; a.cy = pr->cy; a.delta = pr->huber_delta;
-        a.e_chi2 = D + sC + p.o_chi2;
-        a.pose = D + sA + p.o_state; a.pts = a.pose + 8 * P;
-        a.e_obs = D + sU + p.o_obs; a.e_info = a.e_obs + 2 * E;
-        a.e_lin = D + sR + p.o_lin;
-        double* r = D + sR + p.o_scr;
-        a.pose_bak = r; r += 8 * P;
-        a.pts_bak = r; r += 3 * M;
-        a.e_err = r; r += 2 * E;
-        a.e_rho0 = r; r += E;
-        a.e_rho1 = r; r += 2 * E;
-        a.e_ur = nullptr; a.e_err2 = nullptr; a.bf = 0.0; a.delta_s = 0.0;
-        if (stereo) {
-            a.e_ur = a.e_info + E;
-            a.e_err2 = r; r += E;
-            a.bf = sx[b].bf; a.delta_s = sx[b].delta_s;
-        }
-        a.Hpp = r; r += 36 * (size_t)p.np;
-        a.R_lin = r; r += 9 * (size_t)p.np;
-        a.Hll = r; r += 9 * M;
-        a.Dinv = r; r += 9 * M;
-        a.db = r; r += 3 * M;
-        a.Hpp_g = a.Hpp;
-        if (sharded) { a.Hpp_g = r; r += 36 * (size_t)p.np; }
-        a.sync = sharded ? 1 : 0;
-        a.small = (!sharded && 8 * P + 3 * M <= (size_t)small_words && E <= 65536) ? 1 : 0;
-        a.fused = 0;   // set below once the batch's launch width is known
-        a.b = r; r += p.n + 3 * M;
-        a.x = r; r += p.n + 3 * M;
-        a.bs = r; r += p.n;
-        a.red = r;
-        a.S = D + sR + p.o_S;
-        a.Lsave = D + sR + p.o_L;
-        a.part = D + sR + p.o_red2;
-        a.npart_e = (int)((E + 255) / 256);
-        a.npart_m = (int)((std::max(M, (size_t)P) + kBsL - 1) / kBsL);   // k_ba_backsub_errs' workgroups
-        if (p.use_dag) dd[b].buf = D + sR + p.o_dag;
+        a.bf = c.stereo ? c.sx[b].bf : 0.0;
+        a.delta_s = c.stereo ? c.sx[b].delta_s : 0.0;
+        a.sync = c.sharded ? 1 : 0;
+        a.small = (!c.sharded && 8 * P + 3 * M <= (size_t)c.sw.small_words && E <= 65536) ? 1 : 0;
+        a.fused = 0;   // set by ba_enqueue_start once the batch's launch width is known
         a.lambda = ws->lam.p + b;
-        a.lead = shard_mode == kShardLocal ? (b == 0) : (shard_mode == kShardRccl ? (ws->rank == 0 && b == 0) : 1);
+        a.lead = c.shard_mode == kShardLocal ? (b == 0) : (c.rccl ? (ws->rank == 0 && b == 0) : 1);
         a.ctl = ws->ctl.p + b;
     });
-    BAOK(hipMemcpyAsync(D + sA, hd + sA, sizeof(double) * (sR - sA), hipMemcpyHostToDevice, st));
-    // RCCL shards solved by the blocked Cholesky (which reads only the lower triangle inside the
-    // envelope; the one-workgroup solvers also read the mirrored upper triangle) all-reduce S
-    // over its union envelope only: ~5 MB instead of n^2 doubles (46 MB) at C5
-    size_t env_total = 0;
-    if (shard_mode == kShardRccl && !nd_sh && !pp[0].row_first.empty()) {   // union envelope over the ranks
-        int* rf = const_cast<int*>(ha[0].row_first);
-        if (ncclAllReduce(rf, rf, pp[0].row_first.size(), ncclInt32, ncclMin, ws->comm, st) != ncclSuccess)
-            return ORBHIP_ERR_DEVICE;
-        const int nt = (int)pp[0].row_first.size(), n = pp[0].n;
-        std::vector<int> urf(nt);
-        if (n > kCholSmallN || pp[0].use_dag) {
-            BAOK(hipMemcpyAsync(urf.data(), rf, nt * sizeof(int), hipMemcpyDeviceToHost, st));
-            BAOK(hipStreamSynchronize(st));
-        }
-        for (int b = 1; b < B; b++)   // this rank's other shards: the same envelope
-            BAOK(hipMemcpyAsync(const_cast<int*>(ha[b].row_first), rf, nt * sizeof(int), hipMemcpyDeviceToDevice, st));
-        if (pp[0].use_dag) {   // the DAG plan of the union envelope, into the reserved space
-            DagPlan& dp = pp[0].dag;
-            dag_plan(urf.data(), n, dag_helpers, dp);
-            for (int b = 0; b < B; b++) {
-                if (dp.toff.size() + dp.tasks.size() > pp[b].dag_task_cap) return ORBHIP_ERR_DEVICE;
-                BAOK(hipMemcpy(const_cast<int*>(dd[b].toff), dp.toff.data(), dp.toff.size() * sizeof(int),
+    BAOK(hipMemcpyAsync(D + c.sA, hd + c.sA, sizeof(double) * (c.sR - c.sA), hipMemcpyHostToDevice, c.st));
+    return ORBHIP_OK;
+}
+
+// ---- step 6: RCCL shards solved by the blocked or DAG Cholesky (which read only the lower
+// triangle inside the envelope; the one-workgroup solvers also read the mirrored upper triangle)
+// all-reduce S over its union envelope only: ~5 MB instead of n^2 doubles (46 MB) at C5.
+// One collective: row_first, min over the ranks, in place on the device; then the DAG plan of
+// the union envelope into the reserved space ----
+int ba_union_envelope(BaCall& c) {
+    BaWorkspace* ws = c.ws;
+    Prep* pp = c.pp;
+    const int B = c.B;
+    hipStream_t st = c.st;
+    int* rf = const_cast<int*>(c.ha[0].row_first);
+    if (ncclAllReduce(rf, rf, pp[0].row_first.size(), ncclInt32, ncclMin, ws->comm, st) != ncclSuccess)
+        return ORBHIP_ERR_DEVICE;
+    const int nt = (int)pp[0].row_first.size(), n = pp[0].n;
+    std::vector<int> urf(nt);
+    if (n > kCholSmallN || pp[0].use_dag) {
+        BAOK(hipMemcpyAsync(urf.data(), rf, nt * sizeof(int), hipMemcpyDeviceToHost, st));
+        BAOK(hipStreamSynchronize(st));
+    }
+    for (int b = 1; b < B; b++)   // this rank's other shards: the same envelope
+        BAOK(hipMemcpyAsync(const_cast<int*>(c.ha[b].row_first), rf, nt * sizeof(int), hipMemcpyDeviceToDevice, st));
+    if (pp[0].use_dag) {   // the DAG plan of the union envelope, into the reserved space
+        DagPlan& dp = pp[0].dag;
+        dag_plan(urf.data(), n, c.dag_helpers, dp);
+        for (int b = 0; b < B; b++) {
+            DagDev& d = c.dd[b];
+            if (dp.toff.size() + dp.tasks.size() > pp[b].dag_task_cap) return ORBHIP_ERR_DEVICE;
+            BAOK(hipMemcpy(const_cast<int*>(d.toff), dp.toff.data(), dp.toff.size() * sizeof(int), hipMemcpyHostToDevice));
+            d.tasks = d.toff + dp.toff.size();
+            if (!dp.tasks.empty())
+                BAOK(hipMemcpy(const_cast<int*>(d.tasks), dp.tasks.data(), dp.tasks.size() * sizeof(int),
                                hipMemcpyHostToDevice));
-                dd[b].tasks = dd[b].toff + dp.toff.size();
-                if (!dp.tasks.empty())
-                    BAOK(hipMemcpy(const_cast<int*>(dd[b].tasks), dp.tasks.data(), dp.tasks.size() * sizeof(int),
-                                   hipMemcpyHostToDevice));
-                dd[b].G = dp.G;
-                dd[b].pb = dp.pb;
-                dd[b].need_off = dp.toff[dp.G];
-            }
+            d.G = dp.G;
+            d.pb = dp.pb;
+            d.need_off = dp.toff[dp.G];
         }
-        // one shard per rank: S all-reduced over its union envelope, packed; several: the full S
-        // (summed on the device first, then the all-reduce, then copied to the other shards)
-        if (B == 1 && n > kCholSmallN && !std::getenv("ORBHIP_SHARD_FULL_S")) {
+    }
+    // one shard per rank: S all-reduced over its union envelope, packed; several: the full S
+    // (summed on the device first, then the all-reduce, then copied to the other shards)
+    if (B == 1 && n > kCholSmallN && !c.sw.shard_full_s) {
         std::vector<long long> off(nt + 1, 0);
         for (int R = 0; R < nt; R++)
             off[R + 1] = off[R] + (long long)std::min(32, n - 32 * R) * (std::min(32 * R + 32, n) - 32 * urf[R]);
-        env_total = (size_t)off[nt];
-        BAOK(ws->envbuf.ensure(env_total));
+        c.env_total = (size_t)off[nt];
+        BAOK(ws->envbuf.ensure(c.env_total));
         BAOK(ws->envoff.ensure(nt + 1));
         BAOK(hipMemcpyAsync(ws->envoff.p, off.data(), (nt + 1) * sizeof(long long), hipMemcpyHostToDevice, st));
-        }
     }
-    const double t_pack = now();
+    return ORBHIP_OK;
+}
+
+// ---- step 7: the launch widths, the controllers' initial state, the dissections' device data
+// and the timeout words. kRerunNoNd: the device setup refused a lone problem's plan ----
+int ba_init_controllers(BaCall& c) {
+    BaWorkspace* ws = c.ws;
+    const Prep* pp = c.pp;
+    const int B = c.B;
+    hipStream_t st = c.st;
     static LdsAttrOnce chol_attr;   // per device, thread-safe (dev_attr.h)
     BAOK(chol_attr.ensure((const void*)k_ba_cholesky, 160 * 1024));
-    int maxM = 0, maxE = 0, maxP = 0, maxNp = 0, maxBlk = 0, maxN = 0, maxItems = 0;
     bool s_written = false;
-    // "large": solved on its own (DAG or blocked); the rest share one single-workgroup launch
-    auto large = [&](int b) { return pp[b].use_nd || pp[b].use_nd_sh || pp[b].use_dag || pp[b].n > kCholSmallN; };
     for (int b = 0; b < B; b++) {
         const Prep& p = pp[b];
-        maxM = std::max(maxM, p.M); maxE = std::max(maxE, p.E); maxP = std::max(maxP, p.P);
-        maxNp = std::max(maxNp, p.np); maxBlk = std::max(maxBlk, p.nblk);
-        maxItems = std::max(maxItems, (int)(p.items.size() / 4));
-        if (!large(b)) maxN = std::max(maxN, p.n);
+        c.maxM = std::max(c.maxM, p.M); c.maxE = std::max(c.maxE, p.E); c.maxP = std::max(c.maxP, p.P);
+        c.maxNp = std::max(c.maxNp, p.np);
+        c.maxItems = std::max(c.maxItems, (int)(p.items.size() / 4));
+        c.maxPM = std::max(c.maxPM, std::max(8 * p.P, 3 * p.M));
+        if (!c.large(b)) c.maxN = std::max(c.maxN, p.n);
         if (!p.use_dag && !p.use_nd && !p.use_nd_sh && p.n > kCholRegMaxN) s_written = true;   // the LDS and blocked solvers factor S in place
     }
-    const size_t chol_lds = sizeof(double) * chol_lds_doubles(maxN);
+    c.chol_lds = sizeof(double) * chol_lds_doubles(c.maxN);
     // every problem on a solver that reads S and never writes it (register / DAG / dissection) and no
     // sum of S over the shards (the replicated form all-reduces S in place): S is zeroed once, the
     // Schur finisher overwrites its blocks every trial (r05: segment shards too, which saved a
     // 46 MB memset per shard and trial at C5)
-    const bool s_readonly = !s_written && (shard_mode == kShardNone || nd_sh);
-    auto large_solve = [&](int b, const int* gate) -> int {
-        if (pp[b].use_nd) {
-            (void)gate;   // set at nd_setup
-            BAOK(nd_solve(B == 1 ? ws->nd : ws->nds[b], st));
-        } else if (pp[b].use_dag) {
-            BAOK(chol_dag_solve(ha[b].S, pp[b].n, ha[b].row_first, ha[b].bs, ha[b].x, ha[b].flag, dd[b], st, gate));
-        } else {
-            chol_blocked_solve(ha[b].S, pp[b].n, ha[b].Lsave, ha[b].bs, ha[b].x, ha[b].flag, ha[b].row_first, st, gate,
-                               ha[b].cb_tiles, pp[b].cb_off.empty() ? nullptr : pp[b].cb_off.data());
-        }
-        return ORBHIP_OK;
-    };
-    auto gx = [](int n_, int b_) { return (unsigned)std::max(1, (n_ + b_ - 1) / b_); };
+    c.s_readonly = !s_written && (!c.sharded || c.nd_sh);
     (void)hipGetLastError();
-    int* d_act = ws->act.p;
-    int* h_act = ws->h_act;
-    auto upload_act = [&](const std::vector<int>& v) -> int {
-        for (size_t i = 0; i < v.size(); i++) h_act[i] = v[i];
-        BAOK(hipMemcpyAsync(d_act, h_act, v.size() * sizeof(int), hipMemcpyHostToDevice, st));
-        return ORBHIP_OK;
-    };
-    const BaArgs* dA = dArgs;
-    // the edge kernels of this call
-    const auto kErrors = stereo ? k_ba_errors<true> : k_ba_errors<false>;
-    const auto kLin = stereo ? k_ba_lin<true> : k_ba_lin<false>;
-    const auto kSchurItems = stereo ? k_ba_schur_items<true> : k_ba_schur_items<false>;
-    const auto kBacksub = stereo ? k_ba_backsub<true> : k_ba_backsub<false>;
-    const auto kBacksubErrs = stereo ? k_ba_backsub_errs<true> : k_ba_backsub_errs<false>;
-    // stop flag: one consistent decision across ranks (all-reduce max) per batch of slots
-    auto stop_now = [&]() -> bool {
-        const bool local = stop && *stop;
-        if (shard_mode != kShardRccl) return local;
-        *ws->h_stop = local ? 1 : 0;
-        if (hipMemcpyAsync(ws->dstop.p, ws->h_stop, sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) return true;
-        if (ncclAllReduce(ws->dstop.p, ws->dstop.p, 1, ncclInt32, ncclMax, ws->comm, st) != ncclSuccess) return true;
-        if (hipMemcpyAsync(ws->h_stop, ws->dstop.p, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) return true;
-        if (hipStreamSynchronize(st) != hipSuccess) return true;
-        return *ws->h_stop != 0;
-    };
+    c.d_act = ws->act.p;
+    c.h_act = ws->h_act.p;
+    for (int b = 0; b < B; b++) c.h_act[b] = b;   // act slot 0: every problem
+    BAOK(hipMemcpyAsync(c.d_act, c.h_act, B * sizeof(int), hipMemcpyHostToDevice, st));
+    LmCtl* dctl = c.dctl = ws->ctl.p;
+    for (int b = 0; b < B; b++) {
+        LmCtl& l = ws->hctl.p[b];
+        l = LmCtl{};
+        l.ni = 2;
+        l.phase = c.probs[b]->iterations > 0 ? kPhBuild : kPhDone;   // optimize(0): nothing to run
+        l.errors_valid = 1;
+        l.iterations = c.probs[b]->iterations;
+        l.early_stop = c.probs[b]->early_stop;
+    }
+    BAOK(hipMemcpyAsync(dctl, ws->hctl.p, B * sizeof(LmCtl), hipMemcpyHostToDevice, st));
+    if (B > 1)   // shards of the replicated form: each solves the summed S in its own workspace
+        while (ws->nds.size() < (size_t)B) ws->nds.push_back(nd_create());
+    for (int b = 0; b < B; b++)
+        if (pp[b].use_nd) {
+            if (!ws->nd) ws->nd = nd_create();
+            const bool uni = !c.ubi.empty();
+            const int rc = nd_setup(c.nd_of(b), pp[b].nd, uni ? c.ubi.data() : pp[b].blk_i.data(),
+                                    uni ? c.ubj.data() : pp[b].blk_j.data(), uni ? (int)c.ubi.size() : pp[b].nblk,
+                                    c.ha[b].S, c.ha[b].bs, c.ha[b].x, c.ha[b].flag, &dctl[b].phase, st);
+            // a plan the device setup refuses (a segment beyond the back-substitution's LDS, a
+            // separator system beyond the DAG solver; the planner rejects both, so this is a
+            // guard): the same problem again on the plain DAG solve, nothing was run yet
+            if (rc == -5) return hipStreamSynchronize(st) != hipSuccess ? (int)ORBHIP_ERR_DEVICE : (int)kRerunNoNd;
+            if (rc != 0) return ORBHIP_ERR_DEVICE;
+        }
+    if (c.nd_sh) {   // one segment per shard
+        while (ws->nds.size() < (size_t)B) ws->nds.push_back(nd_create());
+        for (int b = 0; b < B; b++)
+            if (nd_setup(ws->nds[b], c.ndp, pp[b].blk_i.data(), pp[b].blk_j.data(), pp[b].nblk, c.ha[b].S, c.ha[b].bs,
+                         c.ha[b].x, c.ha[b].flag, &dctl[b].phase, st, c.seg0 + b) != 0)
+                return ORBHIP_ERR_DEVICE;
+    }
     // ---- hand-off timeouts of the persistent solver: a timed-out solve fails its trial (flag 0),
     // which must never pass for a g2o rejection. Counted per problem (control word 3), read with
     // the outputs (no extra synchronisation), agreed over the ranks of a sharded solve. ----
-    std::vector<const int*> tw;   // the timeout words of every persistent solve of this call
-    int ndag = 0;
-    // the outputs: the timeout words, e_chi2 of every problem + optimised poses/points (one
-    // transfer); r06: enqueued behind the slots that may be the last ones, so a solve that ended
-    // there needs no further host round trip (a wasted copy of ~115 KB at C4 otherwise)
-    auto out_copies = [&]() -> int {
-        for (int i = 0; i < ndag; i++) BAOK(hipMemcpyAsync(ws->hto.p + i, tw[i], sizeof(int), hipMemcpyDeviceToHost, st));
-        BAOK(hipMemcpyAsync(hd, D, sizeof(double) * (nC + nA), hipMemcpyDeviceToHost, st));
+    for (int b = 0; b < B; b++) {
+        if (pp[b].use_dag) c.tw.push_back(c.dd[b].ints + 3);
+        if (pp[b].use_nd) nd_timeout_words(c.nd_of(b), c.tw);
+        if (pp[b].use_nd_sh) nd_timeout_words(ws->nds[b], c.tw);
+    }
+    c.ndag = (int)c.tw.size();
+    if (c.ndag) BAOK(ws->hto.ensure(c.ndag));
+    return ORBHIP_OK;
+}
+
+// ---- step 8: the collectives of a sharded slot (sites) and, for the in-process sums, their
+// pointer tables on the device once ----
+int ba_make_sites(BaCall& c) {
+    BaWorkspace* ws = c.ws;
+    const int B = c.B;
+    const BaArgs* ha = c.ha;
+    c.sites.assign(kSites, Site{});
+    auto site = [&](int id, size_t count, int op, auto src, auto dst) {
+        Site& t = c.sites[id];
+        t.count = count; t.op = op;
+        for (int b = 0; b < B; b++) { t.src.push_back(src(b)); t.dst.push_back(dst(b)); }
+    };
+    auto inplace = [&](int id, size_t count, int op, auto buf) { site(id, count, op, buf, buf); };
+    site(kHpp, 36 * (size_t)c.maxNp, 0, [&](int b) { return ha[b].Hpp; }, [&](int b) { return const_cast<double*>(ha[b].Hpp_g); });
+    inplace(kRed0, 1, 0, [&](int b) { return ha[b].red; });
+    inplace(kRed2, 1, 1, [&](int b) { return ha[b].red + 2; });
+    inplace(kRed01, 2, 0, [&](int b) { return ha[b].red; });
+    if (!c.nd_sh) {
+        inplace(kRepS, (size_t)c.pp[0].n * c.pp[0].n, 0, [&](int b) { return ha[b].S; });
+        inplace(kRepBs, (size_t)c.pp[0].n, 0, [&](int b) { return ha[b].bs; });
+    } else {
+        const NdSepBufs q0 = nd_sep_bufs(ws->nds[0]);
+        inplace(kNdPack, q0.pack_n, 0, [&](int b) { return nd_sep_bufs(ws->nds[b]).pack; });
+        inplace(kNdBz, (size_t)q0.nZ, 0, [&](int b) { return nd_sep_bufs(ws->nds[b]).bZ; });
+        site(kNdX, (size_t)q0.n + 1, 0, [&](int b) { return nd_sep_bufs(ws->nds[b]).x_loc; },
+             [&](int b) { return nd_sep_bufs(ws->nds[b]).xg; });
+    }
+    if (c.shard_mode == kShardLocal || B > 1) {
+        std::vector<double*> tab;
+        for (Site& t : c.sites) {
+            t.tab = tab.size();
+            tab.insert(tab.end(), t.src.begin(), t.src.end());
+            tab.insert(tab.end(), t.dst.begin(), t.dst.end());
+        }
+        BAOK(ws->ptab.ensure(tab.size()));
+        BAOK(hipMemcpy(ws->ptab.p, tab.data(), tab.size() * sizeof(double*), hipMemcpyHostToDevice));
+    }
+    return ORBHIP_OK;
+}
+
+// one collective of a sharded slot. kShardLocal: one k_ba_multi_reduce over the shards. RCCL: one
+// all-reduce of this rank's buffers (B > 1: this rank's sum first, the result copied to its other
+// shards after; S of a lone shard: over its packed union envelope)
+int coll(const BaCall& c, int id) {
+    BaWorkspace* ws = c.ws;
+    const int B = c.B;
+    hipStream_t st = c.st;
+    const Site& t = c.sites[id];
+    if (t.count == 0) return ORBHIP_OK;
+    const dim3 gr((unsigned)std::min<size_t>(1024, (t.count + 255) / 256));
+    double* const* tab = (c.shard_mode == kShardLocal || B > 1) ? ws->ptab.p + t.tab : nullptr;   // [src | dst]
+    if (c.shard_mode == kShardLocal) {
+        hipLaunchKernelGGL(k_ba_multi_reduce, gr, dim3(256), 0, st, (const double* const*)tab, B, tab + B, B,
+                           t.count, t.op);
         return ORBHIP_OK;
-    };
-    bool outputs_in = false;
-    std::vector<LmState> L(B);
+    }
+    if (B > 1) {   // RCCL with several shards per rank: this rank's sum into dst[0] first
+        hipLaunchKernelGGL(k_ba_multi_reduce, gr, dim3(256), 0, st, (const double* const*)tab, B, tab + B, 1,
+                           t.count, t.op);
+        if (ncclAllReduce(t.dst[0], t.dst[0], t.count, ncclDouble, t.op ? ncclMax : ncclSum, ws->comm, st) !=
+            ncclSuccess)
+            return ORBHIP_ERR_DEVICE;
+        hipLaunchKernelGGL(k_ba_multi_reduce, gr, dim3(256), 0, st, (const double* const*)(tab + B), 1,
+                           tab + B + 1, B - 1, t.count, t.op);
+        return ORBHIP_OK;
+    }
+    if (id == kRepS && c.env_total) {   // RCCL, replicated: S over its union envelope, packed
+        const BaArgs& a0 = c.ha[0];
+        const dim3 g(8, (unsigned)c.pp[0].row_first.size());
+        hipLaunchKernelGGL(k_ba_env_pack, g, dim3(256), 0, st, a0.S, a0.n, a0.row_first, ws->envoff.p,
+                           ws->envbuf.p, 0);
+        if (ncclAllReduce(ws->envbuf.p, ws->envbuf.p, c.env_total, ncclDouble, ncclSum, ws->comm, st) != ncclSuccess)
+            return ORBHIP_ERR_DEVICE;
+        hipLaunchKernelGGL(k_ba_env_pack, g, dim3(256), 0, st, a0.S, a0.n, a0.row_first, ws->envoff.p,
+                           ws->envbuf.p, 1);
+        return ORBHIP_OK;
+    }
+    if (ncclAllReduce(t.src[0], t.dst[0], t.count, ncclDouble, t.op ? ncclMax : ncclSum, ws->comm, st) != ncclSuccess)
+        return ORBHIP_ERR_DEVICE;
+    return ORBHIP_OK;
+}
+
+// ---- step 8b: what runs once in front of the slots: the single-workgroup solvers' problem
+// list, S zeroed (when no solver writes it), the initial errors and chi2 (sharded: summed over
+// the shards, collective kRed0), the trial's form, and the host-mapped done / stop words ----
+int ba_enqueue_start(BaCall& c) {
+    BaWorkspace* ws = c.ws;
+    const int B = c.B;
+    hipStream_t st = c.st;
+    const BaArgs* dA = c.dArgs;
+    for (int b = 0; b < B; b++)
+        if (!c.large(b)) c.h_act[2 * B + c.ns++] = b;
+    if (c.ns) BAOK(hipMemcpyAsync(c.d_act + 2 * B, c.h_act + 2 * B, c.ns * sizeof(int), hipMemcpyHostToDevice, st));
+    if (c.s_readonly) hipLaunchKernelGGL(k_ba_zero_s, dim3(64, B), dim3(256), 0, st, dA, c.d_act, 1);
+    const auto kErrors = c.stereo ? k_ba_errors<true> : k_ba_errors<false>;
+    hipLaunchKernelGGL(kErrors, dim3(gx(c.maxE, 256), B), dim3(256), 0, st, dA, c.d_act, 0, nullptr);
+    if (!c.sharded) {
+        hipLaunchKernelGGL(k_ba_ctl_init, dim3(B), dim3(1024), 0, st, dA, c.d_act);
+    } else {   // the initial chi2 over every shard's edges
+        hipLaunchKernelGGL(k_ba_reduce, dim3(B), dim3(1024), 0, st, dA, c.d_act);
+        if (coll(c, kRed0)) return ORBHIP_ERR_DEVICE;
+        hipLaunchKernelGGL(k_ba_sh_init, dim3(B), dim3(64), 0, st, dA, c.d_act);
+    }
+    for (int b = 0; b < B; b++) c.all_small = c.all_small && c.ha[b].small;
+    // a trial takes its errors inside the back-substitution when every problem's partial slots
+    // hold the fused kernel's workgroups (r06: every unsharded problem, small or not; a sharded
+    // trial ends in the split controller)
+    c.gbs = gx(std::max(c.maxM, c.maxP), kBsL);
+    // k_ba_lin's pose work-groups: one pose per work-group (its four waves on its edges) for a
+    // lone problem, four (a wave each) for batches
+    c.lin_ppw = c.sw.lin_ppw ? c.sw.lin_ppw : (B == 1 ? 1 : 4);
+    c.fused = !c.sharded && c.sw.fused;
+    for (int b = 0; b < B && c.fused; b++) c.fused = (int)c.gbs <= c.ha[b].npart_e && c.pp[b].P <= kFusedMaxP;
+    if (c.fused) {
+        for (int b = 0; b < B; b++) c.ha[b].fused = 1;
+        BAOK(hipMemcpyAsync(c.dArgs, c.ha, B * sizeof(BaArgs), hipMemcpyHostToDevice, st));
+    }
+    // the host-mapped words (post_done): B done flags, then the relayed stop flag. The kernels
+    // get them through a device-resident pointer pair: {done, stop} for a solve of its own,
+    // {done, null} for a sharded one (its shards agree on the stop between batches)
+    if (ws->done_cap < (size_t)B) {
+        if (ws->h_done) (void)hipHostFree(ws->h_done);
+        ws->h_done = nullptr; ws->d_done = nullptr; ws->done_cap = 0;
+        BAOK(hipHostMalloc((void**)&ws->h_done, sizeof(int) * (B + 1), hipHostMallocMapped | hipHostMallocCoherent));
+        BAOK(hipHostGetDevicePointer((void**)&ws->d_done, ws->h_done, 0));
+        int* const ptrs[4] = {ws->d_done, ws->d_done + B, ws->d_done, nullptr};
+        BAOK(ws->d_donep.ensure(4));
+        BAOK(hipMemcpy(ws->d_donep.p, ptrs, sizeof(ptrs), hipMemcpyHostToDevice));
+        ws->done_cap = B;
+    }
+    const bool relay = !c.sharded && c.stop;   // a caller's stop flag to relay mid-solve
+    c.donep = ws->d_donep.p + (relay ? 0 : 2);
+    c.h_stopw = relay ? ws->h_done + ws->done_cap : nullptr;
+    for (int b = 0; b < B; b++)
+        __atomic_store_n(ws->h_done + b, c.probs[b]->iterations > 0 ? 0 : 1, __ATOMIC_RELAXED);
+    __atomic_store_n(ws->h_done + ws->done_cap, 0, __ATOMIC_RELAXED);
+    return ORBHIP_OK;
+}
+
+// the linear solve of a large problem (one the single-workgroup launch does not hold)
+int large_solve(const BaCall& c, int b) {
+    const Prep& p = c.pp[b];
+    const BaArgs& a = c.ha[b];
+    const int* gate = &c.dctl[b].phase;
+    if (p.use_nd) {   // (the gate was set at nd_setup)
+        BAOK(nd_solve(c.nd_of(b), c.st));
+    } else if (p.use_dag) {
+        BAOK(chol_dag_solve(a.S, p.n, a.row_first, a.bs, a.x, a.flag, c.dd[b], c.st, gate));
+    } else {
+        chol_blocked_solve(a.S, p.n, a.Lsave, a.bs, a.x, a.flag, a.row_first, c.st, gate, a.cb_tiles,
+                           p.cb_off.empty() ? nullptr : p.cb_off.data());
+    }
+    return ORBHIP_OK;
+}
+
+// ---- step 9: one slot = one LM trial of every problem, with the iteration's linearisation in
+// front when it starts one; the controller applies the g2o rules per problem on the device, so
+// the host only enqueues. Sharded solves run the same slot with their collectives on the stream
+// between the kernels (RCCL across ranks, k_ba_multi_reduce across the shards of this process)
+// and the controller's reductions split from its decisions (BaArgs::sync): every shard sees the
+// same sums, so every shard takes the same decisions. Collectives of a sharded slot, in order:
+// kHpp, kRed2, then kNdPack, kNdBz, kNdX (segments) or kRepS, kRepBs (replicated), then kRed01 ----
+int enqueue_slot(BaCall& c) {
+    BaWorkspace* ws = c.ws;
+    const int B = c.B;
+    hipStream_t st = c.st;
+    const BaArgs* dA = c.dArgs;
+    int* d_act = c.d_act;
+    int* const* donep = c.donep;
+    const dim3 b256(256);
+    // the edge kernels of this call
+    const auto kErrors = c.stereo ? k_ba_errors<true> : k_ba_errors<false>;
+    const auto kLin = c.stereo ? k_ba_lin<true> : k_ba_lin<false>;
+    const auto kSchurItems = c.stereo ? k_ba_schur_items<true> : k_ba_schur_items<false>;
+    const auto kBacksub = c.stereo ? k_ba_backsub<true> : k_ba_backsub<false>;
+    const auto kBacksubErrs = c.stereo ? k_ba_backsub_errs<true> : k_ba_backsub_errs<false>;
+    // the sharded slots' error refresh and budget check; an unsharded problem's iteration
+    // ends in its controller (ctl_end_decide) and its stale errors are refreshed by k_ba_lin
+    if (!c.all_small && c.sharded)
+        hipLaunchKernelGGL(kErrors, dim3(gx(c.maxE, 256), B), b256, 0, st, dA, d_act, 1, donep);
+    hipLaunchKernelGGL(kLin, dim3(gx(c.maxM, kLinL) + gx(c.maxNp, c.lin_ppw), B), b256, 0, st, dA, d_act,
+                       (int)gx(c.maxM, kLinL), c.lin_ppw, donep);
+    if (c.sharded) {   // the trial start on the shards' sums: Hpp, then the largest diagonal
+        if (coll(c, kHpp)) return ORBHIP_ERR_DEVICE;
+        hipLaunchKernelGGL(k_ba_sh_maxdiag, dim3(B), b256, 0, st, dA, d_act);
+        if (coll(c, kRed2)) return ORBHIP_ERR_DEVICE;
+        hipLaunchKernelGGL(k_ba_sh_begin, dim3(B), dim3(64), 0, st, dA, d_act);
+    }
+    if (!c.s_readonly) hipLaunchKernelGGL(k_ba_zero_s, dim3(64, B), b256, 0, st, dA, d_act, 0);
+    if (!c.fused) hipLaunchKernelGGL(k_ba_schur_points, dim3(gx(c.maxM, 256), B), b256, 0, st, dA, d_act);
+    hipLaunchKernelGGL(kSchurItems, dim3(gx(2 * c.maxItems, 256) + gx(c.maxNp, 4) + 1, B), b256, 0, st, dA, d_act,
+                       (int)gx(2 * c.maxItems, 256), donep);
+    if (c.nd_sh) {   // each shard its segment; the separator system and x summed over the shards
+        for (int b = 0; b < B; b++) BAOK(nd_factor_assemble(ws->nds[b], st));
+        for (int b = 0; b < B; b++) BAOK(nd_sep_pack(ws->nds[b], 0, st));
+        if (coll(c, kNdPack) || coll(c, kNdBz)) return ORBHIP_ERR_DEVICE;
+        for (int b = 0; b < B; b++) BAOK(nd_sep_pack(ws->nds[b], 1, st));
+        for (int b = 0; b < B; b++) BAOK(nd_separator_backsolve(ws->nds[b], st));
+        if (coll(c, kNdX)) return ORBHIP_ERR_DEVICE;
+        for (int b = 0; b < B; b++) BAOK(nd_finish(ws->nds[b], st));
+    } else {
+        if (c.sharded && (coll(c, kRepS) || coll(c, kRepBs))) return ORBHIP_ERR_DEVICE;   // replicated solves
+        if (c.ns) {
+            if (c.maxN <= kCholRegMaxN) BAOK(chol_reg_launch(c.maxN, c.ns, dA, d_act + 2 * B, st));
+            else hipLaunchKernelGGL(k_ba_cholesky, dim3(c.ns), dim3(512), c.chol_lds, st, dA, d_act + 2 * B);
+        }
+        for (int b = 0; b < B; b++)
+            if (c.large(b) && large_solve(c, b)) return ORBHIP_ERR_DEVICE;
+    }
+    if (c.fused) {
+        hipLaunchKernelGGL(kBacksubErrs, dim3(c.gbs, B), b256, 0, st, dA, d_act, donep);
+    } else {
+        hipLaunchKernelGGL(kBacksub, dim3(gx(std::max(c.maxM, c.maxP), 256), B), b256, 0, st, dA, d_act);
+        hipLaunchKernelGGL(kErrors, dim3(gx(c.maxE, 256), B), b256, 0, st, dA, d_act, 2, donep);
+    }
+    if (c.sharded) {   // the trial's end on the shards' sums of chi2 and the scale
+        hipLaunchKernelGGL(k_ba_sh_sums, dim3(B), dim3(1024), 0, st, dA, d_act);
+        if (coll(c, kRed01)) return ORBHIP_ERR_DEVICE;
+        hipLaunchKernelGGL(k_ba_sh_end, dim3(B), dim3(64), 0, st, dA, d_act, donep);
+    }
+    if (!c.all_small) hipLaunchKernelGGL(k_ba_pop, dim3(gx(c.maxPM, 256), B), b256, 0, st, dA, d_act);
+    BAOK(hipGetLastError());
+    return ORBHIP_OK;
+}
+
+// stop flag: one consistent decision across ranks (all-reduce max) per batch of slots; a failed
+// collective counts as a stop
+bool stop_now(const BaCall& c) {
+    const bool local = c.stop && *c.stop;
+    if (!c.rccl) return local;
+    int* h = c.ws->h_stop.p;
+    *h = local ? 1 : 0;
+    if (rccl_consensus(c, h, c.ws->dstop.p, 1, ncclMax)) return true;
+    return *h != 0;
+}
+// the outputs: the timeout words, e_chi2 of every problem + optimised poses/points (one
+// transfer); r06: enqueued behind the slots that may be the last ones, so a solve that ended
+// there needs no further host round trip (a wasted copy of ~115 KB at C4 otherwise)
+int out_copies(const BaCall& c) {
+    for (int i = 0; i < c.ndag; i++)
+        BAOK(hipMemcpyAsync(c.ws->hto.p + i, c.tw[i], sizeof(int), hipMemcpyDeviceToHost, c.st));
+    BAOK(hipMemcpyAsync(c.hd, c.D, sizeof(double) * (c.nC + c.nA), hipMemcpyDeviceToHost, c.st));
+    return ORBHIP_OK;
+}
+bool all_done(const BaCall& c) {
+    for (int b = 0; b < c.B; b++)
+        if (!__atomic_load_n(c.ws->h_done + b, __ATOMIC_RELAXED)) return false;
+    return true;
+}
+// with a stop flag to relay: polls, yielding the core between polls (the caller's Tracking
+// thread may need it), and relays the flag into the mapped word; without one: blocks in the runtime
+int wait_ev(const BaCall& c, hipEvent_t e) {
+    if (!c.h_stopw) return hipEventSynchronize(e) == hipSuccess ? ORBHIP_OK : ORBHIP_ERR_DEVICE;
+    for (;;) {
+        std::this_thread::yield();
+        const hipError_t q = hipEventQuery(e);
+        if (q == hipSuccess) return ORBHIP_OK;
+        if (q != hipErrorNotReady) return ORBHIP_ERR_DEVICE;
+        if (c.stop && *c.stop) __atomic_store_n(c.h_stopw, 1, __ATOMIC_RELAXED);
+    }
+}
+int read_ctl(const BaCall& c) {
+    return hipMemcpyAsync(c.ws->hctl.p, c.dctl, c.B * sizeof(LmCtl), hipMemcpyDeviceToHost, c.st) == hipSuccess
+               ? ORBHIP_OK : ORBHIP_ERR_DEVICE;
+}
+
+struct EventPair {   // the two events of the slot loop, destroyed with it
+    hipEvent_t e[2] = {nullptr, nullptr};
+    ~EventPair() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
+    hipEvent_t operator[](int i) const { return e[i]; }
+};
+
+// ---- step 10: slots go out in chunks of kChunk behind one event each (at most two chunks in
+// flight): the host checks the done flags once per chunk, and while it waits it relays the
+// caller's stop flag into the mapped word that every trial's Schur launch copies into the
+// controller (relay_host_stop; checked at the trial's end and the next iteration's start: g2o's
+// force-stop checks), so a stop takes effect within a trial or two however many slots are queued.
+// r04: an event or a store to host memory between every two slots put a ~5 us bubble in front of
+// every trial (the queue drains for the marker; the kernel that wrote host memory ends with a
+// system-scope release).
+// Ranks of an RCCL solve must enqueue the same slots (their collectives pair up): they look at
+// the stop flag only between batches, agreed by an all-reduce (stop_now, the one collective of
+// this loop outside the slots), and never end a batch on the asynchronous done flags; the batch
+// length comes from the LM state read back, which every rank holds identically ----
+int ba_run_slots(BaCall& c) {
+    EventPair ev;
+    for (hipEvent_t& x : ev.e) BAOK(hipEventCreateWithFlags(&x, hipEventDisableTiming | hipEventDisableSystemFence));
+    constexpr int kChunk = 8;
+    const int B = c.B;
+    const bool rccl = c.rccl;
+    const dim3 gB((unsigned)((B + 255) / 256)), b256(256);
+    int rc = ORBHIP_OK;
+    int remaining = 0;   // slots every unfinished problem still needs at least
+    for (int b = 0; b < B; b++) remaining = std::max(remaining, c.probs[b]->iterations);
+    int nchunk = 0;
+    bool last_ev_spec = false;   // the last event recorded follows the speculative copies
     bool ctl_with_outputs = false;   // the final LM state is read back with the outputs
-    std::vector<int> all(B);
-    for (int b = 0; b < B; b++) all[b] = b;
-    if (upload_act(all)) return ORBHIP_ERR_DEVICE;
-    {
-        // ---- device-driven rounds: each slot advances every problem by one LM trial (with the
-        // iteration's linearisation in front when it starts one); the k_ba_ctl_* kernels apply
-        // the g2o rules per problem, so the host only enqueues slots and reads the state back once
-        // per batch of slots. Sharded solves run the same slots with their collectives on the
-        // stream between the kernels (RCCL across ranks, k_ba_multi_reduce across the shards of
-        // this process) and the controller's reductions split from its decisions (BaArgs::sync):
-        // every shard sees the same sums, so every shard takes the same decisions, and the host
-        // decides nothing per trial. ----
-        LmCtl* dctl = ws->ctl.p;
-        for (int b = 0; b < B; b++) {
-            LmCtl& c = ws->hctl.p[b];
-            c = LmCtl{};
-            c.ni = 2;
-            c.phase = probs[b]->iterations > 0 ? kPhBuild : kPhDone;   // optimize(0): nothing to run
-            c.errors_valid = 1;
-            c.iterations = probs[b]->iterations;
-            c.early_stop = probs[b]->early_stop;
+    while (remaining > 0) {
+        if (rccl && !c.stop_sent && stop_now(c)) {
+            hipLaunchKernelGGL(k_ba_ctl_stop, gB, b256, 0, c.st, c.dctl, B, c.donep);
+            c.stop_sent = true;
         }
-        BAOK(hipMemcpyAsync(dctl, ws->hctl.p, B * sizeof(LmCtl), hipMemcpyHostToDevice, st));
-        if (B > 1)   // shards of the replicated form: each solves the summed S in its own workspace
-            while (ws->nds.size() < (size_t)B) ws->nds.push_back(nd_create());
-        for (int b = 0; b < B; b++)
-            if (pp[b].use_nd) {
-                if (!ws->nd) ws->nd = nd_create();
-                const bool uni = !ubi.empty();
-                const int rc = nd_setup(B == 1 ? ws->nd : ws->nds[b], pp[b].nd, uni ? ubi.data() : pp[b].blk_i.data(),
-                                        uni ? ubj.data() : pp[b].blk_j.data(), uni ? (int)ubi.size() : pp[b].nblk,
-                                        ha[b].S, ha[b].bs, ha[b].x, ha[b].flag, &dctl[b].phase, st);
-                // a plan the device setup refuses (a segment beyond the back-substitution's LDS, a
-                // separator system beyond the DAG solver; the planner rejects both, so this is a
-                // guard): the same problem again on the plain DAG solve, nothing was run yet
-                if (rc == -5) {
-                    if (hipStreamSynchronize(st) != hipSuccess) return ORBHIP_ERR_DEVICE;
-                    return ba_solve_batch(ws, probs, B, res, stop, st, shard_mode, no_dag, true, sx);
-                }
-                if (rc != 0) return ORBHIP_ERR_DEVICE;
+        // RCCL: at most kChunk slots per batch, so the agreed stop is looked at every few trials
+        const int batch = rccl ? std::min(remaining, kChunk) : remaining;
+        for (int k = 0; k < batch && rc == ORBHIP_OK;) {
+            if (!rccl && !c.stop_sent && c.stop && *c.stop) {
+                hipLaunchKernelGGL(k_ba_ctl_stop, gB, b256, 0, c.st, c.dctl, B, c.donep);
+                c.stop_sent = true;
             }
-        if (nd_sh) {   // one segment per shard
-            while (ws->nds.size() < (size_t)B) ws->nds.push_back(nd_create());
-            for (int b = 0; b < B; b++)
-                if (nd_setup(ws->nds[b], ndp, pp[b].blk_i.data(), pp[b].blk_j.data(), pp[b].nblk, ha[b].S, ha[b].bs,
-                             ha[b].x, ha[b].flag, &dctl[b].phase, st, seg0 + b) != 0)
-                    return ORBHIP_ERR_DEVICE;
-        }
-        for (int b = 0; b < B; b++) {
-            if (pp[b].use_dag) tw.push_back(dd[b].ints + 3);
-            if (pp[b].use_nd) nd_timeout_words(B == 1 ? ws->nd : ws->nds[b], tw);
-            if (pp[b].use_nd_sh) nd_timeout_words(ws->nds[b], tw);
-        }
-        ndag = (int)tw.size();
-        if (ndag) BAOK(ws->hto.ensure(ndag));
-        // ---- the collectives of a sharded slot: site s sums (or maxes) src[b] into dst[b] over the
-        // shards; RCCL: one all-reduce of this rank's buffers ----
-        enum { kHpp, kRed0, kRed2, kRed01, kRepS, kRepBs, kNdPack, kNdBz, kNdX, kSites };
-        struct Site { std::vector<double*> src, dst; size_t count = 0; int op = 0; size_t tab = 0; };
-        std::vector<Site> sites(sharded ? kSites : 0);
-        if (sharded) {
-            auto site = [&](int id, size_t count, int op, auto src, auto dst) {
-                Site& t = sites[id];
-                t.count = count; t.op = op;
-                for (int b = 0; b < B; b++) { t.src.push_back(src(b)); t.dst.push_back(dst(b)); }
-            };
-            site(kHpp, 36 * (size_t)maxNp, 0, [&](int b) { return ha[b].Hpp; }, [&](int b) { return const_cast<double*>(ha[b].Hpp_g); });
-            site(kRed0, 1, 0, [&](int b) { return ha[b].red; }, [&](int b) { return ha[b].red; });
-            site(kRed2, 1, 1, [&](int b) { return ha[b].red + 2; }, [&](int b) { return ha[b].red + 2; });
-            site(kRed01, 2, 0, [&](int b) { return ha[b].red; }, [&](int b) { return ha[b].red; });
-            if (!nd_sh) {
-                site(kRepS, (size_t)pp[0].n * pp[0].n, 0, [&](int b) { return ha[b].S; }, [&](int b) { return ha[b].S; });
-                site(kRepBs, (size_t)pp[0].n, 0, [&](int b) { return ha[b].bs; }, [&](int b) { return ha[b].bs; });
-            } else {
-                const NdSepBufs q0 = nd_sep_bufs(ws->nds[0]);
-                site(kNdPack, q0.pack_n, 0, [&](int b) { return nd_sep_bufs(ws->nds[b]).pack; },
-                     [&](int b) { return nd_sep_bufs(ws->nds[b]).pack; });
-                site(kNdBz, (size_t)q0.nZ, 0, [&](int b) { return nd_sep_bufs(ws->nds[b]).bZ; },
-                     [&](int b) { return nd_sep_bufs(ws->nds[b]).bZ; });
-                site(kNdX, (size_t)q0.n + 1, 0, [&](int b) { return nd_sep_bufs(ws->nds[b]).x_loc; },
-                     [&](int b) { return nd_sep_bufs(ws->nds[b]).xg; });
+            const int n = std::min(kChunk, batch - k);
+            for (int j = 0; j < n && rc == ORBHIP_OK; j++) rc = enqueue_slot(c);
+            k += n;
+            bool spec = false;   // this batch's last slots: the LM state and outputs behind them
+            if (rc == ORBHIP_OK && !rccl && k == batch) {
+                spec = true;
+                if (read_ctl(c) != ORBHIP_OK || out_copies(c) != ORBHIP_OK) rc = ORBHIP_ERR_DEVICE;
             }
-            if (shard_mode == kShardLocal || B > 1) {   // the pointer tables of the in-process sums, on the device once
-                std::vector<double*> tab;
-                for (Site& t : sites) {
-                    t.tab = tab.size();
-                    tab.insert(tab.end(), t.src.begin(), t.src.end());
-                    tab.insert(tab.end(), t.dst.begin(), t.dst.end());
-                }
-                BAOK(ws->ptab.ensure(tab.size()));
-                BAOK(hipMemcpy(ws->ptab.p, tab.data(), tab.size() * sizeof(double*), hipMemcpyHostToDevice));
-            }
-        }
-        auto coll = [&](int id) -> int {
-            const Site& t = sites[id];
-            if (t.count == 0) return ORBHIP_OK;
-            const dim3 gr((unsigned)std::min<size_t>(1024, (t.count + 255) / 256));
-            double* const* tab = (shard_mode == kShardLocal || B > 1) ? ws->ptab.p + t.tab : nullptr;   // [src | dst]
-            if (shard_mode == kShardLocal) {
-                hipLaunchKernelGGL(k_ba_multi_reduce, gr, dim3(256), 0, st, (const double* const*)tab, B, tab + B, B,
-                                   t.count, t.op);
-                return ORBHIP_OK;
-            }
-            if (B > 1) {   // RCCL with several shards per rank: this rank's sum into dst[0] first
-                hipLaunchKernelGGL(k_ba_multi_reduce, gr, dim3(256), 0, st, (const double* const*)tab, B, tab + B, 1,
-                                   t.count, t.op);
-                if (ncclAllReduce(t.dst[0], t.dst[0], t.count, ncclDouble, t.op ? ncclMax : ncclSum, ws->comm, st) !=
-                    ncclSuccess)
-                    return ORBHIP_ERR_DEVICE;
-                hipLaunchKernelGGL(k_ba_multi_reduce, gr, dim3(256), 0, st, (const double* const*)(tab + B), 1,
-                                   tab + B + 1, B - 1, t.count, t.op);
-                return ORBHIP_OK;
-            }
-            if (id == kRepS && env_total) {   // RCCL, replicated: S over its union envelope, packed
-                const BaArgs& a0 = ha[0];
-                const dim3 g(8, (unsigned)pp[0].row_first.size());
-                hipLaunchKernelGGL(k_ba_env_pack, g, dim3(256), 0, st, a0.S, a0.n, a0.row_first, ws->envoff.p,
-                                   ws->envbuf.p, 0);
-                if (ncclAllReduce(ws->envbuf.p, ws->envbuf.p, env_total, ncclDouble, ncclSum, ws->comm, st) != ncclSuccess)
-                    return ORBHIP_ERR_DEVICE;
-                hipLaunchKernelGGL(k_ba_env_pack, g, dim3(256), 0, st, a0.S, a0.n, a0.row_first, ws->envoff.p,
-                                   ws->envbuf.p, 1);
-                return ORBHIP_OK;
-            }
-            if (ncclAllReduce(t.src[0], t.dst[0], t.count, ncclDouble, t.op ? ncclMax : ncclSum, ws->comm, st) != ncclSuccess)
-                return ORBHIP_ERR_DEVICE;
-            return ORBHIP_OK;
-        };
-        int ns = 0;   // problems on the single-workgroup solvers (act slot 3)
-        for (int b = 0; b < B; b++)
-            if (!large(b)) h_act[2 * B + ns++] = b;
-        if (ns) BAOK(hipMemcpyAsync(d_act + 2 * B, h_act + 2 * B, ns * sizeof(int), hipMemcpyHostToDevice, st));
-        if (s_readonly) hipLaunchKernelGGL(k_ba_zero_s, dim3(64, B), dim3(256), 0, st, dA, d_act, 1);
-        hipLaunchKernelGGL(kErrors, dim3(gx(maxE, 256), B), dim3(256), 0, st, dA, d_act, 0, nullptr);
-        if (!sharded) {
-            hipLaunchKernelGGL(k_ba_ctl_init, dim3(B), dim3(1024), 0, st, dA, d_act);
-        } else {   // the initial chi2 over every shard's edges
-            hipLaunchKernelGGL(k_ba_reduce, dim3(B), dim3(1024), 0, st, dA, d_act, 1);
-            if (coll(kRed0)) return ORBHIP_ERR_DEVICE;
-            hipLaunchKernelGGL(k_ba_sh_init, dim3(B), dim3(64), 0, st, dA, d_act);
-        }
-        const dim3 gB((unsigned)((B + 255) / 256)), b256(256);
-        bool all_small = true;   // every problem restores / refreshes in its trial's last workgroup
-        for (int b = 0; b < B; b++) all_small = all_small && ha[b].small;
-        // ... and takes its errors inside the back-substitution when its partial slots hold the
-        // fused kernel's workgroups (ORBHIP_BA_FUSED=0 keeps the separate k_ba_errors(2))
-        const unsigned gbs = gx(std::max(maxM, maxP), kBsL);
-        // k_ba_lin's pose work-groups: one pose per work-group (its four waves on its edges) for a
-        // lone problem, four (a wave each) for batches; ORBHIP_LIN_PPW=1/4 forces one
-        const char* e_ppw = std::getenv("ORBHIP_LIN_PPW");
-        const int lin_ppw = e_ppw ? (std::atoi(e_ppw) == 1 ? 1 : 4) : (B == 1 ? 1 : 4);
-        const char* fz = std::getenv("ORBHIP_BA_FUSED");   // per call: the tests compare both forms
-        const bool fuse_env = !(fz && fz[0] == '0');
-        // (r06: every unsharded problem, small or not; a sharded trial ends in the split controller)
-        bool fused = !sharded && fuse_env;
-        for (int b = 0; b < B && fused; b++) fused = (int)gbs <= ha[b].npart_e && pp[b].P <= kFusedMaxP;
-        if (fused) {
-            for (int b = 0; b < B; b++) ha[b].fused = 1;
-            BAOK(hipMemcpyAsync(dArgs, ha, B * sizeof(BaArgs), hipMemcpyHostToDevice, st));
-        }
-        // the host-mapped words (post_done): B done flags, then the relayed stop flag. The kernels
-        // get them through a device-resident pointer pair: {done, stop} for a solve of its own,
-        // {done, null} for a sharded one (its shards agree on the stop between batches)
-        if (ws->done_cap < (size_t)B) {
-            if (ws->h_done) (void)hipHostFree(ws->h_done);
-            ws->h_done = nullptr; ws->d_done = nullptr; ws->done_cap = 0;
-            BAOK(hipHostMalloc((void**)&ws->h_done, sizeof(int) * (B + 1), hipHostMallocMapped | hipHostMallocCoherent));
-            BAOK(hipHostGetDevicePointer((void**)&ws->d_done, ws->h_done, 0));
-            int* const ptrs[4] = {ws->d_done, ws->d_done + B, ws->d_done, nullptr};
-            BAOK(ws->d_donep.ensure(4));
-            BAOK(hipMemcpy(ws->d_donep.p, ptrs, sizeof(ptrs), hipMemcpyHostToDevice));
-            ws->done_cap = B;
-        }
-        const bool relay = !sharded && stop;   // a caller's stop flag to relay mid-solve
-        int* const* const donep = ws->d_donep.p + (relay ? 0 : 2);
-        int* const h_stopw = relay ? ws->h_done + ws->done_cap : nullptr;
-        for (int b = 0; b < B; b++) __atomic_store_n(ws->h_done + b, probs[b]->iterations > 0 ? 0 : 1, __ATOMIC_RELAXED);
-        __atomic_store_n(ws->h_done + ws->done_cap, 0, __ATOMIC_RELAXED);
-        auto slot = [&]() -> int {
-            // the sharded slots' error refresh and budget check; an unsharded problem's iteration
-            // ends in its controller (ctl_end_decide) and its stale errors are refreshed by k_ba_lin
-            if (!all_small && sharded)
-                hipLaunchKernelGGL(kErrors, dim3(gx(maxE, 256), B), b256, 0, st, dA, d_act, 1, donep);
-            hipLaunchKernelGGL(kLin, dim3(gx(maxM, kLinL) + gx(maxNp, lin_ppw), B), b256, 0, st, dA, d_act,
-                               (int)gx(maxM, kLinL), lin_ppw, donep);
-            if (sharded) {   // the trial start on the shards' sums: Hpp, then the largest diagonal
-                if (coll(kHpp)) return ORBHIP_ERR_DEVICE;
-                hipLaunchKernelGGL(k_ba_sh_maxdiag, dim3(B), b256, 0, st, dA, d_act);
-                if (coll(kRed2)) return ORBHIP_ERR_DEVICE;
-                hipLaunchKernelGGL(k_ba_sh_begin, dim3(B), dim3(64), 0, st, dA, d_act);
-            }
-            if (!s_readonly) hipLaunchKernelGGL(k_ba_zero_s, dim3(64, B), b256, 0, st, dA, d_act, 0);
-            if (!fused) hipLaunchKernelGGL(k_ba_schur_points, dim3(gx(maxM, 256), B), b256, 0, st, dA, d_act);
-            hipLaunchKernelGGL(kSchurItems, dim3(gx(2 * maxItems, 256) + gx(maxNp, 4) + 1, B), b256, 0, st, dA,
-                               d_act, (int)gx(2 * maxItems, 256), donep);
-            if (nd_sh) {   // each shard its segment; the separator system and x summed over the shards
-                for (int b = 0; b < B; b++) BAOK(nd_factor_assemble(ws->nds[b], st));
-                for (int b = 0; b < B; b++) BAOK(nd_sep_pack(ws->nds[b], 0, st));
-                if (coll(kNdPack) || coll(kNdBz)) return ORBHIP_ERR_DEVICE;
-                for (int b = 0; b < B; b++) BAOK(nd_sep_pack(ws->nds[b], 1, st));
-                for (int b = 0; b < B; b++) BAOK(nd_separator_backsolve(ws->nds[b], st));
-                if (coll(kNdX)) return ORBHIP_ERR_DEVICE;
-                for (int b = 0; b < B; b++) BAOK(nd_finish(ws->nds[b], st));
-            } else {
-                if (sharded && (coll(kRepS) || coll(kRepBs))) return ORBHIP_ERR_DEVICE;   // replicated solves
-                if (ns) {
-                    if (maxN <= kCholRegMaxN) BAOK(chol_reg_launch(maxN, ns, dA, d_act + 2 * B, st));
-                    else hipLaunchKernelGGL(k_ba_cholesky, dim3(ns), dim3(512), chol_lds, st, dA, d_act + 2 * B);
-                }
-                for (int b = 0; b < B; b++)
-                    if (large(b) && large_solve(b, &dctl[b].phase)) return ORBHIP_ERR_DEVICE;
-            }
-            if (fused) {
-                hipLaunchKernelGGL(kBacksubErrs, dim3(gbs, B), b256, 0, st, dA, d_act, donep);
-            } else {
-                hipLaunchKernelGGL(kBacksub, dim3(gx(std::max(maxM, maxP), 256), B), b256, 0, st, dA, d_act);
-                hipLaunchKernelGGL(kErrors, dim3(gx(maxE, 256), B), b256, 0, st, dA, d_act, 2, donep);
-            }
-            if (sharded) {   // the trial's end on the shards' sums of chi2 and the scale
-                hipLaunchKernelGGL(k_ba_sh_sums, dim3(B), dim3(1024), 0, st, dA, d_act);
-                if (coll(kRed01)) return ORBHIP_ERR_DEVICE;
-                hipLaunchKernelGGL(k_ba_sh_end, dim3(B), dim3(64), 0, st, dA, d_act, donep);
-            }
-            int maxPM = 0;
-            for (int b = 0; b < B; b++) maxPM = std::max(maxPM, std::max(8 * pp[b].P, 3 * pp[b].M));
-            if (!all_small) hipLaunchKernelGGL(k_ba_pop, dim3(gx(maxPM, 256), B), b256, 0, st, dA, d_act);
-            BAOK(hipGetLastError());
-            return ORBHIP_OK;
-        };
-        // Slots go out in chunks of kChunk behind one event each (at most two chunks in flight):
-        // the host checks the done flags once per chunk, and while it waits it relays the caller's
-        // stop flag into the mapped word that every trial's Schur launch copies into the controller
-        // (relay_host_stop; checked at the trial's end and the next iteration's start: g2o's
-        // force-stop checks), so a stop takes effect within a trial or two however many slots are
-        // queued. r04: an event or a store to host memory between every two slots put a
-        // ~5 us bubble in front of every trial (the queue drains for the marker; the kernel that
-        // wrote host memory ends with a system-scope release).
-        constexpr int kChunk = 8;
-        int rc = ORBHIP_OK;
-        bool stop_sent = false;
-        hipEvent_t ev[2];
-        const unsigned evf = hipEventDisableTiming | hipEventDisableSystemFence;
-        BAOK(hipEventCreateWithFlags(&ev[0], evf));
-        if (hipEventCreateWithFlags(&ev[1], evf) != hipSuccess) { (void)hipEventDestroy(ev[0]); return ORBHIP_ERR_DEVICE; }
-        auto all_done = [&] {
-            for (int b = 0; b < B; b++)
-                if (!__atomic_load_n(ws->h_done + b, __ATOMIC_RELAXED)) return false;
-            return true;
-        };
-        auto relay_stop = [&] {
-            if (h_stopw && stop && *stop) __atomic_store_n(h_stopw, 1, __ATOMIC_RELAXED);
-        };
-        // with a stop flag to relay: polls, yielding the core between polls (the caller's Tracking
-        // thread may need it); without one: blocks in the runtime
-        auto wait_ev = [&](hipEvent_t e) -> int {
-            if (!h_stopw) return hipEventSynchronize(e) == hipSuccess ? ORBHIP_OK : ORBHIP_ERR_DEVICE;
-            for (;;) {
-                std::this_thread::yield();
-                const hipError_t q = hipEventQuery(e);
-                if (q == hipSuccess) return ORBHIP_OK;
-                if (q != hipErrorNotReady) return ORBHIP_ERR_DEVICE;
-                relay_stop();
-            }
-        };
-        int remaining = 0;   // slots every unfinished problem still needs at least
-        for (int b = 0; b < B; b++) remaining = std::max(remaining, probs[b]->iterations);
-        int nchunk = 0;
-        // ranks of an RCCL solve must enqueue the same slots (their collectives pair up): they look
-        // at the stop flag only between batches, agreed by an all-reduce, and never end a batch on
-        // the asynchronous done flags; the batch length comes from the LM state read back, which
-        // every rank holds identically
-        const bool rccl = shard_mode == kShardRccl;
-        bool last_ev_spec = false;   // the last event recorded follows the speculative copies
-        while (remaining > 0 && rc == ORBHIP_OK) {
-            if (rccl && !stop_sent && stop_now()) {
-                hipLaunchKernelGGL(k_ba_ctl_stop, gB, b256, 0, st, dctl, B, donep);
-                stop_sent = true;
-            }
-            // RCCL: at most kChunk slots per batch, so the agreed stop is looked at every few trials
-            const int batch = rccl ? std::min(remaining, kChunk) : remaining;
-            for (int k = 0; k < batch && rc == ORBHIP_OK;) {
-                if (!rccl && !stop_sent && stop && *stop) {
-                    hipLaunchKernelGGL(k_ba_ctl_stop, gB, b256, 0, st, dctl, B, donep);
-                    stop_sent = true;
-                }
-                const int n = std::min(kChunk, batch - k);
-                for (int j = 0; j < n && rc == ORBHIP_OK; j++) rc = slot();
-                k += n;
-                bool spec = false;   // this batch's last slots: the LM state and outputs behind them
-                if (rc == ORBHIP_OK && !rccl && k == batch) {
-                    spec = true;
-                    if (hipMemcpyAsync(ws->hctl.p, dctl, B * sizeof(LmCtl), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                        out_copies() != ORBHIP_OK)
-                        rc = ORBHIP_ERR_DEVICE;
-                }
-                if (rc == ORBHIP_OK && hipEventRecord(ev[nchunk & 1], st) != hipSuccess) rc = ORBHIP_ERR_DEVICE;
-                if (rc != ORBHIP_OK) break;
-                last_ev_spec = spec;
-                if (nchunk++ >= 1) rc = wait_ev(ev[nchunk & 1]);   // the chunk before this one
-                if (rc == ORBHIP_OK && !rccl && all_done()) break;
-            }
-            if (rc == ORBHIP_OK) rc = wait_ev(ev[(nchunk - 1) & 1]);
+            if (rc == ORBHIP_OK && hipEventRecord(ev[nchunk & 1], c.st) != hipSuccess) rc = ORBHIP_ERR_DEVICE;
             if (rc != ORBHIP_OK) break;
-            if (!rccl && all_done()) {   // every problem ended: its LM state comes with the outputs
-                // (already in when the last event followed the speculative copies)
-                outputs_in = !rccl && last_ev_spec;
-                ctl_with_outputs = !outputs_in;
-                break;
-            }
-            if (hipMemcpyAsync(ws->hctl.p, dctl, B * sizeof(LmCtl), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipStreamSynchronize(st) != hipSuccess) {
-                rc = ORBHIP_ERR_DEVICE;
-                break;
-            }
-            remaining = 0;
-            for (int b = 0; b < B; b++) {
-                const LmCtl& c = ws->hctl.p[b];
-                if (c.phase == kPhDone) continue;
-                remaining = std::max(remaining, stop_sent ? 1 : std::max(1, c.iterations - c.it));
-            }
+            last_ev_spec = spec;
+            if (nchunk++ >= 1) rc = wait_ev(c, ev[nchunk & 1]);   // the chunk before this one
+            if (rc == ORBHIP_OK && !rccl && all_done(c)) break;
         }
-        (void)hipEventDestroy(ev[0]);
-        (void)hipEventDestroy(ev[1]);
+        if (rc == ORBHIP_OK) rc = wait_ev(c, ev[(nchunk - 1) & 1]);
         if (rc != ORBHIP_OK) return rc;
-        // the LM state read back with the outputs below (one synchronisation for all of it: each
-        // read-back + synchronisation of its own cost ~20-30 us of host round trip at C4)
-        if (ctl_with_outputs) BAOK(hipMemcpyAsync(ws->hctl.p, dctl, B * sizeof(LmCtl), hipMemcpyDeviceToHost, st));
-    }
-    const double t_solve = now();
-    if (!outputs_in) {   // (else the speculative copies below the last slots brought them)
-        if (out_copies() != ORBHIP_OK) return ORBHIP_ERR_DEVICE;
-        BAOK(hipStreamSynchronize(st));
-    }
-    {   // the LM state of every problem (read back in the loop, or just now with the outputs)
+        if (!rccl && all_done(c)) {   // every problem ended: its LM state comes with the outputs
+            // (already in when the last event followed the speculative copies)
+            c.outputs_in = last_ev_spec;
+            ctl_with_outputs = !c.outputs_in;
+            break;
+        }
+        if (read_ctl(c) != ORBHIP_OK || hipStreamSynchronize(c.st) != hipSuccess) return ORBHIP_ERR_DEVICE;
+        remaining = 0;
         for (int b = 0; b < B; b++) {
-            const LmCtl& c = ws->hctl.p[b];
-            L[b].currentChi = c.currentChi;
-            L[b].it = c.it;
-            L[b].trials = c.trials;
-            res[b]->initial_chi2 = c.initChi;
+            const LmCtl& l = c.ws->hctl.p[b];
+            if (l.phase == kPhDone) continue;
+            remaining = std::max(remaining, c.stop_sent ? 1 : std::max(1, l.iterations - l.it));
         }
     }
-    {
-        int timeouts = 0;
-        for (int i = 0; i < ndag; i++) timeouts += ws->hto.p[i];
-        if (shard_mode == kShardRccl) {   // one decision for every rank
-            *ws->h_stop = timeouts;
-            if (hipMemcpyAsync(ws->dstop.p, ws->h_stop, sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess ||
-                ncclAllReduce(ws->dstop.p, ws->dstop.p, 1, ncclInt32, ncclMax, ws->comm, st) != ncclSuccess ||
-                hipMemcpyAsync(ws->h_stop, ws->dstop.p, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess ||
-                hipStreamSynchronize(st) != hipSuccess)
-                return ORBHIP_ERR_DEVICE;
-            timeouts = *ws->h_stop;
+    // the LM state read back with the outputs below (one synchronisation for all of it: each
+    // read-back + synchronisation of its own cost ~20-30 us of host round trip at C4)
+    return ctl_with_outputs ? read_ctl(c) : (int)ORBHIP_OK;
+}
+
+// ---- step 11: the outputs and the LM state in host memory; then the hand-off timeouts of the
+// persistent solvers, agreed over the ranks (the last collective of an RCCL call: 1 int, max).
+// kRerunNoDag: some solve timed out and the call is to run again on the other solvers ----
+int ba_read_back(BaCall& c) {
+    BaWorkspace* ws = c.ws;
+    if (!c.outputs_in) {   // (else the speculative copies below the last slots brought them)
+        if (out_copies(c) != ORBHIP_OK) return ORBHIP_ERR_DEVICE;
+        BAOK(hipStreamSynchronize(c.st));
+    }
+    for (int b = 0; b < c.B; b++) c.res[b]->initial_chi2 = ws->hctl.p[b].initChi;
+    int timeouts = 0;
+    for (int i = 0; i < c.ndag; i++) timeouts += ws->hto.p[i];
+    if (c.rccl) {   // one decision for every rank
+        *ws->h_stop.p = timeouts;
+        if (rccl_consensus(c, ws->h_stop.p, ws->dstop.p, 1, ncclMax)) return ORBHIP_ERR_DEVICE;
+        timeouts = *ws->h_stop.p;
+    }
+    if (timeouts == 0) return ORBHIP_OK;
+    ws->dag_timeouts += timeouts;
+    // default: solve again on the non-persistent solvers (blocked / single-workgroup), which
+    // reproduce the schedule g2o would have run; ORBHIP_DAG_RERUN=0 reports the timeout
+    if (c.no_dag || !c.sw.dag_rerun) return ORBHIP_ERR_TIMEOUT;
+    ws->dag_reruns++;
+    return kRerunNoDag;
+}
+
+// the outputs of problem b, edges [e0, e1) (the poses, points and LM words with the first range)
+void write_outputs(const BaCall& c, int b, int e0, int e1) {
+    const Prep& p = c.pp[b];
+    const orbhip_ba_problem* pr = c.probs[b];
+    orbhip_ba_result* r = c.res[b];
+    const double* pose_o = c.hd + c.sA + p.o_state;
+    const double* pts_o = pose_o + 8 * (size_t)p.P;
+    const double* chi2_o = c.hd + c.sC + p.o_chi2;
+    if (e0 == 0) {
+        const LmCtl& l = c.ws->hctl.p[b];   // read back in the slot loop, or with the outputs
+        r->final_chi2 = l.currentChi;
+        r->iterations_done = l.it;
+        r->lm_trials = l.trials;
+        for (int i = 0; i < p.P; i++) {
+            if (r->pose_q) for (int k = 0; k < 4; k++) r->pose_q[4 * i + k] = (float)pose_o[8 * i + k];
+            if (r->pose_t) for (int k = 0; k < 3; k++) r->pose_t[3 * i + k] = (float)pose_o[8 * i + 4 + k];
         }
-        if (timeouts > 0) {
-            ws->dag_timeouts += timeouts;
-            // default: solve again on the non-persistent solvers (blocked / single-workgroup), which
-            // reproduce the schedule g2o would have run; ORBHIP_DAG_RERUN=0 reports the timeout
-            const char* e = std::getenv("ORBHIP_DAG_RERUN");
-            if (no_dag || (e && e[0] == '0')) return ORBHIP_ERR_TIMEOUT;
-            ws->dag_reruns++;
-            return ba_solve_batch(ws, probs, B, res, stop, st, shard_mode, true, no_nd, sx);
+        if (r->points) for (int k = 0; k < 3 * p.M; k++) r->points[k] = (float)pts_o[k];
+    }
+    for (int e = e0; e < e1; e++) {
+        if (r->edge_chi2) r->edge_chi2[e] = (float)chi2_o[e];
+        if (r->edge_depth_ok) {   // isDepthPositive: (T.map(X)).z > 0
+            const double* T = &pose_o[8 * pr->edge_pose[e]];
+            const double* X = &pts_o[3 * pr->edge_point[e]];
+            double ux = T[1] * X[2] - T[2] * X[1], uy = T[2] * X[0] - T[0] * X[2];
+            ux += ux; uy += uy;
+            const double uz2 = 2 * (T[0] * X[1] - T[1] * X[0]);
+            const double cz = T[0] * uy - T[1] * ux;
+            const double z = X[2] + T[3] * uz2 + cz + T[6];
+            r->edge_depth_ok[e] = z > 0.0 ? 1 : 0;
         }
     }
-    // the outputs of problem b, edges [e0, e1) (the poses, points and LM words with the first range)
-    auto outputs = [&](int b, int e0, int e1) {
-        const Prep& p = pp[b];
-        const orbhip_ba_problem* pr = probs[b];
-        orbhip_ba_result* r = res[b];
-        const double* pose_o = hd + sA + p.o_state;
-        const double* pts_o = pose_o + 8 * (size_t)p.P;
-        const double* chi2_o = hd + sC + p.o_chi2;
-        if (e0 == 0) {
-            r->final_chi2 = L[b].currentChi;
-            r->iterations_done = L[b].it;
-            r->lm_trials = L[b].trials;
-            for (int i = 0; i < p.P; i++) {
-                if (r->pose_q) for (int k = 0; k < 4; k++) r->pose_q[4 * i + k] = (float)pose_o[8 * i + k];
-                if (r->pose_t) for (int k = 0; k < 3; k++) r->pose_t[3 * i + k] = (float)pose_o[8 * i + 4 + k];
-            }
-            if (r->points) for (int k = 0; k < 3 * p.M; k++) r->points[k] = (float)pts_o[k];
-        }
-        for (int e = e0; e < e1; e++) {
-            if (r->edge_chi2) r->edge_chi2[e] = (float)chi2_o[e];
-            if (r->edge_depth_ok) {   // isDepthPositive: (T.map(X)).z > 0
-                const double* T = &pose_o[8 * pr->edge_pose[e]];
-                const double* X = &pts_o[3 * pr->edge_point[e]];
-                double ux = T[1] * X[2] - T[2] * X[1], uy = T[2] * X[0] - T[0] * X[2];
-                ux += ux; uy += uy;
-                const double uz2 = 2 * (T[0] * X[1] - T[1] * X[0]);
-                const double cz = T[0] * uy - T[1] * ux;
-                const double z = X[2] + T[3] * uz2 + cz + T[6];
-                r->edge_depth_ok[e] = z > 0.0 ? 1 : 0;
-            }
-        }
-    };
-    if (B == 1 && pp[0].E >= kPrepParallelE && host_pool_on()) {
+}
+// ---- step 12: the results, and the timing line ----
+void ba_write_results(const BaCall& c) {
+    const int B = c.B;
+    if (B == 1 && c.pp[0].E >= kPrepParallelE && host_pool_on()) {
         // one large problem (a GBA): its edges in chunks on the host pool (r06, late: the C5 loop's
         // 80k depth tests and conversions took ~0.2 ms on one core)
-        const int E = pp[0].E, T = std::min(host_threads(), E / 4096 + 1);
-        HostPool::get(host_threads() - 1).run(T, [&](int t) { outputs(0, (int)((long long)E * t / T), (int)((long long)E * (t + 1) / T)); });
+        const int E = c.pp[0].E, T = std::min(host_threads(), E / 4096 + 1);
+        HostPool::get(host_threads() - 1).run(T, [&](int t) {
+            write_outputs(c, 0, (int)((long long)E * t / T), (int)((long long)E * (t + 1) / T));
+        });
     } else {
-        parallel_for(B, nth, [&](int b) { outputs(b, 0, pp[b].E); });
+        parallel_for(B, c.nth, [&](int b) { write_outputs(c, b, 0, c.pp[b].E); });
     }
-    if (timing)
+    if (c.sw.timing)
         std::fprintf(stderr,
                      "orbhip ba timing B=%d: prep %.3f ms (problem structure %.3f), pack+upload %.3f ms, solve %.3f ms, "
                      "outputs %.3f ms\n",
-                     B, t_prep - t_start, t_prepare - t_start, t_pack - t_prep, t_solve - t_pack, now() - t_solve);
+                     B, c.t_prep - c.t_start, c.t_prepare - c.t_start, c.t_pack - c.t_prep, c.t_solve - c.t_pack,
+                     now_ms() - c.t_solve);
+}
+
+}  // namespace
+
+int ba_solve_batch(BaWorkspace* ws, const orbhip_ba_problem* const* probs, int B, orbhip_ba_result* const* res,
+                   const volatile int* stop, hipStream_t st, int shard_mode, bool no_dag, bool no_nd,
+                   const BaStereoExt* sx) {
+    BaCall c{ws, probs, B, res, stop, st, shard_mode, no_dag, no_nd, sx};
+    int rc = ba_validate(ws, probs, B, res, shard_mode, sx, c.stereo);
+    if (rc) return rc;
+    c.sw = read_switches();
+    c.sharded = shard_mode != kShardNone;
+    c.rccl = shard_mode == kShardRccl;
+    c.t_start = now_ms();
+    c.nth = host_threads();
+    if ((rc = ba_prepare_all(c))) return rc;
+    ba_choose_solvers(c);
+    if (c.sharded && (rc = ba_plan_shards(c))) return rc;
+    ba_plan_factors(c);
+    c.t_prep = now_ms();
+    ba_layout(c);
+    if ((rc = ba_pack_upload(c))) return rc;
+    if (c.rccl && !c.nd_sh && !c.pp[0].row_first.empty() && (rc = ba_union_envelope(c))) return rc;
+    c.t_pack = now_ms();
+    rc = ba_init_controllers(c);
+    // (the re-runs re-enter with the same workspace, after this frame's last use of its preparations)
+    if (rc == kRerunNoNd) return ba_solve_batch(ws, probs, B, res, stop, st, shard_mode, no_dag, true, sx);
+    if (rc) return rc;
+    if (c.sharded && (rc = ba_make_sites(c))) return rc;
+    if ((rc = ba_enqueue_start(c))) return rc;
+    if ((rc = ba_run_slots(c))) return rc;
+    c.t_solve = now_ms();
+    rc = ba_read_back(c);
+    if (rc == kRerunNoDag) return ba_solve_batch(ws, probs, B, res, stop, st, shard_mode, true, no_nd, sx);
+    if (rc) return rc;
+    ba_write_results(c);
     return ORBHIP_OK;
 }
 
@@ -3170,43 +2752,6 @@ int ba_solve(BaWorkspace* ws, const orbhip_ba_problem* prob, orbhip_ba_result* r
     const orbhip_ba_problem* pp[1] = {prob};
     orbhip_ba_result* rr[1] = {res};
     return ba_solve_batch(ws, pp, 1, rr, stop, st, kShardNone);
-}
-
-int ba_test_prepare(const orbhip_ba_problem* pr, int threads, double* out4) {
-    Prep a, b;
-    int rc = prepare(pr, a, kSchurChunk, 1);
-    if (rc) return rc;
-    auto ms_since = [](std::chrono::steady_clock::time_point t) {
-        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
-    };
-    // out4[3]: the threaded build (threads > 1) or the serial build into a reused Prep (threads = 1)
-    if (threads == 1) {
-        prep_reset(a);
-        const auto t1 = std::chrono::steady_clock::now();
-        rc = prepare(pr, a, kSchurChunk, 1);
-        const double ms1 = ms_since(t1);
-        if (rc) return rc;
-        if (out4) out4[3] = ms1;
-    }
-    const auto t0 = std::chrono::steady_clock::now();
-    rc = prepare(pr, b, kSchurChunk, threads);
-    const double ms = ms_since(t0);
-    if (rc) return rc;
-    if (threads == 1) {
-        if (out4) { out4[0] = b.nblk; out4[1] = (double)(b.blk_pairs.size() / 2); out4[2] = ms; }
-        return a.blk_pairs == b.blk_pairs ? ORBHIP_OK : -1;
-    }
-    const bool same = a.opt == b.opt && a.pt_ptr == b.pt_ptr && a.pt_edges == b.pt_edges && a.ps_ptr == b.ps_ptr &&
-                      a.ps_edges == b.ps_edges && a.blk_i == b.blk_i && a.blk_j == b.blk_j && a.blk_ptr == b.blk_ptr &&
-                      a.blk_pairs == b.blk_pairs && a.row_first == b.row_first && a.items == b.items && a.fin == b.fin &&
-                      a.nslot == b.nslot && a.nblk == b.nblk;
-    if (out4) {
-        out4[0] = b.nblk;
-        out4[1] = (double)(b.blk_pairs.size() / 2);
-        out4[2] = (double)(b.items.size() / 4);
-        out4[3] = ms;
-    }
-    return same ? ORBHIP_OK : -1;
 }
 
 void ba_stats(BaWorkspace* ws, long long* timeouts, long long* reruns) {
@@ -3224,8 +2769,8 @@ int ba_comm_init(BaWorkspace* ws, int nranks, int rank, const void* id) {
     ws->rank = rank;
     BAOK(ws->dstop.ensure(1));
     BAOK(ws->dint4.ensure(8));
-    if (!ws->h_int4) BAOK(hipHostMalloc((void**)&ws->h_int4, 8 * sizeof(int), hipHostMallocDefault));
-    if (!ws->h_stop) BAOK(hipHostMalloc((void**)&ws->h_stop, sizeof(int), hipHostMallocDefault));
+    BAOK(ws->h_int4.ensure(8));
+    BAOK(ws->h_stop.ensure(1));
     return ORBHIP_OK;
 }
 

@@ -1,6 +1,6 @@
-// CPU microbenchmark of the BA host preparation's structure build (ba_solver.hip prepare()):
+// CPU microbenchmark of the BA host preparation's structure build (csrc/ba_prep.cpp prepare()):
 // the r03 serial form, a row-wise form (each pose row builds its own blocks and pairs in a few KB)
-// and serial2 (the form ba_solver.hip now has: one load per pair endpoint, the dense counts turned
+// and serial2 (the form ba_prep.cpp now has: one load per pair endpoint, the dense counts turned
 // into fill cursors in place, scratch kept across calls), on edge lists dumped from
 // synthetic_ba_problem (C4 / C5), and serial3 (serial2's pair passes over T landmark ranges on
 // T threads). Checks that all produce identical lists. r04 on this container's CPU at C5: serial
