@@ -17,6 +17,7 @@
 #include "dev_attr.h"
 #include "geom.h"
 #include "orbhip_kernels.h"
+#include "rot_filter.h"
 
 namespace orbhip {
 
@@ -131,7 +132,6 @@ __global__ __launch_bounds__(1024) void k_search_bow(BowSide K, BowSide F, float
     const int nseg = S.cnt[2];
     if (tid == 0) S.seg[nseg] = mk;
     __syncthreads();
-    const float factor = 1.0f / 30;
     // ---- 3. one wave per shared node: the reference's greedy loop ----
     for (int sgi = wid; sgi < nseg; sgi += nw) {
         const int a = S.seg[sgi], b = S.seg[sgi + 1];
@@ -178,10 +178,7 @@ __global__ __launch_bounds__(1024) void k_search_bow(BowSide K, BowSide F, float
                     match[fidx] = kidx;
                     int bin = -1;
                     if (check_orientation) {
-                        float rot = K.angle[(int64_t)kidx * K.angle_stride] - F.angle[(int64_t)fidx * F.angle_stride];
-                        if (rot < 0.0) rot += 360.0f;
-                        bin = (int)roundf(rot * factor);
-                        if (bin == 30) bin = 0;
+                        bin = rot_bin(K.angle[(int64_t)kidx * K.angle_stride], F.angle[(int64_t)fidx * F.angle_stride]);
                         atomicAdd(&S.hist[bin], 1);
                     }
                     S.bin[fidx] = (int8_t)bin;
@@ -193,25 +190,14 @@ __global__ __launch_bounds__(1024) void k_search_bow(BowSide K, BowSide F, float
     }
     __syncthreads();
     // ---- 4. rotation consistency ----
-    if (check_orientation && tid == 0) {
-        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-        for (int i = 0; i < 30; i++) {
-            const int s = S.hist[i];
-            if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-            else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-            else if (s > max3) { max3 = s; ind3 = i; }
-        }
-        if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-        else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
-        S.keep[0] = ind1; S.keep[1] = ind2; S.keep[2] = ind3;
-    }
+    if (check_orientation && tid < 64) three_maxima_wave(S.hist, S.keep);   // wave 0 of 1024 threads
     __syncthreads();
     int c = 0;
     for (int i = tid; i < nf; i += blockDim.x) {
         int m = match[i];
         if (m >= 0 && check_orientation) {
             const int bin = S.bin[i];
-            if (bin != S.keep[0] && bin != S.keep[1] && bin != S.keep[2]) { m = -1; match[i] = -1; }
+            if (!rot_kept(bin, S.keep)) { m = -1; match[i] = -1; }
         }
         c += m >= 0;
     }

@@ -19,6 +19,7 @@
 #include "geom.h"
 #include "orbhip_device.h"
 #include "orbhip_kernels.h"
+#include "rot_filter.h"
 
 namespace orbhip {
 
@@ -112,38 +113,6 @@ __global__ __launch_bounds__(256) void k_match_top2(MatchView v, uint2* __restri
     TR_END(4)
 }
 
-// ComputeThreeMaxima over a 30-bin LDS histogram by one wave. The reference inserts bins in
-// index order with strict '>' into a top-3 that starts at 0, so its order is value descending,
-// ties by lower index, positive values only: three wave max-reductions of (value << 8 | 255 - i).
-__device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
-    v = max(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-    v = max(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-    v = max(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x141, 0xF, 0xF, true));   // row_half_mirror
-    v = max(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x140, 0xF, 0xF, true));   // row_mirror
-    const auto a = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-    v = max(a[0], a[1]);
-    const auto b = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-    return max(b[0], b[1]);
-}
-__device__ __forceinline__ void three_maxima_wave(const int* hist, int* keep) {
-    const int lane = threadIdx.x & 63;
-    const int h = lane < 30 ? hist[lane] : 0;
-    uint32_t key = h > 0 ? ((uint32_t)h << 8) | (uint32_t)(255 - lane) : 0u;
-    uint32_t k[3];
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        k[j] = wave_max_u32(key);
-        if (key == k[j]) key = 0u;
-    }
-    const int max1 = (int)(k[0] >> 8), max2 = (int)(k[1] >> 8), max3 = (int)(k[2] >> 8);
-    int ind1 = k[0] ? 255 - (int)(k[0] & 0xFF) : -1;
-    int ind2 = k[1] ? 255 - (int)(k[1] & 0xFF) : -1;
-    int ind3 = k[2] ? 255 - (int)(k[2] & 0xFF) : -1;
-    if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-    else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
-    if (lane == 0) { keep[0] = ind1; keep[1] = ind2; keep[2] = ind3; }
-}
-
 // One workgroup per pair: merge the chunk partials, apply best <= TH_LOW and best < ratio *
 // second, then the HISTO_LENGTH=30 rotation filter (ComputeThreeMaxima). The per-query match and
 // bin stay in LDS between the two passes (queries beyond kFinQ re-read). The train angles are
@@ -169,7 +138,6 @@ __global__ __launch_bounds__(1024) void k_match_finish(MatchView v, const uint2*
     const float* qa = v.qa + (int64_t)p * v.pair_angle_stride;
     const float* ta = v.ta + (int64_t)p * v.pair_angle_stride;
     int32_t* m = match + (int64_t)p * v.out_stride;
-    const float factor = 1.0f / 30;
     const bool tang_lds = nt <= kFinQ;
     uint2 u0[16];
     float qa0 = 0.f;
@@ -211,12 +179,7 @@ __global__ __launch_bounds__(1024) void k_match_finish(MatchView v, const uint2*
         best_out[o] = b;
         second_out[o] = s;
         int bin = -1;
-        if (ok && check_orientation) {
-            float rot = aq - tangle(bi);
-            if (rot < 0.0) rot += 360.0f;
-            bin = (int)roundf(rot * factor);
-            if (bin == 30) bin = 0;
-        }
+        if (ok && check_orientation) bin = rot_bin(aq, tangle(bi));
         // one LDS atomic per distinct bin of the wave (matches crowd into 1-3 bins, and
         // same-address atomics would serialise lane by lane)
         {
@@ -246,14 +209,9 @@ __global__ __launch_bounds__(1024) void k_match_finish(MatchView v, const uint2*
         else {
             t = m[q];
             bin = -1;
-            if (t >= 0 && check_orientation) {
-                float rot = qa[(int64_t)q * v.angle_stride] - tangle(t);
-                if (rot < 0.0) rot += 360.0f;
-                bin = (int)roundf(rot * factor);
-                if (bin == 30) bin = 0;
-            }
+            if (t >= 0 && check_orientation) bin = rot_bin(qa[(int64_t)q * v.angle_stride], tangle(t));
         }
-        if (t >= 0 && check_orientation && bin != keep[0] && bin != keep[1] && bin != keep[2]) t = -1;
+        if (t >= 0 && check_orientation && !rot_kept(bin, keep)) t = -1;
         m[q] = t;
         c += t >= 0;
     }
@@ -382,10 +340,7 @@ __global__ __launch_bounds__(1024) void k_match_fused(MatchView v, int th_low, f
             second_out[o] = s;
             int mt = ok ? bi : -1;
             if (ok && check_orientation) {
-                float rot = aq - (tang_lds ? tang[bi] : ta_p[(int64_t)bi * v.angle_stride]);
-                if (rot < 0.0) rot += 360.0f;
-                int bin = (int)roundf(rot * (1.0f / 30));
-                if (bin == 30) bin = 0;
+                const int bin = rot_bin(aq, tang_lds ? tang[bi] : ta_p[(int64_t)bi * v.angle_stride]);
                 atomicAdd(&hist[bin], 1);
                 mt |= bin << 24;   // tentative: the last workgroup filters
             }
@@ -408,7 +363,7 @@ __global__ __launch_bounds__(1024) void k_match_fused(MatchView v, int th_low, f
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     TR_PHASE(5, 3)
-    if (tid < 30 && hist[tid]) atomicAdd(&ps[1 + tid], hist[tid]);
+    if (tid < kHistoLength && hist[tid]) atomicAdd(&ps[1 + tid], hist[tid]);
     if (tid == 0 && cnt) atomicAdd(&ps[31], cnt);
     wait_vm_all();      // this thread's device atomics are performed
     __syncthreads();    // ... for every thread of the workgroup
@@ -426,7 +381,7 @@ __global__ __launch_bounds__(1024) void k_match_fused(MatchView v, int th_low, f
         }
         return;
     }
-    if (tid < 30) hist[tid] = atomicAdd(&ps[1 + tid], 0);
+    if (tid < kHistoLength) hist[tid] = atomicAdd(&ps[1 + tid], 0);
     if (tid == 0) cnt = 0;
     __syncthreads();
     if (tid < 64) three_maxima_wave(hist, keep);
@@ -438,7 +393,7 @@ __global__ __launch_bounds__(1024) void k_match_fused(MatchView v, int th_low, f
         if (mt >= 0) {
             const int bin = mt >> 24;
             mt &= 0xFFFFFF;
-            if (bin != keep[0] && bin != keep[1] && bin != keep[2]) mt = -1;
+            if (!rot_kept(bin, keep)) mt = -1;
             match[o] = mt;
             c += mt >= 0;
         }

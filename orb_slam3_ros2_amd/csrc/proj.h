@@ -1,4 +1,4 @@
-// Projection-guided matching on the device (proj_kernels.hip).
+// Projection-guided matching on the device (proj_kernels.hip) and SearchForInitialization (init_kernels.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -31,6 +31,7 @@ int proj_test_stats(const ProjWorkspace* ws, int32_t* out4);
 // (thr: level_thresholds(log_sf, n_levels) in device memory)
 void launch_predict_scale_sweep(uint32_t lo_bits, uint32_t hi_bits, float log_sf, const float* thr, int n_levels,
                                 const int8_t* ref, unsigned long long* mismatches, hipStream_t st);
+// SearchForInitialization (init_kernels.hip), on the same workspace (proj_ws.h)
 int init_search(ProjWorkspace* ws, const orbhip_init_frame* F1, const orbhip_init_frame* F2, float* prev_matched,
                 int window_size, float nnratio, int check_orientation, int32_t* matches12, hipStream_t st);
 }  // namespace orbhip

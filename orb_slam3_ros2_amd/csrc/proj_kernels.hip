@@ -37,6 +37,8 @@
 #include "orbhip_device.h"
 #include "orbhip_kernels.h"
 #include "proj.h"
+#include "proj_ws.h"
+#include "rot_filter.h"
 #include "stage.h"
 
 #define HIPOK(x) ORBHIP_HIPOK(" proj", x)
@@ -47,7 +49,7 @@ ORBHIP_TRACE_UNIT(proj)   // kernel id 7: k_proj_lists (phases 1-3), its resolvi
 
 namespace {
 
-constexpr int kThHigh = 100, kHisto = 30;
+constexpr int kThHigh = 100;
 
 struct ProjFrame {     // the current Frame
     int n;
@@ -67,6 +69,25 @@ struct Query {         // one projected MapPoint: GetFeaturesInArea(u, v, r, min
 __device__ __forceinline__ bool stereo_gate(const Query& Q, float u_right) {
     return u_right > 0.0f && fabsf(Q.ur - u_right) > Q.r;
 }
+// GetFeaturesInArea's cell rectangle of a query (nMinCellX .. nMaxCellY), whether it meets the
+// grid at all, and whether the walk tests levels
+struct CellRect {
+    int x0, x1, y0, y1;
+    bool any, bCheckLevels;
+    __device__ __forceinline__ CellRect(const ProjFrame& f, const Query& Q) {
+        x0 = max(0, (int)floorf((Q.u - f.minx - Q.r) * f.invw));
+        x1 = min(kGridCols - 1, (int)ceilf((Q.u - f.minx + Q.r) * f.invw));
+        y0 = max(0, (int)floorf((Q.v - f.miny - Q.r) * f.invh));
+        y1 = min(kGridRows - 1, (int)ceilf((Q.v - f.miny + Q.r) * f.invh));
+        any = x0 < kGridCols && x1 >= 0 && y0 < kGridRows && y1 >= 0;
+        bCheckLevels = (Q.minL > 0) || (Q.maxL >= 0);
+    }
+    // cell = px * kGridRows + py (0xFFFF, k_proj_lists' "no cell": px = 1365, outside)
+    __device__ __forceinline__ bool contains(int c) const {
+        const int px = c / kGridRows, py = c - px * kGridRows;
+        return px >= x0 && px <= x1 && py >= y0 && py <= y1;
+    }
+};
 
 __global__ void k_proj_cells(ProjFrame f, const orbhip_kp* __restrict__ kps, int* __restrict__ cell) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -182,6 +203,25 @@ __device__ __forceinline__ void top2_add(Top2& a, int d, int k, int l) {
     if (lt(d, k, a.d1, a.k1)) { a.d2 = a.d1; a.k2 = a.k1; a.l2 = a.l1; a.d1 = d; a.k1 = k; a.l1 = l; }
     else if (lt(d, k, a.d2, a.k2)) { a.d2 = d; a.k2 = k; a.l2 = l; }
 }
+// the wave's top-2 in every lane (lexicographic: the order of the merge does not matter)
+__device__ __forceinline__ void top2_wave_merge(Top2& t) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const int d1 = __shfl_xor(t.d1, o, 64), k1 = __shfl_xor(t.k1, o, 64), l1 = __shfl_xor(t.l1, o, 64);
+        const int d2 = __shfl_xor(t.d2, o, 64), k2 = __shfl_xor(t.k2, o, 64), l2 = __shfl_xor(t.l2, o, 64);
+        top2_add(t, d1, k1, l1);
+        top2_add(t, d2, k2, l2);
+    }
+}
+// the pick of a query from its top-2. mode 0: LastFrame (best <= TH_HIGH); mode 1: local points
+// (best/second, ratio test when both are on the same level)
+__device__ __forceinline__ int proj_decide(const Top2& t, int mode, float nnratio) {
+    if (t.d1 > kThHigh) return -1;
+    if (mode == 0) return t.k1 & 0xFFFF;
+    const bool same = t.l1 == t.l2;
+    const bool reject = same && (float)t.d1 > nnratio * (float)t.d2;
+    return (!reject && (!same || (float)t.d1 <= nnratio * (float)t.d2)) ? (t.k1 & 0xFFFF) : -1;
+}
 
 // Round r of the fixed point, one wave per query. mode 0: LastFrame (best <= TH_HIGH); mode 1:
 // local points (best/second, ratio test when both on the same level). owner[k] < i excludes
@@ -207,23 +247,16 @@ __global__ __launch_bounds__(256) void k_proj_round(ProjFrame f, int nq, int mod
     const Query Q = qs[i];
     int p = -1;
     if (Q.valid) {
-        const int nMinCellX = max(0, (int)floorf((Q.u - f.minx - Q.r) * f.invw));
-        const int nMaxCellX = min(kGridCols - 1, (int)ceilf((Q.u - f.minx + Q.r) * f.invw));
-        const int nMinCellY = max(0, (int)floorf((Q.v - f.miny - Q.r) * f.invh));
-        const int nMaxCellY = min(kGridRows - 1, (int)ceilf((Q.v - f.miny + Q.r) * f.invh));
-        const bool any = nMinCellX < kGridCols && nMaxCellX >= 0 && nMinCellY < kGridRows && nMaxCellY >= 0;
-        const bool bCheckLevels = (Q.minL > 0) || (Q.maxL >= 0);
+        const CellRect rect(f, Q);
         const uint4* qd4 = (const uint4*)(qdesc + 32 * (size_t)i);
         const uint4 qa = qd4[0], qb = qd4[1];
         Top2 t{256, INT_MAX, -1, 256, INT_MAX, -1};
-        if (any) {
+        if (rect.any) {
             for (int k = lane; k < f.n; k += 64) {
                 const int c = cell[k];
-                if (c < 0) continue;
-                const int px = c / kGridRows, py = c - px * kGridRows;
-                if (px < nMinCellX || px > nMaxCellX || py < nMinCellY || py > nMaxCellY) continue;
+                if (c < 0 || !rect.contains(c)) continue;
                 const orbhip_kp kp = kps[k];
-                if (bCheckLevels) {
+                if (rect.bCheckLevels) {
                     if (kp.octave < Q.minL) continue;
                     if (Q.maxL >= 0 && kp.octave > Q.maxL) continue;
                 }
@@ -237,23 +270,8 @@ __global__ __launch_bounds__(256) void k_proj_round(ProjFrame f, int nq, int mod
                 top2_add(t, d, (c << 16) | k, kp.octave);
             }
         }
-        // wave merge (lexicographic: the order of the merge does not matter)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const int d1 = __shfl_xor(t.d1, o, 64), k1 = __shfl_xor(t.k1, o, 64), l1 = __shfl_xor(t.l1, o, 64);
-            const int d2 = __shfl_xor(t.d2, o, 64), k2 = __shfl_xor(t.k2, o, 64), l2 = __shfl_xor(t.l2, o, 64);
-            top2_add(t, d1, k1, l1);
-            top2_add(t, d2, k2, l2);
-        }
-        if (t.d1 <= kThHigh) {
-            if (mode == 0) {
-                p = t.k1 & 0xFFFF;
-            } else {
-                const bool same = t.l1 == t.l2;
-                const bool reject = same && (float)t.d1 > nnratio * (float)t.d2;
-                if (!reject && (!same || (float)t.d1 <= nnratio * (float)t.d2)) p = t.k1 & 0xFFFF;
-            }
-        }
+        top2_wave_merge(t);
+        p = proj_decide(t, mode, nnratio);
     }
     if (lane == 0) {
         if (pick[i] != p) chg[r] = 1;
@@ -270,39 +288,18 @@ __global__ __launch_bounds__(1024) void k_proj_finish(int nq, int check_orientat
     if (threadIdx.x < 32) hist[threadIdx.x] = 0;
     if (threadIdx.x == 0) cnt = 0;
     __syncthreads();
-    const float factor = 1.0f / kHisto;
-    auto bin_of = [&](int i, int k) {
-        float rot = qangle[i] - kps[k].angle;
-        if (rot < 0.0) rot += 360.0f;
-        int b = (int)roundf(rot * factor);
-        if (b == kHisto) b = 0;
-        return b;
-    };
+    auto bin_of = [&](int i, int k) { return rot_bin(qangle[i], kps[k].angle); };
     if (check_orientation) {
         for (int i = threadIdx.x; i < nq; i += blockDim.x)
             if (pick[i] >= 0) atomicAdd(&hist[bin_of(i, pick[i])], 1);
         __syncthreads();
-        if (threadIdx.x == 0) {   // ComputeThreeMaxima
-            int m1 = 0, m2 = 0, m3 = 0, i1 = -1, i2 = -1, i3 = -1;
-            for (int b = 0; b < kHisto; b++) {
-                const int s = hist[b];
-                if (s > m1) { m3 = m2; m2 = m1; m1 = s; i3 = i2; i2 = i1; i1 = b; }
-                else if (s > m2) { m3 = m2; m2 = s; i3 = i2; i2 = b; }
-                else if (s > m3) { m3 = s; i3 = b; }
-            }
-            if (m2 < 0.1f * (float)m1) { i2 = -1; i3 = -1; }
-            else if (m3 < 0.1f * (float)m1) { i3 = -1; }
-            keep[0] = i1; keep[1] = i2; keep[2] = i3;
-        }
+        if (threadIdx.x < 64) three_maxima_wave(hist, keep);   // wave 0 of 1024 threads
         __syncthreads();
     }
     int c = 0;
     for (int i = threadIdx.x; i < nq; i += blockDim.x) {
         int k = pick[i];
-        if (k >= 0 && check_orientation) {
-            const int b = bin_of(i, k);
-            if (b != keep[0] && b != keep[1] && b != keep[2]) k = -1;
-        }
+        if (k >= 0 && check_orientation && !rot_kept(bin_of(i, k), keep)) k = -1;
         match[i] = k;
         c += k >= 0;
     }
@@ -351,14 +348,6 @@ __device__ __forceinline__ void st_ag(int* p, int v) {
 }
 __device__ __forceinline__ int ld_ag(const int* p) {
     return __hip_atomic_load((pj_gint*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ int proj_decide(const Top2& t, int mode, float nnratio) {
-    if (t.d1 > kThHigh) return -1;
-    if (mode == 0) return t.k1 & 0xFFFF;
-    const bool same = t.l1 == t.l2;
-    const bool reject = same && (float)t.d1 > nnratio * (float)t.d2;
-    return (!reject && (!same || (float)t.d1 <= nnratio * (float)t.d2)) ? (t.k1 & 0xFFFF) : -1;
 }
 
 // the one-launch form: the last work-group of k_proj_lists runs resolve_body (arrive: a counter,
@@ -446,12 +435,8 @@ __global__ __launch_bounds__(1024) void k_proj_lists(ProjFrame f, int nq, PrepLa
     int cnt = 0;
     Top2 t{256, INT_MAX, -1, 256, INT_MAX, -1};
     if (i < nq && Q.valid) {
-        const int nMinCellX = max(0, (int)floorf((Q.u - f.minx - Q.r) * f.invw));
-        const int nMaxCellX = min(kGridCols - 1, (int)ceilf((Q.u - f.minx + Q.r) * f.invw));
-        const int nMinCellY = max(0, (int)floorf((Q.v - f.miny - Q.r) * f.invh));
-        const int nMaxCellY = min(kGridRows - 1, (int)ceilf((Q.v - f.miny + Q.r) * f.invh));
-        const bool any = nMinCellX < kGridCols && nMaxCellX >= 0 && nMinCellY < kGridRows && nMaxCellY >= 0;
-        const bool bCheckLevels = (Q.minL > 0) || (Q.maxL >= 0);
+        const CellRect rect(f, Q);
+        const bool any = rect.any;
         uint64_t* out = lists + (size_t)i * cap;
         // pass 1, LDS only: the indices of the keypoints passing the window tests into the wave's
         // slice of the index buffer (the first `cap`; the count goes on). Four keypoints per lane
@@ -460,17 +445,13 @@ __global__ __launch_bounds__(1024) void k_proj_lists(ProjFrame f, int nq, PrepLa
         const uint64_t* kc8 = (const uint64_t*)kc;
         const uint64_t lt = (1ull << lane) - 1ull;
         TR_PHASE(7, 5)
-        auto in_rect = [&](int c) {
-            const int px = c / kGridRows, py = c - px * kGridRows;   // c = 0xFFFF: px = 1365, out
-            return px >= nMinCellX && px <= nMaxCellX && py >= nMinCellY && py <= nMaxCellY;
-        };
         // 1a: the cell rectangle alone, four cells per lane from one 8-byte read
         int nr = 0;
         for (int s0 = 0; any && s0 < n; s0 += 256) {
             const uint64_t v = kc8[(s0 >> 2) + lane];
 #pragma unroll
             for (int u = 0; u < 4; u++) {
-                const bool r = in_rect((int)((v >> (16 * u)) & 0xFFFF));
+                const bool r = rect.contains((int)((v >> (16 * u)) & 0xFFFF));
                 const uint64_t m = __ballot(r);
                 const int pos = nr + __popcll(m & lt);
                 if (r && pos < kRectCap) wr[pos] = (uint16_t)(s0 + 4 * lane + u);
@@ -492,8 +473,8 @@ __global__ __launch_bounds__(1024) void k_proj_lists(ProjFrame f, int nq, PrepLa
                 const uint4 e = kl[k];
                 const uint32_t oct = e.z & 0xFF;
                 const float x = __uint_as_float(e.x), y = __uint_as_float(e.y);
-                ok = !all || in_rect((int)(e.z >> 16));
-                if (ok && bCheckLevels) ok = (int)oct >= Q.minL && !(Q.maxL >= 0 && (int)oct > Q.maxL);
+                ok = !all || rect.contains((int)(e.z >> 16));
+                if (ok && rect.bCheckLevels) ok = (int)oct >= Q.minL && !(Q.maxL >= 0 && (int)oct > Q.maxL);
                 ok = ok && fabsf(x - Q.u) < Q.r && fabsf(y - Q.v) < Q.r && !((e.z >> 8) & 1u) &&
                      !stereo_gate(Q, __uint_as_float(e.w));
             }
@@ -530,13 +511,7 @@ __global__ __launch_bounds__(1024) void k_proj_lists(ProjFrame f, int nq, PrepLa
             if (d != 256) top2_add(t, d, (int)key, (int)(oct & 15u));
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const int d1 = __shfl_xor(t.d1, o, 64), k1 = __shfl_xor(t.k1, o, 64), l1 = __shfl_xor(t.l1, o, 64);
-        const int d2 = __shfl_xor(t.d2, o, 64), k2 = __shfl_xor(t.k2, o, 64), l2 = __shfl_xor(t.l2, o, 64);
-        top2_add(t, d1, k1, l1);
-        top2_add(t, d2, k2, l2);
-    }
+    top2_wave_merge(t);
     if (lane == 0 && i < nq) {
         st_ag(lcnt + i, cnt);
         st_ag(pick0 + i, proj_decide(t, MODE, nnratio));
@@ -675,37 +650,16 @@ __device__ void resolve_body(unsigned char* rsm, int n, int nq, float nnratio, i
     }
     mark(2);
     // ---- the rotation filter of SearchByProjection(CurrentFrame, LastFrame), the count ----
-    const float factor = 1.0f / kHisto;
-    auto bin_of = [&](int i, int k) {
-        float rot = qangle[i] - kps[k].angle;
-        if (rot < 0.0) rot += 360.0f;
-        int b = (int)roundf(rot * factor);
-        if (b == kHisto) b = 0;
-        return b;
-    };
+    auto bin_of = [&](int i, int k) { return rot_bin(qangle[i], kps[k].angle); };
     const bool rot = MODE == 0 && check_orientation;
     if (rot) {
         for (int i = tid; i < nq; i += nt)
             if (pk[i] >= 0) atomicAdd(&hist[bin_of(i, pk[i])], 1);
         __syncthreads();
-        if (tid == 0) {   // ComputeThreeMaxima
-            int m1 = 0, m2 = 0, m3 = 0, i1 = -1, i2 = -1, i3 = -1;
-            for (int b = 0; b < kHisto; b++) {
-                const int v = hist[b];
-                if (v > m1) { m3 = m2; m2 = m1; m1 = v; i3 = i2; i2 = i1; i1 = b; }
-                else if (v > m2) { m3 = m2; m2 = v; i3 = i2; i2 = b; }
-                else if (v > m3) { m3 = v; i3 = b; }
-            }
-            if (m2 < 0.1f * (float)m1) { i2 = -1; i3 = -1; }
-            else if (m3 < 0.1f * (float)m1) { i3 = -1; }
-            keep[0] = i1; keep[1] = i2; keep[2] = i3;
-        }
+        if (tid < 64) three_maxima_wave(hist, keep);   // wave 0 of 1024 threads
         __syncthreads();
         for (int i = tid; i < nq; i += nt)   // each thread rewrites only its own queries
-            if (pk[i] >= 0) {
-                const int b = bin_of(i, pk[i]);
-                if (b != keep[0] && b != keep[1] && b != keep[2]) pk[i] = -1;
-            }
+            if (pk[i] >= 0 && !rot_kept(bin_of(i, pk[i]), keep)) pk[i] = -1;
     }
     // the count first, then the stores (match / res may be host memory: no barrier waits on them)
     int c = 0;
@@ -736,544 +690,11 @@ __global__ __launch_bounds__(1024) void k_proj_resolve(int n, int nq, float nnra
                        res);
 }
 
-// ---------------------------------------------------------------------------
-// SearchForInitialization(F1, F2, vbPrevMatched, vnMatches12, windowSize)
-//   (U:src/ORBmatcher.cc; monocular initialisation, Tracking::MonocularInitialization)
-//
-// The reference walks the F1 keypoints of octave 0 in index order; each reads and writes the
-// per-F2-keypoint state (vMatchedDistance, vnMatches21), so query i depends on every earlier
-// query. The device splits that into the state-free part and the chain:
-//   k_init_prep     one WG: F2 octave-0 keypoints with a grid cell, ranked in walk order
-//                   (cell = px * 48 + py, then index); F1 octave-0 keypoints -> query slots
-//   k_init_cands    one wave per query: GetFeaturesInArea(prev, windowSize, 0, 0) as a
-//                   rectangle/level/|d| < r test over the ranked F2 keypoints, Hamming distance,
-//                   ballot-compacted list of (dist << 21 | rank << 5 | rotation bin), and the
-//                   list's 16 smallest entries (per-lane sorted top-4, 16 wave-min extractions)
-//   k_init_greedy   one WG: wave 0 runs the chain with the state in LDS. Per query: the
-//                   eligible entries (dist < vMatchedDistance[rank]) among its 16 smallest by one
-//                   ballot; the first two set bits are the reference's best and second best
-//                   whenever two are eligible or the list has <= 16 entries (else the whole list
-//                   is scanned, a DPP/permlane top-2 butterfly); TH_LOW / ratio test; the steal
-//                   update. Four queries share a 64-lane register, blocks of four are in flight.
-//                   Then the whole WG applies the rotation histogram (ComputeThreeMaxima over the
-//                   pushes, stale ones included) and writes vnMatches12 / vbPrevMatched.
-// (dist, rank) order is the walk order tie-break of "dist < bestDist", and the second-best
-// distance is the second element of the multiset, so the chain is exact. The bin of the pair
-// (the rotHist push) rides in the low bits, so the chain never touches the keypoints.
-// ---------------------------------------------------------------------------
-constexpr int kThLow = 50;
-constexpr int kInitK = 16;   // smallest list entries per query handed to the chain
-constexpr int kInitR = 4;    // ring of 4-query blocks in flight in the chain
-constexpr int kInitMaxRounds = 64;   // parallel rounds before the chain takes over
-
-// min over the wave, every lane gets it
-__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
-    v = min(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
-    v = min(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
-    v = min(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x141, 0xF, 0xF, true));   // row_half_mirror
-    v = min(v, (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x140, 0xF, 0xF, true));   // row_mirror
-    const auto a = __builtin_amdgcn_permlane16_swap(v, v, false, false);
-    v = min(a[0], a[1]);
-    const auto b = __builtin_amdgcn_permlane32_swap(v, v, false, false);
-    return min(b[0], b[1]);
-}
-
-struct InitGeom {
-    int n1, n2;
-    float minx, maxx, miny, maxy, invw, invh, r;
-    int list_cap;    // entries per query list (>= number of ranked F2 keypoints, multiple of 64)
-};
-
-// counts[0] = queries (F1 octave 0), counts[1] = ranked F2 keypoints, counts[2] = nmatches
-__global__ __launch_bounds__(1024) void k_init_prep(InitGeom g, const orbhip_kp* __restrict__ kps1,
-                                                    const orbhip_kp* __restrict__ kps2, int* __restrict__ slot,
-                                                    int* __restrict__ qlist, int* __restrict__ counts,
-                                                    int* __restrict__ cnt3, int* __restrict__ flags, int nflags) {
-    __shared__ int cnt[kGridCells], start[kGridCells], scratch[20], tot;
-    const int tid = threadIdx.x, nt = blockDim.x;
-    for (int c = tid; c < kGridCells; c += nt) cnt[c] = 0;
-    __syncthreads();
-    for (int k = tid; k < g.n2; k += nt) {
-        const orbhip_kp kp = kps2[k];
-        const int c = kp.octave == 0 ? grid_cell(g.minx, g.miny, g.invw, g.invh, kp.x, kp.y) : -1;
-        if (c >= 0) atomicAdd(&cnt[c], 1);
-    }
-    __syncthreads();
-    // exclusive scan of the 3072 cell counts (3 per thread, in order)
-    {
-        int v[3], s = 0;
-        for (int j = 0; j < 3; j++) { const int c = tid * 3 + j; v[j] = c < kGridCells ? cnt[c] : 0; s += v[j]; }
-        int total;
-        int base = block_excl_scan(s, scratch, &total);
-        for (int j = 0; j < 3; j++) { const int c = tid * 3 + j; if (c < kGridCells) start[c] = base; base += v[j]; }
-        if (tid == 0) tot = total;
-    }
-    __syncthreads();
-    for (int c = tid; c < kGridCells; c += nt) cnt[c] = 0;
-    __syncthreads();
-    for (int k = tid; k < g.n2; k += nt) {
-        const orbhip_kp kp = kps2[k];
-        const int c = kp.octave == 0 ? grid_cell(g.minx, g.miny, g.invw, g.invh, kp.x, kp.y) : -1;
-        if (c >= 0) slot[start[c] + atomicAdd(&cnt[c], 1)] = k;
-    }
-    __syncthreads();
-    // index order inside each cell (cells hold a handful of keypoints)
-    for (int c = tid; c < kGridCells; c += nt) {
-        int* a = slot + start[c];
-        const int m = cnt[c];
-        for (int i = 1; i < m; i++) {
-            const int v = a[i];
-            int j = i - 1;
-            while (j >= 0 && a[j] > v) { a[j + 1] = a[j]; j--; }
-            a[j + 1] = v;
-        }
-    }
-    // F1 octave-0 keypoints in index order
-    int run = 0;
-    for (int k0 = 0; k0 < g.n1; k0 += nt) {
-        const int k = k0 + tid;
-        const int f = (k < g.n1 && kps1[k].octave == 0) ? 1 : 0;   // level1 > 0 -> skipped
-        int total;
-        const int pos = block_excl_scan(f, scratch, &total);
-        if (f) qlist[run + pos] = k;
-        run += total;
-    }
-    if (tid == 0) { counts[0] = run; counts[1] = tot; }
-    // the parallel rounds' first two claim tables and flags start empty
-    for (int k = tid; k < 2 * tot; k += nt) cnt3[k] = 0;
-    for (int k = tid; k < nflags; k += nt) flags[k] = 0;
-}
-
-// one wave per query slot: the candidate list of GetFeaturesInArea(prev[i1], r, 0, 0)
-__global__ __launch_bounds__(256) void k_init_cands(InitGeom g, const orbhip_kp* __restrict__ kps1,
-                                                    const uint8_t* __restrict__ desc1,
-                                                    const orbhip_kp* __restrict__ kps2,
-                                                    const uint8_t* __restrict__ desc2, const float* __restrict__ prev,
-                                                    const int* __restrict__ slot, const int* __restrict__ qlist,
-                                                    const int* __restrict__ counts, uint32_t* __restrict__ lists,
-                                                    int* __restrict__ lens, uint32_t* __restrict__ topk,
-                                                    int* __restrict__ need) {
-    const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    const int nq = counts[0], nr = counts[1];
-    if (q >= nq) return;
-    const int i1 = qlist[q];
-    const float x = prev[2 * i1], y = prev[2 * i1 + 1], r = g.r;
-    const int nMinCellX = max(0, (int)floorf((x - g.minx - r) * g.invw));
-    const int nMaxCellX = min(kGridCols - 1, (int)ceilf((x - g.minx + r) * g.invw));
-    const int nMinCellY = max(0, (int)floorf((y - g.miny - r) * g.invh));
-    const int nMaxCellY = min(kGridRows - 1, (int)ceilf((y - g.miny + r) * g.invh));
-    const bool any = nMinCellX < kGridCols && nMaxCellX >= 0 && nMinCellY < kGridRows && nMaxCellY >= 0;
-    uint32_t* out = lists + (size_t)q * g.list_cap;
-    const float a1 = kps1[i1].angle, factor = 1.0f / kHisto;
-    int n = 0, seen = 0;
-    uint32_t t0 = ~0u, t1 = ~0u, t2 = ~0u, t3 = ~0u;
-    if (any) {
-        const uint4* qd4 = (const uint4*)(desc1 + 32 * (size_t)i1);
-        const uint4 qa = qd4[0], qb = qd4[1];
-        for (int b = 0; b < nr; b += 64) {
-            const int rk = b + lane;
-            bool ok = false;
-            uint32_t v = 0;
-            if (rk < nr) {
-                const int k = slot[rk];
-                const orbhip_kp kp = kps2[k];
-                const int c = grid_cell(g.minx, g.miny, g.invw, g.invh, kp.x, kp.y);
-                const int px = c / kGridRows, py = c - px * kGridRows;
-                if (px >= nMinCellX && px <= nMaxCellX && py >= nMinCellY && py <= nMaxCellY &&
-                    fabsf(kp.x - x) < r && fabsf(kp.y - y) < r) {
-                    const uint4* kd4 = (const uint4*)(desc2 + 32 * (size_t)k);
-                    const uint4 ka = kd4[0], kb = kd4[1];
-                    const int d = hamming256(qa, qb, ka, kb);
-                    float rot = a1 - kp.angle;
-                    if (rot < 0.0) rot += 360.0f;
-                    int bin = (int)roundf(rot * factor);
-                    if (bin == kHisto) bin = 0;
-                    v = ((uint32_t)d << 21) | ((uint32_t)rk << 5) | (uint32_t)bin;
-                    ok = true;
-                }
-            }
-            const uint64_t m = __ballot(ok);
-            if (ok) out[n + __popcll(m & ((1ull << lane) - 1ull))] = v;
-            n += __popcll(m);
-            // per-lane sorted top-4 (branch-free insert)
-            const uint32_t w = ok ? v : ~0u;
-            t3 = min(t3, max(t2, w)); t2 = min(t2, max(t1, w)); t1 = min(t1, max(t0, w)); t0 = min(t0, w);
-            seen += ok;
-        }
-    }
-    // the list's 16 smallest entries: 16 rounds of wave-min over the lane heads, the winning lane
-    // pops. A lane that pops all 4 of its kept entries while it had more may have lost one of
-    // the 16: then the chain scans the whole list (need = 2).
-    uint32_t mine = ~0u;
-    int popped = 0;
-#pragma unroll
-    for (int j = 0; j < kInitK; j++) {
-        const uint32_t mn = wave_min_u32(t0);
-        if (lane == j) mine = mn;
-        if (t0 == mn && mn != ~0u) { t0 = t1; t1 = t2; t2 = t3; t3 = ~0u; popped++; }
-    }
-    const bool lost = __ballot(popped == 4 && seen > 4) != 0;
-    if (lane < kInitK) topk[(size_t)q * kInitK + lane] = mine;
-    if (lane == 0) {
-        lens[q] = n;
-        need[q] = lost ? 2 : (n > kInitK ? 1 : 0);
-    }
-}
-
-// (m1, m2) = the two smallest values of the multiset union of two disjoint lane sets
-__device__ __forceinline__ void top2_merge(uint32_t& m1, uint32_t& m2, uint32_t o1, uint32_t o2) {
-    const uint32_t hi = max(m1, o1);
-    m1 = min(m1, o1);
-    m2 = min(hi, min(m2, o2));
-}
-template <int CTRL>
-__device__ __forceinline__ void top2_dpp(uint32_t& m1, uint32_t& m2) {
-    const uint32_t o1 = (uint32_t)__builtin_amdgcn_mov_dpp((int)m1, CTRL, 0xF, 0xF, true);
-    const uint32_t o2 = (uint32_t)__builtin_amdgcn_mov_dpp((int)m2, CTRL, 0xF, 0xF, true);
-    top2_merge(m1, m2, o1, o2);
-}
-// butterfly over the wave: xor 1, xor 2, half-row mirror, row mirror (each pairs lanes whose
-// sets are disjoint), then rows 0<->1, 2<->3 and halves by permlane swaps; every lane ends with
-// the wave's top-2
-__device__ __forceinline__ void wave_top2(uint32_t& m1, uint32_t& m2) {
-    top2_dpp<0xB1>(m1, m2);
-    top2_dpp<0x4E>(m1, m2);
-    top2_dpp<0x141>(m1, m2);
-    top2_dpp<0x140>(m1, m2);
-    {
-        const auto a = __builtin_amdgcn_permlane16_swap(m1, m1, false, false);
-        const auto b = __builtin_amdgcn_permlane16_swap(m2, m2, false, false);
-        m1 = a[0]; m2 = b[0];
-        top2_merge(m1, m2, a[1], b[1]);
-    }
-    {
-        const auto a = __builtin_amdgcn_permlane32_swap(m1, m1, false, false);
-        const auto b = __builtin_amdgcn_permlane32_swap(m2, m2, false, false);
-        m1 = a[0]; m2 = b[0];
-        top2_merge(m1, m2, a[1], b[1]);
-    }
-}
-
-
-// LDS: ST u32[nr] = vMatchedDistance (low 16 bits, 0xFFFF = INT_MAX) | vnMatches21 as a query
-// slot (high 16, 0xFFFF none); CL u32[nq] = the rank query q claimed | its rotHist push bin << 16
-// (~0u none). vnMatches12 is implied: the claim of q survives iff ST[rank].hi == q at the end (a
-// steal only ever replaces it), so the chain never reads a match back.
-__global__ __launch_bounds__(256) void k_init_greedy(InitGeom g, float nnratio, int check_orientation,
-                                                     const orbhip_kp* __restrict__ kps2, const int* __restrict__ slot,
-                                                     const int* __restrict__ qlist, const int* __restrict__ counts,
-                                                     const uint32_t* __restrict__ lists, const int* __restrict__ lens,
-                                                     const uint32_t* __restrict__ topk, const int* __restrict__ need,
-                                                     int32_t* __restrict__ matches12, float* __restrict__ prev,
-                                                     int* __restrict__ nmatch) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    __shared__ int hist[32], keep[3], cnt;
-    const int nq = counts[0], nr = counts[1];
-    uint32_t* ST = (uint32_t*)smem;
-    uint32_t* CL = ST + nr;
-    const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63;
-    for (int k = tid; k < nr; k += nt) ST[k] = ~0u;
-    for (int q = tid; q < nq; q += nt) CL[q] = ~0u;
-    for (int i = tid; i < g.n1; i += nt) matches12[i] = -1;
-    if (tid < 32) hist[tid] = 0;
-    if (tid == 0) cnt = 0;
-    __syncthreads();
-    if (tid < 64 && nq > 0) {
-        // blocks of 4 queries: lane 16j + e holds entry e of query 4b + j's top-16 (one 256-byte
-        // row per block), and lane j < 4 its `need`. A ring of kInitR blocks is in flight; the
-        // loads are unconditional (clamped block) so the waits count only the oldest block.
-        // vMatchedDistance of a block's entries is read from LDS one block ahead (mdv) and kept
-        // current by forwarding (the chain is the only writer, one rank per accepted query): a
-        // block's own updates go into its mdv at once and into the next block's at its start.
-        const int nb = (nq + 3) >> 2;
-        uint32_t tk[kInitR];
-        int nd[kInitR], mdv[kInitR];
-        auto load = [&](int b, int r) {
-            const int bb = min(b, nb - 1);
-            tk[r] = topk[(size_t)bb * 64 + lane];
-            nd[r] = need[min(4 * bb + (lane & 3), nq - 1)];
-        };
-        auto rank_of = [&](uint32_t v) { return v == ~0u ? 0 : (int)((v >> 5) & 0xFFFF); };
-#pragma unroll
-        for (int r = 0; r < kInitR; r++) load(r, r);
-        mdv[0] = (int)(ST[rank_of(tk[0])] & 0xFFFF);
-        for (int b0 = 0; b0 < nb; b0 += kInitR) {
-#pragma unroll
-            for (int r = 0; r < kInitR; r++) {
-                const int b = b0 + r;
-                const int rn = (r + 1) % kInitR;
-                mdv[rn] = (int)(ST[rank_of(tk[rn])] & 0xFFFF);   // next block, before this block's writes
-                const int rk_c = rank_of(tk[r]), rk_n = rank_of(tk[rn]);
-                int upd_rk[4] = {-1, -1, -1, -1}, upd_d[4] = {0, 0, 0, 0};
-#pragma unroll
-                for (int j = 0; j < 4; j++) {
-                    const int q = 4 * b + j;
-                    if (q < nq) {
-                        const uint32_t v = tk[r];
-                        const bool elig = v != ~0u && (int)(v >> 21) < mdv[r];
-                        const uint32_t mask = (uint32_t)(__ballot(elig) >> (16 * j)) & 0xFFFFu;
-                        const int nq_need = __builtin_amdgcn_readlane(nd[r], j);
-                        uint32_t m1 = ~0u, m2 = ~0u;
-                        if (nq_need == 0 || (nq_need == 1 && __popc(mask) >= 2)) {
-                            // the two smallest eligible entries are among the list's 16 smallest
-                            if (mask) m1 = (uint32_t)__builtin_amdgcn_readlane((int)v, 16 * j + __ffs(mask) - 1);
-                            const uint32_t rest = mask & (mask - 1);
-                            if (rest) m2 = (uint32_t)__builtin_amdgcn_readlane((int)v, 16 * j + __ffs(rest) - 1);
-                        } else {
-                            // whole-list scan (fewer than two eligible among the 16, or a lost entry)
-                            const int lc = lens[q];
-                            const uint32_t* lq = lists + (size_t)q * g.list_cap;
-                            for (int e = lane; e < lc; e += 64) {
-                                const uint32_t w0 = lq[e];
-                                const uint32_t w = (w0 >> 21) < (ST[(w0 >> 5) & 0xFFFF] & 0xFFFF) ? w0 : ~0u;
-                                m2 = min(m2, max(m1, w));
-                                m1 = min(m1, w);
-                            }
-                            wave_top2(m1, m2);
-                            m1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)m1);
-                            m2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)m2);
-                        }
-                        if (m1 != ~0u) {
-                            const int d1 = (int)(m1 >> 21);
-                            const int d2 = m2 == ~0u ? INT_MAX : (int)(m2 >> 21);
-                            if (d1 <= kThLow && (float)d1 < (float)d2 * nnratio) {
-                                const int rk = (int)((m1 >> 5) & 0xFFFF);
-                                if (lane == 0) {
-                                    CL[q] = (uint32_t)rk | ((m1 & 31) << 16);
-                                    ST[rk] = (uint32_t)d1 | ((uint32_t)q << 16);
-                                }
-                                // forward into this block's registers now, the next block's later
-                                mdv[r] = rk_c == rk ? d1 : mdv[r];
-                                upd_rk[j] = rk;
-                                upd_d[j] = d1;
-                                // a wave's LDS operations complete in order: only keep the compiler
-                                // from moving later MD reads above these writes
-                                asm volatile("" ::: "memory");
-                            }
-                        }
-                    }
-                }
-#pragma unroll
-                for (int j = 0; j < 4; j++) mdv[rn] = rk_n == upd_rk[j] ? upd_d[j] : mdv[rn];
-                load(b + kInitR, r);
-            }
-        }
-    }
-    __syncthreads();
-    if (check_orientation) {
-        for (int q = tid; q < nq; q += nt)
-            if (CL[q] != ~0u) atomicAdd(&hist[CL[q] >> 16], 1);   // every push, stolen ones included
-        __syncthreads();
-        if (tid == 0) {   // ComputeThreeMaxima
-            int m1 = 0, m2 = 0, m3 = 0, i1 = -1, i2 = -1, i3 = -1;
-            for (int b = 0; b < kHisto; b++) {
-                const int s = hist[b];
-                if (s > m1) { m3 = m2; m2 = m1; m1 = s; i3 = i2; i2 = i1; i1 = b; }
-                else if (s > m2) { m3 = m2; m2 = s; i3 = i2; i2 = b; }
-                else if (s > m3) { m3 = s; i3 = b; }
-            }
-            if (m2 < 0.1f * (float)m1) { i2 = -1; i3 = -1; }
-            else if (m3 < 0.1f * (float)m1) { i3 = -1; }
-            keep[0] = i1; keep[1] = i2; keep[2] = i3;
-        }
-        __syncthreads();
-    }
-    int c = 0;
-    for (int q = tid; q < nq; q += nt) {
-        int rk = CL[q] == ~0u ? -1 : (int)(CL[q] & 0xFFFF);
-        if (rk >= 0 && (int)(ST[rk] >> 16) != q) rk = -1;   // stolen by a later query
-        if (rk >= 0 && check_orientation) {
-            const int b = (int)(CL[q] >> 16);
-            if (b != keep[0] && b != keep[1] && b != keep[2]) rk = -1;
-        }
-        if (rk >= 0) {
-            const int i1 = qlist[q], k = slot[rk];
-            matches12[i1] = k;
-            prev[2 * i1] = kps2[k].x;
-            prev[2 * i1 + 1] = kps2[k].y;
-            c++;
-        }
-    }
-    atomicAdd(&cnt, c);
-    __syncthreads();
-    if (tid == 0) *nmatch = cnt;
-}
-
-// ---------------------------------------------------------------------------
-// The same greedy pass as a parallel fixed point. Round r recomputes every query's pick from the
-// picks of round r - 1: query q's vMatchedDistance of rank k is the smallest distance among the
-// earlier queries (j < q) that picked k in round r - 1 (in the sequential pass each later claimant
-// is strictly closer, so the last write is the minimum). Query 0 is right in round 0, and a query
-// is right once every earlier one was right a round before, so a round that changes nothing ends
-// at the sequential result. The claims of a round go to a per-rank table (kInitC slots of
-// q << 9 | dist); three tables rotate (read r, fill r + 1, clear r + 2), as in k_proj_round. A
-// rank with more than kInitC claimants in one round sets the overflow flag and the host runs the
-// chain kernel instead. The 16-lane row of a query holds its 16 smallest entries; the selection
-// is the chain's (first two eligible bits, or the whole-list scan reduced within the row).
-// flags[0] = overflow, flags[1 + r] = "round r changed a pick".
-// ---------------------------------------------------------------------------
-constexpr int kInitC = 8;
-
-__device__ __forceinline__ int init_md(const int* __restrict__ cnt, const uint32_t* __restrict__ ent, int rk, int q) {
-    const int c = min(cnt[rk], kInitC);
-    int md = INT_MAX;
-    for (int t = 0; t < c; t++) {
-        const uint32_t e = ent[(size_t)rk * kInitC + t];
-        md = (int)(e >> 9) < q ? min(md, (int)(e & 511)) : md;
-    }
-    return md;
-}
-
-__global__ __launch_bounds__(256) void k_init_round(InitGeom g, float nnratio, int r, const int* __restrict__ counts,
-                                                    const uint32_t* __restrict__ lists, const int* __restrict__ lens,
-                                                    const uint32_t* __restrict__ topk, const int* __restrict__ need,
-                                                    int* __restrict__ cnt3, uint32_t* __restrict__ ent3,
-                                                    uint32_t* __restrict__ pick, int* __restrict__ flags) {
-    if (flags[0] || (r > 0 && flags[r] == 0)) return;   // overflow, or converged a round ago
-    const int nq = counts[0], nr = counts[1];
-    const int* cc = cnt3 + (size_t)(r % 3) * nr;
-    const uint32_t* ec = ent3 + (size_t)(r % 3) * nr * kInitC;
-    int* cn = cnt3 + (size_t)((r + 1) % 3) * nr;
-    uint32_t* en = ent3 + (size_t)((r + 1) % 3) * nr * kInitC;
-    int* cz = cnt3 + (size_t)((r + 2) % 3) * nr;
-    for (int k = blockIdx.x * blockDim.x + threadIdx.x; k < nr; k += gridDim.x * blockDim.x) cz[k] = 0;
-
-    const int lane = threadIdx.x & 63, row = lane >> 4, e = lane & 15;
-    const int q = (blockIdx.x * 4 + (threadIdx.x >> 6)) * 4 + row;
-    const bool qv = q < nq;
-    const uint32_t v = qv ? topk[(size_t)q * kInitK + e] : ~0u;
-    const int nd = qv ? need[q] : 0;
-    const int md = v != ~0u ? init_md(cc, ec, (int)((v >> 5) & 0xFFFF), q) : INT_MAX;
-    const bool elig = v != ~0u && (int)(v >> 21) < md;
-    const uint32_t mask = (uint32_t)(__ballot(elig) >> (16 * row)) & 0xFFFFu;
-    const uint32_t rest = mask & (mask - 1);
-    // first two eligible entries of the row (all lanes shuffle, so no source lane is inactive)
-    const uint32_t a = (uint32_t)__shfl((int)v, 16 * row + (mask ? __ffs(mask) - 1 : 0));
-    const uint32_t b = (uint32_t)__shfl((int)v, 16 * row + (rest ? __ffs(rest) - 1 : 0));
-    const bool full = qv && (nd == 2 || (nd == 1 && __popc(mask) < 2));
-    uint32_t f1 = ~0u, f2 = ~0u;
-    if (full) {   // whole list, 16 lanes of the row
-        const int lc = lens[q];
-        const uint32_t* lq = lists + (size_t)q * g.list_cap;
-        for (int t = e; t < lc; t += 16) {
-            const uint32_t w0 = lq[t];
-            const uint32_t w = (int)(w0 >> 21) < init_md(cc, ec, (int)((w0 >> 5) & 0xFFFF), q) ? w0 : ~0u;
-            f2 = min(f2, max(f1, w));
-            f1 = min(f1, w);
-        }
-    }
-    // top-2 within each 16-lane row (rows that did not scan reduce ~0u)
-    top2_dpp<0xB1>(f1, f2);
-    top2_dpp<0x4E>(f1, f2);
-    top2_dpp<0x141>(f1, f2);
-    top2_dpp<0x140>(f1, f2);
-    const uint32_t m1 = full ? f1 : (mask ? a : ~0u);
-    const uint32_t m2 = full ? f2 : (rest ? b : ~0u);
-    uint32_t np = ~0u;
-    if (m1 != ~0u) {
-        const int d1 = (int)(m1 >> 21);
-        const int d2 = m2 == ~0u ? INT_MAX : (int)(m2 >> 21);
-        if (d1 <= kThLow && (float)d1 < (float)d2 * nnratio) np = m1;
-    }
-    if (qv && e == 0) {
-        const uint32_t was = r == 0 ? ~0u : pick[q];   // round 0 starts from "no picks"
-        if (r == 0 || was != np) pick[q] = np;
-        if (was != np) flags[1 + r] = 1;
-        if (np != ~0u) {
-            const int rk = (int)((np >> 5) & 0xFFFF);
-            const int s = atomicAdd(&cn[rk], 1);
-            if (s < kInitC) en[(size_t)rk * kInitC + s] = ((uint32_t)q << 9) | (np >> 21);
-            else flags[0] = 1;
-        }
-    }
-}
-
-// Applies converged picks: the last claimant of each rank keeps it (the steals), the rotation
-// histogram counts every pick, as k_init_greedy. Writes matches12 and prev_out for all of F1 (so
-// a finish over a not yet converged round, which the host discards, leaves nothing behind).
-__global__ __launch_bounds__(1024) void k_init_finish(InitGeom g, int check_orientation, const orbhip_kp* __restrict__ kps2,
-                                                      const int* __restrict__ slot, const int* __restrict__ qlist,
-                                                      const int* __restrict__ counts, const uint32_t* __restrict__ pick,
-                                                      const float* __restrict__ prev_in, int32_t* __restrict__ matches12,
-                                                      float* __restrict__ prev_out, int* __restrict__ nmatch) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    __shared__ int hist[32], keep[3], cnt;
-    int* owner = (int*)smem;
-    const int nq = counts[0], nr = counts[1];
-    const int tid = threadIdx.x, nt = blockDim.x;
-    for (int k = tid; k < nr; k += nt) owner[k] = -1;
-    for (int i = tid; i < g.n1; i += nt) {
-        matches12[i] = -1;
-        prev_out[2 * i] = prev_in[2 * i];
-        prev_out[2 * i + 1] = prev_in[2 * i + 1];
-    }
-    if (tid < 32) hist[tid] = 0;
-    if (tid == 0) cnt = 0;
-    __syncthreads();
-    for (int q = tid; q < nq; q += nt) {
-        const uint32_t p = pick[q];
-        if (p != ~0u) {
-            atomicMax(&owner[(p >> 5) & 0xFFFF], q);
-            if (check_orientation) atomicAdd(&hist[p & 31], 1);
-        }
-    }
-    __syncthreads();
-    if (check_orientation) {
-        if (tid == 0) {   // ComputeThreeMaxima
-            int m1 = 0, m2 = 0, m3 = 0, i1 = -1, i2 = -1, i3 = -1;
-            for (int b = 0; b < kHisto; b++) {
-                const int s = hist[b];
-                if (s > m1) { m3 = m2; m2 = m1; m1 = s; i3 = i2; i2 = i1; i1 = b; }
-                else if (s > m2) { m3 = m2; m2 = s; i3 = i2; i2 = b; }
-                else if (s > m3) { m3 = s; i3 = b; }
-            }
-            if (m2 < 0.1f * (float)m1) { i2 = -1; i3 = -1; }
-            else if (m3 < 0.1f * (float)m1) { i3 = -1; }
-            keep[0] = i1; keep[1] = i2; keep[2] = i3;
-        }
-        __syncthreads();
-    }
-    int c = 0;
-    for (int q = tid; q < nq; q += nt) {
-        const uint32_t p = pick[q];
-        int rk = p == ~0u ? -1 : (int)((p >> 5) & 0xFFFF);
-        if (rk >= 0 && owner[rk] != q) rk = -1;   // stolen by a later query
-        if (rk >= 0 && check_orientation) {
-            const int b = (int)(p & 31);
-            if (b != keep[0] && b != keep[1] && b != keep[2]) rk = -1;
-        }
-        if (rk >= 0) {
-            const int i1 = qlist[q], k = slot[rk];
-            matches12[i1] = k;
-            prev_out[2 * i1] = kps2[k].x;
-            prev_out[2 * i1 + 1] = kps2[k].y;
-            c++;
-        }
-    }
-    atomicAdd(&cnt, c);
-    __syncthreads();
-    if (tid == 0) *nmatch = cnt;
-}
-
 }  // namespace
 
 // ---------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------
-struct ProjWorkspace {
-    StageBlock s{true};      // the two-launch form writes its results straight into the pinned image
-    int* arrive = nullptr;   // the one-launch search's arrival counter (0 between launches)
-    int ahead = 4;   // rounds launched per host sync (adapts to the last search)
-    int init_ahead = 6;   // the same for SearchForInitialization's rounds
-    // the last projection search (orbhip_test_proj_stats): the form that produced the result (0 lists
-    // + resolve, 1 a list overflowed and the rounds produced it, 2 rounds only, -1 none yet or no
-    // queries), its rounds, the list entries the resolve saw (form 0) and the call's ent_cap
-    int st_form = -1, st_rounds = 0, st_entries = 0, st_ent_cap = 0;
-    ~ProjWorkspace() {
-        if (arrive) (void)hipFree(arrive);
-    }
-};
 ProjWorkspace* proj_ws_create() { return new ProjWorkspace(); }
 void proj_ws_destroy(ProjWorkspace* w) { delete w; }
 
@@ -1295,54 +716,6 @@ ProjFrame make_frame(const orbhip_frame* F) {
     const float v[3] = {f.t[0] * -1.0f, f.t[1] * -1.0f, f.t[2] * -1.0f};
     quat_rotate(qc, v, f.Ow);
     return f;
-}
-
-// the block of `total` bytes on both sides, and the arrival counter
-int ensure(ProjWorkspace* ws, size_t total) {
-    if (!ws->arrive) {
-        HIPOK(hipMalloc((void**)&ws->arrive, sizeof(int)));
-        HIPOK(hipMemset(ws->arrive, 0, sizeof(int)));
-    }
-    HIPOK(ws->s.ensure(total, total));
-    return ORBHIP_OK;
-}
-
-// The fixed-point rounds, launched `ws->ahead` at a time with the finishing work (`tail`: the
-// finish kernel and the result downloads) behind them and ONE host sync per batch: rounds after
-// convergence exit on the device, so the common case is a single round trip. Returns the number
-// of rounds that did work (< 0 on error).
-template <typename Tail>
-int run_rounds(ProjWorkspace* ws, const ProjFrame& f, int nq, int mode, float nnratio, char* D, size_t o_q,
-               size_t o_kps, size_t o_kd, size_t o_cell, const uint8_t* claimed, size_t o_own, size_t o_qd,
-               size_t o_pick, size_t o_chg, char* H, hipStream_t st, const float* u_right, Tail&& tail) {
-    const dim3 gq((unsigned)std::max(1, (nq + 3) / 4));
-    const int cap = nq + 2;   // a fixed point is reached within nq + 1 rounds
-    int* chg = (int*)(D + o_chg);
-    const int* hchg = (const int*)(H + o_chg);
-    HIPOK(hipMemsetAsync(D + o_own, 0x7F, 3 * sizeof(int) * (size_t)std::max(f.n, 1), st));   // > any query
-    HIPOK(hipMemsetAsync(chg, 0, sizeof(int) * (size_t)cap, st));
-    int r = 0;
-    for (;;) {
-        const int R = std::min(ws->ahead, cap - r);
-        for (int j = 0; j < R; j++)
-            hipLaunchKernelGGL(k_proj_round, gq, dim3(256), 0, st, f, nq, mode, nnratio, r + j,
-                               (const Query*)(D + o_q), (const orbhip_kp*)(D + o_kps), (const uint8_t*)(D + o_kd),
-                               (const int*)(D + o_cell), claimed, (int*)(D + o_own), (const uint8_t*)(D + o_qd),
-                               (int*)(D + o_pick), chg, u_right);
-        HIPOK(hipGetLastError());
-        if (int rc = tail()) return rc;
-        HIPOK(hipMemcpyAsync(H + o_chg + sizeof(int) * r, chg + r, sizeof(int) * R, hipMemcpyDeviceToHost, st));
-        HIPOK(hipStreamSynchronize(st));
-        for (int j = 0; j < R; j++)
-            if (hchg[r + j] == 0) {
-                const int rounds = r + j + 1;
-                ws->ahead = std::min(16, std::max(2, rounds + 1));
-                return rounds;
-            }
-        r += R;
-        if (r >= cap) return r;
-        ws->ahead = std::min(16, 2 * ws->ahead);
-    }
 }
 
 // the two-launch form applies: every octave fits the list entry's 4 bits, the owner tables fit LDS
@@ -1394,6 +767,156 @@ struct OutBlock {
         bytes = res + 16;
     }
 };
+
+// What both searches decide from a call's sizes before they lay out their block, and the
+// device-only tail of that block behind the caller's uploaded inputs:
+//  [cells | owners x 3 | queries | changed flags | picks | outputs (OutBlock) | lists | list counts |
+//   first picks]
+struct ProjPlan {
+    int n, nq;
+    bool onepass;   // the list form applies (else the rounds alone)
+    int cap;        // list entries per query
+    OutBlock ob;
+    size_t o_cell = 0, o_own = 0, o_q = 0, o_chg = 0, o_pick = 0, o_out = 0, o_list = 0, o_lcnt = 0, o_pick0 = 0;
+    ProjPlan(const orbhip_frame* F, int nq_) : n(F->n), nq(nq_), onepass(onepass_ok(F, nq_)), cap(proj_cap()), ob(nq_) {}
+    void take_tail(StageLayout& lay) {
+        o_cell = lay.take(4 * (size_t)n);
+        o_own = lay.take(12 * (size_t)std::max(n, 1));
+        o_q = lay.take(sizeof(Query) * nq);
+        o_chg = lay.take(4 * ((size_t)nq + 2));
+        o_pick = lay.take(4 * (size_t)nq);
+        o_out = lay.take(ob.bytes);
+        o_list = onepass ? lay.take(8 * (size_t)nq * cap) : 0;
+        o_lcnt = lay.take(4 * (size_t)nq);
+        o_pick0 = lay.take(4 * (size_t)nq);
+    }
+};
+
+// One search as its caller staged it: where the kernels find the uploaded inputs, and the
+// arguments of the call's mode (0: LastFrame, 1: local points; the other mode's stay empty)
+struct ProjCall {
+    ProjFrame f;
+    size_t o_kps, o_kd, o_qd;
+    const uint8_t* dcl;     // the frame's claimed flags on the device, or null
+    const float* dur;       // mvuRight on the device (null: no stereo gate)
+    PrepLast pl{};
+    PrepLocal pc{};
+    float nnratio = 0.f;
+    int check_orientation = 0;
+    const float* qangle = nullptr;   // the queries' angles on the device (mode 0)
+    bool want_xr = false;            // mode 1: mTrackProjXR wanted, o_xr its nq floats
+    size_t o_xr = 0;
+};
+
+// The fixed-point rounds, launched `ws->ahead` at a time with the finishing work (`tail`: the
+// finish kernel and the result downloads) behind them and ONE host sync per batch: rounds after
+// convergence exit on the device, so the common case is a single round trip. Returns the number
+// of rounds that did work (< 0 on error).
+template <typename Tail>
+int run_rounds(ProjWorkspace* ws, const ProjPlan& p, const ProjCall& c, int mode, hipStream_t st, Tail&& tail) {
+    char* D = (char*)ws->s.d;
+    char* H = (char*)ws->s.h;
+    const int nq = p.nq;
+    const dim3 gq((unsigned)std::max(1, (nq + 3) / 4));
+    const int cap = nq + 2;   // a fixed point is reached within nq + 1 rounds
+    int* chg = (int*)(D + p.o_chg);
+    const int* hchg = (const int*)(H + p.o_chg);
+    HIPOK(hipMemsetAsync(D + p.o_own, 0x7F, 3 * sizeof(int) * (size_t)std::max(p.n, 1), st));   // > any query
+    HIPOK(hipMemsetAsync(chg, 0, sizeof(int) * (size_t)cap, st));
+    int r = 0;
+    for (;;) {
+        const int R = std::min(ws->ahead, cap - r);
+        for (int j = 0; j < R; j++)
+            hipLaunchKernelGGL(k_proj_round, gq, dim3(256), 0, st, c.f, nq, mode, c.nnratio, r + j,
+                               (const Query*)(D + p.o_q), (const orbhip_kp*)(D + c.o_kps),
+                               (const uint8_t*)(D + c.o_kd), (const int*)(D + p.o_cell), c.dcl, (int*)(D + p.o_own),
+                               (const uint8_t*)(D + c.o_qd), (int*)(D + p.o_pick), chg, c.dur);
+        HIPOK(hipGetLastError());
+        if (int rc = tail()) return rc;
+        HIPOK(hipMemcpyAsync(H + p.o_chg + sizeof(int) * r, chg + r, sizeof(int) * R, hipMemcpyDeviceToHost, st));
+        HIPOK(hipStreamSynchronize(st));
+        for (int j = 0; j < R; j++)
+            if (hchg[r + j] == 0) {
+                const int rounds = r + j + 1;
+                ws->ahead = std::min(16, std::max(2, rounds + 1));
+                return rounds;
+            }
+        r += R;
+        if (r >= cap) return r;
+        ws->ahead = std::min(16, 2 * ws->ahead);
+    }
+}
+
+// The search itself, with the inputs uploaded: the list form (one launch, or two), and when it does
+// not apply or a list overflowed (status word) the rounds, which find the inputs on the device.
+// (proj_stats_reset and proj_begin first: the last search's statistics start empty, the kernels may use their LDS.)
+// Either way the outputs end in the pinned image (OutBlock at o_out, mTrackProjXR at o_xr) for the
+// caller to copy out. Returns the number of matches (< 0 on error).
+void proj_stats_reset(ProjWorkspace* ws) {
+    ws->st_form = -1;
+    ws->st_rounds = ws->st_entries = ws->st_ent_cap = 0;
+}
+int proj_begin(const ProjPlan& p) {
+    if (p.onepass) HIPOK(proj_lds_attr());
+    return ORBHIP_OK;
+}
+template <int MODE>
+int proj_search(ProjWorkspace* ws, const ProjPlan& p, const ProjCall& c, int* rounds_out, hipStream_t st) {
+    char* H = (char*)ws->s.h;
+    char* HD = (char*)ws->s.hd;   // the list form writes its results straight into H
+    char* D = (char*)ws->s.d;
+    const int n = p.n, nq = p.nq;
+    const OutBlock& ob = p.ob;
+    const orbhip_kp* dkps = (const orbhip_kp*)(D + c.o_kps);
+    const int* hres = (const int*)(H + p.o_out + ob.res);
+    if (p.onepass) {
+        const bool fused = proj_fused();
+        const ResolveArgs ra{fused ? 1 : 0, c.check_orientation, resolve_ent_cap(n, nq), c.qangle,
+                             (int*)(HD + p.o_out + ob.match), (int*)(HD + p.o_out + ob.res), ws->arrive};
+        hipLaunchKernelGGL(k_proj_lists<MODE>, dim3((unsigned)((nq + kListQ - 1) / kListQ)), dim3(1024),
+                           fused ? kResolveLds : list_lds_bytes(n), st, c.f, nq, c.pl, c.pc, p.cap, c.nnratio, dkps,
+                           (const uint8_t*)(D + c.o_kd), c.dcl, (const uint8_t*)(D + c.o_qd),
+                           (uint64_t*)(D + p.o_list), (int*)(D + p.o_lcnt), (int*)(D + p.o_pick0),
+                           MODE == 1 ? (uint8_t*)(HD + p.o_out + ob.iv) : nullptr,
+                           MODE == 1 ? (int*)(HD + p.o_out + ob.lvl) : nullptr, ra, c.dur,
+                           c.want_xr ? (float*)(HD + c.o_xr) : nullptr);
+        if (!fused)
+            hipLaunchKernelGGL(k_proj_resolve<MODE>, dim3(1), dim3(1024), kResolveLds, st, n, nq, c.nnratio,
+                               c.check_orientation, p.cap, ra.ent_cap, ra.qangle, dkps,
+                               (const uint64_t*)(D + p.o_list), (const int*)(D + p.o_lcnt),
+                               (const int*)(D + p.o_pick0), ra.match, ra.res);
+        HIPOK(hipGetLastError());
+        HIPOK(hipStreamSynchronize(st));
+        ws->st_ent_cap = ra.ent_cap;
+        if (hres[1] == 0) {
+            if (rounds_out) *rounds_out = hres[2];
+            ws->st_form = 0; ws->st_rounds = hres[2]; ws->st_entries = hres[3];
+            return hres[0];
+        }
+    }
+    HIPOK(hipMemsetAsync(D + p.o_pick, 0xFF, 4 * (size_t)nq, st));   // -1: the first round always "changes"
+    if (n) hipLaunchKernelGGL(k_proj_cells, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c.f, dkps,
+                              (int*)(D + p.o_cell));
+    if constexpr (MODE == 0)
+        hipLaunchKernelGGL(k_proj_prep_last, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, c.f, nq, c.pl,
+                           (Query*)(D + p.o_q));
+    else
+        hipLaunchKernelGGL(k_proj_prep_local, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, c.f, nq, c.pc,
+                           (Query*)(D + p.o_q), (uint8_t*)(D + p.o_out + ob.iv), (int*)(D + p.o_out + ob.lvl),
+                           c.want_xr ? (float*)(D + c.o_xr) : nullptr);
+    auto tail = [&]() -> int {
+        hipLaunchKernelGGL(k_proj_finish, dim3(1), dim3(1024), 0, st, nq, c.check_orientation, c.qangle, dkps,
+                           (const int*)(D + p.o_pick), (int*)(D + p.o_out + ob.match), (int*)(D + p.o_out + ob.res));
+        HIPOK(hipMemcpyAsync(H + p.o_out, D + p.o_out, ob.bytes, hipMemcpyDeviceToHost, st));
+        if (c.want_xr) HIPOK(hipMemcpyAsync(H + c.o_xr, D + c.o_xr, 4 * (size_t)nq, hipMemcpyDeviceToHost, st));
+        return 0;
+    };
+    const int rounds = run_rounds(ws, p, c, MODE, st, tail);
+    if (rounds < 0) return rounds;
+    if (rounds_out) *rounds_out = rounds;
+    ws->st_form = p.onepass ? 1 : 2; ws->st_rounds = rounds;
+    return hres[0];
+}
 
 }  // namespace
 
@@ -1454,30 +977,20 @@ int proj_search_last(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_proj
     for (int i = 0; i < L->n; i++)
         if (L->octave[i] < 0 || L->octave[i] >= F->n_levels) return ORBHIP_ERR_ARG;
     const int n = F->n, nq = L->n;
-    ws->st_form = -1;
-    ws->st_rounds = ws->st_entries = ws->st_ent_cap = 0;
+    proj_stats_reset(ws);
     if (nq == 0) return 0;
-    const bool onepass = onepass_ok(F, nq);
-    const int cap = proj_cap();
-    if (onepass) HIPOK(proj_lds_attr());
-    const OutBlock ob(nq);
+    ProjPlan p(F, nq);
+    if (int rc = proj_begin(p)) return rc;
     // uploaded: [keypoints | descriptors | claimed | scale factors | points | point descriptors |
-    //  octaves | angles], then device only [cells | owners x 3 | queries | changed flags | picks |
-    //  outputs (OutBlock) | lists | list counts | first picks]
+    //  octaves | angles | mvuRight], then the device-only tail
     StageLayout lay(256);
     const size_t o_kps = lay.take(sizeof(orbhip_kp) * n), o_kd = lay.take(32 * (size_t)n), o_cl = lay.take(n);
     const size_t o_scale = lay.take(sizeof(float) * F->n_levels);
     const size_t o_pts = lay.take(12 * (size_t)nq), o_qd = lay.take(32 * (size_t)nq), o_oct = lay.take(4 * (size_t)nq);
     const size_t o_ang = lay.take(4 * (size_t)nq), o_ur = lay.take(sx ? 4 * (size_t)n : 0), o_in_end = lay.total();
-    const size_t o_cell = lay.take(4 * (size_t)n), o_own = lay.take(12 * (size_t)std::max(n, 1));
-    const size_t o_q = lay.take(sizeof(Query) * nq), o_chg = lay.take(4 * ((size_t)nq + 2));
-    const size_t o_pick = lay.take(4 * (size_t)nq), o_out = lay.take(ob.bytes);
-    const size_t o_list = onepass ? lay.take(8 * (size_t)nq * cap) : 0, o_lcnt = lay.take(4 * (size_t)nq);
-    const size_t o_pick0 = lay.take(4 * (size_t)nq);
-    if (int rc = ensure(ws, lay.total())) return rc;
+    p.take_tail(lay);
+    if (int rc = proj_ws_ensure(ws, lay.total())) return rc;
     StageBlock& S = ws->s;
-    char* H = (char*)S.h;
-    char* HD = (char*)S.hd;   // the two-launch form writes its results straight into H
     char* D = (char*)S.d;
     put_keyframe(S, o_kps, o_kd, 0, F->kps, F->desc, n);
     if (F->claimed) S.put(o_cl, F->claimed, n);
@@ -1487,57 +1000,18 @@ int proj_search_last(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_proj
     S.put(o_oct, L->octave, 4 * (size_t)nq);
     S.put(o_ang, L->angle, 4 * (size_t)nq);
     if (sx) S.put(o_ur, sx->u_right, 4 * (size_t)n);
-    HIPOK(upload_inputs(S.hd, D, H, o_in_end, st));
-    ProjFrame f = make_frame(F);
-    if (sx) f.bf = sx->bf;
-    const float* dur = sx ? (const float*)(D + o_ur) : nullptr;   // mvuRight on the device (null: no gate)
-    const PrepLast pl{(const float*)(D + o_pts), (const int*)(D + o_oct), (const float*)(D + o_scale), th,
-                      sx ? sx->dir : 0};
-    const uint8_t* dcl = F->claimed ? (const uint8_t*)(D + o_cl) : nullptr;
-    int* hres = (int*)(H + o_out + ob.res);
-    if (onepass) {
-        const bool fused = proj_fused();
-        const ResolveArgs ra{fused ? 1 : 0, check_orientation, resolve_ent_cap(n, nq), (const float*)(D + o_ang),
-                             (int*)(HD + o_out + ob.match), (int*)(HD + o_out + ob.res),
-                             ws->arrive};
-        hipLaunchKernelGGL(k_proj_lists<0>, dim3((unsigned)((nq + kListQ - 1) / kListQ)), dim3(1024),
-                           fused ? kResolveLds : list_lds_bytes(n), st, f, nq, pl, PrepLocal{}, cap, 0.f,
-                           (const orbhip_kp*)(D + o_kps), (const uint8_t*)(D + o_kd), dcl, (const uint8_t*)(D + o_qd),
-                           (uint64_t*)(D + o_list), (int*)(D + o_lcnt), (int*)(D + o_pick0), nullptr, nullptr, ra, dur,
-                           nullptr);
-        if (!fused)
-            hipLaunchKernelGGL(k_proj_resolve<0>, dim3(1), dim3(1024), kResolveLds, st, n, nq, 0.f, check_orientation,
-                               cap, ra.ent_cap, ra.qangle, (const orbhip_kp*)(D + o_kps), (const uint64_t*)(D + o_list),
-                               (const int*)(D + o_lcnt), (const int*)(D + o_pick0), ra.match, ra.res);
-        HIPOK(hipGetLastError());
-        HIPOK(hipStreamSynchronize(st));
-        ws->st_ent_cap = ra.ent_cap;
-        if (hres[1] == 0) {
-            std::memcpy(match, H + o_out + ob.match, 4 * (size_t)nq);
-            if (rounds_out) *rounds_out = hres[2];
-            ws->st_form = 0; ws->st_rounds = hres[2]; ws->st_entries = hres[3];
-            return hres[0];
-        }
-    }
-    HIPOK(hipMemsetAsync(D + o_pick, 0xFF, 4 * (size_t)nq, st));   // -1: the first round always "changes"
-    if (n) hipLaunchKernelGGL(k_proj_cells, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, f,
-                              (const orbhip_kp*)(D + o_kps), (int*)(D + o_cell));
-    hipLaunchKernelGGL(k_proj_prep_last, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, f, nq, pl,
-                       (Query*)(D + o_q));
-    auto tail = [&]() -> int {
-        hipLaunchKernelGGL(k_proj_finish, dim3(1), dim3(1024), 0, st, nq, check_orientation,
-                           (const float*)(D + o_ang), (const orbhip_kp*)(D + o_kps), (const int*)(D + o_pick),
-                           (int*)(D + o_out + ob.match), (int*)(D + o_out + ob.res));
-        HIPOK(hipMemcpyAsync(H + o_out, D + o_out, ob.bytes, hipMemcpyDeviceToHost, st));
-        return 0;
-    };
-    const int rounds = run_rounds(ws, f, nq, 0, 0.f, D, o_q, o_kps, o_kd, o_cell, dcl, o_own, o_qd, o_pick, o_chg, H,
-                                  st, dur, tail);
-    if (rounds < 0) return rounds;
-    std::memcpy(match, H + o_out + ob.match, 4 * (size_t)nq);
-    if (rounds_out) *rounds_out = rounds;
-    ws->st_form = onepass ? 1 : 2; ws->st_rounds = rounds;
-    return hres[0];
+    HIPOK(upload_inputs(S.hd, D, (char*)S.h, o_in_end, st));
+    ProjCall c{make_frame(F), o_kps, o_kd, o_qd, F->claimed ? (const uint8_t*)(D + o_cl) : nullptr,
+               sx ? (const float*)(D + o_ur) : nullptr};
+    if (sx) c.f.bf = sx->bf;
+    c.pl = PrepLast{(const float*)(D + o_pts), (const int*)(D + o_oct), (const float*)(D + o_scale), th,
+                    sx ? sx->dir : 0};
+    c.check_orientation = check_orientation;
+    c.qangle = (const float*)(D + o_ang);
+    const int nmatches = proj_search<0>(ws, p, c, rounds_out, st);
+    if (nmatches < 0) return nmatches;
+    std::memcpy(match, S.h + p.o_out + p.ob.match, 4 * (size_t)nq);
+    return nmatches;
 }
 
 int proj_search_local(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_local_points* M, float view_cos_limit,
@@ -1549,33 +1023,22 @@ int proj_search_local(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_loc
         return ORBHIP_ERR_ARG;
     if (sx && ((F->n && !sx->u_right) || !(sx->bf > 0.0f))) return ORBHIP_ERR_ARG;
     const int n = F->n, nq = M->n;
-    ws->st_form = -1;
-    ws->st_rounds = ws->st_entries = ws->st_ent_cap = 0;
+    proj_stats_reset(ws);
     if (nq == 0) return 0;
-    const bool onepass = onepass_ok(F, nq);
-    const int cap = proj_cap();
-    if (onepass) HIPOK(proj_lds_attr());
-    const OutBlock ob(nq);
-    // uploaded: [keypoints | descriptors | claimed | scale factors, level steps | points normals min max desc skip],
-    // then device only as proj_search_last
+    ProjPlan p(F, nq);
+    if (int rc = proj_begin(p)) return rc;
+    // uploaded: [keypoints | descriptors | claimed | scale factors, level steps | points normals min max
+    //  desc skip | mvuRight], then the device-only tail and mTrackProjXR (an output of its own)
     StageLayout lay(256);
     const size_t o_kps = lay.take(sizeof(orbhip_kp) * n), o_kd = lay.take(32 * (size_t)n), o_cl = lay.take(n);
     const size_t o_scale = lay.take(sizeof(float) * 2 * F->n_levels);   // + PredictScale's steps
     const PointsLayout o_mp(lay, (size_t)nq);
-    const size_t o_qd = o_mp.desc;
-    const size_t o_ur = lay.take(sx ? 4 * (size_t)n : 0);
-    const size_t o_in_end = lay.total();
-    const size_t o_cell = lay.take(4 * (size_t)n), o_own = lay.take(12 * (size_t)std::max(n, 1));
-    const size_t o_q = lay.take(sizeof(Query) * nq), o_chg = lay.take(4 * ((size_t)nq + 2));
-    const size_t o_pick = lay.take(4 * (size_t)nq), o_out = lay.take(ob.bytes);
-    const size_t o_list = onepass ? lay.take(8 * (size_t)nq * cap) : 0, o_lcnt = lay.take(4 * (size_t)nq);
-    const size_t o_pick0 = lay.take(4 * (size_t)nq);
+    const size_t o_ur = lay.take(sx ? 4 * (size_t)n : 0), o_in_end = lay.total();
+    p.take_tail(lay);
     const bool want_xr = sx && sx->proj_xr;
-    const size_t o_xr = lay.take(want_xr ? 4 * (size_t)nq : 0);   // mTrackProjXR (an output of its own)
-    if (int rc = ensure(ws, lay.total())) return rc;
+    const size_t o_xr = lay.take(want_xr ? 4 * (size_t)nq : 0);
+    if (int rc = proj_ws_ensure(ws, lay.total())) return rc;
     StageBlock& S = ws->s;
-    char* H = (char*)S.h;
-    char* HD = (char*)S.hd;   // the two-launch form writes its results straight into H
     char* D = (char*)S.d;
     put_keyframe(S, o_kps, o_kd, 0, F->kps, F->desc, n);
     if (F->claimed) S.put(o_cl, F->claimed, n);
@@ -1584,186 +1047,27 @@ int proj_search_local(ProjWorkspace* ws, const orbhip_frame* F, const orbhip_loc
           sizeof(float) * F->n_levels);
     const DevPoints mp = o_mp.put(S, *M, false);   // no skip array: a null pointer
     if (sx) S.put(o_ur, sx->u_right, 4 * (size_t)n);
-    HIPOK(upload_inputs(S.hd, D, H, o_in_end, st));
-    ProjFrame f = make_frame(F);
-    if (sx) f.bf = sx->bf;
-    const float* dur = sx ? (const float*)(D + o_ur) : nullptr;
-    const PrepLocal pc{mp.pts, mp.nrm, mp.mind, mp.maxd, mp.skip,
-                       (const float*)(D + o_scale), F->n_levels, view_cos_limit, th, far_points, th_far,
-                       level_steps(F->log_scale_factor, F->n_levels)};
-    const uint8_t* dcl = F->claimed ? (const uint8_t*)(D + o_cl) : nullptr;
-    uint8_t* d_iv = (uint8_t*)(D + o_out + ob.iv);
-    int* d_lvl = (int*)(D + o_out + ob.lvl);
-    int* hres = (int*)(H + o_out + ob.res);
-    auto outputs = [&]() {
-        std::memcpy(match, H + o_out + ob.match, 4 * (size_t)nq);
-        std::memcpy(level, H + o_out + ob.lvl, 4 * (size_t)nq);
-        std::memcpy(in_view, H + o_out + ob.iv, nq);
-        if (want_xr) {   // only where in view: the rest of the caller's array stays as it was
-            const float* hx = (const float*)(H + o_xr);
-            for (int m = 0; m < nq; m++)
-                if (in_view[m]) sx->proj_xr[m] = hx[m];
-        }
-    };
-    if (onepass) {
-        const bool fused = proj_fused();
-        const ResolveArgs ra{fused ? 1 : 0, 0, resolve_ent_cap(n, nq), nullptr,
-                             (int*)(HD + o_out + ob.match), (int*)(HD + o_out + ob.res), ws->arrive};
-        hipLaunchKernelGGL(k_proj_lists<1>, dim3((unsigned)((nq + kListQ - 1) / kListQ)), dim3(1024),
-                           fused ? kResolveLds : list_lds_bytes(n), st, f, nq, PrepLast{}, pc, cap, nnratio,
-                           (const orbhip_kp*)(D + o_kps), (const uint8_t*)(D + o_kd), dcl, (const uint8_t*)(D + o_qd),
-                           (uint64_t*)(D + o_list), (int*)(D + o_lcnt), (int*)(D + o_pick0),
-                           (uint8_t*)(HD + o_out + ob.iv), (int*)(HD + o_out + ob.lvl), ra, dur,
-                           want_xr ? (float*)(HD + o_xr) : nullptr);
-        if (!fused)
-            hipLaunchKernelGGL(k_proj_resolve<1>, dim3(1), dim3(1024), kResolveLds, st, n, nq, nnratio, 0, cap,
-                               ra.ent_cap, (const float*)nullptr, (const orbhip_kp*)(D + o_kps),
-                               (const uint64_t*)(D + o_list), (const int*)(D + o_lcnt), (const int*)(D + o_pick0),
-                               ra.match, ra.res);
-        HIPOK(hipGetLastError());
-        HIPOK(hipStreamSynchronize(st));
-        ws->st_ent_cap = ra.ent_cap;
-        if (hres[1] == 0) {
-            outputs();
-            if (rounds_out) *rounds_out = hres[2];
-            ws->st_form = 0; ws->st_rounds = hres[2]; ws->st_entries = hres[3];
-            return hres[0];
-        }
+    HIPOK(upload_inputs(S.hd, D, (char*)S.h, o_in_end, st));
+    ProjCall c{make_frame(F), o_kps, o_kd, o_mp.desc, F->claimed ? (const uint8_t*)(D + o_cl) : nullptr,
+               sx ? (const float*)(D + o_ur) : nullptr};
+    if (sx) c.f.bf = sx->bf;
+    c.pc = PrepLocal{mp.pts, mp.nrm, mp.mind, mp.maxd, mp.skip, (const float*)(D + o_scale), F->n_levels,
+                     view_cos_limit, th, far_points, th_far, level_steps(F->log_scale_factor, F->n_levels)};
+    c.nnratio = nnratio;
+    c.want_xr = want_xr;
+    c.o_xr = o_xr;
+    const int nmatches = proj_search<1>(ws, p, c, rounds_out, st);
+    if (nmatches < 0) return nmatches;
+    const uint8_t* H = S.h + p.o_out;
+    std::memcpy(match, H + p.ob.match, 4 * (size_t)nq);
+    std::memcpy(level, H + p.ob.lvl, 4 * (size_t)nq);
+    std::memcpy(in_view, H + p.ob.iv, nq);
+    if (want_xr) {   // only where in view: the rest of the caller's array stays as it was
+        const float* hx = (const float*)(S.h + o_xr);
+        for (int m = 0; m < nq; m++)
+            if (in_view[m]) sx->proj_xr[m] = hx[m];
     }
-    HIPOK(hipMemsetAsync(D + o_pick, 0xFF, 4 * (size_t)nq, st));
-    if (n) hipLaunchKernelGGL(k_proj_cells, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, f,
-                              (const orbhip_kp*)(D + o_kps), (int*)(D + o_cell));
-    hipLaunchKernelGGL(k_proj_prep_local, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, f, nq, pc,
-                       (Query*)(D + o_q), d_iv, d_lvl, want_xr ? (float*)(D + o_xr) : nullptr);
-    auto tail = [&]() -> int {
-        hipLaunchKernelGGL(k_proj_finish, dim3(1), dim3(1024), 0, st, nq, 0, (const float*)nullptr,
-                           (const orbhip_kp*)(D + o_kps), (const int*)(D + o_pick), (int*)(D + o_out + ob.match),
-                           (int*)(D + o_out + ob.res));
-        HIPOK(hipMemcpyAsync(H + o_out, D + o_out, ob.bytes, hipMemcpyDeviceToHost, st));
-        if (want_xr) HIPOK(hipMemcpyAsync(H + o_xr, D + o_xr, 4 * (size_t)nq, hipMemcpyDeviceToHost, st));
-        return 0;
-    };
-    const int rounds = run_rounds(ws, f, nq, 1, nnratio, D, o_q, o_kps, o_kd, o_cell, dcl, o_own, o_qd, o_pick, o_chg,
-                                  H, st, dur, tail);
-    if (rounds < 0) return rounds;
-    outputs();
-    if (rounds_out) *rounds_out = rounds;
-    ws->st_form = onepass ? 1 : 2; ws->st_rounds = rounds;
-    return hres[0];
-}
-
-int init_search(ProjWorkspace* ws, const orbhip_init_frame* F1, const orbhip_init_frame* F2, float* prev_matched,
-                int window_size, float nnratio, int check_orientation, int32_t* matches12, hipStream_t st) {
-    if (!ws || !F1 || !F2 || !prev_matched || !matches12 || F1->n < 0 || F2->n < 0 || F1->n > 65535 ||
-        F2->n > 65535 || (F1->n && (!F1->kps || !F1->desc)) || (F2->n && (!F2->kps || !F2->desc)) ||
-        !(F2->max_x > F2->min_x) || !(F2->max_y > F2->min_y))
-        return ORBHIP_ERR_ARG;
-    const int n1 = F1->n, n2 = F2->n;
-    for (int i = 0; i < n1; i++) matches12[i] = -1;
-    if (n1 == 0) return 0;
-    // capacity from the octave-0 counts (bounds of the device-side queries / ranks)
-    // (octaves are >= 0: ORBextractor levels; a negative octave would disable the level check)
-    int nq0 = 0, nr0 = 0;
-    for (int i = 0; i < n1; i++) {
-        if (F1->kps[i].octave < 0) return ORBHIP_ERR_ARG;
-        nq0 += F1->kps[i].octave == 0;
-    }
-    for (int k = 0; k < n2; k++) nr0 += F2->kps[k].octave == 0;
-    const size_t lds = 4 * (size_t)nr0 + 4 * (size_t)nq0 + 16;
-    if (lds > 150 * 1024) return ORBHIP_ERR_UNSUPPORTED;
-    const int list_cap = std::max(64, (nr0 + 63) & ~63);
-    if ((size_t)std::max(nq0, 1) * list_cap > ((size_t)1 << 28)) return ORBHIP_ERR_UNSUPPORTED;
-    // the kernel's static LDS (histogram) comes on top of the dynamic 150 KiB envelope
-    static LdsAttrOnce attr;   // per device, thread-safe (dev_attr.h)
-    static const void* const fs[] = {(const void*)k_init_greedy, (const void*)k_init_finish};
-    HIPOK(attr.ensure(fs, 2, 152 * 1024));
-    // uploaded: [F1 keypoints | F1 descriptors | F2 keypoints | F2 descriptors | prev_matched], read
-    // back: [matches | counts], then device only: the slots, lists and claim tables of the rounds
-    StageLayout lay(256);
-    const size_t o_k1 = lay.take(sizeof(orbhip_kp) * n1), o_d1 = lay.take(32 * (size_t)n1);
-    const size_t o_k2 = lay.take(sizeof(orbhip_kp) * std::max(n2, 1)), o_d2 = lay.take(32 * (size_t)std::max(n2, 1));
-    const size_t o_prev = lay.take(8 * (size_t)n1), o_in_end = lay.total();
-    const size_t o_match = lay.take(4 * (size_t)n1), o_cnt = lay.take(16), o_out_end = lay.total();
-    const size_t o_slot = lay.take(4 * (size_t)std::max(n2, 1)), o_ql = lay.take(4 * (size_t)n1);
-    const size_t o_len = lay.take(4 * ((size_t)n1 + 1)), o_list = lay.take(4 * (size_t)std::max(nq0, 1) * list_cap);
-    const size_t o_topk = lay.take(4 * (size_t)kInitK * (((size_t)std::max(nq0, 1) + 3) & ~size_t(3)));
-    const size_t o_need = lay.take(4 * (size_t)std::max(nq0, 1));
-    const int cap = std::min(kInitMaxRounds, nq0 + 2);
-    const size_t o_cnt3 = lay.take(4 * 3 * (size_t)std::max(nr0, 1));
-    const size_t o_ent3 = lay.take(4 * 3 * (size_t)std::max(nr0, 1) * kInitC);
-    const size_t o_pick = lay.take(4 * (size_t)std::max(nq0, 1));
-    const size_t o_pout = lay.take(8 * (size_t)n1);
-    const size_t o_flags = lay.take(4 * ((size_t)cap + 1));
-    if (int rc = ensure(ws, lay.total())) return rc;
-    StageBlock& S = ws->s;
-    char* H = (char*)S.h;
-    char* D = (char*)S.d;
-    put_keyframe(S, o_k1, o_d1, 0, F1->kps, F1->desc, n1);
-    put_keyframe(S, o_k2, o_d2, 0, F2->kps, F2->desc, n2);
-    S.put(o_prev, prev_matched, 8 * (size_t)n1);
-    HIPOK(upload_inputs(S.hd, D, H, o_in_end, st));
-    InitGeom g{};
-    g.n1 = n1; g.n2 = n2;
-    g.minx = F2->min_x; g.maxx = F2->max_x; g.miny = F2->min_y; g.maxy = F2->max_y;
-    g.invw = (float)kGridCols / (g.maxx - g.minx);
-    g.invh = (float)kGridRows / (g.maxy - g.miny);
-    g.r = (float)window_size;
-    g.list_cap = list_cap;
-    const orbhip_kp* dk1 = (const orbhip_kp*)(D + o_k1);
-    const orbhip_kp* dk2 = (const orbhip_kp*)(D + o_k2);
-    int* counts = (int*)(D + o_cnt);
-    int* flags = (int*)(D + o_flags);
-    hipLaunchKernelGGL(k_init_prep, dim3(1), dim3(1024), 0, st, g, dk1, dk2, (int*)(D + o_slot), (int*)(D + o_ql),
-                       counts, (int*)(D + o_cnt3), flags, cap + 1);
-    hipLaunchKernelGGL(k_init_cands, dim3((unsigned)std::max(1, (nq0 + 3) / 4)), dim3(256), 0, st, g, dk1,
-                       (const uint8_t*)(D + o_d1), dk2, (const uint8_t*)(D + o_d2), (const float*)(D + o_prev),
-                       (const int*)(D + o_slot), (const int*)(D + o_ql), (const int*)counts, (uint32_t*)(D + o_list),
-                       (int*)(D + o_len), (uint32_t*)(D + o_topk), (int*)(D + o_need));
-    HIPOK(hipGetLastError());
-    // parallel rounds, launched init_ahead at a time with the finish and the read-back behind them
-    const int* hflags = (const int*)(H + o_flags);
-    const dim3 gq((unsigned)std::max(1, (nq0 + 15) / 16));
-    bool done = false;
-    for (int r = 0; r < cap && !done && std::getenv("ORBHIP_INIT_CHAIN") == nullptr;) {
-        const int R = std::min(ws->init_ahead, cap - r);
-        for (int j = 0; j < R; j++)
-            hipLaunchKernelGGL(k_init_round, gq, dim3(256), 0, st, g, nnratio, r + j, (const int*)counts,
-                               (const uint32_t*)(D + o_list), (const int*)(D + o_len),
-                               (const uint32_t*)(D + o_topk), (const int*)(D + o_need), (int*)(D + o_cnt3),
-                               (uint32_t*)(D + o_ent3), (uint32_t*)(D + o_pick), flags);
-        hipLaunchKernelGGL(k_init_finish, dim3(1), dim3(1024), 4 * (size_t)std::max(nr0, 1), st, g,
-                           check_orientation, dk2, (const int*)(D + o_slot), (const int*)(D + o_ql),
-                           (const int*)counts, (const uint32_t*)(D + o_pick), (const float*)(D + o_prev),
-                           (int32_t*)(D + o_match), (float*)(D + o_pout), counts + 2);
-        HIPOK(hipGetLastError());
-        HIPOK(hipMemcpyAsync(H + o_match, D + o_match, o_out_end - o_match, hipMemcpyDeviceToHost, st));
-        HIPOK(hipMemcpyAsync(H + o_pout, D + o_pout, 8 * (size_t)n1, hipMemcpyDeviceToHost, st));
-        HIPOK(hipMemcpyAsync(H + o_flags, flags, 4 * ((size_t)cap + 1), hipMemcpyDeviceToHost, st));
-        HIPOK(hipStreamSynchronize(st));
-        if (hflags[0]) break;   // a rank overflowed its claim slots: the chain decides
-        for (int j = 0; j < R && !done; j++)
-            if (hflags[1 + r + j] == 0) {
-                done = true;
-                ws->init_ahead = std::min(16, std::max(3, r + j + 2));
-            }
-        r += R;
-        if (!done) ws->init_ahead = std::min(16, 2 * ws->init_ahead);
-    }
-    if (done) {
-        std::memcpy(matches12, H + o_match, 4 * (size_t)n1);
-        std::memcpy(prev_matched, H + o_pout, 8 * (size_t)n1);
-        return ((int*)(H + o_cnt))[2];
-    }
-    hipLaunchKernelGGL(k_init_greedy, dim3(1), dim3(256), lds, st, g, nnratio, check_orientation, dk2,
-                       (const int*)(D + o_slot), (const int*)(D + o_ql), (const int*)counts,
-                       (const uint32_t*)(D + o_list), (const int*)(D + o_len), (const uint32_t*)(D + o_topk),
-                       (const int*)(D + o_need), (int32_t*)(D + o_match), (float*)(D + o_prev), counts + 2);
-    HIPOK(hipGetLastError());
-    HIPOK(hipMemcpyAsync(H + o_prev, D + o_prev, o_out_end - o_prev, hipMemcpyDeviceToHost, st));
-    HIPOK(hipStreamSynchronize(st));
-    std::memcpy(matches12, H + o_match, 4 * (size_t)n1);
-    std::memcpy(prev_matched, H + o_prev, 8 * (size_t)n1);
-    return ((int*)(H + o_cnt))[2];
+    return nmatches;
 }
 
 }  // namespace orbhip

@@ -27,6 +27,7 @@
 #include "geom.h"
 #include "orbhip_device.h"
 #include "orbhip_kernels.h"
+#include "rot_filter.h"
 #include "stage.h"
 
 #define HIPOK(x) ORBHIP_HIPOK(" triangulation", x)
@@ -190,7 +191,6 @@ __global__ __launch_bounds__(kTriThreads) void k_tri_search(const TriSide* __res
     const TriGeom g = geom[b];
     const float* F = g.F;
     const float ex = g.ep[0], ey = g.ep[1];
-    const float factor = 1.0f / 30;
     const int kThLow = 50;
     for (int t = tid; t < m1; t += kTriThreads) {
         const int p = tri_lower_bound(S.node1, m1, S.node1[t]);
@@ -238,28 +238,14 @@ __global__ __launch_bounds__(kTriThreads) void k_tri_search(const TriSide* __res
             const int bestIdx2 = 0xFFFF - (bestKey & 0xFFFF);
             S.match[idx1] = (short)bestIdx2;
             if (check_orientation) {
-                float rot = kp1.angle - N.kps[bestIdx2].angle;
-                if (rot < 0.0) rot += 360.0f;
-                int bin = (int)roundf(rot * factor);
-                if (bin == 30) bin = 0;
-                if ((unsigned)bin < 30u) { atomicAdd(&S.hist[bin], 1); S.bin[idx1] = (int8_t)bin; }
+                const int bin = rot_bin(kp1.angle, N.kps[bestIdx2].angle);
+                if ((unsigned)bin < (unsigned)kHistoLength) { atomicAdd(&S.hist[bin], 1); S.bin[idx1] = (int8_t)bin; }
             }
         }
     }
     __syncthreads();
     // ---- 3. rotation consistency: ComputeThreeMaxima over the 30 bins (as k_search_bow) ----
-    if (check_orientation && tid == 0) {
-        int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-        for (int i = 0; i < 30; i++) {
-            const int s = S.hist[i];
-            if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = i; }
-            else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = i; }
-            else if (s > max3) { max3 = s; ind3 = i; }
-        }
-        if (max2 < 0.1f * (float)max1) { ind2 = -1; ind3 = -1; }
-        else if (max3 < 0.1f * (float)max1) { ind3 = -1; }
-        S.keep[0] = ind1; S.keep[1] = ind2; S.keep[2] = ind3;
-    }
+    if (check_orientation && tid < 64) three_maxima_wave(S.hist, S.keep);   // wave 0 of kTriThreads
     __syncthreads();
     int c = 0;
     int32_t* out = match12 + (int64_t)b * n1;
@@ -267,7 +253,7 @@ __global__ __launch_bounds__(kTriThreads) void k_tri_search(const TriSide* __res
         int m = S.match[i];
         if (m >= 0 && check_orientation) {
             const int bin = S.bin[i];
-            if (bin != S.keep[0] && bin != S.keep[1] && bin != S.keep[2]) m = -1;
+            if (!rot_kept(bin, S.keep)) m = -1;
         }
         out[i] = m;
         c += m >= 0;

@@ -9,50 +9,16 @@ The restatement keeps every float operation the reference performs as one np.flo
 bin = round(rot * (1.0f / HISTO_LENGTH)) with C round (halves away from zero) and bin 30 -> 0."""
 import numpy as np
 
+from helpers import HISTO_LENGTH, c_round, rotation_bin, three_maxima  # noqa: F401 (the tests use them as B.*)
 from orb_slam3_ros2_amd.vocabulary import L1_NORM, TF_IDF, Vocabulary
 
 f32 = np.float32
-HISTO_LENGTH = 30
 TH_LOW = 50
 _POP = np.array([bin(i).count("1") for i in range(256)], np.int64)
 
 
 def hamming(a, b) -> int:
     return int(_POP[np.bitwise_xor(a, b)].sum())
-
-
-def c_round(v) -> int:
-    """C round(): halves away from zero (np.round rounds them to even)."""
-    v = float(v)
-    return int(np.floor(v + 0.5)) if v >= 0 else -int(np.floor(-v + 0.5))
-
-
-def rotation_bin(kf_angle, f_angle) -> int:
-    rot = f32(kf_angle) - f32(f_angle)
-    if rot < 0.0:
-        rot = rot + f32(360.0)
-    b = c_round(rot * (f32(1.0) / f32(HISTO_LENGTH)))
-    return 0 if b == HISTO_LENGTH else b
-
-
-def three_maxima(sizes):
-    """ORBmatcher::ComputeThreeMaxima over the histogram's bin sizes: (ind1, ind2, ind3), -1 = dropped."""
-    max1 = max2 = max3 = 0
-    ind1 = ind2 = ind3 = -1
-    for i, s in enumerate(sizes):
-        if s > max1:
-            max3, max2, max1 = max2, max1, s
-            ind3, ind2, ind1 = ind2, ind1, i
-        elif s > max2:
-            max3, max2 = max2, s
-            ind3, ind2 = ind2, i
-        elif s > max3:
-            max3, ind3 = s, i
-    if f32(max2) < f32(0.1) * f32(max1):
-        ind2 = ind3 = -1
-    elif f32(max3) < f32(0.1) * f32(max1):
-        ind3 = -1
-    return ind1, ind2, ind3
 
 
 def search_bow_numpy(kf_desc, kf_angle, kf_node, kf_valid, f_desc, f_angle, f_node, ratio=0.7,

@@ -152,6 +152,63 @@ def diff_report(gk, gd, ok, od, max_lines=10) -> str:
     return "\n".join(lines)
 
 
+# ---- ORBmatcher's rotation-consistency filter, restated once for every test model ----
+
+HISTO_LENGTH = 30
+
+
+def c_round(v) -> int:
+    """C round() / roundf(): halves away from zero (np.round rounds them to even)."""
+    v = float(v)
+    return int(np.floor(v + 0.5)) if v >= 0 else -int(np.floor(-v + 0.5))
+
+
+def rotation_bin(angle1, angle2) -> int:
+    """rot = angle1 - angle2 (+ 360 when negative), bin = round(rot * (1.0f / HISTO_LENGTH)), bin 30 -> 0:
+    every float operation of the reference as one np.float32 operation."""
+    f32 = np.float32
+    rot = f32(angle1) - f32(angle2)
+    if rot < 0.0:
+        rot = rot + f32(360.0)
+    b = c_round(rot * (f32(1.0) / f32(HISTO_LENGTH)))
+    return 0 if b == HISTO_LENGTH else b
+
+
+def three_maxima(sizes):
+    """ORBmatcher::ComputeThreeMaxima over the histogram's bin sizes: (ind1, ind2, ind3), -1 = dropped."""
+    f32 = np.float32
+    max1 = max2 = max3 = 0
+    ind1 = ind2 = ind3 = -1
+    for i, s in enumerate(sizes):
+        s = int(s)
+        if s > max1:
+            max3, max2, max1 = max2, max1, s
+            ind3, ind2, ind1 = ind2, ind1, i
+        elif s > max2:
+            max3, max2 = max2, s
+            ind3, ind2 = ind2, i
+        elif s > max3:
+            max3, ind3 = s, i
+    if f32(max2) < f32(0.1) * f32(max1):
+        ind2 = ind3 = -1
+    elif f32(max3) < f32(0.1) * f32(max1):
+        ind3 = -1
+    return ind1, ind2, ind3
+
+
+# Small histograms at the filter's two rules, for scenes of one match per query: {bin: matches} ->
+# matches kept. "12-1": 1 < 0.1f * 12, the single match goes. "ties": four equal bins, the three of
+# lower index stay. A pair of angles (30 b, 0) lands in bin b (30 b * (1.0f / 30) rounds to b).
+ROT_EDGE_HISTS = {"12-1": ({2: 12, 5: 1}, 12), "ties": ({3: 6, 7: 6, 9: 6, 11: 6}, 18)}
+
+
+def rot_edge_bins(name):
+    """(the bin of each of the scene's matches in a fixed shuffled order, matches kept)."""
+    hist, kept = ROT_EDGE_HISTS[name]
+    bins = np.concatenate([np.full(c, b) for b, c in hist.items()])
+    return np.random.default_rng(len(bins)).permutation(bins), kept
+
+
 # ---- the brute-force matcher: its dispatch route and data sets with matches by construction ----
 
 def match_route(npairs: int, max_q: int, max_t: int, fused_allowed: bool = True) -> dict:

@@ -48,7 +48,6 @@ def search_pair(kf1, kf2, scale_factors, level_sigma2, check_orientation, F12=No
     cnt = dict(epipole=0, epiline=0, ties=0, shared=0, pruned=0, epipole_radius=0, epi_matches=0)
     fv1, fv2 = T._feature_vector(kf1), T._feature_vector(kf2)
     d2all = np.asarray(kf2.desc, np.uint8).reshape(-1, 32)
-    factor = f32(1.0) / f32(T.HISTO_LENGTH)
     rot_hist = [[] for _ in range(T.HISTO_LENGTH)]
     with np.errstate(all="ignore"):
         for node in sorted(set(fv1) & set(fv2)):
@@ -95,12 +94,7 @@ def search_pair(kf1, kf2, scale_factors, level_sigma2, check_orientation, F12=No
                     match[idx1] = best_idx2
                     cnt["epi_matches"] += best_inside
                     if check_orientation:
-                        rot = f32(kf1.kps["angle"][idx1]) - f32(kf2.kps["angle"][best_idx2])
-                        if rot < 0:
-                            rot = rot + f32(360)
-                        bin_ = T.roundf(rot * factor)
-                        if bin_ == T.HISTO_LENGTH:
-                            bin_ = 0
+                        bin_ = T.rotation_bin(kf1.kps["angle"][idx1], kf2.kps["angle"][best_idx2])
                         rot_hist[bin_].append(idx1)
     targets = match[match >= 0]
     cnt["shared"] = int((np.bincount(targets, minlength=1) > 1).sum()) if targets.size else 0

@@ -11,6 +11,8 @@ import math
 
 import numpy as np
 
+from helpers import HISTO_LENGTH, rotation_bin, three_maxima
+
 F32 = np.float32
 CHI2_MONO, CHI2_STEREO = float(F32(5.991)), float(F32(7.815))
 DELTA_MONO, DELTA_STEREO = float(F32(np.sqrt(5.991))), float(F32(np.sqrt(7.815)))
@@ -295,7 +297,7 @@ def pose_optimization(prob):
 
 
 # ------------------------------------------------------------------ the frame grid (float32)
-COLS, ROWS, TH_HIGH, HISTO = 64, 48, 100, 30
+COLS, ROWS, TH_HIGH = 64, 48, 100
 _POP = np.array([bin(i).count("1") for i in range(256)], np.int32)
 
 
@@ -370,24 +372,6 @@ def _hamming(d, D):
     return _POP[np.bitwise_xor(D, d[None, :])].sum(1)
 
 
-def _three_maxima(h):
-    m1 = m2 = m3 = 0
-    i1 = i2 = i3 = -1
-    for i in range(HISTO):
-        s = int(h[i])
-        if s > m1:
-            m3, m2, m1, i3, i2, i1 = m2, m1, s, i2, i1, i
-        elif s > m2:
-            m3, m2, i3, i2 = m2, s, i2, i
-        elif s > m3:
-            m3, i3 = s, i
-    if F32(m2) < F32(0.1) * F32(m1):
-        i2 = i3 = -1
-    elif F32(m3) < F32(0.1) * F32(m1):
-        i3 = -1
-    return i1, i2, i3
-
-
 def direction(frame, last_pose, b):
     """1 forward (tlc.z > b), -1 backward (-tlc.z > b), 0 neither; (dir, tlc.z)."""
     Rc, Rl = _qtomat32(frame.pose_q), _qtomat32(last_pose[0])
@@ -419,8 +403,7 @@ def search_by_projection_last(frame, points, mp_desc, last_octave, last_angle, t
     taken = np.zeros(G.n, bool) if frame.claimed is None else frame.claimed[:G.n].astype(bool).copy()
     match = np.full(nq, -1, np.int32)
     bins = np.full(nq, -1)
-    hist = np.zeros(HISTO, np.int64)
-    factor = F32(1.0) / F32(HISTO)
+    hist = np.zeros(HISTO_LENGTH, np.int64)
     Xc = _qrot32(np.asarray(frame.pose_q, F32), pts) + np.asarray(frame.pose_t, F32)
     gated = 0
     for i in range(nq):
@@ -456,16 +439,11 @@ def search_by_projection_last(frame, points, mp_desc, last_octave, last_angle, t
             taken[k] = True
             match[i] = k
             if check_orientation:
-                rot = F32(last_angle[i]) - F32(G.kps["angle"][k])
-                if rot < 0.0:
-                    rot = rot + F32(360.0)
-                bb = int(_round_half_away(np.array([rot * factor], F32))[0])
-                if bb == HISTO:
-                    bb = 0
+                bb = rotation_bin(last_angle[i], G.kps["angle"][k])
                 bins[i] = bb
                 hist[bb] += 1
     if check_orientation:
-        keep = _three_maxima(hist)
+        keep = three_maxima(hist)
         for i in range(nq):
             if match[i] >= 0 and bins[i] not in keep:
                 match[i] = -1

@@ -58,7 +58,28 @@ def test_search_bow_scene_matches_oracle(oracle, name, ratio, ori):
     n, m = _device(sc, ratio, ori)
     on, om = _oracle(oracle, name, sc, ratio, ori)
     assert n == on and np.array_equal(m, om)
+    if ori and name.startswith("rot"):   # k_search_bow's rotation filter removes matches in these scenes
+        assert on < _oracle(oracle, name, sc, ratio, False)[0]
     assert n > 0
+
+
+@pytest.mark.parametrize("hist", ["12-1", "ties"])
+def test_rotation_filter_rules(oracle, hist):
+    """ComputeThreeMaxima's two rules in k_search_bow: one node, every KF feature with its twin in
+    the frame (the same descriptor, every other one random), so each matches it and the angles alone
+    decide. A single match beside twelve is dropped (1 < 0.1f * 12); of four equal bins the three
+    of lower index stay."""
+    from helpers import rot_edge_bins
+    bins, kept = rot_edge_bins(hist)
+    n = len(bins)
+    d = np.random.default_rng(100 + n).integers(0, 256, (n, 32), dtype=np.uint8)
+    node, w = np.zeros(n, np.int32), np.ones(n)
+    sc = dict(kd=d, ka=(30.0 * bins).astype(np.float32), kn=node, kw=w, kv=np.ones(n, np.uint8), fd=d,
+              fa=np.zeros(n, np.float32), fn=node, fw=w)
+    on, om = _oracle(oracle, "rules-" + hist, sc, 0.7, True)
+    assert _oracle(oracle, "rules-" + hist, sc, 0.7, False)[0] == n > on == kept
+    gn, gm = _device(sc, 0.7, True)
+    assert gn == on and np.array_equal(gm, om)
 
 
 def test_search_bow_th_low_30(oracle):

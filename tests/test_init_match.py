@@ -136,11 +136,44 @@ def test_search_for_initialization_matches_oracle(oracle, monkeypatch, path):
         monkeypatch.setenv("ORBHIP_INIT_CHAIN", "1")
     for seed in range(6):
         k1, d1, k2, d2, prev = synthetic_init_pair(n1=1500 + 500 * seed, seed=20 + seed)
+        kept = {}
         for window, ratio, ori in [(100, 0.9, True), (100, 0.9, False), (50, 0.7, True), (200, 0.9, True)]:
             mt = ORBmatcher(ratio, ori)
             n, m, p = mt.SearchForInitialization(k1, d1, k2, d2, prev, window)
             on, om, op = oracle.search_for_initialization(k1, d1, k2, d2, prev, window, ratio, ori)
             assert n == on and np.array_equal(m, om) and np.array_equal(p, op), (seed, window, ratio, ori)
+            kept[(window, ratio, ori)] = on
+        # the rotation filter (k_init_finish behind the rounds, k_init_greedy's tail in the chain)
+        # removes matches in every scene: the oracle keeps more without the orientation check
+        assert kept[(100, 0.9, True)] < kept[(100, 0.9, False)], seed
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("hist", ["12-1", "ties"])
+@pytest.mark.parametrize("path", ["rounds", "chain"])
+def test_rotation_filter_rules(oracle, monkeypatch, path, hist):
+    """ComputeThreeMaxima's two rules in k_init_finish (rounds) and k_init_greedy (chain): every F1
+    keypoint has its twin in F2 (same place, same descriptor, 30 px from the next), so each matches
+    it and the angles alone decide. A single match beside twelve is dropped (1 < 0.1f * 12); of four
+    equal bins the three of lower index stay."""
+    from helpers import rot_edge_bins
+    from orb_slam3_ros2_amd import ORBmatcher
+    from orb_slam3_ros2_amd._lib import KP_DTYPE
+    bins, kept = rot_edge_bins(hist)
+    n = len(bins)
+    k1 = np.zeros(n, KP_DTYPE)
+    k1["x"], k1["y"] = 40.0 + 30.0 * (np.arange(n) % 8), 40.0 + 30.0 * (np.arange(n) // 8)
+    k1["size"], k1["response"] = 31.0, 50.0
+    k2 = k1.copy()
+    k1["angle"] = 30.0 * bins
+    d = np.random.default_rng(n).integers(0, 256, (n, 32), dtype=np.uint8)
+    prev = np.stack([k1["x"], k1["y"]], 1).astype(np.float32)
+    if path == "chain":
+        monkeypatch.setenv("ORBHIP_INIT_CHAIN", "1")
+    on, om, op = oracle.search_for_initialization(k1, d, k2, d, prev, 10, 0.9, True)
+    assert oracle.search_for_initialization(k1, d, k2, d, prev, 10, 0.9, False)[0] == n > on == kept
+    gn, gm, gp = ORBmatcher(0.9, True).SearchForInitialization(k1, d, k2, d, prev, 10)
+    assert gn == on and np.array_equal(gm, om) and np.array_equal(gp, op)
 
 
 @pytest.mark.gpu

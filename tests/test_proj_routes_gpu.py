@@ -90,10 +90,31 @@ def test_chain_last(ctx, oracle, form, K, ori):
     if not (ori and K == 70):
         assert np.array_equal(m, s["expect"])
     else:
-        assert n == 67
+        # the rotation filter (k_proj_finish behind the rounds, resolve_body's tail in the list
+        # forms) has something to remove: the oracle keeps more without the orientation check
+        assert n == 67 < oracle_last(oracle, s, frame_of(s), False, s["th_last"])[0]
     assert st["form"] == want_form(form, K) and st["rounds"] >= K, st
     if st["form"] == 0:
         assert st["entries"] == K * K <= st["ent_cap"]
+
+
+@pytest.mark.parametrize("hist", ["12-1", "ties"])
+def test_rotation_filter_rules(ctx, oracle, form, hist):
+    """ComputeThreeMaxima's two rules in k_proj_finish (behind the rounds) and resolve_body's tail
+    (the list forms): one keypoint under every query's projection, so each query matches and the
+    angles alone decide. A single match beside twelve is dropped (1 < 0.1f * 12); of four equal
+    bins the three of lower index stay."""
+    from helpers import rot_edge_bins
+    bins, kept = rot_edge_bins(hist)
+    n = len(bins)
+    uv = np.array(pc.LATTICE[:n])
+    qd = np.random.default_rng(700 + n).integers(0, 256, (n, 32), dtype=np.uint8)
+    s = pc._scene(pc._kps(uv + 0.5, 0), np.stack([pc.flip_low_bits(d, 5) for d in qd]), uv, qd,
+                  last_angle=(30.0 * bins).astype(np.float32))
+    assert oracle_last(oracle, s, frame_of(s), False)[0] == n
+    (gn, gm), st = run_last(ctx, oracle, s, frame_of(s), True)
+    assert gn == kept < n
+    assert st["form"] == want_form(form, 1), st
 
 
 @pytest.mark.parametrize("mode,K", [("local", 70), ("ratio", 12)])

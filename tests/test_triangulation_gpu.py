@@ -53,6 +53,11 @@ def test_parity_scene_set(ctx, k, ori):
     fires, ties, shared targets, orientation pruning)."""
     rn, rm, cnt = _scene_parity(ctx, T.parity_scene(k), ori)
     assert (rn > 0).all()
+    if ori:   # k_tri_search's rotation filter removes matches of every pair
+        s = T.parity_scene(k)
+        geoms = [s["kf1"].geometry(x) for x in s["neighbours"]]
+        off = T.search_for_triangulation(s["kf1"], s["neighbours"], s["scale_factors"], s["level_sigma2"], 0, geoms)[0]
+        assert (rn < off).all()
 
 
 @ORI

@@ -7,9 +7,10 @@ fuse), so the library's fp32 results can be compared bit for bit. Not used by th
 Keyframes are objects with the attributes of orb_slam3_ros2_amd.matcher.TriKeyFrame."""
 import numpy as np
 
+from helpers import HISTO_LENGTH, c_round as roundf, rotation_bin, three_maxima  # noqa: F401 (used as T.* too)
+
 f32 = np.float32
 TH_LOW = 50
-HISTO_LENGTH = 30
 _POP = np.array([bin(i).count("1") for i in range(256)], np.int64)
 
 
@@ -65,32 +66,6 @@ def geometry(kf1, kf2):
         return np.array(F, f32).reshape(3, 3), ep
 
 
-def roundf(v) -> int:
-    """C roundf: halves away from zero (np.round rounds them to even)."""
-    v = float(v)
-    return int(np.floor(v + 0.5)) if v >= 0 else -int(np.floor(-v + 0.5))
-
-
-def three_maxima(hist):
-    """ORBmatcher::ComputeThreeMaxima over bin counts."""
-    max1 = max2 = max3 = 0
-    ind1 = ind2 = ind3 = -1
-    for i, s in enumerate(hist):
-        if s > max1:
-            max3, max2, max1 = max2, max1, s
-            ind3, ind2, ind1 = ind2, ind1, i
-        elif s > max2:
-            max3, max2 = max2, s
-            ind3, ind2 = ind2, i
-        elif s > max3:
-            max3, ind3 = s, i
-    if f32(max2) < f32(0.1) * f32(max1):
-        ind2 = ind3 = -1
-    elif f32(max3) < f32(0.1) * f32(max1):
-        ind3 = -1
-    return ind1, ind2, ind3
-
-
 def _feature_vector(kf):
     """node -> ascending feature indices (weight > 0 and node >= 0 only), as Frame::ComputeBoW."""
     fv = {}
@@ -117,7 +92,6 @@ def search_pair(kf1, kf2, scale_factors, level_sigma2, check_orientation, F12=No
     cnt = dict(epipole=0, epiline=0, ties=0, shared=0, pruned=0)
     fv1, fv2 = _feature_vector(kf1), _feature_vector(kf2)
     d2all = np.asarray(kf2.desc, np.uint8).reshape(-1, 32)
-    factor = f32(1.0) / f32(HISTO_LENGTH)
     rot_hist = [[] for _ in range(HISTO_LENGTH)]
     with np.errstate(all="ignore"):
         for node in sorted(set(fv1) & set(fv2)):
@@ -159,12 +133,7 @@ def search_pair(kf1, kf2, scale_factors, level_sigma2, check_orientation, F12=No
                 if best_idx2 >= 0:
                     match[idx1] = best_idx2
                     if check_orientation:
-                        rot = f32(kf1.kps["angle"][idx1]) - f32(kf2.kps["angle"][best_idx2])
-                        if rot < 0:
-                            rot = rot + f32(360)
-                        bin_ = roundf(rot * factor)
-                        if bin_ == HISTO_LENGTH:
-                            bin_ = 0
+                        bin_ = rotation_bin(kf1.kps["angle"][idx1], kf2.kps["angle"][best_idx2])
                         assert 0 <= bin_ < HISTO_LENGTH
                         rot_hist[bin_].append(idx1)
     targets = match[match >= 0]
