@@ -245,7 +245,8 @@ int orbhip_frontend_context(orbhip_frontend* fe, int j, orbhip_ctx** out);
  * and the search of one call form one pair, 8 Fuse and Fuse with a Sim3: the grid build and the
  * search of one call form one pair, 9 SearchByProjection with a Sim3: the grid build, the search and
  * the resolve of one call form one pair, 10 the triangulation of CreateNewMapPoints: k_tri_points
- * and k_tri_claim of one call form one pair). orbhip_profile_collect synchronises and
+ * and k_tri_claim of one call form one pair, 11 Sim3Solver: k_sim3_ransac and k_sim3_select of one
+ * call form one pair). orbhip_profile_collect synchronises and
  * returns the summed duration (ms) and the number of bracketed launches, then resets. The one-launch
  * pyramid (k_pyr_cone) and the octree also time themselves on the device (first workgroup start to
  * last workgroup end, s_memrealtime: the span rocprofv3's kernel trace reports); their stages
@@ -776,6 +777,64 @@ int orbhip_fuse_sim3(orbhip_ctx* ctx, const orbhip_frame* kfs, int B, const orbh
 int orbhip_search_by_projection_sim3(orbhip_ctx* ctx, const orbhip_frame* kf, const orbhip_local_points* mps,
                                      float th, float ratio_hamming, int32_t* match /* n */,
                                      int32_t* match_dist /* n or NULL */, int32_t* level /* n or NULL */);
+
+/* ---- LoopClosing: Sim3Solver (Horn's closed form on RANSAC triples) -------------------
+ * U:src/Sim3Solver.cc (LoopClosing::DetectCommonRegionsFromBoW, between SearchByBoW and
+ * SearchByProjection(Scw)). Every hypothesis of every candidate keyframe in one call: the
+ * hypotheses are independent once their triples are drawn, and upstream's sequential rule ("the
+ * first above mRansacMinInliers converges, else the best so far") is applied afterwards in its
+ * order-free form, with the same result (DESIGN.md "Sim3Solver" has the operation order).
+ *
+ * A problem is what upstream's constructor prepares: the n correspondences its filter leaves, X1 /
+ * X2 = the map points in the frames of camera 1 / 2 (Rcw Xw + tcw), the two pinhole cameras as
+ * (fx, fy, cx, cy), and the error bounds mvnMaxError1 / 2. QUIRK: upstream keeps 9.210 *
+ * sigma2[octave] in a vector<size_t>, so its bound is that product TRUNCATED to an integer; the
+ * adapter passes max_err = (float)(size_t)(9.210 * (double)sigma2). The library only compares
+ * against the bound. min_inliers = mRansacMinInliers, fix_scale = mbFixScale. The library draws no
+ * random numbers: triples holds n_hyp triples of indices into [0, n), drawn by the caller as
+ * upstream draws them.
+ *
+ * Per hypothesis h: ComputeSim3 on the triple in fp32 (the rotation from the eigenvector of Horn's
+ * 4x4 matrix, computed by a fixed number of fp64 Jacobi sweeps and converted through the
+ * quaternion, not through atan2 / the angle-axis vector), then CheckInliers over all n
+ * correspondences: an inlier iff both squared reprojection errors are BELOW their bounds; there is
+ * no depth test. A degenerate triple gives NaN or inf, which fail every comparison: 0 inliers, no
+ * special case. n_inliers[h] = the count, hyp[13 h ..] = (s, R row-major, t) of T12 = [s R | t].
+ * Selection, for h ascending as upstream's iterate(): converged = the first h with n_inliers[h] >
+ * min_inliers, or -1; best = converged, or without one the LAST h of the largest count (upstream
+ * replaces the best on >=, and a count of 0 qualifies). sel and inliers (one byte per
+ * correspondence) are those of hypothesis `best`.
+ *
+ * Returns the number of problems that converged. B = 0: 0. B > 64, n > 8192 or n_hyp > 4096:
+ * ORBHIP_ERR_UNSUPPORTED. ORBHIP_ERR_ARG, before anything is uploaded and with no output touched: n <
+ * 3, n_hyp < 1, a NULL required pointer, a triple index outside [0, n) or repeated within its triple,
+ * a focal length that is not positive and finite, min_inliers < 0. One upload, two launches, one
+ * read-back. */
+typedef struct {
+    float cam1[4], cam2[4];        /* fx, fy, cx, cy */
+    int32_t n;                     /* correspondences */
+    const float* X1;               /* n x 3 */
+    const float* X2;               /* n x 3 */
+    const float* max_err1;         /* n: the truncated bounds (above) */
+    const float* max_err2;         /* n */
+    int32_t fix_scale;
+    int32_t min_inliers;
+    int32_t n_hyp;
+    const int32_t* triples;        /* n_hyp x 3 */
+} orbhip_sim3_problem;
+
+typedef struct {                   /* the pointers are the caller's */
+    int32_t* n_inliers;            /* n_hyp */
+    float* hyp;                    /* n_hyp x 13, or NULL */
+    uint8_t* inliers;              /* n, or NULL */
+    float sel[13];                 /* (s, R row-major, t) of hypothesis `best` */
+    int32_t converged;             /* hypothesis index, or -1 */
+    int32_t best;
+} orbhip_sim3_result;
+
+int orbhip_sim3_solve_batch(orbhip_ctx* ctx, const orbhip_sim3_problem* probs, int B, orbhip_sim3_result* res);
+/* B = 1 */
+int orbhip_sim3_solve(orbhip_ctx* ctx, const orbhip_sim3_problem* prob, orbhip_sim3_result* res);
 
 /* ---- multi-GPU BundleAdjustment (SURVEY.md §8e, C5 GlobalBundleAdjustment) --------
  * One process per GPU. Landmarks (with their edges) are partitioned across ranks; every rank

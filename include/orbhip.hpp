@@ -509,6 +509,122 @@ public:
     bool mbCheckOrientation;
 };
 
+// U:include/Sim3Solver.h — Horn's closed form on RANSAC triples; every hypothesis in one device call
+// (orbhip_sim3_solve_batch), then upstream's iterate() over the stored results.
+// The adapter fills the correspondences its constructor's filter leaves: X1 / X2 (the map points in
+// the two cameras' frames), the truncated error bounds (MaxError), indices1 = mvnIndices1, n1 = mN1.
+class Sim3Solver {
+public:
+    // mvnMaxError: upstream keeps 9.210 * sigma2 in a vector<size_t>
+    static float MaxError(float sigma2) { return (float)(size_t)(9.210 * (double)sigma2); }
+
+    // upstream's draw from a fresh mvAllIndices per iteration; RandomInt(lo, hi), both ends included
+    template <class RandomInt>
+    static std::vector<int32_t> DrawTriples(int N, int H, RandomInt&& randint) {
+        std::vector<int32_t> out((size_t)H * 3), avail;
+        for (int h = 0; h < H; h++) {
+            avail.resize(N);
+            for (int i = 0; i < N; i++) avail[i] = i;
+            for (int k = 0; k < 3; k++) {
+                const int r = randint(0, (int)avail.size() - 1);
+                out[(size_t)3 * h + k] = avail[r];
+                avail[r] = avail.back();
+                avail.pop_back();
+            }
+        }
+        return out;
+    }
+
+    std::vector<float> X1, X2, vMaxError1, vMaxError2;   // N x 3, N x 3, N, N
+    std::vector<int> vnIndices1;                         // N
+    int mN1 = 0;
+    float cam1[4] = {0, 0, 0, 0}, cam2[4] = {0, 0, 0, 0};   // fx, fy, cx, cy
+    bool mbFixScale = false;
+    double mRansacProb = 0.99;
+    int mRansacMinInliers = 6, mRansacMaxIts = 300, mnIterations = 0, mnBestInliers = 0;
+    float mBestT12[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};   // row-major 4 x 4
+
+    int N() const { return (int)vMaxError1.size(); }
+
+    void SetRansacParameters(double probability = 0.99, int minInliers = 6, int maxIterations = 300) {
+        mRansacProb = probability;
+        mRansacMinInliers = minInliers;
+        int nIterations = maxIterations;
+        if (minInliers == N()) {
+            nIterations = 1;
+        } else if (N() > 0) {
+            const float epsilon = (float)minInliers / N();
+            const double rest = 1.0 - std::pow((double)epsilon, 3);
+            if (rest > 0.0 && rest < 1.0) {
+                const double v = std::ceil(std::log(1.0 - probability) / std::log(rest));
+                nIterations = v < (double)maxIterations ? (int)v : maxIterations;
+            }
+        }
+        mRansacMaxIts = std::max(1, std::min(nIterations, maxIterations));
+        mnIterations = 0;
+        solved_ = false;
+    }
+
+    // every one of the mRansacMaxIts hypotheses in one call; vTriples: at least mRansacMaxIts x 3
+    void solve(orbhip_ctx* ctx, const std::vector<int32_t>& vTriples) {
+        solved_ = false;
+        if (N() < std::max(3, mRansacMinInliers)) return;   // iterate() gives up at once
+        if (vTriples.size() < (size_t)mRansacMaxIts * 3) throw Error(ORBHIP_ERR_ARG, "Sim3Solver: vTriples");
+        orbhip_sim3_problem p{};
+        std::memcpy(p.cam1, cam1, sizeof cam1);
+        std::memcpy(p.cam2, cam2, sizeof cam2);
+        p.n = N(); p.X1 = X1.data(); p.X2 = X2.data(); p.max_err1 = vMaxError1.data(); p.max_err2 = vMaxError2.data();
+        p.fix_scale = mbFixScale; p.min_inliers = mRansacMinInliers; p.n_hyp = mRansacMaxIts; p.triples = vTriples.data();
+        nInliers_.assign(mRansacMaxIts, 0);
+        hyp_.assign((size_t)mRansacMaxIts * 13, 0.f);
+        inliers_.assign(N(), 0);
+        orbhip_sim3_result r{};
+        r.n_inliers = nInliers_.data(); r.hyp = hyp_.data(); r.inliers = inliers_.data();
+        check(orbhip_sim3_solve(ctx, &p, &r), "orbhip_sim3_solve");
+        solved_ = true;
+    }
+
+    // upstream's iterate(): returns mBestT12 (row-major 4 x 4, [s R | t])
+    const float* iterate(int nIterations, bool& bNoMore, std::vector<bool>& vbInliers, int& nInliers, bool& bConverge) {
+        static const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+        bNoMore = false;
+        bConverge = false;
+        vbInliers.assign(mN1, false);
+        nInliers = 0;
+        if (N() < mRansacMinInliers) { bNoMore = true; return kIdentity; }
+        if (!solved_) throw Error(ORBHIP_ERR_ARG, "Sim3Solver::iterate before solve");
+        int nCurrentIterations = 0;
+        while (mnIterations < mRansacMaxIts && nCurrentIterations < nIterations) {
+            const int h = mnIterations;
+            nCurrentIterations++;
+            mnIterations++;
+            if (nInliers_[h] >= mnBestInliers) {
+                mnBestInliers = nInliers_[h];
+                const float* y = &hyp_[(size_t)13 * h];
+                for (int i = 0; i < 3; i++) {
+                    for (int j = 0; j < 3; j++) mBestT12[4 * i + j] = y[0] * y[1 + 3 * i + j];
+                    mBestT12[4 * i + 3] = y[10 + i];
+                }
+                if (nInliers_[h] > mRansacMinInliers) {   // h == the call's `converged`: its mask came back
+                    nInliers = nInliers_[h];
+                    for (int i = 0; i < N(); i++)
+                        if (inliers_[i]) vbInliers[vnIndices1[i]] = true;
+                    bConverge = true;
+                    return mBestT12;
+                }
+            }
+        }
+        if (mnIterations >= mRansacMaxIts) bNoMore = true;
+        return mBestT12;
+    }
+
+private:
+    std::vector<int32_t> nInliers_;
+    std::vector<float> hyp_;
+    std::vector<uint8_t> inliers_;
+    bool solved_ = false;
+};
+
 // U:include/KeyFrameDatabase.h — the device database; slots stand for KeyFrames.
 class KeyFrameDatabase {
 public:

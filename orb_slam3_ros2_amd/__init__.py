@@ -16,6 +16,7 @@ Host-side mirror of the reference's hot-path interfaces over th
   ORBmatcher.SearchForTriangulation(kf1, neighbours, ...)                   U:src/ORBmatcher.cc
   ORBmatcher.Fuse(kfs, points, ...)                                         U:src/ORBmatcher.cc
   ORBmatcher.FuseSim3 / SearchByProjectionSim3(...)   (LoopClosing)         U:src/ORBmatcher.cc
+  Sim3Solver(...).solve(triples) / iterate(n) / solve_batch   (LoopClosing)  U:src/Sim3Solver.cc
   KeyFrameDatabase(max_kf).DetectRelocalizationCandidates / DetectNBestCandidates
                                                                             U:src/KeyFrameDatabase.cc
   stereo_frame(ext, left, right, bf, b) -> StereoFrame   Frame's stereo ctor: both ExtractORB
@@ -37,7 +38,8 @@ from .kfdb import KeyFrameDatabase  # noqa: F401
 from .frontend import FrameStream  # noqa: F401
 from .camera import PinholeCamera  # noqa: F401
 from .stereo import StereoFrame, stereo_frame  # noqa: F401
+from .sim3solver import Sim3Solver, draw_triples  # noqa: F401
 
-__all__ = ["StereoFrame", "stereo_frame", "ORBextractor", "KeyPoint", "ORBmatcher", "Optimizer", "BAProblem", "StereoBAProblem", "BAResult", "PoseProblem", "PoseResult", "ORBVocabulary", "KeyFrameDatabase", "FrameStream", "PinholeCamera",
+__all__ = ["Sim3Solver", "draw_triples", "StereoFrame", "stereo_frame", "ORBextractor", "KeyPoint", "ORBmatcher", "Optimizer", "BAProblem", "StereoBAProblem", "BAResult", "PoseProblem", "PoseResult", "ORBVocabulary", "KeyFrameDatabase", "FrameStream", "PinholeCamera",
            "OrbHipError",
            "lib", "library_path"]

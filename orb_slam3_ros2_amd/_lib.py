@@ -145,6 +145,18 @@ class LocalPointsC(ctypes.Structure):
                 ("skip", ctypes.c_void_p)]
 
 
+class Sim3ProblemC(ctypes.Structure):
+    _fields_ = [("cam1", ctypes.c_float * 4), ("cam2", ctypes.c_float * 4), ("n", ctypes.c_int32),
+                ("X1", ctypes.c_void_p), ("X2", ctypes.c_void_p), ("max_err1", ctypes.c_void_p),
+                ("max_err2", ctypes.c_void_p), ("fix_scale", ctypes.c_int32), ("min_inliers", ctypes.c_int32),
+                ("n_hyp", ctypes.c_int32), ("triples", ctypes.c_void_p)]
+
+
+class Sim3ResultC(ctypes.Structure):
+    _fields_ = [("n_inliers", ctypes.c_void_p), ("hyp", ctypes.c_void_p), ("inliers", ctypes.c_void_p),
+                ("sel", ctypes.c_float * 13), ("converged", ctypes.c_int32), ("best", ctypes.c_int32)]
+
+
 # every symbol include/orbhip.h declares (tests check the export table against this list)
 EXPORTED = ["orbhip_abi_version", "orbhip_create", "orbhip_destroy", "orbhip_level_info", "orbhip_max_keypoints",
             "orbhip_extract", "orbhip_extract_batch_device", "orbhip_extract_stereo", "orbhip_extract_stereo_device",
@@ -165,6 +177,7 @@ EXPORTED = ["orbhip_abi_version", "orbhip_create", "orbhip_destroy", "orbhip_lev
             "orbhip_search_for_triangulation_stereo", "orbhip_create_new_map_points_stereo",
             "orbhip_triangulate_matches_stereo",
             "orbhip_fuse_sim3", "orbhip_search_by_projection_sim3",
+            "orbhip_sim3_solve", "orbhip_sim3_solve_batch",
             "orbhip_kfdb_create", "orbhip_kfdb_destroy", "orbhip_kfdb_add", "orbhip_kfdb_erase",
             "orbhip_kfdb_detect_relocalization", "orbhip_kfdb_detect_nbest",
             "orbhip_frontend_create", "orbhip_frontend_destroy", "orbhip_frontend_push", "orbhip_frontend_view",
@@ -268,6 +281,8 @@ def lib():
     L.orbhip_fuse_sim3.argtypes = [vp, ctypes.POINTER(FrameC), i32, ctypes.POINTER(LocalPointsC), vp, f32, vp, vp, vp, vp]
     L.orbhip_search_by_projection_sim3.argtypes = [vp, ctypes.POINTER(FrameC), ctypes.POINTER(LocalPointsC), f32, f32,
                                                    vp, vp, vp]
+    L.orbhip_sim3_solve.argtypes = [vp, ctypes.POINTER(Sim3ProblemC), ctypes.POINTER(Sim3ResultC)]
+    L.orbhip_sim3_solve_batch.argtypes = [vp, ctypes.POINTER(Sim3ProblemC), i32, ctypes.POINTER(Sim3ResultC)]
     L.orbhip_kfdb_create.argtypes = [vp, i32, ctypes.POINTER(vp)]
     L.orbhip_kfdb_destroy.argtypes = [vp]
     L.orbhip_kfdb_add.argtypes = [vp, i32, vp, vp, i32]

@@ -42,6 +42,7 @@ struct orbhip_ctx {
     ProjWorkspace* proj = nullptr;
     StageBlock tri_stage{false};    // SearchForTriangulation's block (stage.h)
     StageBlock fuse_stage{false};   // Fuse's, Fuse with a Sim3's and the Sim3 projection search's
+    StageBlock sim3_stage{false};   // Sim3Solver's
     StageTimer timer;
     GraphCache graphs;   // replays of repeated per-frame launch sequences (graph_cache.h)
 };
@@ -276,7 +277,7 @@ int orbhip_launch_graphs(orbhip_ctx* c) {
 }
 
 int orbhip_profile_stage(orbhip_ctx* c, int stage) {
-    if (!c || stage < 0 || stage > 10) return ORBHIP_ERR_ARG;
+    if (!c || stage < 0 || stage > 11) return ORBHIP_ERR_ARG;
     HIPOK(hipSetDevice(c->device));
     StageTimer& t = c->timer;
     if (!t.created) {
@@ -754,6 +755,18 @@ int orbhip_search_by_projection_sim3(orbhip_ctx* c, const orbhip_frame* kf, cons
     if (!c) return ORBHIP_ERR_ARG;
     HIPOK(hipSetDevice(c->device));
     return sim3_search(c->fuse_stage, c->timer, c->stream, kf, mps, th, ratio_hamming, match, match_dist, level);
+}
+
+// ---- LoopClosing: Sim3Solver, every hypothesis of every candidate ----
+int orbhip_sim3_solve_batch(orbhip_ctx* c, const orbhip_sim3_problem* probs, int B, orbhip_sim3_result* res) {
+    if (!c) return ORBHIP_ERR_ARG;
+    HIPOK(hipSetDevice(c->device));
+    return sim3_solve_batch(c->sim3_stage, c->timer, c->stream, probs, B, res);
+}
+
+int orbhip_sim3_solve(orbhip_ctx* c, const orbhip_sim3_problem* prob, orbhip_sim3_result* res) {
+    if (!prob || !res) return ORBHIP_ERR_ARG;
+    return orbhip_sim3_solve_batch(c, prob, 1, res);
 }
 
 // the stored list capacity of the Sim3 projection search; the resolve has no round cap other than

@@ -246,6 +246,10 @@ constexpr int kSim3ListCap = 8;        // smallest keys k_sim3_search stores per
 int sim3_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_frame* kf,
                 const orbhip_local_points* mps, float th, float ratio_hamming, int32_t* match, int32_t* match_dist,
                 int32_t* level);
+// Sim3Solver (sim3_solver_kernels.hip): every hypothesis of every problem, then the selection; stage 11
+constexpr int kSim3MaxBatch = 64;   // problems (candidate keyframes) per call
+int sim3_solve_batch(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_sim3_problem* probs, int B,
+                     orbhip_sim3_result* res);
 
 // ---- ingest ----
 void launch_bgr2gray(const uint8_t* src, int B, int w, int h, int sstride, int64_t sfstride, uint8_t* dst, int dstride,

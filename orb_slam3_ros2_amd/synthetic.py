@@ -1297,3 +1297,52 @@ def synthetic_stereo_ba_problem(n_kf=50, n_pts=2000, stereo_frac=0.7, seed=7, ur
     sp = StereoBAProblem(**prob.__dict__, edge_ur=np.where(stereo, ur, -1.0).astype(np.float32), bf=bf,
                          huber_delta_stereo=TH_HUBER_STEREO)
     return sp, dict(gt, stereo=stereo, ur=ur)
+
+
+# ---------------------------------------------------------------------------
+# Sim3Solver scenes (LoopClosing::DetectCommonRegionsFromBoW)
+# ---------------------------------------------------------------------------
+def synthetic_sim3_solver_scene(n=100, outlier_frac=0.5, seed=0, fix_scale=False, n_hyp=300, min_inliers=15,
+                                n_levels=8, scale_factor=1.2, noise_px=0.7, cam1=None, cam2=None, n_degenerate=2):
+    """What Sim3Solver's constructor leaves of a loop candidate: n correspondences X1 / X2 (the map
+    points in the two cameras' frames, float32) with points in front of camera 1, a true Sim3
+    (X1 = s R X2 + t; s = 1 when the scale is fixed), noise of noise_px pixels at each point's depth,
+    a share of the X2 replaced by unrelated points (outliers), random octaves and with them upstream's
+    truncated error bounds, and n_hyp triples drawn by draw_triples from a seeded generator. Also
+    indices1 / n1 (mvnIndices1, mN1), the true (s, R, t), and n_degenerate planted hypotheses
+    (degenerate_h) whose three correspondences are copies of one."""
+    from .sim3solver import draw_triples, error_bounds
+    rng = np.random.default_rng(seed)
+    c1 = dict(D435I) if cam1 is None else dict(cam1)
+    c2 = dict(fx=600.0, fy=605.0, cx=318.5, cy=242.25) if cam2 is None else dict(cam2)
+    X1 = np.stack([rng.uniform(-2.0, 2.0, n), rng.uniform(-1.5, 1.5, n), rng.uniform(2.5, 8.0, n)], 1)
+    R = _rodrigues(rng.normal(size=3) * 0.12)
+    t = rng.normal(size=3) * 0.25
+    s = 1.0 if fix_scale else float(rng.uniform(0.8, 1.25))
+    X2 = (X1 - t) @ R / s                      # rows: R^T (X1 - t) / s
+    out = rng.random(n) < outlier_frac
+    X2[out] = np.stack([rng.uniform(-2.0, 2.0, n), rng.uniform(-1.5, 1.5, n), rng.uniform(2.0, 9.0, n)], 1)[out]
+    for X, c in ((X1, c1), (X2, c2)):          # pixel noise at the point's depth, and a little in depth
+        X[:, 0] += rng.normal(size=n) * noise_px * X[:, 2] / c["fx"]
+        X[:, 1] += rng.normal(size=n) * noise_px * X[:, 2] / c["fy"]
+        X[:, 2] *= 1.0 + rng.normal(size=n) * 1e-3
+    _, s2 = orb_scale_tables(n_levels, scale_factor)
+    oct1, oct2 = rng.integers(0, n_levels, n), rng.integers(0, n_levels, n)
+    n1 = n + n // 3
+    indices1 = np.sort(rng.choice(n1, n, replace=False))
+    draw = np.random.default_rng(seed + 7919)
+    triples = draw_triples(n, n_hyp, lambda lo, hi: int(draw.integers(lo, hi + 1)))
+    # degenerate hypotheses: three correspondences that coincide (M = 0: NaN scale when it is free),
+    # their triple planted at two places
+    degenerate_h = []
+    if n_degenerate and n >= 6 and n_hyp >= 4:
+        pool = np.nonzero(out)[0] if out.sum() >= 3 else np.arange(n)   # outliers: the counts hardly move
+        i0, i1, i2 = (int(i) for i in rng.choice(pool, 3, replace=False))
+        X1[[i1, i2]], X2[[i1, i2]] = X1[i0], X2[i0]
+        degenerate_h = [1, n_hyp // 2][:n_degenerate]
+        triples[degenerate_h] = (i0, i1, i2)
+    cams =[np.array([c[k] for k in ("fx", "fy", "cx", "cy")], np.float32) for c in (c1, c2)]
+    return dict(X1=X1.astype(np.float32), X2=X2.astype(np.float32), octaves1=oct1, octaves2=oct2,
+                level_sigma2=s2, max_err1=error_bounds(oct1, s2), max_err2=error_bounds(oct2, s2),
+                cam1=cams[0], cam2=cams[1], fix_scale=bool(fix_scale), min_inliers=int(min_inliers),
+                triples=triples, indices1=indices1, n1=n1, outlier=out, degenerate_h=degenerate_h, true_s=s, true_R=R, true_t=t)
