@@ -316,6 +316,10 @@ def lib():
     # host only: the projection searches' route for a call's sizes; the last search on a context
     L.orbhip_test_proj_route.argtypes = [i32, i32, i32, vp]
     L.orbhip_test_proj_stats.argtypes = [vp, vp]
+    # the last SearchForInitialization on a context: form, round, init_ahead, sizes, need counts
+    L.orbhip_test_init_stats.argtypes = [vp, vp]
+    # host only: SearchForInitialization's envelope (return code, LDS, list capacity, round cap)
+    L.orbhip_test_init_route.argtypes = [i32, i32, i32, i32, vp]
     # the device's PredictScale against host levels over a range of float bit patterns
     L.orbhip_test_predict_scale_sweep.argtypes = [ctypes.c_uint32, ctypes.c_uint32, f32, i32, vp]
     L.orbhip_test_predict_scale_sweep.restype = ctypes.c_int64

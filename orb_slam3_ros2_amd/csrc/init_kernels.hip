@@ -139,7 +139,11 @@ __global__ __launch_bounds__(256) void k_init_cands(InitGeom g, const orbhip_kp*
     const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     const int nq = counts[0], nr = counts[1];
-    if (q >= nq) return;
+    if (q >= nq) {
+        // the slots that fill the last block of four: the chain loads their rows too (empty, not stale)
+        if (lane < kInitK) topk[(size_t)q * kInitK + lane] = ~0u;
+        return;
+    }
     const int i1 = qlist[q];
     const float x = prev[2 * i1], y = prev[2 * i1 + 1], r = g.r;
     const int nMinCellX = max(0, (int)floorf((x - g.minx - r) * g.invw));
@@ -513,11 +517,41 @@ __global__ __launch_bounds__(1024) void k_init_finish(InitGeom g, int check_orie
     if (tid == 0) *nmatch = cnt;
 }
 
+// The envelope of a call from its sizes (n1 / n2 keypoints, nq0 / nr0 of them on octave 0): ranks and
+// query slots fit 16 bits, the chain's state (4 bytes per rank and per query + 16) fits 150 KiB of
+// dynamic LDS, the lists hold at most 2^28 entries. Decided before anything is allocated.
+struct InitEnvelope {
+    size_t lds;     // k_init_greedy's dynamic LDS
+    int list_cap;   // entries per query list
+    int cap;        // parallel rounds before the chain takes over
+};
+int init_envelope(int n1, int n2, int nq0, int nr0, InitEnvelope* e) {
+    if (n1 < 0 || n2 < 0 || n1 > 65535 || n2 > 65535) return ORBHIP_ERR_ARG;
+    e->lds = 4 * (size_t)nr0 + 4 * (size_t)nq0 + 16;
+    e->list_cap = std::max(64, (nr0 + 63) & ~63);
+    e->cap = std::min(kInitMaxRounds, nq0 + 2);
+    if (e->lds > 150 * 1024) return ORBHIP_ERR_UNSUPPORTED;
+    if ((size_t)std::max(nq0, 1) * e->list_cap > ((size_t)1 << 28)) return ORBHIP_ERR_UNSUPPORTED;
+    return ORBHIP_OK;
+}
+
 }  // namespace
+
+// orbhip_test_init_route (host only): out4 = {init_envelope's return code, LDS bytes, list_cap, round cap}
+int init_test_route(int n1, int n2, int nq0, int nr0, int32_t* out4) {
+    if (!out4 || nq0 < 0 || nr0 < 0 || nq0 > n1 || nr0 > n2) return ORBHIP_ERR_ARG;
+    InitEnvelope e{};
+    out4[0] = init_envelope(n1, n2, nq0, nr0, &e);
+    out4[1] = (int32_t)e.lds; out4[2] = e.list_cap; out4[3] = e.cap;
+    return ORBHIP_OK;
+}
 
 int init_search(ProjWorkspace* ws, const orbhip_init_frame* F1, const orbhip_init_frame* F2, float* prev_matched,
                 int window_size, float nnratio, int check_orientation, int32_t* matches12, hipStream_t st) {
-    if (!ws || !F1 || !F2 || !prev_matched || !matches12 || F1->n < 0 || F2->n < 0 || F1->n > 65535 ||
+    if (!ws) return ORBHIP_ERR_ARG;
+    ws->in_form = -1;   // orbhip_test_init_stats: nothing to report until a form has produced a result
+    ws->in_round = ws->in_nq0 = ws->in_nr0 = 0;
+    if (!F1 || !F2 || !prev_matched || !matches12 || F1->n < 0 || F2->n < 0 || F1->n > 65535 ||
         F2->n > 65535 || (F1->n && (!F1->kps || !F1->desc)) || (F2->n && (!F2->kps || !F2->desc)) ||
         !(F2->max_x > F2->min_x) || !(F2->max_y > F2->min_y))
         return ORBHIP_ERR_ARG;
@@ -532,10 +566,10 @@ int init_search(ProjWorkspace* ws, const orbhip_init_frame* F1, const orbhip_ini
         nq0 += F1->kps[i].octave == 0;
     }
     for (int k = 0; k < n2; k++) nr0 += F2->kps[k].octave == 0;
-    const size_t lds = 4 * (size_t)nr0 + 4 * (size_t)nq0 + 16;
-    if (lds > 150 * 1024) return ORBHIP_ERR_UNSUPPORTED;
-    const int list_cap = std::max(64, (nr0 + 63) & ~63);
-    if ((size_t)std::max(nq0, 1) * list_cap > ((size_t)1 << 28)) return ORBHIP_ERR_UNSUPPORTED;
+    InitEnvelope env{};
+    if (int rc = init_envelope(n1, n2, nq0, nr0, &env)) return rc;
+    const size_t lds = env.lds;
+    const int list_cap = env.list_cap;
     // the kernel's static LDS (histogram) comes on top of the dynamic 150 KiB envelope
     static LdsAttrOnce attr;   // per device, thread-safe (dev_attr.h)
     static const void* const fs[] = {(const void*)k_init_greedy, (const void*)k_init_finish};
@@ -551,13 +585,15 @@ int init_search(ProjWorkspace* ws, const orbhip_init_frame* F1, const orbhip_ini
     const size_t o_len = lay.take(4 * ((size_t)n1 + 1)), o_list = lay.take(4 * (size_t)std::max(nq0, 1) * list_cap);
     const size_t o_topk = lay.take(4 * (size_t)kInitK * (((size_t)std::max(nq0, 1) + 3) & ~size_t(3)));
     const size_t o_need = lay.take(4 * (size_t)std::max(nq0, 1));
-    const int cap = std::min(kInitMaxRounds, nq0 + 2);
+    const int cap = env.cap;
     const size_t o_cnt3 = lay.take(4 * 3 * (size_t)std::max(nr0, 1));
     const size_t o_ent3 = lay.take(4 * 3 * (size_t)std::max(nr0, 1) * kInitC);
     const size_t o_pick = lay.take(4 * (size_t)std::max(nq0, 1));
     const size_t o_pout = lay.take(8 * (size_t)n1);
     const size_t o_flags = lay.take(4 * ((size_t)cap + 1));
     if (int rc = proj_ws_ensure(ws, lay.total())) return rc;
+    ws->in_nq0 = nq0; ws->in_nr0 = nr0;
+    ws->in_need_off = o_need; ws->in_need_live = true;
     StageBlock& S = ws->s;
     char* H = (char*)S.h;
     char* D = (char*)S.d;
@@ -587,7 +623,9 @@ int init_search(ProjWorkspace* ws, const orbhip_init_frame* F1, const orbhip_ini
     const int* hflags = (const int*)(H + o_flags);
     const dim3 gq((unsigned)std::max(1, (nq0 + 15) / 16));
     bool done = false;
-    for (int r = 0; r < cap && !done && std::getenv("ORBHIP_INIT_CHAIN") == nullptr;) {
+    const bool chain_only = std::getenv("ORBHIP_INIT_CHAIN") != nullptr;
+    int form = chain_only ? 3 : 2, rounds = chain_only ? 0 : cap;   // of the chain, unless the rounds end it
+    for (int r = 0; r < cap && !done && !chain_only;) {
         const int R = std::min(ws->init_ahead, cap - r);
         for (int j = 0; j < R; j++)
             hipLaunchKernelGGL(k_init_round, gq, dim3(256), 0, st, g, nnratio, r + j, (const int*)counts,
@@ -603,10 +641,14 @@ int init_search(ProjWorkspace* ws, const orbhip_init_frame* F1, const orbhip_ini
         HIPOK(hipMemcpyAsync(H + o_pout, D + o_pout, 8 * (size_t)n1, hipMemcpyDeviceToHost, st));
         HIPOK(hipMemcpyAsync(H + o_flags, flags, 4 * ((size_t)cap + 1), hipMemcpyDeviceToHost, st));
         HIPOK(hipStreamSynchronize(st));
-        if (hflags[0]) break;   // a rank overflowed its claim slots: the chain decides
+        if (hflags[0]) {   // a rank overflowed its claim slots: the chain decides
+            form = 1; rounds = r + R;
+            break;
+        }
         for (int j = 0; j < R && !done; j++)
             if (hflags[1 + r + j] == 0) {
                 done = true;
+                form = 0; rounds = r + j;
                 ws->init_ahead = std::min(16, std::max(3, r + j + 2));
             }
         r += R;
@@ -615,6 +657,7 @@ int init_search(ProjWorkspace* ws, const orbhip_init_frame* F1, const orbhip_ini
     if (done) {
         std::memcpy(matches12, H + o_match, 4 * (size_t)n1);
         std::memcpy(prev_matched, H + o_pout, 8 * (size_t)n1);
+        ws->in_form = form; ws->in_round = rounds;
         return ((int*)(H + o_cnt))[2];
     }
     hipLaunchKernelGGL(k_init_greedy, dim3(1), dim3(256), lds, st, g, nnratio, check_orientation, dk2,
@@ -626,7 +669,31 @@ int init_search(ProjWorkspace* ws, const orbhip_init_frame* F1, const orbhip_ini
     HIPOK(hipStreamSynchronize(st));
     std::memcpy(matches12, H + o_match, 4 * (size_t)n1);
     std::memcpy(prev_matched, H + o_prev, 8 * (size_t)n1);
+    ws->in_form = form; ws->in_round = rounds;
     return ((int*)(H + o_cnt))[2];
+}
+
+// orbhip_test_init_stats: the last SearchForInitialization on this workspace (ProjWorkspace::in_*).
+// out8 = {form, round, init_ahead, nq0, nr0, queries with need == 1, with need == 2, 0}; the two
+// counts come from that call's need[] while the block still holds it (-1 each once another call
+// has laid the block out, or when no call got as far as the kernels)
+int init_test_stats(ProjWorkspace* ws, int32_t* out8, hipStream_t st) {
+    if (!out8) return ORBHIP_ERR_ARG;
+    for (int i = 0; i < 8; i++) out8[i] = 0;
+    out8[0] = ws ? ws->in_form : -1;
+    out8[5] = out8[6] = -1;
+    if (!ws) return ORBHIP_OK;
+    out8[1] = ws->in_round; out8[2] = ws->init_ahead; out8[3] = ws->in_nq0; out8[4] = ws->in_nr0;
+    if (ws->in_form < 0 || !ws->in_need_live) return ORBHIP_OK;
+    const size_t nq = (size_t)ws->in_nq0;
+    if (ws->in_need_off + 4 * nq > ws->s.dcap || ws->in_need_off + 4 * nq > ws->s.hcap) return ORBHIP_ERR_CAPACITY;
+    // the pinned image's need segment is unused by the search itself
+    int* hn = (int*)(ws->s.h + ws->in_need_off);
+    if (nq) HIPOK(hipMemcpyAsync(hn, ws->s.d + ws->in_need_off, 4 * nq, hipMemcpyDeviceToHost, st));
+    HIPOK(hipStreamSynchronize(st));
+    out8[5] = out8[6] = 0;
+    for (size_t q = 0; q < nq; q++) out8[5] += hn[q] == 1, out8[6] += hn[q] == 2;
+    return ORBHIP_OK;
 }
 
 }  // namespace orbhip

@@ -837,6 +837,24 @@ int orbhip_test_proj_stats(orbhip_ctx* c, int32_t* out4) {
     if (!c) return ORBHIP_ERR_ARG;
     return proj_test_stats(c->proj, out4);
 }
+// the last SearchForInitialization on this context: out8 = {form (0 the rounds converged, 1 the
+// chain after a claim-slot overflow, 2 the chain after the round cap, 3 the chain by
+// ORBHIP_INIT_CHAIN, -1 none yet / no queries / an error), the round that changed nothing (else the
+// rounds run), init_ahead after the call, octave-0 keypoints of F1, of F2, queries with need == 1,
+// with need == 2 (one device-to-host copy of that call's need[]; -1 when it is gone), 0}
+// host only (no device): SearchForInitialization's envelope for a call's sizes (n1 / n2 keypoints,
+// nq0 / nr0 of them on octave 0), the function init_search itself follows. out4 = {the return code
+// the call would get from its sizes (0, ORBHIP_ERR_ARG, ORBHIP_ERR_UNSUPPORTED), the chain's
+// dynamic LDS bytes, entries per query list, parallel rounds before the chain takes over}
+int orbhip_test_init_route(int n1, int n2, int nq0, int nr0, int32_t* out4) {
+    return init_test_route(n1, n2, nq0, nr0, out4);
+}
+int orbhip_test_init_stats(orbhip_ctx* c, int32_t* out8) {
+    if (!c) return ORBHIP_ERR_ARG;
+    HIPOK(hipSetDevice(c->device));
+    if (!c->proj) c->proj = proj_ws_create();   // a fresh context reports the workspace's initial state
+    return init_test_stats(c->proj, out8, c->stream);
+}
 
 // the persistent KeyFrame members of a KeyFrameDatabase (mode 0: mnRelocQuery / mnRelocWords /
 // mRelocScore, mode 1: the mnPlaceRecognition* ones), max_kf entries each, after a stream sync

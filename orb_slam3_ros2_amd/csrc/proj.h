@@ -34,4 +34,8 @@ void launch_predict_scale_sweep(uint32_t lo_bits, uint32_t hi_bits, float log_sf
 // SearchForInitialization (init_kernels.hip), on the same workspace (proj_ws.h)
 int init_search(ProjWorkspace* ws, const orbhip_init_frame* F1, const orbhip_init_frame* F2, float* prev_matched,
                 int window_size, float nnratio, int check_orientation, int32_t* matches12, hipStream_t st);
+// test hooks (orbhip_test_init_route: a call's envelope from its sizes, host only;
+// orbhip_test_init_stats: the route of the last init_search on the workspace)
+int init_test_route(int n1, int n2, int nq0, int nr0, int32_t* out4);
+int init_test_stats(ProjWorkspace* ws, int32_t* out8, hipStream_t st);
 }  // namespace orbhip

@@ -246,6 +246,30 @@ def proj_stats(ctx) -> dict:
     return {"form": out[0], "rounds": out[1], "entries": out[2], "ent_cap": out[3]}
 
 
+def init_route(n1: int, n2: int, nq0: int, nr0: int) -> dict:
+    """SearchForInitialization's envelope for a call's sizes (the function init_search follows): rc =
+    the return code the sizes earn (0, -1 ORBHIP_ERR_ARG, -5 ORBHIP_ERR_UNSUPPORTED), lds = the
+    chain's dynamic LDS bytes, list_cap = entries per query list, cap = parallel rounds at most."""
+    import ctypes
+    from orb_slam3_ros2_amd._lib import lib
+    out = (ctypes.c_int32 * 4)()
+    assert lib().orbhip_test_init_route(n1, n2, nq0, nr0, out) == 0
+    return {"rc": out[0], "lds": out[1], "list_cap": out[2], "cap": out[3]}
+
+
+def init_stats(ctx) -> dict:
+    """The last SearchForInitialization on this context: form 0 = the rounds converged, 1 = the chain
+    after a claim-slot overflow, 2 = the chain after the round cap, 3 = the chain by ORBHIP_INIT_CHAIN,
+    -1 = none yet / no queries / an error; round = the round that changed nothing (else the rounds
+    run); init_ahead after the call; the octave-0 counts; the queries with need == 1 and need == 2."""
+    import ctypes
+    from orb_slam3_ros2_amd._lib import lib
+    out = (ctypes.c_int32 * 8)()
+    assert lib().orbhip_test_init_stats(ctx.handle, out) == 0
+    return {"form": out[0], "round": out[1], "init_ahead": out[2], "nq0": out[3], "nr0": out[4], "need1": out[5],
+            "need2": out[6]}
+
+
 class PlantedSet:
     """q (nq, 32) / qa (nq,), t (nt, 32) / ta (nt,); per query: train (the train it was planted
     from, -1 = random query), bin (its rotation bin), flips (its distance to that train)."""
