@@ -219,6 +219,8 @@ def lib():
     # the stereo kernels alone on caller-supplied keypoints (tests compare them with the restatement)
     L.orbhip_test_stereo_match.argtypes = [vp, vp, vp, i32, i32, sp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp,
                                            ctypes.POINTER(i32)]
+    # k_stereo_median alone on caller-supplied status / SAD arrays
+    L.orbhip_test_stereo_median.argtypes = [vp, vp, vp, vp, vp, i32, ctypes.POINTER(i32)]
     L.orbhip_descriptor_distance.argtypes = [vp, vp]
     L.orbhip_match_bf.argtypes = [vp, vp, vp, i32, vp, vp, i32, i32, f32, i32, vp, vp, vp]
     L.orbhip_match_pairs_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, vp, vp, vp, vp]

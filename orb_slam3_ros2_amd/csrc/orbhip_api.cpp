@@ -958,6 +958,15 @@ int orbhip_test_stereo_match(orbhip_ctx* c, const uint8_t* left, const uint8_t* 
                              depth, status, best_r, sad, n_stereo);
 }
 
+// k_stereo_median alone on one pair's n entries: status (1 = accepted) with u_right and depth are
+// updated in place by the median cut, n_stereo is the number left at 1.
+int orbhip_test_stereo_median(orbhip_ctx* c, int32_t* status, const int32_t* sad, float* u_right, float* depth, int n,
+                              int* n_stereo) {
+    if (!c || n < 0 || !n_stereo || (n > 0 && (!status || !sad || !u_right || !depth))) return ORBHIP_ERR_ARG;
+    HIPOK(hipSetDevice(c->device));
+    return stereo_test_median(status, sad, u_right, depth, n, n_stereo);
+}
+
 int orbhip_test_candidates(orbhip_ctx* c, int w, int h, int frame, int64_t* n) {
     if (!c || !n || frame < 0) return ORBHIP_ERR_ARG;
     HIPOK(hipSetDevice(c->device));

@@ -1,4 +1,4 @@
-// The stereo stage, host side (stereo.h): the device form, the host-image form and the test hook.
+// The stereo stage, host side (stereo.h): the device form, the host-image form and the test hooks.
 // Each runs behind an extraction (or a pyramid stage) of the same call and on the same stream, and
 // reads the pyramids where that left them.
 #include "stereo.h"
@@ -154,6 +154,45 @@ int stereo_test_match(ExtractWorkspace* ws, const uint8_t* left, const uint8_t* 
     }
     HIPOK(hipMemcpyAsync(n_stereo, s.n_stereo, sizeof(int), hipMemcpyDeviceToHost, st));
     HIPOK(hipStreamSynchronize(st));
+    return ORBHIP_OK;
+}
+
+int stereo_test_median(int32_t* status, const int32_t* sad, float* u_right, float* depth, int n, int* n_stereo) {
+    if (n < 0 || n > kStereoMaxKp) return ORBHIP_ERR_ARG;
+    const int cap = std::max(n, 1);
+    const size_t bytes = (size_t)n * 4;
+    Tmp d_status, d_sad, d_u, d_depth, d_n, d_nst;
+    HIPOK(d_status.alloc((size_t)cap * 4));
+    HIPOK(d_sad.alloc((size_t)cap * 4));
+    HIPOK(d_u.alloc((size_t)cap * 4));
+    HIPOK(d_depth.alloc((size_t)cap * 4));
+    HIPOK(d_n.alloc(2 * sizeof(int32_t)));
+    HIPOK(d_nst.alloc(sizeof(int32_t)));
+    const int32_t nn[2] = {n, 0};
+    HIPOK(hipMemcpy(d_n.p, nn, sizeof(nn), hipMemcpyHostToDevice));
+    HIPOK(hipMemset(d_nst.p, 0xFF, sizeof(int32_t)));   // the kernel must write it, also with n == 0
+    if (n) {
+        HIPOK(hipMemcpy(d_status.p, status, bytes, hipMemcpyHostToDevice));
+        HIPOK(hipMemcpy(d_sad.p, sad, bytes, hipMemcpyHostToDevice));
+        HIPOK(hipMemcpy(d_u.p, u_right, bytes, hipMemcpyHostToDevice));
+        HIPOK(hipMemcpy(d_depth.p, depth, bytes, hipMemcpyHostToDevice));
+    }
+    StereoArgs a{};
+    a.cap = cap;
+    a.P = 1;
+    a.n = (const int32_t*)d_n.p;
+    a.status = (int32_t*)d_status.p; a.sad = (int32_t*)d_sad.p;
+    a.u_right = (float*)d_u.p; a.depth = (float*)d_depth.p; a.n_stereo = (int32_t*)d_nst.p;
+    (void)hipGetLastError();
+    launch_stereo_median(a, nullptr);
+    HIPOK(hipGetLastError());
+    HIPOK(hipDeviceSynchronize());
+    if (n) {
+        HIPOK(hipMemcpy(status, d_status.p, bytes, hipMemcpyDeviceToHost));
+        HIPOK(hipMemcpy(u_right, d_u.p, bytes, hipMemcpyDeviceToHost));
+        HIPOK(hipMemcpy(depth, d_depth.p, bytes, hipMemcpyDeviceToHost));
+    }
+    HIPOK(hipMemcpy(n_stereo, d_nst.p, sizeof(int), hipMemcpyDeviceToHost));
     return ORBHIP_OK;
 }
 

@@ -34,6 +34,8 @@ struct StereoArgs {
     int32_t* best_r;             // nullable (test hook)
 };
 void launch_stereo(const StereoArgs& a, hipStream_t st);
+// k_stereo_median alone (test hook): reads n, status and sad, writes status, u_right, depth, n_stereo
+void launch_stereo_median(const StereoArgs& a, hipStream_t st);
 
 struct ExtractWorkspace;
 int stereo_device(ExtractWorkspace* ws, const uint8_t* d_imgs, int P, int w, int h, int stride, int64_t fstride,
@@ -48,5 +50,8 @@ int stereo_test_match(ExtractWorkspace* ws, const uint8_t* left, const uint8_t* 
                       const orbhip_stereo_params& prm, const orbhip_kp* kps_l, const uint8_t* desc_l, int n_l,
                       const orbhip_kp* kps_r, const uint8_t* desc_r, int n_r, float* u_right, float* depth,
                       int32_t* status, int32_t* best_r, int32_t* sad, int* n_stereo);
+// test hook: k_stereo_median alone on one pair's n caller-supplied entries (status, u_right and depth
+// in place; device arrays of its own, the null stream)
+int stereo_test_median(int32_t* status, const int32_t* sad, float* u_right, float* depth, int n, int* n_stereo);
 
 }  // namespace orbhip

@@ -254,4 +254,9 @@ void launch_stereo(const StereoArgs& a, hipStream_t st) {
     hipLaunchKernelGGL(k_stereo_median, dim3(a.P), dim3(1024), 0, st, a);
 }
 
+void launch_stereo_median(const StereoArgs& a, hipStream_t st) {
+    if (a.P <= 0 || a.cap <= 0) return;
+    hipLaunchKernelGGL(k_stereo_median, dim3(a.P), dim3(1024), 0, st, a);
+}
+
 }  // namespace orbhip

@@ -99,3 +99,17 @@ def stereo_match_raw(ctx, left, right, kps_l, desc_l, kps_r, desc_r, bf, b, cent
                                          n, ptr(kr), ptr(dr), len(kr), ptr(u), ptr(z), ptr(st), ptr(br), ptr(sad),
                                          ctypes.byref(ns)), "orbhip_test_stereo_match")
     return u, z, st, br, sad, ns.value
+
+
+def stereo_median_raw(ctx, status, sad, u_right, depth):
+    """Test hook (orbhip_test_stereo_median): the median-cut kernel alone on one pair's entries.
+    -> (status, u_right, depth, n_stereo), the three arrays as the kernel left them."""
+    st = np.array(status, np.int32)
+    sd = np.ascontiguousarray(sad, np.int32)
+    u, z = np.array(u_right, np.float32), np.array(depth, np.float32)
+    n = len(st)
+    assert len(sd) == n and len(u) == n and len(z) == n
+    ns = ctypes.c_int(0)
+    check(lib().orbhip_test_stereo_median(ctx.handle, ptr(st), ptr(sd), ptr(u), ptr(z), n, ctypes.byref(ns)),
+          "orbhip_test_stereo_median")
+    return st, u, z, ns.value

@@ -16,6 +16,7 @@ TH_HIGH, TH_LOW = 100, 50
 TH_ORB_DIST = (TH_HIGH + TH_LOW) // 2   # 75
 W, L = 5, 5
 INT_MAX = 2 ** 31 - 1
+NO_INC = -99
 _POP = np.array([bin(i).count("1") for i in range(256)], np.int64)
 
 ST_OK, ST_NO_ROW, ST_ORB_DIST, ST_INI_END, ST_AT_END, ST_DELTA, ST_DISPARITY, ST_MEDIAN, ST_GUARD = range(1, 10)
@@ -74,7 +75,10 @@ class StereoResult:
 
 def compute_stereo_matches(kps_l, desc_l, kps_r, desc_r, pyr_l, pyr_r, scale, inv_scale, bf, b, center_patch=0):
     """-> StereoResult with u_right, depth (float32), status, best_r, sad (int32), n_stereo and
-    `events`, the counts of the rare branches (tests assert that their scenes reach them)."""
+    `events`, the counts of the rare branches (tests assert that their scenes reach them). For the
+    planted scenes of tests/stereo_cases.py also, per left keypoint: best_dist (TH_HIGH where no
+    candidate is below it), n_tied (candidates at the best distance), best_inc (NO_INC where no SAD
+    was formed), sub (the disparity <= 0 substitution was made) and sul / svl / sur0."""
     nl, nr = len(kps_l), len(kps_r)
     nlev = len(scale)
     rows = pyr_l[0].shape[0]
@@ -89,6 +93,11 @@ def compute_stereo_matches(kps_l, desc_l, kps_r, desc_r, pyr_l, pyr_r, scale, in
     best_r = np.full(nl, -1, np.int32)
     sad = np.full(nl, -1, np.int32)
     events = dict(hamming_tie=0, sad_tie=0, disparity_sub=0, max_abs_delta=0.0)
+    best_dists = np.full(nl, TH_HIGH, np.int32)
+    n_tied = np.zeros(nl, np.int32)
+    best_incs = np.full(nl, NO_INC, np.int32)
+    sub = np.zeros(nl, bool)
+    scaled = np.full((nl, 3), -1, np.int64)
 
     # the row table: right keypoint iR is a candidate of every row in [lo, hi]
     oct_r = np.asarray(kps_r["octave"], np.int64) if nr else np.zeros(0, np.int64)
@@ -122,15 +131,18 @@ def compute_stereo_matches(kps_l, desc_l, kps_r, desc_r, pyr_l, pyr_r, scale, in
             k = int(np.argmin(d))   # the first minimum: ascending iR, strict <
             if d[k] < TH_HIGH:
                 best_dist, best_idx = int(d[k]), int(idx[k])
+                n_tied[il] = (d == d[k]).sum()
                 if (d == d[k]).sum() > 1:
                     events["hamming_tie"] += 1
         best_r[il] = best_idx
+        best_dists[il] = best_dist
         if best_dist >= TH_ORB_DIST:
             status[il] = ST_ORB_DIST
             continue
         ur0 = xr[best_idx]
         inv = inv_scale[lev]
         sul, svl, sur0 = std_round(ul * inv), std_round(vl * inv), std_round(ur0 * inv)
+        scaled[il] = sul, svl, sur0
         lev_l, lev_r = pyr_l[lev], pyr_r[lev]
         h, w = lev_l.shape
         iniu = sur0 + L - W
@@ -147,6 +159,7 @@ def compute_stereo_matches(kps_l, desc_l, kps_r, desc_r, pyr_l, pyr_r, scale, in
             events["sad_tie"] += 1
         best_inc = kb - L
         sad[il] = dists[kb]
+        best_incs[il] = best_inc
         if best_inc == -L or best_inc == L:
             status[il] = ST_AT_END
             continue
@@ -165,6 +178,7 @@ def compute_stereo_matches(kps_l, desc_l, kps_r, desc_r, pyr_l, pyr_r, scale, in
             disparity = f32(0.01)
             best_ur = f32(np.float64(ul) - 0.01)
             events["disparity_sub"] += 1
+            sub[il] = True
         depth[il] = bf / disparity
         u_right[il] = best_ur
         status[il] = ST_OK
@@ -178,6 +192,7 @@ def compute_stereo_matches(kps_l, desc_l, kps_r, desc_r, pyr_l, pyr_r, scale, in
     res.u_right, res.depth, res.status, res.best_r, res.sad = u_right, depth, status, best_r, sad
     res.n_stereo = int((status == ST_OK).sum())
     res.events = events
+    res.best_dist, res.n_tied, res.best_inc, res.sub, res.scaled = best_dists, n_tied, best_incs, sub, scaled
     return res
 
 
@@ -304,3 +319,18 @@ def restate(s, center_patch=0):
         s[key] = compute_stereo_matches(s["kps_l"], s["desc_l"], s["kps_r"], s["desc_r"], s["pyr_l"], s["pyr_r"],
                                         s["scale"], s["inv_scale"], s["bf"], s["b"], center_patch)
     return s[key]
+
+
+# ---------------------------------------------------------------------------
+# comparisons shared by the GPU tests (test_stereo_gpu.py, test_stereo_cases_gpu.py)
+# ---------------------------------------------------------------------------
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def assert_outputs(u, z, st, e, what=""):
+    bad = np.flatnonzero(st != e.status)
+    assert bad.size == 0, f"{what}: status differs at {bad[:8].tolist()}: gpu {st[bad[:8]].tolist()} " \
+                          f"restatement {e.status[bad[:8]].tolist()}"
+    assert np.array_equal(bits(u), bits(e.u_right)), what
+    assert np.array_equal(bits(z), bits(e.depth)), what

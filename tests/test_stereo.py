@@ -10,6 +10,7 @@ import pytest
 from orb_slam3_ros2_amd.synthetic import synthetic_frame, synthetic_stereo_pair
 
 import stereo_numpy as S
+from stereo_cases import upstream_median_loop
 
 f32 = np.float32
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "stereo_320x240_s5.npz")
@@ -88,20 +89,13 @@ def test_sad_equals_a_plain_double_loop(oracle, cp):
 
 def test_median_cut_equals_upstreams_loop():
     """Upstream sorts (SAD, iL), takes sorted[size / 2].first and walks back from the end until the
-    first SAD below thDist."""
+    first SAD below thDist (stereo_cases.upstream_median_loop, shared with test_stereo_cases.py)."""
     rng = np.random.default_rng(11)
     for n in (1, 2, 3, 10, 101, 500):
         for hi in (3, 40, 60000):
             sads = rng.integers(0, hi, size=n + 5)
             acc = np.sort(rng.choice(n + 5, size=n, replace=False))
-            v = sorted((int(sads[i]), int(i)) for i in acc)
-            th = f32(f32(1.5) * f32(1.4)) * f32(v[len(v) // 2][0])
-            cut = []
-            for k in range(len(v) - 1, -1, -1):
-                if f32(v[k][0]) < th:
-                    break
-                cut.append(v[k][1])
-            assert sorted(S.median_cut(sads, acc)) == sorted(cut)
+            assert sorted(S.median_cut(sads, acc)) == sorted(upstream_median_loop(sads, acc))
     assert S.median_cut(np.zeros(4, int), []) == []
     assert S.median_cut(np.array([7]), [0]) == []          # alone: 7 < 2.1 * 7
     assert S.median_cut(np.array([0]), [0]) == [0]         # alone with SAD 0: 0 >= 0

@@ -11,6 +11,7 @@ from orb_slam3_ros2_amd.stereo import extract_stereo_device, stereo_frame, stere
 from orb_slam3_ros2_amd.synthetic import synthetic_frame, synthetic_stereo_pair
 
 import stereo_numpy as S
+from stereo_numpy import assert_outputs, bits
 
 pytestmark = pytest.mark.gpu
 CP = pytest.mark.parametrize("cp", [0, 1])
@@ -23,20 +24,8 @@ def ext():
     return ORBextractor(o["nfeatures"], o["scale_factor"], o["nlevels"], o["ini_th"], o["min_th"])
 
 
-def bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
 def same_kps(a, b):
     return len(a) == len(b) and all(np.array_equal(a[f], b[f]) for f in KP_DTYPE.names)
-
-
-def assert_outputs(u, z, st, e, what=""):
-    bad = np.flatnonzero(st != e.status)
-    assert bad.size == 0, f"{what}: status differs at {bad[:8].tolist()}: gpu {st[bad[:8]].tolist()} " \
-                          f"restatement {e.status[bad[:8]].tolist()}"
-    assert np.array_equal(bits(u), bits(e.u_right)), what
-    assert np.array_equal(bits(z), bits(e.depth)), what
 
 
 def raw(ext, s, cp, left_idx=None, right_idx=None):
