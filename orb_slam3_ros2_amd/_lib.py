@@ -327,6 +327,10 @@ def lib():
     L.orbhip_test_predict_scale_sweep.restype = ctypes.c_int64
     # host only: the steps the device compares a ratio against (one per level, from the host's log)
     L.orbhip_test_level_thresholds.argtypes = [f32, i32, vp]
+    # one host frame's intermediates (pyramid levels 1.., candidates per cell, kept keypoints per level,
+    # the device error word) and a plan's cell table: tests compare every stage with the oracle
+    L.orbhip_test_extract_debug.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
+    L.orbhip_test_cells.argtypes = [vp, i32, i32, vp, i32]
     _lib = L
     return L
 

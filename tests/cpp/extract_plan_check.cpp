@@ -2,6 +2,7 @@
 // frame sizes, ORB parameters and plan switches, checks the invariants the kernels rely on and
 // prints the ORBextractor ctor tables per shape. Exits non-zero on any violation.
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -20,6 +21,9 @@ static char g_what[256];
 
 // last_h: rows of the last level (ComputePyramid's rounding), checked for every shape
 struct Shape { int w, h, L; float sf; int nfeat; bool ok; int last_h; };
+// the largest nfeatures that plans at 320x240, 8 levels, 1.2 (tests/test_extract_cases.py finds the
+// same value by bisection over this program's "plan" mode)
+constexpr int kNStar = 6158;
 static const Shape kShapes[] = {
     // 67 rows is the smallest last level that plans: its cell area (rows 16 .. h - 16) holds one
     // 35-px cell row from 67 rows on (ComputeKeyPointsOctTree's nRows = (h - 32) / 35)
@@ -34,6 +38,27 @@ static const Shape kShapes[] = {
     {320, 240, 1, 1.2f, 1000, true, 240},  {320, 240, 2, 1.2f, 1000, true, 200},
     {320, 240, 3, 1.2f, 1000, true, 167},  {320, 240, 4, 1.2f, 1000, true, 139},
     {641, 481, 5, 1.5f, 1000, true, 95},  {1001, 751, 3, 2.5f, 1000, true, 120},   // the per-row resize path
+    // The envelope catalogue of tests/extract_cases.py (the kernels run at these shapes on the GPU).
+    // One level: 67x67 is the smallest frame that plans (one 35x35 cell, one root), 101x101 the
+    // largest single cell (69x69, window 75), 102x102 the first 2x2 grid, 136x101 two roots.
+    {67, 67, 1, 1.2f, 100, true, 67},  {101, 101, 1, 1.2f, 200, true, 101},  {102, 102, 1, 1.2f, 200, true, 102},
+    {136, 101, 1, 1.2f, 200, true, 101},
+    // box 101x68 (ratio 1.485, one root) against box 102x68 (ratio 1.5, two): std::round in n_ini
+    {133, 100, 1, 1.2f, 100, true, 100},  {134, 100, 1, 1.2f, 100, true, 100},
+    {240, 240, 8, 1.2f, 1000, true, 67},   // the smallest square 8-level frame
+    // strips: one cell row per level; 32 roots; 61 roots and a 4068-px box, next to both limits
+    {1000, 100, 2, 1.2f, 500, true, 83},  {2200, 100, 1, 1.2f, 500, true, 100},  {4100, 99, 1, 1.2f, 500, true, 99},
+    {640, 480, 8, 1.2f, 1, true, 134},  {640, 480, 8, 1.2f, 7, true, 134},   // levels with a quota of 0
+    {320, 240, 8, 1.2f, 7, true, 67},                                         // ... and two roots
+    // the octree's LDS budget bounds nfeatures at 320x240: kNStar is the largest that plans
+    {320, 240, 8, 1.2f, 5000, true, 67},  {320, 240, 8, 1.2f, kNStar, true, 67},
+    {320, 240, 8, 1.2f, kNStar + 1, false, 67},  {320, 240, 8, 1.2f, 20000, false, 67},
+    {640, 480, 9, 1.2f, 1000, true, 112},  {640, 480, 12, 1.1f, 1000, true, 168},   // more than 8 levels
+    {1920, 1080, 8, 1.2f, 2000, true, 301},
+    // rejected: no cell row / column; a portrait strip whose root count rounds to 0; past the root
+    // and box limits
+    {66, 67, 1, 1.2f, 100, false, 67},  {67, 66, 1, 1.2f, 100, false, 66},  {100, 1000, 1, 1.2f, 100, false, 1000},
+    {4400, 99, 1, 1.2f, 500, false, 99},
 };
 static const PlanSwitches kDefault = {10, 32, 0, -1, -1};
 
@@ -239,7 +264,36 @@ static void print_levels(int w, int h, int nfeat, float sf, int L) {
     std::printf("\n");
 }
 
-int main() {
+// "plan w h nlevels scale nfeatures": one shape at the default switches. Prints "plan rc" and, when it
+// plans, per level "level l w h n_cols n_rows w_cell h_cell n_cells n_ini n_feat kp_cap", the cell
+// table as "cell level x0 y0 wc hc slots", and "octree node_cap sort_cap key_cap lds_bytes".
+static int print_plan(int w, int h, int L, float sf, int nfeat) {
+    const orbhip_orb_params prm = {nfeat, sf, L, 20, 7};
+    HostPlan hp;
+    const int rc = L < 1 || L > kMaxLevels ? ORBHIP_ERR_ARG : plan_build_host(prm, build_orb_tables(prm), w, h, kDefault, hp);
+    std::printf("plan %d\n", rc);
+    if (rc != ORBHIP_OK) return 0;
+    std::snprintf(g_what, sizeof(g_what), "%dx%d L%d sf%g nfeat%d", w, h, L, sf, nfeat);
+    check_plan(hp, kDefault);
+    for (int l = 0; l < L; l++) {
+        const LevelGeom& G = hp.h.lv[l];
+        std::printf("level %d %d %d %d %d %d %d %d %d %d %d\n", l, G.w, G.h, G.n_cols, G.n_rows, G.w_cell, G.h_cell,
+                    G.n_cells, G.n_ini, G.n_feat, G.kp_cap);
+    }
+    for (size_t i = 0; i < hp.cells.size(); i++) {
+        const CellGeom& c = hp.cells[i];
+        const int next = i + 1 < hp.cells.size() ? hp.cells[i + 1].slot_off : hp.h.n_slots_total;
+        std::printf("cell %d %d %d %d %d %d\n", c.level, c.x0, c.y0, c.wc, c.hc, next - c.slot_off);
+    }
+    std::printf("octree %d %d %d %zu\n", hp.oct.node_cap, hp.oct.sort_cap, hp.oct.key_cap,
+                octree_lds_bytes(hp.h, hp.oct));
+    return g_fail ? 1 : 0;
+}
+
+int main(int argc, char** argv) {
+    if (argc == 7 && std::strcmp(argv[1], "plan") == 0)
+        return print_plan(std::atoi(argv[2]), std::atoi(argv[3]), std::atoi(argv[4]), (float)std::atof(argv[5]),
+                          std::atoi(argv[6]));
     std::vector<PlanSwitches> sws = {kDefault};
     auto vary = [&](int PlanSwitches::*m, std::initializer_list<int> vals) {
         for (int v : vals) {

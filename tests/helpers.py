@@ -2,7 +2,8 @@
 the dense-solver tests (SPD test matrices, a long-double reference solve, the backward error);
 the BA result comparison against the oracle; the brute-force matcher's route hook and data sets
 with matches planted by construction; device frame layouts (padded rows, offset base pointers, odd
-strides inside a poisoned buffer) for the extraction tests."""
+strides inside a poisoned buffer) for the extraction tests; the stage-by-stage comparison of one
+frame's extraction (pyramid, FAST candidates, kept keypoints, error word) with the oracle."""
 import numpy as np
 
 from orb_slam3_ros2_amd._lib import KP_DTYPE
@@ -453,3 +454,129 @@ def assert_frames_equal_oracle(got: list, want: list, what="") -> None:
                 and np.array_equal(gd, od))
         assert same, f"{what} frame {f}: n gpu={n} monoIndex gpu={mono} oracle={omono}\n" + diff_report(gk, gd, ok, od)
         assert n > 0, f"{what} frame {f}: no keypoints"
+
+
+# ---- extraction stage by stage: the device's intermediates of one host frame against the oracle's ----
+
+LEVEL_KP_DTYPE = np.dtype([("x", np.int16), ("y", np.int16), ("srl", np.uint32)])   # orbhip_plan.h LevelKp
+
+
+def extract_debug(ext, img, lap=(0, 1000)) -> dict:
+    """orbhip_test_extract_debug + orbhip_test_cells on one host frame (the host-frame path with the
+    context's plan): pyr = levels 1.. as [h, w] arrays, cand = packed candidates by slot, ccnt = per
+    cell, cells = (level, x0, y0, wc, hc, slot_off) rows, lvl = LevelKp slots, lcnt / lnlap per
+    level, sizes = (n_slots_total, n_cells_total, kp_slots_total, device error word)."""
+    from orb_slam3_ros2_amd._lib import lib, ptr
+    L = lib()
+    img = np.ascontiguousarray(img, np.uint8)
+    h, w = img.shape
+    nl = ext.nlevels
+    info = ext.level_info(w, h)
+    sizes = np.zeros(4, np.int32)
+    rc = L.orbhip_test_extract_debug(ext.ctx.handle, ptr(img), w, h, int(lap[0]), int(lap[1]), None, None, None,
+                                     None, None, None, ptr(sizes))
+    assert rc == 0, f"orbhip_test_extract_debug (size query): {rc}"
+    dims = [(int(info["h"][l]), int(info["w"][l])) for l in range(nl)]
+    pyr = np.zeros(max(sum(a * b for a, b in dims[1:]), 1), np.uint8)   # never a null pointer: null = size query
+    cand = np.zeros(max(int(sizes[0]), 1), np.uint32)
+    ccnt = np.zeros(max(int(sizes[1]), 1), np.int32)
+    lvl = np.zeros(max(int(sizes[2]), 1), LEVEL_KP_DTYPE)
+    lcnt = np.zeros(nl, np.int32)
+    lnlap = np.zeros(nl, np.int32)
+    rc = L.orbhip_test_extract_debug(ext.ctx.handle, ptr(img), w, h, int(lap[0]), int(lap[1]), ptr(pyr), ptr(cand),
+                                     ptr(ccnt), ptr(lvl), ptr(lcnt), ptr(lnlap), ptr(sizes))
+    assert rc == 0, f"orbhip_test_extract_debug: {rc}"
+    cells = np.zeros((max(int(sizes[1]), 1), 6), np.int32)
+    assert L.orbhip_test_cells(ext.ctx.handle, w, h, ptr(cells), int(sizes[1])) == int(sizes[1])
+    levels, off = [], 0
+    for a, b in dims[1:]:
+        levels.append(pyr[off: off + a * b].reshape(a, b))
+        off += a * b
+    return dict(pyr=levels, cand=cand[: sizes[0]], ccnt=ccnt[: sizes[1]], cells=cells[: sizes[1]], lvl=lvl[: sizes[2]],
+                lcnt=lcnt, lnlap=lnlap, sizes=sizes, info=info)
+
+
+def _multiset_diff(got, want, what, names):
+    """got / want: integer arrays [n, k]. Equal as multisets, else an AssertionError naming `what`, both
+    sizes and up to five entries that only one side has."""
+    from collections import Counter
+    g = got[np.lexsort(got.T[::-1])] if len(got) else got
+    o = want[np.lexsort(want.T[::-1])] if len(want) else want
+    if g.shape == o.shape and np.array_equal(g, o):
+        return
+    cg, co = Counter(map(tuple, got.tolist())), Counter(map(tuple, want.tolist()))
+    only_g = sorted((cg - co).elements())[:5]
+    only_o = sorted((co - cg).elements())[:5]
+    raise AssertionError(f"{what}: gpu {len(got)} oracle {len(want)} {names}; only on the gpu {only_g}; "
+                         f"only in the oracle {only_o}")
+
+
+def compare_extract_stages(ext, oracle, img, lap=(0, 1000), what="") -> dict:
+    """Every stage of one host frame on the device against the oracle, exactly, in pipeline order; the
+    first stage and level that differ are named, with up to five differing entries.
+
+    pyramid      levels 1 .. L - 1 byte for byte against oracle.pyramid.
+    candidates   per level the multiset of (x, y, score) and its size against oracle.extract_levels'
+                 cand list. Both sides count x and y from the border box's origin (16, 16) of the
+                 level: the device packs cg.x0 + 3 + px - G.min_bx (k_fast_cells, at pack_cand), the
+                 oracle returns fast16's window position plus the cell's offset j * wCell, before
+                 minBorderX is added (vToDistributeKeys). A cell's run is cand[slot_off : slot_off + ccnt]
+                 from the orbhip_test_cells table; it must fit the cell's slot range.
+    kept         per level lvl_cnt LevelKp entries (x, y, score byte) against the kept list, as a
+                 multiset and in number. Both sides are level pixels: the device writes cand_x + min_bx
+                 (k_octree's output loop), the oracle adds minBorderX after DistributeOctTree. A level's
+                 slots start at the sum of the kp_cap = n_feat + 3 + 4 * nIni of the levels before it,
+                 nIni = round(box_w / box_h) as in DistributeOctTree; the caps must add up to
+                 kp_slots_total. The lapping flags' number per level is the oracle's as well.
+    error word   sizes[3] == 0.
+    Nothing is left out: every level, every cell, no tolerance. Returns the device's stages."""
+    img = np.ascontiguousarray(img, np.uint8)
+    h, w = img.shape
+    nl = ext.nlevels
+    d = extract_debug(ext, img, lap)
+    tag = f"{what} {w}x{h}".strip()
+    err = int(d["sizes"][3])
+    opyr = oracle.pyramid(img, ext.scaleFactor, nl)
+    for l in range(1, nl):
+        g, o = d["pyr"][l - 1], opyr[l]
+        assert g.shape == o.shape, f"{tag}: stage pyramid level {l}: size gpu {g.shape} oracle {o.shape} (err {err})"
+        if not np.array_equal(g, o):
+            ys, xs = np.nonzero(g != o)
+            first = [(int(x), int(y), int(g[y, x]), int(o[y, x])) for y, x in zip(ys[:5], xs[:5])]
+            raise AssertionError(f"{tag}: stage pyramid level {l}: {len(ys)} bytes differ, first (x, y, gpu, oracle) "
+                                 f"{first} (err {err})")
+    ocand, okept = oracle.extract_levels(img, ext.nfeatures, ext.scaleFactor, nl, ext.iniThFAST, ext.minThFAST)
+    cells, ccnt, cand = d["cells"], d["ccnt"], d["cand"]
+    ends = np.append(cells[1:, 5], d["sizes"][0]) if len(cells) else np.zeros(0, np.int32)
+    for l in range(nl):
+        runs = []
+        for ci in np.flatnonzero(cells[:, 0] == l):
+            n, lo, hi = int(ccnt[ci]), int(cells[ci, 5]), int(ends[ci])
+            assert 0 <= n <= hi - lo, f"{tag}: stage candidates level {l}: cell {ci} holds {n} in {hi - lo} slots (err {err})"
+            runs.append(cand[lo: lo + n])
+        packed = np.concatenate(runs) if runs else np.zeros(0, np.uint32)
+        got = np.stack([packed & 0xFFF, (packed >> 12) & 0xFFF, packed >> 24], axis=1).astype(np.int64)
+        want = ocand[l][:, [0, 1, 4]].astype(np.int64)
+        assert np.array_equal(want, ocand[l][:, [0, 1, 4]]), "the oracle's candidates are integers"
+        _multiset_diff(got, want, f"{tag}: stage candidates level {l} (err {err})", "(x, y, score) from the box origin")
+    f32 = np.float32
+    base, scales = 0, d["info"]["scales"]
+    for l in range(nl):
+        lw, lh = int(d["info"]["w"][l]), int(d["info"]["h"][l])
+        n_ini = c_round(f32(lw - 32) / f32(lh - 32))
+        cap = int(d["info"]["feats"][l]) + 3 + 4 * n_ini
+        n = int(d["lcnt"][l])
+        assert 0 <= n <= cap, f"{tag}: stage kept level {l}: count {n} beyond the level's {cap} slots (err {err})"
+        rec = d["lvl"][base: base + n]
+        got = np.stack([rec["x"], rec["y"], rec["srl"] & 0xFF], axis=1).astype(np.int64)
+        want = okept[l][:, [0, 1, 4]].astype(np.int64)
+        _multiset_diff(got, want, f"{tag}: stage kept level {l} (err {err})", "(x, y, score) in level pixels")
+        xs = okept[l][:, 0] if l == 0 else okept[l][:, 0] * scales[l]
+        onlap = int(np.count_nonzero((xs >= f32(lap[0])) & (xs <= f32(lap[1]))))
+        glap = int(np.count_nonzero((rec["srl"] >> 8) & 1))
+        assert glap == onlap and int(d["lnlap"][l]) == onlap, \
+            f"{tag}: stage kept level {l}: lapping flags gpu {glap} / lvl_nlap {int(d['lnlap'][l])} oracle {onlap} (err {err})"
+        base += cap
+    assert base == int(d["sizes"][2]), f"{tag}: stage kept: level caps add up to {base}, kp_slots_total {int(d['sizes'][2])}"
+    assert err == 0, f"{tag}: stage error word: {err}"
+    return d

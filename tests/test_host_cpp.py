@@ -55,8 +55,8 @@ def test_extract_plan_invariants():
 
 def test_extract_plan_level_tables_match_oracle(oracle):
     """ORBextractor's constructor tables (level sizes, features per level, scale factors, umax) as
-    the planner computes them against the oracle's, exactly: every 8-level shape of the program,
-    and nfeatures = 1250 at 640x480 against the values pinned in test_oracle_kats.py."""
+    the planner computes them against the oracle's, exactly: every shape of the program, whatever
+    its level count, and nfeatures = 1250 at 640x480 against the values pinned in test_oracle_kats.py."""
     r = _run_plan_check()
     seen = {}
     for ln in r.stdout.splitlines():
@@ -66,8 +66,6 @@ def test_extract_plan_level_tables_match_oracle(oracle):
         w, h, nfeat, sf, nlev = int(head[0]), int(head[1]), int(head[2]), np.float32(head[3]), int(head[4])
         assert [len(c) for c in cols] == [nlev] * 4 + [16], ln
         seen[(w, h, nfeat, nlev)] = cols
-        if nlev != 8:
-            continue
         o = oracle.level_info(w, h, nfeat, float(sf), nlev)
         assert [int(v) for v in cols[0]] == o["w"].tolist(), ln
         assert [int(v) for v in cols[1]] == o["h"].tolist(), ln
@@ -75,7 +73,9 @@ def test_extract_plan_level_tables_match_oracle(oracle):
         assert np.array_equal(np.array(cols[3], np.float32), o["scales"]), ln
         assert [int(v) for v in cols[4]] == o["umax"].tolist(), ln
     for key in [(320, 240, 1000, 8), (641, 479, 1000, 8), (306, 230, 1000, 8), (306, 228, 1000, 8),
-                (316, 237, 1000, 8), (640, 480, 1250, 8)]:
+                (316, 237, 1000, 8), (640, 480, 1250, 8), (320, 240, 1000, 1), (641, 481, 1000, 5),
+                (1001, 751, 1000, 3), (67, 67, 100, 1), (1000, 100, 500, 2), (640, 480, 1000, 9),
+                (640, 480, 1000, 12), (4100, 99, 500, 1)]:
         assert key in seen, key
     c = seen[(640, 480, 1250, 8)]
     assert [int(v) for v in c[0]] == [640, 533, 444, 370, 309, 257, 214, 179]

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Run the GPU extractor on seeded frames and dump every intermediate to an .npz so a
-parity mismatch can be localised offline against the oracle (tools/compare_extract_debug.py).
+parity mismatch can be looked at offline. The comparison itself, stage by stage against the oracle,
+is tests/helpers.py::compare_extract_stages (tests/test_extract_cases_gpu.py runs it).
 
 Usage (GPU box): python tools/dump_extract_debug.py gpurun_out/extract_debug.npz
 """
