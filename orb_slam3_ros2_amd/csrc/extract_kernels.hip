@@ -447,26 +447,39 @@ __device__ __forceinline__ void pyr_cone_body(const ExtractPlan* __restrict__ P,
         return ConeRect{(int16_t)(d0 & 0xFFFF), (int16_t)(d0 >> 16), (int16_t)(d1 & 0xFFFF), (int16_t)(d1 >> 16),
                         (int16_t)(d2 & 0xFFFF), (int16_t)(d2 >> 16), (int16_t)(d3 & 0xFFFF), (int16_t)(d3 >> 16)};
     };
-    int boff[kMaxLevels], toff[kMaxLevels];
-    int tot = 0;
+    // every level's geometry the level loop needs, fetched here like the rects: lane 4l + k holds
+    // word k of level l (gw0: pyr_off low, pyr_off high, pitch, xmax; gw1: vend, rz_noclamp), and
+    // lane 4l the level's 1 / nw. Read from P->lv[l] inside the loop they were three scalar
+    // round trips and an IEEE divide sequence on the chain of each level, none depending on a pixel
+    constexpr int kGPyr = offsetof(LevelGeom, pyr_off) / 4, kGPitch = offsetof(LevelGeom, pitch) / 4,
+                  kGXmax = offsetof(LevelGeom, xmax) / 4, kGVend = offsetof(LevelGeom, vend) / 4,
+                  kGNoclamp = offsetof(LevelGeom, rz_noclamp) / 4;
+    const int gk = threadIdx.x & 3;
+    const int* gl = (const int*)&P->lv[(threadIdx.x >> 2) & (kMaxLevels - 1)];
+    const int gw0 = gl[gk == 0 ? kGPyr : (gk == 1 ? kGPyr + 1 : (gk == 2 ? kGPitch : kGXmax))];
+    const int gw1 = gl[(gk & 1) ? kGNoclamp : kGVend];
+    float linv = 1.0f / (float)((int)(int16_t)(rdw >> 16) - (int)(int16_t)(rdw & 0xFFFF));
+    uint8_t* pyr_f = fb.pyr + (int64_t)f * P->pyr_bytes;
+    // both held here, ahead of the staging round (left alone the compiler sinks them below the
+    // staging barrier, in front of the first level)
+    asm volatile("" : "+v"(linv), "+s"(pyr_f));
     // the source level s0 (0: the frame; s0 >= 1: a pyramid level written by k_resize) is staged
     // as aligned dwords: rows of P0 = round_up(width + 3, 4) bytes, the region starting at byte
     // sh0 of its row (sh0: the address misalignment, 0 on the byte path)
     const ConeRect Rs0 = rect(s0);
     const int P0 = (Rs0.nx1 - Rs0.nx0 + 6) & ~3;
+    // LDS bytes of level l's cone (the level loop keeps the running offsets in scalar registers)
+    auto cone_bytes = [&](const ConeRect& r, bool staged) {
+        return ((staged ? P0 : (r.nx1 - r.nx0)) * (r.ny1 - r.ny0) + 15) & ~15;
+    };
+    int tot = 0, ttot = 0;
     for (int l = s0; l < L; l++) {
         const ConeRect r = rect(l);
-        boff[l] = tot;
-        tot += ((l == s0 ? P0 : (r.nx1 - r.nx0)) * (r.ny1 - r.ny0) + 15) & ~15;
+        tot += cone_bytes(r, l == s0);
+        if (l > s0) ttot += 2 * (r.nx1 - r.nx0) + 3 * (r.ny1 - r.ny0);
     }
     int sh0 = 0;
     int* tab = (int*)(cone + tot);
-    int ttot = 0;
-    for (int l = s0 + 1; l < L; l++) {
-        toff[l] = ttot;
-        const ConeRect r = rect(l);
-        ttot += 2 * (r.nx1 - r.nx0) + 3 * (r.ny1 - r.ny0);
-    }
     // staged table entry i (LDS layout: per level l > s0, xofs[nw] | xalpha[nw] | (r0, r1, beta)[nh]):
     // the host's per-tile copy (r05: computing the tables in the kernel, bit-exact, cut the cone's
     // HBM bytes 2.44 -> 1.98 MB per 640x480 launch but took the launch 21 -> 35 us in the 16-camera
@@ -489,7 +502,7 @@ __device__ __forceinline__ void pyr_cone_body(const ExtractPlan* __restrict__ P,
         const int nwd = dw ? (nw + sh0 + 3) >> 2 : 0;   // dwords per row (<= P0 / 4)
         const int tot0 = dw ? nwd * nh : nw * nh;
         const float inv_n = 1.0f / (float)(dw ? nwd : nw);
-        uint8_t* lv0 = cone + boff[s0];
+        uint8_t* lv0 = cone;
         if (dw && tot0 <= 1024 && ttot <= 2 * 1024 && nt == 1024) {
             const uint32_t* s4 = (const uint32_t*)(src0 - sh0);
             const int p4 = in0.pitch >> 2;
@@ -542,51 +555,107 @@ __device__ __forceinline__ void pyr_cone_body(const ExtractPlan* __restrict__ P,
     }
     __syncthreads();
     TR_PHASE(0, 0)
+    const int wave0 = __builtin_amdgcn_readfirstlane(tid);   // the wave's lowest pixel index
+    ConeRect rp = Rs0;
+    int nwp = P0, bsrc = 0, bdst = cone_bytes(Rs0, true), toff = 0;   // LDS offsets: level l - 1, level l, l's tables
     for (int l = s0 + 1; l < L; l++) {
-        const LevelGeom& D = P->lv[l];
-        const ConeRect r = rect(l), rp = rect(l - 1);
-        const int nw = r.nx1 - r.nx0, nh = r.ny1 - r.ny0, nwp = l == s0 + 1 ? P0 : rp.nx1 - rp.nx0;
-        const int* t = tab + toff[l];
-        const uint8_t* src = cone + boff[l - 1] + (l == s0 + 1 ? sh0 : 0);
-        uint8_t* dst = fb.pyr + (int64_t)f * P->pyr_bytes + D.pyr_off;
-        const float inv_nw = 1.0f / (float)nw;
-        const bool noclamp = D.rz_noclamp != 0;
-        for (int i = tid; i < nw * nh; i += nt) {
-            const int yy = small_div(i, inv_nw), xx = i - yy * nw;
-            const int x = r.nx0 + xx, y = r.ny0 + yy;
-            const int sx = t[xx] - rp.nx0;
-            const uint8_t* S0 = src + (t[2 * nw + 3 * yy] - rp.ny0) * nwp;
-            const uint8_t* S1 = src + (t[2 * nw + 3 * yy + 1] - rp.ny0) * nwp;
-            int h0, h1;
-            if (x < D.xmax) {
-                const int aa = t[nw + xx];
-                const int a0 = (int)(short)(aa & 0xFFFF), a1 = (int)(short)(aa >> 16);
-                h0 = S0[sx] * a0 + S0[sx + 1] * a1;
-                h1 = S1[sx] * a0 + S1[sx + 1] * a1;
-            } else {
-                h0 = S0[sx] * 2048;
-                h1 = S1[sx] * 2048;
+        const ConeRect r = rect(l);
+        const int nw = r.nx1 - r.nx0, nh = r.ny1 - r.ny0, n = nw * nh;
+        const int* t = tab + toff;
+        const uint8_t* src = cone + bsrc + (l == s0 + 1 ? sh0 : 0);
+        uint8_t* out = cone + bdst;
+        const int pitch = __builtin_amdgcn_readlane(gw0, 4 * l + 2), xmax = __builtin_amdgcn_readlane(gw0, 4 * l + 3),
+                  vend = __builtin_amdgcn_readlane(gw1, 4 * l);
+        const bool noclamp = __builtin_amdgcn_readlane(gw1, 4 * l + 1) != 0;
+        uint8_t* dst = pyr_f + (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readlane(gw0, 4 * l + 1) << 32) |
+                                         (uint32_t)__builtin_amdgcn_readlane(gw0, 4 * l));
+        const float inv_nw = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, linv), 4 * l));
+        // U of the thread's pixels (i0 + u * nt) as one chain: every table word of the group, then
+        // every source byte, then the arithmetic, then the stores: two LDS round trips per group
+        // where a pixel-by-pixel loop waited out four per pixel. The loads are unconditional (the
+        // xalpha word exists for every column; past xmax the single tap is the pair (2048, 0) on
+        // the byte after it, inside the LDS block) and the forms are selects, so no branch
+        // separates them. Past the end a lane repeats pixel n - 1 and stores nothing
+        auto group = [&](auto UC, auto NC, int i0) {
+            constexpr int U = decltype(UC)::value;
+            constexpr bool kNoclamp = decltype(NC)::value;
+            int xx[U], yy[U], sx[U], aa[U], r0[U], r1[U], bb[U], p00[U], p01[U], p10[U], p11[U];
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const int i = min(i0 + u * nt, n - 1);
+                yy[u] = small_div(i, inv_nw);
+                xx[u] = i - yy[u] * nw;
+                const int* ty = t + 2 * nw + 3 * yy[u];
+                sx[u] = t[xx[u]];
+                aa[u] = t[nw + xx[u]];
+                r0[u] = ty[0];
+                r1[u] = ty[1];
+                bb[u] = ty[2];
             }
-            const int bb = t[2 * nw + 3 * yy + 2];
-            const int b0 = (int)(short)(bb & 0xFFFF), b1 = (int)(short)(bb >> 16);
-            int v;
-            if (x < D.vend && noclamp) {   // as below; taps checked on the host (k_resize notes)
-                v = ((__mul24(h0 >> 4, b0) >> 16) + (__mul24(h1 >> 4, b1) >> 16) + 2) >> 2;
-            } else if (x < D.vend) {   // VResizeLinearVec_32s8u lanes (128-bit baseline)
-                int s0 = min(max(h0 >> 4, -32768), 32767);
-                int s1 = min(max(h1 >> 4, -32768), 32767);
-                int tt = ((s0 * b0) >> 16) + ((s1 * b1) >> 16);
-                tt = min(max(tt, -32768), 32767);
-                v = (tt + 2) >> 2;
-            } else {            // FixedPtCast<int, uchar, 22>
-                v = (h0 * b0 + h1 * b1 + (1 << 21)) >> 22;
+            // the phases stay phases: no load of the next one moves up into the wait of this one,
+            // and no select on a loaded word turns back into a branch around its load
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int u = 0; u < U; u++) asm volatile("" : "+v"(sx[u]), "+v"(aa[u]), "+v"(r0[u]), "+v"(r1[u]), "+v"(bb[u]));
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const uint8_t* S0 = src + (r0[u] - rp.ny0) * nwp + (sx[u] - rp.nx0);
+                const uint8_t* S1 = src + (r1[u] - rp.ny0) * nwp + (sx[u] - rp.nx0);
+                p00[u] = S0[0];
+                p01[u] = S0[1];
+                p10[u] = S1[0];
+                p11[u] = S1[1];
             }
-            const uint8_t u = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
-            cone[boff[l] + i] = u;
-            if (x >= r.ox0 && x < r.ox1 && y >= r.oy0 && y < r.oy1) dst[(int64_t)y * D.pitch + x] = u;
-        }
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int u = 0; u < U; u++) asm volatile("" : "+v"(p00[u]), "+v"(p01[u]), "+v"(p10[u]), "+v"(p11[u]));
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const int i = i0 + u * nt;
+                const int x = r.nx0 + xx[u], y = r.ny0 + yy[u];
+                const int a = x < xmax ? aa[u] : 2048;
+                const int a0 = (int)(short)(a & 0xFFFF), a1 = (int)(short)(a >> 16);
+                const int b0 = (int)(short)(bb[u] & 0xFFFF), b1 = (int)(short)(bb[u] >> 16);
+                const int h0 = p00[u] * a0 + p01[u] * a1, h1 = p10[u] * a0 + p11[u] * a1;
+                int vv;
+                if (kNoclamp) {   // as below; taps checked on the host (k_resize notes)
+                    vv = ((__mul24(h0 >> 4, b0) >> 16) + (__mul24(h1 >> 4, b1) >> 16) + 2) >> 2;
+                } else {          // VResizeLinearVec_32s8u lanes (128-bit baseline)
+                    const int c0 = min(max(h0 >> 4, -32768), 32767);
+                    const int c1 = min(max(h1 >> 4, -32768), 32767);
+                    int tt = ((c0 * b0) >> 16) + ((c1 * b1) >> 16);
+                    tt = min(max(tt, -32768), 32767);
+                    vv = (tt + 2) >> 2;
+                }
+                const int vt = (h0 * b0 + h1 * b1 + (1 << 21)) >> 22;   // FixedPtCast<int, uchar, 22>
+                const int v = x < vend ? vv : vt;
+                const uint8_t px = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
+                if (i < n) {
+                    out[i] = px;
+                    if (x >= r.ox0 && x < r.ox1 && y >= r.oy0 && y < r.oy1) dst[(int64_t)y * pitch + x] = px;
+                }
+            }
+        };
+        // groups of 4 while the wave has that many pixels per lane left, then one group of exactly
+        // the rest (wave-uniform: a wave whose lanes all lie past the end issues nothing)
+        auto level = [&](auto NC) {
+            int i0 = tid;
+            for (int left = n - wave0; left > 0; left -= 4 * nt, i0 += 4 * nt) {
+                if (left > 3 * nt) group(std::integral_constant<int, 4>{}, NC, i0);
+                else if (left > 2 * nt) group(std::integral_constant<int, 3>{}, NC, i0);
+                else if (left > nt) group(std::integral_constant<int, 2>{}, NC, i0);
+                else group(std::integral_constant<int, 1>{}, NC, i0);
+            }
+        };
+        if (noclamp) level(std::true_type{});
+        else level(std::false_type{});
         lds_only_barrier();   // the next level reads this one's LDS cone; the stores stay in flight
         TR_PHASE(0, l)
+        toff += 2 * nw + 3 * nh;
+        bsrc = bdst;
+        bdst += cone_bytes(r, false);
+        rp = r;
+        nwp = nw;
     }
     TR_END(0)
 }
