@@ -246,7 +246,7 @@ int orbhip_frontend_context(orbhip_frontend* fe, int j, orbhip_ctx** out);
  * search of one call form one pair, 9 SearchByProjection with a Sim3: the grid build, the search and
  * the resolve of one call form one pair, 10 the triangulation of CreateNewMapPoints: k_tri_points
  * and k_tri_claim of one call form one pair, 11 Sim3Solver: k_sim3_ransac and k_sim3_select of one
- * call form one pair). orbhip_profile_collect synchronises and
+ * call form one pair, 13 OptimizeSim3: k_sim3_opt; 12 is not a stage and is refused). orbhip_profile_collect synchronises and
  * returns the summed duration (ms) and the number of bracketed launches, then resets. The one-launch
  * pyramid (k_pyr_cone) and the octree also time themselves on the device (first workgroup start to
  * last workgroup end, s_memrealtime: the span rocprofv3's kernel trace reports); their stages
@@ -835,6 +835,63 @@ typedef struct {                   /* the pointers are the caller's */
 int orbhip_sim3_solve_batch(orbhip_ctx* ctx, const orbhip_sim3_problem* probs, int B, orbhip_sim3_result* res);
 /* B = 1 */
 int orbhip_sim3_solve(orbhip_ctx* ctx, const orbhip_sim3_problem* prob, orbhip_sim3_result* res);
+
+/* ---- LoopClosing: Optimizer::OptimizeSim3 (the Sim3 refinement between the two projection searches)
+ * U:src/Optimizer.cc::OptimizeSim3 (LoopClosing::DetectCommonRegionsFromBoW step 4 and the end of
+ * DetectAndReffineSim3FromLastKF). One VertexSim3Expmap S12 = (r, t, s), map(X) = s r X + t; per kept
+ * correspondence an EdgeSim3ProjectXYZ (obs1 - cam1.project(S12.map(X2c)), information
+ * inv_sigma2_1) and an EdgeInverseSim3ProjectXYZ (obs2 - cam2.project(S12^-1.map(X1c)),
+ * inv_sigma2_2), both Huber (float)sqrt(th2), with g2o's numeric Jacobians (central differences,
+ * 1e-9). optimize(5); pairs with either chi2 > th2 are removed (n_bad; the chi2 of the last
+ * computeActiveErrors that saw the edge) and the kernels dropped; n - n_bad < 10 returns 0 with
+ * S12 untouched; optimize(n_bad > 0 ? 10 : 5); pairs with either recomputed chi2 > th2 are cleared,
+ * the others counted in n_in. DESIGN.md "OptimizeSim3" has the operation order.
+ *
+ * A problem is what upstream's filter loop leaves: X1c / X2c = the map points
+ * in the frames of camera 1 / 2 (float products Rcw Xw + tcw), obs1 / obs2 as upstream sets them
+ * (obs2 of a match without a keypoint in KF2 is the NORMALISED x / z, y / z: upstream's quirk,
+ * kept by the adapter), the information values already looked up per correspondence, the two
+ * pinhole cameras as (fx, fy, cx, cy), and g2oS12 in double: the rotation as the quaternion
+ * q = (x, y, z, w) of Eigen::Quaterniond(R) (taken as given, not normalised, as g2o::Sim3 holds it),
+ * t and s. LoopClosing passes th2 = 10.
+ *
+ * keep[i] (caller-owned, may be NULL) = 1 where the match survives, 0 where upstream sets
+ * vpMatches1[idx] = NULL. lm_trials counts the Levenberg trials of both rounds. mAcumHessian is
+ * zero upstream (its accumulation is commented out) and is not returned.
+ *
+ * orbhip_optimize_sim3_batch returns ORBHIP_OK, orbhip_optimize_sim3 n_in (upstream's return
+ * value). n = 0: n_in = 0 and S12 copied through. B = 0: ORBHIP_OK. B > 64 or n > 8192:
+ * ORBHIP_ERR_UNSUPPORTED. ORBHIP_ERR_ARG, before anything is uploaded and with no output touched: a NULL
+ * required pointer with n > 0, n < 0, a focal length, th2 or s that is not positive and finite, a
+ * non-finite q or t. One upload, one launch, one read-back. */
+typedef struct {
+    int32_t n;                     /* correspondences */
+    const float* X1c;              /* n x 3 */
+    const float* X2c;              /* n x 3 */
+    const float* obs1;             /* n x 2 */
+    const float* obs2;             /* n x 2 */
+    const float* inv_sigma2_1;     /* n */
+    const float* inv_sigma2_2;     /* n */
+    float cam1[4], cam2[4];        /* fx, fy, cx, cy */
+    double q[4];                   /* S12 rotation, quaternion (x, y, z, w) */
+    double t[3];
+    double s;
+    double th2;
+    int32_t fix_scale;
+} orbhip_sim3_opt_problem;
+
+typedef struct {
+    double q[4], t[3], s;          /* the optimised S12 (the input where n_in = 0 by the < 10 rule) */
+    int32_t n_in;                  /* upstream's return value */
+    int32_t n_bad;                 /* pairs removed after the first round */
+    int32_t lm_trials;
+    uint8_t* keep;                 /* n, or NULL; the caller's */
+} orbhip_sim3_opt_result;
+
+int orbhip_optimize_sim3_batch(orbhip_ctx* ctx, const orbhip_sim3_opt_problem* probs, int B,
+                               orbhip_sim3_opt_result* res);
+/* B = 1; returns n_in */
+int orbhip_optimize_sim3(orbhip_ctx* ctx, const orbhip_sim3_opt_problem* prob, orbhip_sim3_opt_result* res);
 
 /* ---- multi-GPU BundleAdjustment (SURVEY.md §8e, C5 GlobalBundleAdjustment) --------
  * One process per GPU. Landmarks (with their edges) are partitioned across ranks; every rank

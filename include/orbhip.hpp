@@ -684,6 +684,15 @@ struct StereoBAProblem : BAProblem {
     float huber_delta_stereo = 2.7955321f;   // sqrt(7.815): thHuberStereo (LBA), thHuber3D (GBA)
 };
 
+// What OptimizeSim3's filter loop leaves of (pKF1, pKF2, vpMatches1): per kept correspondence the two
+// map points in their cameras' frames, the two observations and the two information values
+struct Sim3Problem {
+    std::vector<float> X1c, X2c;                  // N x 3: R1w X1w + t1w, R2w X2w + t2w
+    std::vector<float> obs1, obs2;                // N x 2 (obs2 of a match without a keypoint: upstream's x / z, y / z)
+    std::vector<float> inv_sigma2_1, inv_sigma2_2;   // N
+    float cam1[4] = {0, 0, 0, 0}, cam2[4] = {0, 0, 0, 0};   // fx, fy, cx, cy
+};
+
 class Optimizer {
 public:
     // LocalBundleAdjustment's optimize(10) with Huber sqrt(5.991). The reference's bool*
@@ -729,6 +738,37 @@ public:
         check(rc, "orbhip_pose_optimization_stereo");
         for (int k = 0; k < 4; k++) Tcw_q[k] = r.pose_q[k];
         for (int k = 0; k < 3; k++) Tcw_t[k] = r.pose_t[k];
+        return rc;
+    }
+
+    // OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale, ...): the adapter's filter loop fills
+    // the Sim3Problem; g2oS12 = (q: x, y, z, w; t; s) is updated in place unless
+    // the call returns 0 by the "fewer than 10 left" rule, vbKeep gets 0 where upstream sets
+    // vpMatches1[idx] = NULL. Returns nIn.
+    static int OptimizeSim3(orbhip_ctx* ctx, const Sim3Problem& p, double q[4], double t[3], double& s, float th2,
+                            bool bFixScale, std::vector<uint8_t>& vbKeep, int* pnBad = nullptr) {
+        const size_t n = p.inv_sigma2_1.size();
+        if (p.X1c.size() != 3 * n || p.X2c.size() != 3 * n || p.obs1.size() != 2 * n || p.obs2.size() != 2 * n ||
+            p.inv_sigma2_2.size() != n)
+            throw std::invalid_argument("Sim3Problem: every array needs one entry per correspondence");
+        orbhip_sim3_opt_problem c{};
+        c.n = (int32_t)n;
+        c.X1c = p.X1c.data(); c.X2c = p.X2c.data(); c.obs1 = p.obs1.data(); c.obs2 = p.obs2.data();
+        c.inv_sigma2_1 = p.inv_sigma2_1.data(); c.inv_sigma2_2 = p.inv_sigma2_2.data();
+        std::memcpy(c.cam1, p.cam1, sizeof c.cam1);
+        std::memcpy(c.cam2, p.cam2, sizeof c.cam2);
+        for (int k = 0; k < 4; k++) c.q[k] = q[k];
+        for (int k = 0; k < 3; k++) c.t[k] = t[k];
+        c.s = s; c.th2 = th2; c.fix_scale = bFixScale;
+        vbKeep.assign(n, 0);
+        orbhip_sim3_opt_result r{};
+        r.keep = vbKeep.data();
+        const int rc = orbhip_optimize_sim3(ctx, &c, &r);
+        check(rc, "orbhip_optimize_sim3");
+        for (int k = 0; k < 4; k++) q[k] = r.q[k];
+        for (int k = 0; k < 3; k++) t[k] = r.t[k];
+        s = r.s;
+        if (pnBad) *pnBad = r.n_bad;
         return rc;
     }
 

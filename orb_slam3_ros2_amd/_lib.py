@@ -157,6 +157,20 @@ class Sim3ResultC(ctypes.Structure):
                 ("sel", ctypes.c_float * 13), ("converged", ctypes.c_int32), ("best", ctypes.c_int32)]
 
 
+class Sim3OptProblemC(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_int32), ("X1c", ctypes.c_void_p), ("X2c", ctypes.c_void_p), ("obs1", ctypes.c_void_p),
+                ("obs2", ctypes.c_void_p), ("inv_sigma2_1", ctypes.c_void_p), ("inv_sigma2_2", ctypes.c_void_p),
+                ("cam1", ctypes.c_float * 4), ("cam2", ctypes.c_float * 4), ("q", ctypes.c_double * 4),
+                ("t", ctypes.c_double * 3), ("s", ctypes.c_double), ("th2", ctypes.c_double),
+                ("fix_scale", ctypes.c_int32)]
+
+
+class Sim3OptResultC(ctypes.Structure):
+    _fields_ = [("q", ctypes.c_double * 4), ("t", ctypes.c_double * 3), ("s", ctypes.c_double),
+                ("n_in", ctypes.c_int32), ("n_bad", ctypes.c_int32), ("lm_trials", ctypes.c_int32),
+                ("keep", ctypes.c_void_p)]
+
+
 # every symbol include/orbhip.h declares (tests check the export table against this list)
 EXPORTED = ["orbhip_abi_version", "orbhip_create", "orbhip_destroy", "orbhip_level_info", "orbhip_max_keypoints",
             "orbhip_extract", "orbhip_extract_batch_device", "orbhip_extract_stereo", "orbhip_extract_stereo_device",
@@ -178,6 +192,7 @@ EXPORTED = ["orbhip_abi_version", "orbhip_create", "orbhip_destroy", "orbhip_lev
             "orbhip_triangulate_matches_stereo",
             "orbhip_fuse_sim3", "orbhip_search_by_projection_sim3",
             "orbhip_sim3_solve", "orbhip_sim3_solve_batch",
+            "orbhip_optimize_sim3", "orbhip_optimize_sim3_batch",
             "orbhip_kfdb_create", "orbhip_kfdb_destroy", "orbhip_kfdb_add", "orbhip_kfdb_erase",
             "orbhip_kfdb_detect_relocalization", "orbhip_kfdb_detect_nbest",
             "orbhip_frontend_create", "orbhip_frontend_destroy", "orbhip_frontend_push", "orbhip_frontend_view",
@@ -285,6 +300,8 @@ def lib():
                                                    vp, vp, vp]
     L.orbhip_sim3_solve.argtypes = [vp, ctypes.POINTER(Sim3ProblemC), ctypes.POINTER(Sim3ResultC)]
     L.orbhip_sim3_solve_batch.argtypes = [vp, ctypes.POINTER(Sim3ProblemC), i32, ctypes.POINTER(Sim3ResultC)]
+    L.orbhip_optimize_sim3.argtypes = [vp, ctypes.POINTER(Sim3OptProblemC), ctypes.POINTER(Sim3OptResultC)]
+    L.orbhip_optimize_sim3_batch.argtypes = [vp, ctypes.POINTER(Sim3OptProblemC), i32, ctypes.POINTER(Sim3OptResultC)]
     L.orbhip_kfdb_create.argtypes = [vp, i32, ctypes.POINTER(vp)]
     L.orbhip_kfdb_destroy.argtypes = [vp]
     L.orbhip_kfdb_add.argtypes = [vp, i32, vp, vp, i32]

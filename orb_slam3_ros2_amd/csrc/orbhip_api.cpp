@@ -14,6 +14,7 @@
 #include "orbhip_ctx.h"
 #include "orbhip_ba.h"
 #include "pose_opt.h"
+#include "sim3_opt.h"
 #include "proj.h"
 #include "kfdb.h"
 #include "ba_chol_blocked.h"
@@ -43,6 +44,7 @@ struct orbhip_ctx {
     StageBlock tri_stage{false};    // SearchForTriangulation's block (stage.h)
     StageBlock fuse_stage{false};   // Fuse's, Fuse with a Sim3's and the Sim3 projection search's
     StageBlock sim3_stage{false};   // Sim3Solver's
+    StageBlock sim3_opt_stage{false};   // OptimizeSim3's
     StageTimer timer;
     GraphCache graphs;   // replays of repeated per-frame launch sequences (graph_cache.h)
 };
@@ -277,7 +279,7 @@ int orbhip_launch_graphs(orbhip_ctx* c) {
 }
 
 int orbhip_profile_stage(orbhip_ctx* c, int stage) {
-    if (!c || stage < 0 || stage > 11) return ORBHIP_ERR_ARG;
+    if (!c || stage < 0 || stage > 13 || stage == 12) return ORBHIP_ERR_ARG;   // 12 is no stage: callers rely on its refusal
     HIPOK(hipSetDevice(c->device));
     StageTimer& t = c->timer;
     if (!t.created) {
@@ -767,6 +769,20 @@ int orbhip_sim3_solve_batch(orbhip_ctx* c, const orbhip_sim3_problem* probs, int
 int orbhip_sim3_solve(orbhip_ctx* c, const orbhip_sim3_problem* prob, orbhip_sim3_result* res) {
     if (!prob || !res) return ORBHIP_ERR_ARG;
     return orbhip_sim3_solve_batch(c, prob, 1, res);
+}
+
+// ---- LoopClosing: OptimizeSim3, every candidate's refinement in one launch ----
+int orbhip_optimize_sim3_batch(orbhip_ctx* c, const orbhip_sim3_opt_problem* probs, int B,
+                               orbhip_sim3_opt_result* res) {
+    if (!c) return ORBHIP_ERR_ARG;
+    HIPOK(hipSetDevice(c->device));
+    return sim3_opt_batch(c->sim3_opt_stage, c->timer, c->stream, probs, B, res);
+}
+
+int orbhip_optimize_sim3(orbhip_ctx* c, const orbhip_sim3_opt_problem* prob, orbhip_sim3_opt_result* res) {
+    if (!prob || !res) return ORBHIP_ERR_ARG;
+    const int rc = orbhip_optimize_sim3_batch(c, prob, 1, res);
+    return rc < 0 ? rc : res->n_in;
 }
 
 // the stored list capacity of the Sim3 projection search; the resolve has no round cap other than

@@ -14,8 +14,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import (BAProblemC, BAResultC, BAStereoProblemC, Context, PoseProblemC, PoseResultC, PoseStereoProblemC, check, lib,
-                   ptr)
+from ._lib import (BAProblemC, BAResultC, BAStereoProblemC, Context, PoseProblemC, PoseResultC, PoseStereoProblemC,
+                   Sim3OptProblemC, Sim3OptResultC, check, lib, ptr)
 
 TH_HUBER_MONO = float(np.sqrt(np.float32(5.991)))
 TH_HUBER_STEREO = float(np.sqrt(np.float32(7.815)))
@@ -158,6 +158,56 @@ class PoseResult:
     outlier: np.ndarray         # [N] uint8: mvbOutlier
     n_inliers: int              # PoseOptimization return value
     lm_trials: int
+
+
+@dataclass
+class Sim3Problem:
+    """What Optimizer::OptimizeSim3's filter loop leaves of (pKF1, pKF2, vpMatches1, g2oS12): per kept
+    correspondence the two map points in their cameras' frames, the two observations (obs2 of a match
+    without a keypoint in KF2 is upstream's normalised x / z, y / z) and the two information values;
+    the cameras; S12 as Eigen's quaternion (x, y, z, w), t, s in float64."""
+    X1c: np.ndarray             # [N,3] float32 R1w X1w + t1w
+    X2c: np.ndarray             # [N,3] float32
+    obs1: np.ndarray            # [N,2] float32
+    obs2: np.ndarray            # [N,2] float32
+    inv_sigma2_1: np.ndarray    # [N] float32
+    inv_sigma2_2: np.ndarray    # [N] float32
+    cam1: np.ndarray            # [4] float32 fx, fy, cx, cy
+    cam2: np.ndarray            # [4] float32
+    q: np.ndarray               # [4] float64 (x, y, z, w)
+    t: np.ndarray               # [3] float64
+    s: float
+    th2: float = 10.0
+    fix_scale: bool = False
+
+    def normalized(self) -> "Sim3Problem":
+        c = lambda a, dt, shape: np.ascontiguousarray(a, dtype=dt).reshape(shape)  # noqa: E731
+        p = Sim3Problem(c(self.X1c, np.float32, (-1, 3)), c(self.X2c, np.float32, (-1, 3)),
+                        c(self.obs1, np.float32, (-1, 2)), c(self.obs2, np.float32, (-1, 2)),
+                        c(self.inv_sigma2_1, np.float32, -1), c(self.inv_sigma2_2, np.float32, -1),
+                        c(self.cam1, np.float32, 4), c(self.cam2, np.float32, 4), c(self.q, np.float64, 4),
+                        c(self.t, np.float64, 3), float(self.s), float(self.th2), bool(self.fix_scale))
+        n = p.X1c.shape[0]
+        if not all(a.shape[0] == n for a in (p.X2c, p.obs1, p.obs2, p.inv_sigma2_1, p.inv_sigma2_2)):
+            raise ValueError("Sim3Problem: every per-correspondence array needs the same length")
+        return p
+
+    def to_c(self) -> Sim3OptProblemC:
+        f4, d4, d3 = ctypes.c_float * 4, ctypes.c_double * 4, ctypes.c_double * 3
+        return Sim3OptProblemC(self.X1c.shape[0], ptr(self.X1c), ptr(self.X2c), ptr(self.obs1), ptr(self.obs2),
+                               ptr(self.inv_sigma2_1), ptr(self.inv_sigma2_2), f4(*self.cam1), f4(*self.cam2),
+                               d4(*self.q), d3(*self.t), self.s, self.th2, int(self.fix_scale))
+
+
+@dataclass
+class Sim3Result:
+    q: np.ndarray               # [4] float64: the optimised g2oS12 (the input where n_in = 0 by the < 10 rule)
+    t: np.ndarray               # [3] float64
+    s: float
+    n_in: int                   # OptimizeSim3's return value
+    n_bad: int                  # pairs removed after the first round
+    lm_trials: int
+    keep: np.ndarray            # [N] uint8: 0 where upstream sets vpMatches1[idx] = NULL
 
 
 @dataclass
@@ -348,3 +398,28 @@ class Optimizer:
                   "orbhip_pose_optimization_batch")
         return [PoseResult(np.array(r.pose_q[:], np.float32), np.array(r.pose_t[:], np.float32), o, r.n_inliers,
                            r.lm_trials) for r, o in zip(cres, outl)]
+
+    # ---- LoopClosing's Sim3 refinement ----
+    def OptimizeSim3(self, prob: Sim3Problem) -> Sim3Result:
+        """U:src/Optimizer.cc::Optimizer::OptimizeSim3 for one candidate (orbhip_optimize_sim3)."""
+        p = prob.normalized()
+        keep = np.zeros(p.X1c.shape[0], np.uint8)
+        pc, r = p.to_c(), Sim3OptResultC()
+        r.keep = ptr(keep)
+        check(lib().orbhip_optimize_sim3(self.ctx.handle, ctypes.byref(pc), ctypes.byref(r)), "orbhip_optimize_sim3")
+        return Sim3Result(np.array(r.q[:]), np.array(r.t[:]), r.s, r.n_in, r.n_bad, r.lm_trials, keep)
+
+    def OptimizeSim3_batch(self, probs) -> list:
+        """The candidates of one DetectCommonRegionsFromBoW round in one launch (one wavefront group
+        per candidate; at most 64)."""
+        ps = [p.normalized() for p in probs]
+        if not ps:
+            return []
+        keeps = [np.zeros(p.X1c.shape[0], np.uint8) for p in ps]
+        cres = (Sim3OptResultC * len(ps))()
+        for i, k in enumerate(keeps):
+            cres[i].keep = ptr(k)
+        cprobs = (Sim3OptProblemC * len(ps))(*[p.to_c() for p in ps])
+        check(lib().orbhip_optimize_sim3_batch(self.ctx.handle, cprobs, len(ps), cres), "orbhip_optimize_sim3_batch")
+        return [Sim3Result(np.array(r.q[:]), np.array(r.t[:]), r.s, r.n_in, r.n_bad, r.lm_trials, k)
+                for r, k in zip(cres, keeps)]

@@ -1346,3 +1346,51 @@ def synthetic_sim3_solver_scene(n=100, outlier_frac=0.5, seed=0, fix_scale=False
                 level_sigma2=s2, max_err1=error_bounds(oct1, s2), max_err2=error_bounds(oct2, s2),
                 cam1=cams[0], cam2=cams[1], fix_scale=bool(fix_scale), min_inliers=int(min_inliers),
                 triples=triples, indices1=indices1, n1=n1, outlier=out, degenerate_h=degenerate_h, true_s=s, true_R=R, true_t=t)
+
+
+# ---------------------------------------------------------------------------
+# OptimizeSim3 problems (LoopClosing's Sim3 refinement)
+# ---------------------------------------------------------------------------
+def synthetic_sim3_opt_problem(n=100, outlier_frac=0.2, seed=0, fix_scale=False, proj_frac=0.0, noise_px=0.7,
+                               rot_noise=0.02, trans_noise=0.05, scale_noise=0.03, n_levels=8, scale_factor=1.2,
+                               cam1=None, cam2=None):
+    """What OptimizeSim3's filter loop leaves of two keyframes that see the same n map points: X1c /
+    X2c (the points in the two cameras' frames, float32) under a true Sim3 X1 = s R X2 + t (s = 1 when
+    the scale is fixed), keypoints = the projections plus noise_px pixels scaled by each keypoint's
+    octave, and with the octaves the information values. A share outlier_frac of the pairs are gross
+    mismatches (the keypoint in KF1 moved by 25 to 80 pixels); a share proj_frac of the others have no
+    keypoint in KF2 (upstream's i2 < 0 with bAllPoints) and get upstream's obs2 for them: the NORMALISED
+    x / z, y / z of the point and the information of a track level. The initial S12 is the true one
+    moved by rot_noise rad, trans_noise and a relative scale_noise (no scale change when fixed).
+    Returns (Sim3Problem, dict(R, t, s, bad = mismatch or without keypoint, by_projection))."""
+    from .optimizer import Sim3Problem
+    rng = np.random.default_rng(seed)
+    c1 = dict(D435I) if cam1 is None else dict(cam1)
+    c2 = dict(fx=600.0, fy=605.0, cx=318.5, cy=242.25) if cam2 is None else dict(cam2)
+    X1 = np.stack([rng.uniform(-2.0, 2.0, n), rng.uniform(-1.5, 1.5, n), rng.uniform(2.5, 8.0, n)], 1)
+    R = _rodrigues(rng.normal(size=3) * 0.12)
+    t = rng.normal(size=3) * 0.25
+    s = 1.0 if fix_scale else float(rng.uniform(0.8, 1.25))
+    X2 = (X1 - t) @ R / s                      # rows: R^T (X1 - t) / s
+    X1f, X2f = X1.astype(np.float32), X2.astype(np.float32)
+    _, s2 = orb_scale_tables(n_levels, scale_factor)
+    oct1, oct2 = rng.integers(0, n_levels, n), rng.integers(0, n_levels, n)
+    obs = []
+    for X, c, o in ((X1f.astype(np.float64), c1, oct1), (X2f.astype(np.float64), c2, oct2)):
+        sd = noise_px * np.sqrt(s2[o])
+        obs.append(np.stack([c["fx"] * X[:, 0] / X[:, 2] + c["cx"] + rng.normal(size=n) * sd,
+                             c["fy"] * X[:, 1] / X[:, 2] + c["cy"] + rng.normal(size=n) * sd], 1))
+    bad = rng.random(n) < outlier_frac
+    ang = rng.uniform(0, 2 * np.pi, n)
+    obs[0][bad] += (rng.uniform(25.0, 80.0, n)[:, None] * np.stack([np.cos(ang), np.sin(ang)], 1))[bad]
+    by_proj = (rng.random(n) < proj_frac) & ~bad
+    z2 = X2f[:, 2:3].astype(np.float64)
+    obs[1][by_proj] = (X2f[:, :2].astype(np.float64) / z2)[by_proj]
+    R0 = _rodrigues(rng.normal(size=3) * rot_noise) @ R
+    t0 = t + rng.normal(size=3) * trans_noise
+    s0 = s if fix_scale else s * (1.0 + float(rng.normal()) * scale_noise)
+    cams = [np.array([c[k] for k in ("fx", "fy", "cx", "cy")], np.float32) for c in (c1, c2)]
+    prob = Sim3Problem(X1f, X2f, obs[0].astype(np.float32), obs[1].astype(np.float32),
+                       (1.0 / s2[oct1]).astype(np.float32), (1.0 / s2[oct2]).astype(np.float32), cams[0], cams[1],
+                       _mat_to_quat(R0), t0, float(s0), 10.0, bool(fix_scale))
+    return prob, dict(R=R, t=t, s=s, bad=bad | by_proj, by_projection=by_proj)
