@@ -246,7 +246,8 @@ int orbhip_frontend_context(orbhip_frontend* fe, int j, orbhip_ctx** out);
  * search of one call form one pair, 9 SearchByProjection with a Sim3: the grid build, the search and
  * the resolve of one call form one pair, 10 the triangulation of CreateNewMapPoints: k_tri_points
  * and k_tri_claim of one call form one pair, 11 Sim3Solver: k_sim3_ransac and k_sim3_select of one
- * call form one pair, 13 OptimizeSim3: k_sim3_opt; 12 is not a stage and is refused). orbhip_profile_collect synchronises and
+ * call form one pair, 13 OptimizeSim3: k_sim3_opt, 15 OptimizeEssentialGraph: the first to the last kernel of
+ * one call form one pair; 12 and 14 are no stages and are refused). orbhip_profile_collect synchronises and
  * returns the summed duration (ms) and the number of bracketed launches, then resets. The one-launch
  * pyramid (k_pyr_cone) and the octree also time themselves on the device (first workgroup start to
  * last workgroup end, s_memrealtime: the span rocprofv3's kernel trace reports); their stages
@@ -892,6 +893,62 @@ int orbhip_optimize_sim3_batch(orbhip_ctx* ctx, const orbhip_sim3_opt_problem* p
                                orbhip_sim3_opt_result* res);
 /* B = 1; returns n_in */
 int orbhip_optimize_sim3(orbhip_ctx* ctx, const orbhip_sim3_opt_problem* prob, orbhip_sim3_opt_result* res);
+
+/* ---- LoopClosing: OptimizeEssentialGraph (CorrectLoop, MergeLocal) -------------------
+ * U:src/Optimizer.cc::Optimizer::OptimizeEssentialGraph on the device: the 7-dof pose graph over the
+ * keyframes of a map. The adapter builds the graph from the Map; the library receives
+ * arrays only, so one call serves both upstream overloads: the caller decides which vertices are fixed
+ * (CorrectLoop: the map's initial keyframe; MergeLocal: its list of fixed keyframes).
+ * OptimizeEssentialGraph4DoF is not covered.
+ *
+ * Vertices are VertexSim3Expmap: the estimate (q xyzw, t, s) as g2o::Sim3, never renormalised, one
+ * fix_scale for the graph (oplus(u): u[6] = 0, estimate = Sim3(u) * estimate). Edges are
+ * EdgeSim3(i, j, Sji) with vertex(0) = i, vertex(1) = j, information I7 and no robust kernel:
+ * e = (Sji * Si * Sj^-1).log(), chi2 = e.e, g2o's numeric Jacobians (central differences of 1e-9;
+ * a fixed vertex gets none). Several edges between one pair sum. BlockSolver_7_3 + Levenberg with
+ * setUserLambdaInit(lambda_init): initializeOptimization(); computeActiveErrors();
+ * optimize(iterations); each trial is one solve of (H + lambda I) x = b over the free vertices, a
+ * failed pivot a rejected trial. Then every map point m: P' = Swc_corrected[ref].map(Scw_before[ref]
+ * .map(P)), Scw_before the vertex's input estimate, Swc_corrected the inverse of its optimised one,
+ * in double, P float in and out.
+ *
+ * The library does not reorder: H's blocks follow the caller's vertex order. Keyframe-id order keeps
+ * the spanning-tree and covisibility blocks near the diagonal and puts the loop edges' rows last,
+ * where their fill is cheap. solver reports the linear solver: 0 the persistent tiled solver, 1 the
+ * blocked one (7 x free vertices < 70, or ORBHIP_EG_BLOCKED=1 in the environment), 2 the blocked one
+ * after a hand-off timeout of the persistent one (the call ran again).
+ *
+ * Envelope: 7 x free vertices <= 4096 (585 free vertices), n_edges <= 65536, n_points <= 2^22,
+ * n_vertices <= 65535; beyond it ORBHIP_ERR_UNSUPPORTED. ORBHIP_ERR_ARG, before anything is uploaded
+ * and with no output touched: a NULL required pointer, a negative count, an edge index out of range
+ * or i == j, a point_ref out of range, an estimate or measurement that is not finite or whose s is
+ * not positive, lambda_init <= 0, iterations < 0. n_edges = 0, iterations = 0 or no free vertex: the
+ * estimates are copied through and the points still corrected (by the identity), ORBHIP_OK.
+ * Profile stage 15 brackets the call's launches (14 is no stage and stays refused). */
+typedef struct {
+    int32_t n_vertices;            /* caller's order, recommended: keyframe id */
+    const double* S;               /* n_vertices x 8: q(x,y,z,w), t, s */
+    const uint8_t* fixed;          /* n_vertices */
+    int32_t n_edges;
+    const int32_t* edge_ij;        /* n_edges x 2: vertex(0) = i, vertex(1) = j */
+    const double* edge_S;          /* n_edges x 8: the measurement Sji */
+    int32_t fix_scale, iterations; /* upstream: 20 */
+    double lambda_init;            /* upstream: 1e-16; must be > 0 */
+    int32_t n_points;              /* may be 0 */
+    const float* points;           /* n_points x 3 */
+    const int32_t* point_ref;      /* n_points: vertex index */
+} orbhip_essential_graph_problem;
+
+typedef struct {
+    double* S;                     /* n_vertices x 8, the caller's: corrected Siw (fixed ones copied through bit for bit) */
+    float* points;                 /* n_points x 3, the caller's, or NULL when n_points = 0 */
+    double chi2_initial, chi2_final;
+    int32_t iterations_run, lm_trials, lm_rejected;
+    int32_t solver;                /* 0 dag, 1 blocked, 2 blocked after a timeout */
+} orbhip_essential_graph_result;
+
+int orbhip_optimize_essential_graph(orbhip_ctx* ctx, const orbhip_essential_graph_problem* prob,
+                                    orbhip_essential_graph_result* res);
 
 /* ---- multi-GPU BundleAdjustment (SURVEY.md §8e, C5 GlobalBundleAdjustment) --------
  * One process per GPU. Landmarks (with their edges) are partitioned across ranks; every rank

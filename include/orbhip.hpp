@@ -693,6 +693,22 @@ struct Sim3Problem {
     float cam1[4] = {0, 0, 0, 0}, cam2[4] = {0, 0, 0, 0};   // fx, fy, cx, cy
 };
 
+// The graph OptimizeEssentialGraph builds from the Map: VertexSim3Expmap estimates (q xyzw, t, s per
+// vertex, in keyframe-id order for a near-diagonal system), the fixed flags, EdgeSim3 (i, j, Sji)
+// edges with vertex(0) = i, and the map points with the vertex of their reference keyframe
+struct EssentialGraph {
+    std::vector<double> S;            // V x 8, in and out
+    std::vector<uint8_t> fixed;       // V
+    std::vector<int32_t> edge_ij;     // E x 2
+    std::vector<double> edge_S;       // E x 8: Sji
+    std::vector<float> points;        // M x 3, in and out
+    std::vector<int32_t> point_ref;   // M
+};
+struct EssentialGraphResult {
+    double chi2_initial, chi2_final;
+    int iterations_run, lm_trials, lm_rejected, solver;
+};
+
 class Optimizer {
 public:
     // LocalBundleAdjustment's optimize(10) with Huber sqrt(5.991). The reference's bool*
@@ -770,6 +786,30 @@ public:
         s = r.s;
         if (pnBad) *pnBad = r.n_bad;
         return rc;
+    }
+
+    // OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections,
+    // bFixScale) and MergeLocal's overload: the adapter builds the graph from the Map (INTEGRATION.md
+    // 3i) and decides which vertices are fixed. Returns the corrected Siw in g.S (n x 8: q xyzw, t,
+    // s; the adapter sets Tiw = [R | t / s]) and the corrected map points in g.points.
+    static EssentialGraphResult OptimizeEssentialGraph(orbhip_ctx* ctx, EssentialGraph& g, bool bFixScale,
+                                                       int nIterations = 20, double lambdaInit = 1e-16) {
+        const size_t nv = g.fixed.size(), ne = g.edge_ij.size() / 2, np = g.point_ref.size();
+        if (g.S.size() != 8 * nv || g.edge_ij.size() != 2 * ne || g.edge_S.size() != 8 * ne || g.points.size() != 3 * np)
+            throw std::invalid_argument("EssentialGraph: S / fixed, edge_ij / edge_S and points / point_ref need the same lengths");
+        orbhip_essential_graph_problem c{};
+        c.n_vertices = (int32_t)nv; c.S = g.S.data(); c.fixed = g.fixed.data();
+        c.n_edges = (int32_t)ne; c.edge_ij = g.edge_ij.data(); c.edge_S = g.edge_S.data();
+        c.fix_scale = bFixScale; c.iterations = nIterations; c.lambda_init = lambdaInit;
+        c.n_points = (int32_t)np; c.points = g.points.data(); c.point_ref = g.point_ref.data();
+        std::vector<double> S(8 * nv);
+        std::vector<float> pts(3 * np);
+        orbhip_essential_graph_result r{};
+        r.S = S.data(); r.points = pts.data();
+        check(orbhip_optimize_essential_graph(ctx, &c, &r), "orbhip_optimize_essential_graph");
+        g.S.swap(S);
+        g.points.swap(pts);
+        return EssentialGraphResult{r.chi2_initial, r.chi2_final, r.iterations_run, r.lm_trials, r.lm_rejected, r.solver};
     }
 
 private:

@@ -18,6 +18,7 @@ Host-side mirror of the reference's hot-path interfaces over th
   ORBmatcher.FuseSim3 / SearchByProjectionSim3(...)   (LoopClosing)         U:src/ORBmatcher.cc
   Sim3Solver(...).solve(triples) / iterate(n) / solve_batch   (LoopClosing)  U:src/Sim3Solver.cc
   Optimizer.OptimizeSim3(Sim3Problem) / OptimizeSim3_batch   (LoopClosing)   U:src/Optimizer.cc
+  Optimizer.OptimizeEssentialGraph(EssentialGraphProblem)    (CorrectLoop)   U:src/Optimizer.cc
   KeyFrameDatabase(max_kf).DetectRelocalizationCandidates / DetectNBestCandidates
                                                                             U:src/KeyFrameDatabase.cc
   stereo_frame(ext, left, right, bf, b) -> StereoFrame   Frame's stereo ctor: both ExtractORB
@@ -35,6 +36,7 @@ from .extractor import KeyPoint, ORBextractor  # noqa: F401
 from .matcher import ORBmatcher  # noqa: F401
 from .optimizer import BAProblem, BAResult, Optimizer, PoseProblem, PoseResult, StereoBAProblem  # noqa: F401
 from .optimizer import Sim3Problem, Sim3Result  # noqa: F401
+from .optimizer import EssentialGraphProblem, EssentialGraphResult  # noqa: F401
 from .bow import ORBVocabulary  # noqa: F401
 from .kfdb import KeyFrameDatabase  # noqa: F401
 from .frontend import FrameStream  # noqa: F401
@@ -42,6 +44,6 @@ from .camera import PinholeCamera  # noqa: F401
 from .stereo import StereoFrame, stereo_frame  # noqa: F401
 from .sim3solver import Sim3Solver, draw_triples  # noqa: F401
 
-__all__ = ["Sim3Solver", "draw_triples", "StereoFrame", "stereo_frame", "ORBextractor", "KeyPoint", "ORBmatcher", "Optimizer", "BAProblem", "StereoBAProblem", "BAResult", "PoseProblem", "PoseResult", "Sim3Problem", "Sim3Result", "ORBVocabulary", "KeyFrameDatabase", "FrameStream", "PinholeCamera",
+__all__ = ["Sim3Solver", "draw_triples", "StereoFrame", "stereo_frame", "ORBextractor", "KeyPoint", "ORBmatcher", "Optimizer", "BAProblem", "StereoBAProblem", "BAResult", "PoseProblem", "PoseResult", "Sim3Problem", "Sim3Result", "EssentialGraphProblem", "EssentialGraphResult", "ORBVocabulary", "KeyFrameDatabase", "FrameStream", "PinholeCamera",
            "OrbHipError",
            "lib", "library_path"]

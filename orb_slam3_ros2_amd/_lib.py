@@ -171,6 +171,19 @@ class Sim3OptResultC(ctypes.Structure):
                 ("keep", ctypes.c_void_p)]
 
 
+class EssentialGraphProblemC(ctypes.Structure):
+    _fields_ = [("n_vertices", ctypes.c_int32), ("S", ctypes.c_void_p), ("fixed", ctypes.c_void_p),
+                ("n_edges", ctypes.c_int32), ("edge_ij", ctypes.c_void_p), ("edge_S", ctypes.c_void_p),
+                ("fix_scale", ctypes.c_int32), ("iterations", ctypes.c_int32), ("lambda_init", ctypes.c_double),
+                ("n_points", ctypes.c_int32), ("points", ctypes.c_void_p), ("point_ref", ctypes.c_void_p)]
+
+
+class EssentialGraphResultC(ctypes.Structure):
+    _fields_ = [("S", ctypes.c_void_p), ("points", ctypes.c_void_p), ("chi2_initial", ctypes.c_double),
+                ("chi2_final", ctypes.c_double), ("iterations_run", ctypes.c_int32), ("lm_trials", ctypes.c_int32),
+                ("lm_rejected", ctypes.c_int32), ("solver", ctypes.c_int32)]
+
+
 # every symbol include/orbhip.h declares (tests check the export table against this list)
 EXPORTED = ["orbhip_abi_version", "orbhip_create", "orbhip_destroy", "orbhip_level_info", "orbhip_max_keypoints",
             "orbhip_extract", "orbhip_extract_batch_device", "orbhip_extract_stereo", "orbhip_extract_stereo_device",
@@ -192,7 +205,7 @@ EXPORTED = ["orbhip_abi_version", "orbhip_create", "orbhip_destroy", "orbhip_lev
             "orbhip_triangulate_matches_stereo",
             "orbhip_fuse_sim3", "orbhip_search_by_projection_sim3",
             "orbhip_sim3_solve", "orbhip_sim3_solve_batch",
-            "orbhip_optimize_sim3", "orbhip_optimize_sim3_batch",
+            "orbhip_optimize_sim3", "orbhip_optimize_sim3_batch", "orbhip_optimize_essential_graph",
             "orbhip_kfdb_create", "orbhip_kfdb_destroy", "orbhip_kfdb_add", "orbhip_kfdb_erase",
             "orbhip_kfdb_detect_relocalization", "orbhip_kfdb_detect_nbest",
             "orbhip_frontend_create", "orbhip_frontend_destroy", "orbhip_frontend_push", "orbhip_frontend_view",
@@ -302,6 +315,8 @@ def lib():
     L.orbhip_sim3_solve_batch.argtypes = [vp, ctypes.POINTER(Sim3ProblemC), i32, ctypes.POINTER(Sim3ResultC)]
     L.orbhip_optimize_sim3.argtypes = [vp, ctypes.POINTER(Sim3OptProblemC), ctypes.POINTER(Sim3OptResultC)]
     L.orbhip_optimize_sim3_batch.argtypes = [vp, ctypes.POINTER(Sim3OptProblemC), i32, ctypes.POINTER(Sim3OptResultC)]
+    L.orbhip_optimize_essential_graph.argtypes = [vp, ctypes.POINTER(EssentialGraphProblemC),
+                                                  ctypes.POINTER(EssentialGraphResultC)]
     L.orbhip_kfdb_create.argtypes = [vp, i32, ctypes.POINTER(vp)]
     L.orbhip_kfdb_destroy.argtypes = [vp]
     L.orbhip_kfdb_add.argtypes = [vp, i32, vp, vp, i32]
@@ -348,6 +363,9 @@ def lib():
     # the device error word) and a plan's cell table: tests compare every stage with the oracle
     L.orbhip_test_extract_debug.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
     L.orbhip_test_cells.argtypes = [vp, i32, i32, vp, i32]
+    # host only: OptimizeEssentialGraph's argument check; n, the solver route and H's block count
+    L.orbhip_test_essential_graph_check.argtypes = [ctypes.POINTER(EssentialGraphProblemC),
+                                                    ctypes.POINTER(EssentialGraphResultC), vp]
     _lib = L
     return L
 

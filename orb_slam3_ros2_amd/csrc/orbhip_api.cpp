@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <vector>
@@ -15,6 +16,7 @@
 #include "orbhip_ba.h"
 #include "pose_opt.h"
 #include "sim3_opt.h"
+#include "essential_graph.h"
 #include "proj.h"
 #include "kfdb.h"
 #include "ba_chol_blocked.h"
@@ -45,6 +47,8 @@ struct orbhip_ctx {
     StageBlock fuse_stage{false};   // Fuse's, Fuse with a Sim3's and the Sim3 projection search's
     StageBlock sim3_stage{false};   // Sim3Solver's
     StageBlock sim3_opt_stage{false};   // OptimizeSim3's
+    StageBlock eg_stage{false};     // OptimizeEssentialGraph's
+    EgWorkspace* eg = nullptr;      // its dense system and solver buffers (created with the first call)
     StageTimer timer;
     GraphCache graphs;   // replays of repeated per-frame launch sequences (graph_cache.h)
 };
@@ -151,6 +155,7 @@ int orbhip_destroy(orbhip_ctx* c) {
     if (c->stream) dag_stream_retired(c->stream);   // before the stream goes: no solve may wait on it
     pose_ws_destroy(c->pose);
     proj_ws_destroy(c->proj);
+    eg_ws_destroy(c->eg);
     extract_ws_destroy(c->ext);
     match_ws_destroy(c->match);
     bow_ws_destroy(c->bow);
@@ -279,7 +284,7 @@ int orbhip_launch_graphs(orbhip_ctx* c) {
 }
 
 int orbhip_profile_stage(orbhip_ctx* c, int stage) {
-    if (!c || stage < 0 || stage > 13 || stage == 12) return ORBHIP_ERR_ARG;   // 12 is no stage: callers rely on its refusal
+    if (!c || stage < 0 || stage > 15 || stage == 12 || stage == 14) return ORBHIP_ERR_ARG;   // 12 and 14 are no stages: callers rely on their refusal
     HIPOK(hipSetDevice(c->device));
     StageTimer& t = c->timer;
     if (!t.created) {
@@ -779,6 +784,15 @@ int orbhip_optimize_sim3_batch(orbhip_ctx* c, const orbhip_sim3_opt_problem* pro
     return sim3_opt_batch(c->sim3_opt_stage, c->timer, c->stream, probs, B, res);
 }
 
+// ---- LoopClosing: OptimizeEssentialGraph ----
+int orbhip_optimize_essential_graph(orbhip_ctx* c, const orbhip_essential_graph_problem* prob,
+                                    orbhip_essential_graph_result* res) {
+    if (!c) return ORBHIP_ERR_ARG;
+    HIPOK(hipSetDevice(c->device));
+    if (!c->eg) c->eg = eg_ws_create();
+    return eg_optimize(c->eg, c->eg_stage, c->timer, c->stream, prob, res);
+}
+
 int orbhip_optimize_sim3(orbhip_ctx* c, const orbhip_sim3_opt_problem* prob, orbhip_sim3_opt_result* res) {
     if (!prob || !res) return ORBHIP_ERR_ARG;
     const int rc = orbhip_optimize_sim3_batch(c, prob, 1, res);
@@ -788,6 +802,21 @@ int orbhip_optimize_sim3(orbhip_ctx* c, const orbhip_sim3_opt_problem* prob, orb
 // the stored list capacity of the Sim3 projection search; the resolve has no round cap other than
 // (points with a list) + 1 (tests assert that their chain is deeper than the capacity)
 int orbhip_test_sim3_list_cap(void) { return kSim3ListCap; }
+
+// host only: OptimizeEssentialGraph's argument check, and for a problem it accepts the size of its
+// system, the solver route (0 dag, 1 blocked) and the number of blocks of H's lower triangle
+int orbhip_test_essential_graph_check(const orbhip_essential_graph_problem* prob,
+                                      const orbhip_essential_graph_result* res, int32_t* out3) {
+    const int rc = eg_check(prob, res);
+    if (rc || !out3) return rc;
+    EgStructure s;
+    eg_structure(prob, s);
+    const char* env = std::getenv("ORBHIP_EG_BLOCKED");
+    out3[0] = s.n;
+    out3[1] = ((env && env[0] == '1') || s.n < kEgDagMinN) ? 1 : 0;
+    out3[2] = (int32_t)s.blocks.size();
+    return ORBHIP_OK;
+}
 
 // ---- test hooks (not part of the reference surface) ----
 int orbhip_test_cholesky(const double* A, const double* b, double* x, int n, unsigned long long* phases5,

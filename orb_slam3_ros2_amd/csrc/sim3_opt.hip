@@ -26,6 +26,7 @@
 #include "../../include/orbhip.h"
 #include "ba_se3.h"
 #include "orbhip_kernels.h"
+#include "sim3_dev.h"
 #include "sim3_opt.h"
 #include "stage.h"
 #include "wave_f64.h"
@@ -39,101 +40,6 @@ namespace {
 constexpr int kAcc = 36;     // 28 upper-triangle H + 7 b + chi2
 constexpr int kChunk = 18;   // sums reduced per pass of the partial table
 constexpr int kPert = 14 * 16;   // 14 perturbed estimates, each (S, S^-1) as 2 x 8 doubles
-
-struct S3 {
-    DQ q;
-    double tx, ty, tz, s;
-};
-
-__device__ __forceinline__ S3 s3_load(const double* p) { return S3{DQ{p[0], p[1], p[2], p[3]}, p[4], p[5], p[6], p[7]}; }
-__device__ __forceinline__ void s3_store(const S3& a, double* p) {
-    p[0] = a.q.x; p[1] = a.q.y; p[2] = a.q.z; p[3] = a.q.w;
-    p[4] = a.tx; p[5] = a.ty; p[6] = a.tz; p[7] = a.s;
-}
-
-// g2o::Sim3::operator*: (a.r b.r, a.s (a.r b.t) + a.t, a.s b.s); no normalisation
-__device__ __forceinline__ S3 s3_mul(const S3& a, const S3& b) {
-    S3 r;
-    r.q = DQ{a.q.w * b.q.x + a.q.x * b.q.w + a.q.y * b.q.z - a.q.z * b.q.y,
-             a.q.w * b.q.y + a.q.y * b.q.w + a.q.z * b.q.x - a.q.x * b.q.z,
-             a.q.w * b.q.z + a.q.z * b.q.w + a.q.x * b.q.y - a.q.y * b.q.x,
-             a.q.w * b.q.w - a.q.x * b.q.x - a.q.y * b.q.y - a.q.z * b.q.z};
-    double x, y, z;
-    qrot(a.q, b.tx, b.ty, b.tz, x, y, z);
-    r.tx = a.s * x + a.tx; r.ty = a.s * y + a.ty; r.tz = a.s * z + a.tz;
-    r.s = a.s * b.s;
-    return r;
-}
-
-// g2o::Sim3::inverse: (r*, r* ((-1 / s) t), 1 / s)
-__device__ __forceinline__ S3 s3_inv(const S3& a) {
-    S3 r;
-    r.q = DQ{-a.q.x, -a.q.y, -a.q.z, a.q.w};
-    const double k = -1.0 / a.s;
-    qrot(r.q, k * a.tx, k * a.ty, k * a.tz, r.tx, r.ty, r.tz);
-    r.s = 1.0 / a.s;
-    return r;
-}
-
-// g2o::Sim3(const Vector7d&), u = (omega, upsilon, sigma): the four branches of sim3.h
-__device__ __forceinline__ S3 s3_exp(const double* u) {
-    const double ox = u[0], oy = u[1], oz = u[2], sigma = u[6];
-    const double theta = sqrt(ox * ox + oy * oy + oz * oz);
-    const double O[9] = {0.0, -oz, oy, oz, 0.0, -ox, -oy, ox, 0.0};
-    double O2[9];
-#pragma unroll
-    for (int r = 0; r < 3; r++)
-#pragma unroll
-        for (int c = 0; c < 3; c++) O2[3 * r + c] = O[3 * r] * O[c] + O[3 * r + 1] * O[3 + c] + O[3 * r + 2] * O[6 + c];
-    const double s = exp(sigma);
-    const double eps = 0.00001;
-    double A, B, C, ka = 1.0, kb = 1.0;   // R = (I + ka Omega) + kb Omega^2
-    const bool small = theta < eps;
-    double st = 0.0, ct = 1.0;
-    if (!small) {
-        sincos(theta, &st, &ct);
-        ka = st / theta;
-        kb = (1 - ct) / (theta * theta);
-    }
-    if (fabs(sigma) < eps) {
-        C = 1.0;
-        if (small) {
-            A = 1.0 / 2.0;
-            B = 1.0 / 6.0;
-        } else {
-            const double theta2 = theta * theta;
-            A = (1 - ct) / theta2;
-            B = (theta - st) / (theta2 * theta);
-        }
-    } else {
-        C = (s - 1) / sigma;
-        if (small) {
-            const double sigma2 = sigma * sigma;
-            A = ((sigma - 1) * s + 1) / sigma2;
-            B = ((0.5 * sigma2 - sigma + 1) * s) / (sigma2 * sigma);
-        } else {
-            const double a = s * st, b = s * ct;
-            const double theta2 = theta * theta, sigma2 = sigma * sigma;
-            const double c = theta2 + sigma2;
-            A = (a * sigma + (1 - b) * theta) / (theta * c);
-            B = (C - ((b - 1) * sigma + a * theta) / c) * 1.0 / theta2;
-        }
-    }
-    double R[9], Wm[9];
-#pragma unroll
-    for (int i = 0; i < 9; i++) {
-        const double id = i % 4 == 0 ? 1.0 : 0.0;
-        R[i] = small ? (id + O[i]) + O2[i] : (id + ka * O[i]) + kb * O2[i];
-        Wm[i] = (A * O[i] + B * O2[i]) + C * id;
-    }
-    S3 r;
-    r.q = mattoq(R);
-    r.tx = Wm[0] * u[3] + Wm[1] * u[4] + Wm[2] * u[5];
-    r.ty = Wm[3] * u[3] + Wm[4] * u[4] + Wm[5] * u[5];
-    r.tz = Wm[6] * u[3] + Wm[7] * u[4] + Wm[8] * u[5];
-    r.s = s;
-    return r;
-}
 
 // e = obs - cam.project(S.map(X)); project = (x / z fx + cx, y / z fy + cy)
 __device__ __forceinline__ void proj_err(const S3& S, const double* X, const double* obs, const double* cam, double& e0,

@@ -14,8 +14,8 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import (BAProblemC, BAResultC, BAStereoProblemC, Context, PoseProblemC, PoseResultC, PoseStereoProblemC,
-                   Sim3OptProblemC, Sim3OptResultC, check, lib, ptr)
+from ._lib import (BAProblemC, BAResultC, BAStereoProblemC, Context, EssentialGraphProblemC, EssentialGraphResultC,
+                   PoseProblemC, PoseResultC, PoseStereoProblemC, Sim3OptProblemC, Sim3OptResultC, check, lib, ptr)
 
 TH_HUBER_MONO = float(np.sqrt(np.float32(5.991)))
 TH_HUBER_STEREO = float(np.sqrt(np.float32(7.815)))
@@ -208,6 +208,53 @@ class Sim3Result:
     n_bad: int                  # pairs removed after the first round
     lm_trials: int
     keep: np.ndarray            # [N] uint8: 0 where upstream sets vpMatches1[idx] = NULL
+
+
+@dataclass
+class EssentialGraphProblem:
+    """The graph Optimizer::OptimizeEssentialGraph builds from the Map, as arrays: VertexSim3Expmap
+    estimates as g2o::Sim3 rows (Eigen's quaternion x, y, z, w, then t, then s; never renormalised) in
+    the caller's order (recommended: keyframe id), the fixed flags, EdgeSim3 (i, j, Sji) edges with
+    vertex(0) = i and vertex(1) = j, and the map points with their reference vertex."""
+    S: np.ndarray               # [V,8] float64
+    fixed: np.ndarray           # [V] uint8
+    edge_ij: np.ndarray         # [E,2] int32
+    edge_S: np.ndarray          # [E,8] float64: the measurement Sji
+    fix_scale: bool = False
+    iterations: int = 20
+    lambda_init: float = 1e-16
+    points: np.ndarray | None = None      # [M,3] float32
+    point_ref: np.ndarray | None = None   # [M] int32
+
+    def normalized(self) -> "EssentialGraphProblem":
+        c = lambda a, dt, shape: np.ascontiguousarray(a, dtype=dt).reshape(shape)  # noqa: E731
+        pts = c(self.points if self.points is not None else np.zeros((0, 3)), np.float32, (-1, 3))
+        ref = c(self.point_ref if self.point_ref is not None else np.zeros(0), np.int32, -1)
+        p = EssentialGraphProblem(c(self.S, np.float64, (-1, 8)), c(self.fixed, np.uint8, -1),
+                                  c(self.edge_ij, np.int32, (-1, 2)), c(self.edge_S, np.float64, (-1, 8)),
+                                  bool(self.fix_scale), int(self.iterations), float(self.lambda_init), pts, ref)
+        if p.S.shape[0] != p.fixed.shape[0] or p.edge_ij.shape[0] != p.edge_S.shape[0] or \
+                pts.shape[0] != ref.shape[0]:
+            raise ValueError("EssentialGraphProblem: S / fixed, edge_ij / edge_S and points / point_ref need "
+                             "the same lengths")
+        return p
+
+    def to_c(self) -> EssentialGraphProblemC:
+        return EssentialGraphProblemC(self.S.shape[0], ptr(self.S), ptr(self.fixed), self.edge_ij.shape[0],
+                                      ptr(self.edge_ij), ptr(self.edge_S), int(self.fix_scale), self.iterations,
+                                      self.lambda_init, self.points.shape[0], ptr(self.points), ptr(self.point_ref))
+
+
+@dataclass
+class EssentialGraphResult:
+    S: np.ndarray               # [V,8] float64: the corrected Siw (fixed vertices bit for bit the input)
+    points: np.ndarray          # [M,3] float32: the corrected map points
+    chi2_initial: float
+    chi2_final: float
+    iterations_run: int
+    lm_trials: int
+    lm_rejected: int
+    solver: int                 # 0 the persistent tiled solver, 1 the blocked one, 2 blocked after a timeout
 
 
 @dataclass
@@ -423,3 +470,17 @@ class Optimizer:
         check(lib().orbhip_optimize_sim3_batch(self.ctx.handle, cprobs, len(ps), cres), "orbhip_optimize_sim3_batch")
         return [Sim3Result(np.array(r.q[:]), np.array(r.t[:]), r.s, r.n_in, r.n_bad, r.lm_trials, k)
                 for r, k in zip(cres, keeps)]
+
+    # ---- CorrectLoop's / MergeLocal's pose graph ----
+    def OptimizeEssentialGraph(self, prob: EssentialGraphProblem) -> EssentialGraphResult:
+        """U:src/Optimizer.cc::Optimizer::OptimizeEssentialGraph and the map-point correction that
+        follows it (orbhip_optimize_essential_graph)."""
+        p = prob.normalized()
+        S = np.zeros_like(p.S)
+        pts = np.zeros_like(p.points)
+        pc, r = p.to_c(), EssentialGraphResultC()
+        r.S, r.points = ptr(S), ptr(pts)
+        check(lib().orbhip_optimize_essential_graph(self.ctx.handle, ctypes.byref(pc), ctypes.byref(r)),
+              "orbhip_optimize_essential_graph")
+        return EssentialGraphResult(S, pts, r.chi2_initial, r.chi2_final, r.iterations_run, r.lm_trials,
+                                    r.lm_rejected, r.solver)

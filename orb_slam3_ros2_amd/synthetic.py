@@ -1394,3 +1394,101 @@ def synthetic_sim3_opt_problem(n=100, outlier_frac=0.2, seed=0, fix_scale=False,
                        (1.0 / s2[oct1]).astype(np.float32), (1.0 / s2[oct2]).astype(np.float32), cams[0], cams[1],
                        _mat_to_quat(R0), t0, float(s0), 10.0, bool(fix_scale))
     return prob, dict(R=R, t=t, s=s, bad=bad | by_proj, by_projection=by_proj)
+
+
+# ---------------------------------------------------------------------------
+# OptimizeEssentialGraph problems (CorrectLoop's pose graph)
+# ---------------------------------------------------------------------------
+def _s3(R, t, s):
+    """(R, t, s) as a g2o::Sim3 row: Eigen's quaternion (x, y, z, w), t, s."""
+    return np.concatenate([_mat_to_quat(R), np.asarray(t, np.float64), [float(s)]])
+
+
+def _s3_parts(a):
+    x, y, z, w = a[0:4]
+    R = np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                  [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                  [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
+    return R, a[4:7], a[7]
+
+
+def _s3_mul(a, b):
+    Ra, ta, sa = _s3_parts(a)
+    Rb, tb, sb = _s3_parts(b)
+    return _s3(Ra @ Rb, sa * (Ra @ tb) + ta, sa * sb)
+
+
+def _s3_inv(a):
+    R, t, s = _s3_parts(a)
+    return _s3(R.T, -(R.T @ t) / s, 1.0 / s)
+
+
+def synthetic_essential_graph(n_kf=100, k_covis=3, loop_span=5, drift=0.01, scale_drift=0.002, fix_scale=False,
+                              seed=0, n_points=0):
+    """The graph CorrectLoop hands to OptimizeEssentialGraph after a loop over n_kf keyframes on a
+    closed trajectory (a circle of radius 5 looking along the motion). The tracked poses accumulate a
+    Sim3 drift per step: `drift` rad of rotation, `drift` of the step length in translation and a
+    relative `scale_drift` of the map's scale (none when fix_scale). Vertices are in keyframe-id order
+    and keyframe 0 is fixed. The last loop_span keyframes (the current keyframe's neighbourhood) carry
+    corrected estimates (upstream's CorrectedSim3: Sic * Scw_corrected, the loop's Sim3 carried
+    through the tracked relative poses), every other one its tracked SE3 pose as a Sim3 with s = 1.
+    Edges, each (i, j, Sji) with i > j: the chain spanning tree (i, i - 1), covisibility edges to the
+    k_covis keyframes before the parent, both measured from the tracked (non-corrected) poses as
+    upstream computes Sji = Sjw * Swi; and loop-connection edges from the last loop_span keyframes to
+    the first ones, measured from the estimates (upstream's vScw). n_points map points hang off random
+    reference keyframes, in front of their tracked cameras. Returns (EssentialGraphProblem,
+    dict(true = the true Scw rows, tracked = the non-corrected rows, corrected = the corrected ids))."""
+    from .optimizer import EssentialGraphProblem
+    rng = np.random.default_rng(seed)
+    n = int(n_kf)
+    span = max(1, min(int(loop_span), n // 2))
+    ang = 2 * np.pi * np.arange(n) / n
+    true = []
+    for a in ang:   # camera at (5 cos a, 0, 5 sin a), z along the tangent
+        zc = np.array([-np.sin(a), 0.0, np.cos(a)])
+        yc = np.array([0.0, 1.0, 0.0])
+        xc = np.cross(yc, zc)
+        Rwc = np.stack([xc, yc, zc], 1)
+        twc = np.array([5 * np.cos(a), 0.0, 5 * np.sin(a)])
+        true.append(_s3(Rwc.T, -Rwc.T @ twc, 1.0))
+    tracked = [true[0].copy()]
+    sc = 1.0
+    for k in range(1, n):
+        rel = _s3_mul(true[k], _s3_inv(true[k - 1]))
+        R, t, _ = _s3_parts(rel)
+        if not fix_scale:
+            sc *= 1.0 + scale_drift * float(rng.normal())
+        Rn = _rodrigues(rng.normal(size=3) * drift) @ R
+        tn = sc * t + rng.normal(size=3) * drift * np.linalg.norm(t)
+        tracked.append(_s3_mul(_s3(Rn, tn, 1.0), tracked[k - 1]))
+    cur = n - 1
+    Rc, tc, _ = _s3_parts(true[cur])
+    Scw = _s3(Rc, sc * tc, sc)            # the loop's Sim3 of the current keyframe
+    S = [t.copy() for t in tracked]
+    corrected = list(range(n - span, n))
+    for i in corrected:
+        S[i] = _s3_mul(_s3_mul(tracked[i], _s3_inv(tracked[cur])), Scw)
+    ij, Sji = [], []
+    for i in range(1, n):
+        for j in range(i - 1, max(-1, i - 2 - int(k_covis)), -1):
+            ij.append((i, j))
+            Sji.append(_s3_mul(tracked[j], _s3_inv(tracked[i])))
+    for a, i in enumerate(corrected):
+        for j in (a, a + 1):
+            if j < span and j < n - span:
+                ij.append((i, j))
+                Sji.append(_s3_mul(S[j], _s3_inv(S[i])))
+    fixed = np.zeros(n, np.uint8)
+    fixed[0] = 1
+    pts, ref = None, None
+    if n_points:
+        ref = rng.integers(0, n, int(n_points)).astype(np.int32)
+        Xc = np.stack([rng.uniform(-1.5, 1.5, n_points), rng.uniform(-1.0, 1.0, n_points),
+                       rng.uniform(2.0, 6.0, n_points)], 1)
+        pts = np.empty((int(n_points), 3), np.float32)
+        for m in range(int(n_points)):
+            R, t, s = _s3_parts(_s3_inv(tracked[ref[m]]))
+            pts[m] = s * (R @ Xc[m]) + t
+    prob = EssentialGraphProblem(np.array(S), fixed, np.array(ij, np.int32).reshape(-1, 2),
+                                 np.array(Sji).reshape(-1, 8), bool(fix_scale), 20, 1e-16, pts, ref)
+    return prob, dict(true=np.array(true), tracked=np.array(tracked), corrected=corrected)
