@@ -247,7 +247,8 @@ int orbhip_frontend_context(orbhip_frontend* fe, int j, orbhip_ctx** out);
  * the resolve of one call form one pair, 10 the triangulation of CreateNewMapPoints: k_tri_points
  * and k_tri_claim of one call form one pair, 11 Sim3Solver: k_sim3_ransac and k_sim3_select of one
  * call form one pair, 13 OptimizeSim3: k_sim3_opt, 15 OptimizeEssentialGraph: the first to the last kernel of
- * one call form one pair; 12 and 14 are no stages and are refused). orbhip_profile_collect synchronises and
+ * one call form one pair, 16 TwoViewReconstruction: the four launches of one call form one pair;
+ * 12 and 14 are no stages and are refused). orbhip_profile_collect synchronises and
  * returns the summed duration (ms) and the number of bracketed launches, then resets. The one-launch
  * pyramid (k_pyr_cone) and the octree also time themselves on the device (first workgroup start to
  * last workgroup end, s_memrealtime: the span rocprofv3's kernel trace reports); their stages
@@ -836,6 +837,71 @@ typedef struct {                   /* the pointers are the caller's */
 int orbhip_sim3_solve_batch(orbhip_ctx* ctx, const orbhip_sim3_problem* probs, int B, orbhip_sim3_result* res);
 /* B = 1 */
 int orbhip_sim3_solve(orbhip_ctx* ctx, const orbhip_sim3_problem* prob, orbhip_sim3_result* res);
+
+/* ---- Tracking: TwoViewReconstruction (monocular initialisation) --------------------------
+ * U:src/TwoViewReconstruction.cc (Tracking::MonocularInitialization, between SearchForInitialization
+ * and CreateInitialMapMonocular). Both RANSACs (homography and fundamental matrix), the model
+ * choice, the motion hypotheses and their CheckRT for every frame pair of a call (DESIGN.md
+ * "TwoViewReconstruction" has the operation order).
+ *
+ * A problem is what upstream's Reconstruct receives: the undistorted keypoints of the two frames
+ * (only x and y are read), matches12 = vMatches12 (n1 entries, -1 = unmatched), K as (fx, fy, cx,
+ * cy), sigma = mSigma and n_hyp = mMaxIterations. mvMatches12 is the list of pairs (i, matches12[i])
+ * with a match, in index order; N is its length. The library draws no random numbers: sets holds
+ * n_hyp sets of 8 indices into [0, N), drawn by the caller as upstream draws them.
+ *
+ * Per set h and model: Normalize (once per problem, upstream's running fp32 sums), ComputeH21 /
+ * ComputeF21 with the null vector from a fixed number of fp64 Jacobi sweeps on the system's 9x9 Gram
+ * matrix, CheckHomography / CheckFundamental over all N matches in fp32. The score is the sum of
+ * upstream's fp32 terms, added in fp64 (exact, hence order-free) and rounded once. best_h / best_f =
+ * the first hypothesis whose score is above every earlier one, from 0 (-1: none; a NaN score never
+ * wins); SH / SF its score, H21 / F21 its matrix, inliers_h / inliers_f (optional, N bytes, by match)
+ * its vbMatchesInliers. model = 0 (H) when SH / (SH + SF) > 0.50, else 1 (F); -1 when SH + SF == 0,
+ * which fails. ReconstructH (the eight Faugeras hypotheses, none at the d1/d2, d2/d3 exit) or
+ * ReconstructF (the four of DecomposeE) with minParallax = 1.0 and minTriangulated = 50: per motion
+ * hypothesis m CheckRT gives n_good[m], cos_sel[m] (the min(50, n_good - 1)-th smallest cosine, by
+ * counting) and parallax[m] in degrees (through the device's acosf); chosen = the accepted
+ * hypothesis or -1. On success R21 / t21 are its motion, p3d[3 i ..] the point of keypoint i of
+ * frame 1 where CheckRT counted it (0 elsewhere) and triangulated[i] = vbTriangulated[i]; on failure
+ * R21, t21, p3d and triangulated are 0.
+ *
+ * Returns the number of problems that succeeded. B = 0: 0. B > 64, N > 8192 or n_hyp > 4096:
+ * ORBHIP_ERR_UNSUPPORTED. ORBHIP_ERR_ARG, before anything is uploaded and with no output touched: N <
+ * 8, n_hyp < 1, a NULL required pointer, a matches12 entry outside [-1, n2), a set index outside
+ * [0, N) or repeated within its set, a focal length or sigma that is not positive and finite. One
+ * upload, four launches, one read-back. */
+typedef struct {
+    int32_t n1, n2;                /* keypoints of frame 1 / 2 */
+    const orbhip_kp* kps1;         /* n1, undistorted */
+    const orbhip_kp* kps2;         /* n2 */
+    const int32_t* matches12;      /* n1: index into kps2, or -1 */
+    float K[4];                    /* fx, fy, cx, cy */
+    float sigma;
+    int32_t n_hyp;
+    const int32_t* sets;           /* n_hyp x 8 */
+} orbhip_two_view_problem;
+
+typedef struct {                   /* the pointers are the caller's */
+    float* p3d;                    /* n1 x 3 */
+    uint8_t* triangulated;         /* n1 */
+    uint8_t* inliers_h;            /* N, or NULL */
+    uint8_t* inliers_f;            /* N, or NULL */
+    int32_t success;
+    int32_t model;                 /* 0 = H, 1 = F, -1 = neither */
+    int32_t best_h, best_f;        /* hypothesis index, or -1 */
+    int32_t chosen;                /* motion hypothesis index, or -1 */
+    float SH, SF;
+    float H21[9], F21[9];          /* row-major */
+    float R21[9], t21[3];
+    int32_t n_good[8];
+    float parallax[8];
+    float cos_sel[8];
+} orbhip_two_view_result;
+
+int orbhip_two_view_reconstruct_batch(orbhip_ctx* ctx, const orbhip_two_view_problem* probs, int B,
+                                      orbhip_two_view_result* res);
+/* B = 1 */
+int orbhip_two_view_reconstruct(orbhip_ctx* ctx, const orbhip_two_view_problem* prob, orbhip_two_view_result* res);
 
 /* ---- LoopClosing: Optimizer::OptimizeSim3 (the Sim3 refinement between the two projection searches)
  * U:src/Optimizer.cc::OptimizeSim3 (LoopClosing::DetectCommonRegionsFromBoW step 4 and the end of

@@ -625,6 +625,73 @@ private:
     bool solved_ = false;
 };
 
+// U:include/TwoViewReconstruction.h — the homography / fundamental-matrix RANSAC of monocular
+// initialisation, the model choice and the motion recovery in one device call
+// (orbhip_two_view_reconstruct). The adapter passes the undistorted keypoints of
+// the two frames and vMatches12 as Tracking holds them, and the 8-sets from DrawSets.
+class TwoViewReconstruction {
+public:
+    // K as (fx, fy, cx, cy); sigma and iterations as upstream's constructor takes them
+    TwoViewReconstruction(const float K[4], float sigma = 1.0f, int iterations = 200)
+        : mSigma(sigma), mMaxIterations(iterations) {
+        std::memcpy(mK, K, sizeof mK);
+    }
+
+    // upstream's draw from a fresh vAvailableIndices per iteration; RandomInt(lo, hi), both ends
+    // included (upstream calls DUtils::Random::SeedRandOnce(0) first). N = the number of matches
+    template <class RandomInt>
+    static std::vector<int32_t> DrawSets(int N, int H, RandomInt&& randint) {
+        if (N < 8) throw Error(ORBHIP_ERR_ARG, "TwoViewReconstruction::DrawSets: N < 8");
+        std::vector<int32_t> out((size_t)H * 8), avail;
+        for (int h = 0; h < H; h++) {
+            avail.resize(N);
+            for (int i = 0; i < N; i++) avail[i] = i;
+            for (int k = 0; k < 8; k++) {
+                const int r = randint(0, (int)avail.size() - 1);
+                out[(size_t)8 * h + k] = avail[r];
+                avail[r] = avail.back();
+                avail.pop_back();
+            }
+        }
+        return out;
+    }
+
+    // Reconstruct(vKeys1, vKeys2, vMatches12, T21, vP3D, vbTriangulated): T21 row-major 4 x 4, vP3D
+    // n1 x 3; vSets: at least mMaxIterations x 8 indices into the matches in index order. The
+    // diagnostics of the call stay in `last`.
+    bool Reconstruct(orbhip_ctx* ctx, const std::vector<orbhip_kp>& vKeys1, const std::vector<orbhip_kp>& vKeys2,
+                     const std::vector<int>& vMatches12, const std::vector<int32_t>& vSets, float T21[16],
+                     std::vector<float>& vP3D, std::vector<bool>& vbTriangulated) {
+        if (vMatches12.size() != vKeys1.size()) throw Error(ORBHIP_ERR_ARG, "TwoViewReconstruction: vMatches12");
+        if (vSets.size() < (size_t)mMaxIterations * 8) throw Error(ORBHIP_ERR_ARG, "TwoViewReconstruction: vSets");
+        const std::vector<int32_t> m(vMatches12.begin(), vMatches12.end());
+        orbhip_two_view_problem p{};
+        p.n1 = (int32_t)vKeys1.size(); p.n2 = (int32_t)vKeys2.size();
+        p.kps1 = vKeys1.data(); p.kps2 = vKeys2.data(); p.matches12 = m.data();
+        std::memcpy(p.K, mK, sizeof mK);
+        p.sigma = mSigma; p.n_hyp = mMaxIterations; p.sets = vSets.data();
+        vP3D.assign(vKeys1.size() * 3, 0.f);
+        std::vector<uint8_t> tri(vKeys1.size(), 0);
+        last = orbhip_two_view_result{};
+        last.p3d = vP3D.data(); last.triangulated = tri.data();
+        check(orbhip_two_view_reconstruct(ctx, &p, &last), "orbhip_two_view_reconstruct");
+        last.p3d = nullptr; last.triangulated = nullptr;
+        vbTriangulated.assign(tri.begin(), tri.end());
+        for (int i = 0; i < 3; i++) {
+            for (int j = 0; j < 3; j++) T21[4 * i + j] = last.R21[3 * i + j];
+            T21[4 * i + 3] = last.t21[i];
+            T21[12 + i] = 0.f;
+        }
+        T21[15] = 1.f;
+        return last.success != 0;
+    }
+
+    float mK[4];
+    float mSigma;
+    int mMaxIterations;
+    orbhip_two_view_result last{};
+};
+
 // U:include/KeyFrameDatabase.h — the device database; slots stand for KeyFrames.
 class KeyFrameDatabase {
 public:

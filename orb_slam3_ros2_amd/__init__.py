@@ -17,6 +17,7 @@ Host-side mirror of the reference's hot-path interfaces over th
   ORBmatcher.Fuse(kfs, points, ...)                                         U:src/ORBmatcher.cc
   ORBmatcher.FuseSim3 / SearchByProjectionSim3(...)   (LoopClosing)         U:src/ORBmatcher.cc
   Sim3Solver(...).solve(triples) / iterate(n) / solve_batch   (LoopClosing)  U:src/Sim3Solver.cc
+  TwoViewReconstruction(K).Reconstruct(keys1, keys2, matches, sets)   (Tracking)  U:src/TwoViewReconstruction.cc
   Optimizer.OptimizeSim3(Sim3Problem) / OptimizeSim3_batch   (LoopClosing)   U:src/Optimizer.cc
   Optimizer.OptimizeEssentialGraph(EssentialGraphProblem)    (CorrectLoop)   U:src/Optimizer.cc
   KeyFrameDatabase(max_kf).DetectRelocalizationCandidates / DetectNBestCandidates
@@ -43,7 +44,8 @@ from .frontend import FrameStream  # noqa: F401
 from .camera import PinholeCamera  # noqa: F401
 from .stereo import StereoFrame, stereo_frame  # noqa: F401
 from .sim3solver import Sim3Solver, draw_triples  # noqa: F401
+from .two_view import TwoViewReconstruction, draw_sets  # noqa: F401
 
-__all__ = ["Sim3Solver", "draw_triples", "StereoFrame", "stereo_frame", "ORBextractor", "KeyPoint", "ORBmatcher", "Optimizer", "BAProblem", "StereoBAProblem", "BAResult", "PoseProblem", "PoseResult", "Sim3Problem", "Sim3Result", "EssentialGraphProblem", "EssentialGraphResult", "ORBVocabulary", "KeyFrameDatabase", "FrameStream", "PinholeCamera",
+__all__ = ["Sim3Solver", "draw_triples", "TwoViewReconstruction", "draw_sets", "StereoFrame", "stereo_frame", "ORBextractor", "KeyPoint", "ORBmatcher", "Optimizer", "BAProblem", "StereoBAProblem", "BAResult", "PoseProblem", "PoseResult", "Sim3Problem", "Sim3Result", "EssentialGraphProblem", "EssentialGraphResult", "ORBVocabulary", "KeyFrameDatabase", "FrameStream", "PinholeCamera",
            "OrbHipError",
            "lib", "library_path"]

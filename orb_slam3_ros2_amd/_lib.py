@@ -157,6 +157,21 @@ class Sim3ResultC(ctypes.Structure):
                 ("sel", ctypes.c_float * 13), ("converged", ctypes.c_int32), ("best", ctypes.c_int32)]
 
 
+class TwoViewProblemC(ctypes.Structure):
+    _fields_ = [("n1", ctypes.c_int32), ("n2", ctypes.c_int32), ("kps1", ctypes.c_void_p), ("kps2", ctypes.c_void_p),
+                ("matches12", ctypes.c_void_p), ("K", ctypes.c_float * 4), ("sigma", ctypes.c_float),
+                ("n_hyp", ctypes.c_int32), ("sets", ctypes.c_void_p)]
+
+
+class TwoViewResultC(ctypes.Structure):
+    _fields_ = [("p3d", ctypes.c_void_p), ("triangulated", ctypes.c_void_p), ("inliers_h", ctypes.c_void_p),
+                ("inliers_f", ctypes.c_void_p), ("success", ctypes.c_int32), ("model", ctypes.c_int32),
+                ("best_h", ctypes.c_int32), ("best_f", ctypes.c_int32), ("chosen", ctypes.c_int32),
+                ("SH", ctypes.c_float), ("SF", ctypes.c_float), ("H21", ctypes.c_float * 9),
+                ("F21", ctypes.c_float * 9), ("R21", ctypes.c_float * 9), ("t21", ctypes.c_float * 3),
+                ("n_good", ctypes.c_int32 * 8), ("parallax", ctypes.c_float * 8), ("cos_sel", ctypes.c_float * 8)]
+
+
 class Sim3OptProblemC(ctypes.Structure):
     _fields_ = [("n", ctypes.c_int32), ("X1c", ctypes.c_void_p), ("X2c", ctypes.c_void_p), ("obs1", ctypes.c_void_p),
                 ("obs2", ctypes.c_void_p), ("inv_sigma2_1", ctypes.c_void_p), ("inv_sigma2_2", ctypes.c_void_p),
@@ -205,6 +220,7 @@ EXPORTED = ["orbhip_abi_version", "orbhip_create", "orbhip_destroy", "orbhip_lev
             "orbhip_triangulate_matches_stereo",
             "orbhip_fuse_sim3", "orbhip_search_by_projection_sim3",
             "orbhip_sim3_solve", "orbhip_sim3_solve_batch",
+            "orbhip_two_view_reconstruct", "orbhip_two_view_reconstruct_batch",
             "orbhip_optimize_sim3", "orbhip_optimize_sim3_batch", "orbhip_optimize_essential_graph",
             "orbhip_kfdb_create", "orbhip_kfdb_destroy", "orbhip_kfdb_add", "orbhip_kfdb_erase",
             "orbhip_kfdb_detect_relocalization", "orbhip_kfdb_detect_nbest",
@@ -313,6 +329,9 @@ def lib():
                                                    vp, vp, vp]
     L.orbhip_sim3_solve.argtypes = [vp, ctypes.POINTER(Sim3ProblemC), ctypes.POINTER(Sim3ResultC)]
     L.orbhip_sim3_solve_batch.argtypes = [vp, ctypes.POINTER(Sim3ProblemC), i32, ctypes.POINTER(Sim3ResultC)]
+    L.orbhip_two_view_reconstruct.argtypes = [vp, ctypes.POINTER(TwoViewProblemC), ctypes.POINTER(TwoViewResultC)]
+    L.orbhip_two_view_reconstruct_batch.argtypes = [vp, ctypes.POINTER(TwoViewProblemC), i32,
+                                                    ctypes.POINTER(TwoViewResultC)]
     L.orbhip_optimize_sim3.argtypes = [vp, ctypes.POINTER(Sim3OptProblemC), ctypes.POINTER(Sim3OptResultC)]
     L.orbhip_optimize_sim3_batch.argtypes = [vp, ctypes.POINTER(Sim3OptProblemC), i32, ctypes.POINTER(Sim3OptResultC)]
     L.orbhip_optimize_essential_graph.argtypes = [vp, ctypes.POINTER(EssentialGraphProblemC),

@@ -47,6 +47,7 @@ struct orbhip_ctx {
     StageBlock fuse_stage{false};   // Fuse's, Fuse with a Sim3's and the Sim3 projection search's
     StageBlock sim3_stage{false};   // Sim3Solver's
     StageBlock sim3_opt_stage{false};   // OptimizeSim3's
+    StageBlock two_view_stage{false};   // TwoViewReconstruction's
     StageBlock eg_stage{false};     // OptimizeEssentialGraph's
     EgWorkspace* eg = nullptr;      // its dense system and solver buffers (created with the first call)
     StageTimer timer;
@@ -284,7 +285,7 @@ int orbhip_launch_graphs(orbhip_ctx* c) {
 }
 
 int orbhip_profile_stage(orbhip_ctx* c, int stage) {
-    if (!c || stage < 0 || stage > 15 || stage == 12 || stage == 14) return ORBHIP_ERR_ARG;   // 12 and 14 are no stages: callers rely on their refusal
+    if (!c || stage < 0 || stage > 16 || stage == 12 || stage == 14) return ORBHIP_ERR_ARG;   // 12 and 14 are no stages: callers rely on their refusal
     HIPOK(hipSetDevice(c->device));
     StageTimer& t = c->timer;
     if (!t.created) {
@@ -774,6 +775,19 @@ int orbhip_sim3_solve_batch(orbhip_ctx* c, const orbhip_sim3_problem* probs, int
 int orbhip_sim3_solve(orbhip_ctx* c, const orbhip_sim3_problem* prob, orbhip_sim3_result* res) {
     if (!prob || !res) return ORBHIP_ERR_ARG;
     return orbhip_sim3_solve_batch(c, prob, 1, res);
+}
+
+// ---- Tracking: TwoViewReconstruction, every frame pair of a call ----
+int orbhip_two_view_reconstruct_batch(orbhip_ctx* c, const orbhip_two_view_problem* probs, int B,
+                                      orbhip_two_view_result* res) {
+    if (!c) return ORBHIP_ERR_ARG;
+    HIPOK(hipSetDevice(c->device));
+    return two_view_batch(c->two_view_stage, c->timer, c->stream, probs, B, res);
+}
+
+int orbhip_two_view_reconstruct(orbhip_ctx* c, const orbhip_two_view_problem* prob, orbhip_two_view_result* res) {
+    if (!prob || !res) return ORBHIP_ERR_ARG;
+    return orbhip_two_view_reconstruct_batch(c, prob, 1, res);
 }
 
 // ---- LoopClosing: OptimizeSim3, every candidate's refinement in one launch ----

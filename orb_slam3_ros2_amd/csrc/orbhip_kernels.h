@@ -250,6 +250,11 @@ int sim3_search(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_f
 constexpr int kSim3MaxBatch = 64;   // problems (candidate keyframes) per call
 int sim3_solve_batch(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_sim3_problem* probs, int B,
                      orbhip_sim3_result* res);
+// TwoViewReconstruction (two_view_kernels.hip): both RANSACs, the model choice, the motion hypotheses
+// and CheckRT of every frame pair; stage 16
+constexpr int kTvMaxBatch = 64;   // frame pairs per call
+int two_view_batch(StageBlock& S, StageTimer& timer, hipStream_t st, const orbhip_two_view_problem* probs, int B,
+                   orbhip_two_view_result* res);
 
 // ---- ingest ----
 void launch_bgr2gray(const uint8_t* src, int B, int w, int h, int sstride, int64_t sfstride, uint8_t* dst, int dstride,

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "geom.h"
+#include "jacobi4.h"
 #include "orbhip_device.h"
 #include "orbhip_kernels.h"
 #include "rot_filter.h"
@@ -428,28 +429,6 @@ static void tri_camera(const orbhip_tri_keyframe& k, TriCam& c) {
     for (int i = 0; i < 3; i++) c.t[i] = k.pose_t[i];
     for (int i = 0; i < 3; i++) c.Ow[i] = -((c.R[i] * c.t[0] + c.R[3 + i] * c.t[1]) + c.R[6 + i] * c.t[2]);
     c.fx = k.fx; c.fy = k.fy; c.cx = k.cx; c.cy = k.cy; c.pad = 0.f;
-}
-
-// one rotation of the one-sided Jacobi on the columns (P, Q) of U (4x4, row-major), applied to V too
-template <int P, int Q>
-__device__ __forceinline__ void tri_jacobi_pair(double (&U)[16], double (&V)[16]) {
-    const double a = ((U[P] * U[P] + U[4 + P] * U[4 + P]) + U[8 + P] * U[8 + P]) + U[12 + P] * U[12 + P];
-    const double b = ((U[Q] * U[Q] + U[4 + Q] * U[4 + Q]) + U[8 + Q] * U[8 + Q]) + U[12 + Q] * U[12 + Q];
-    const double g = ((U[P] * U[Q] + U[4 + P] * U[4 + Q]) + U[8 + P] * U[8 + Q]) + U[12 + P] * U[12 + Q];
-    if (g == 0.0) return;
-    const double zeta = (b - a) / (2.0 * g);
-    double t = 1.0 / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-    if (zeta < 0.0) t = -t;
-    const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const double x = U[4 * i + P], y = U[4 * i + Q];
-        U[4 * i + P] = c * x - s * y;
-        U[4 * i + Q] = s * x + c * y;
-        const double vx = V[4 * i + P], vy = V[4 * i + Q];
-        V[4 * i + P] = c * vx - s * vy;
-        V[4 * i + Q] = s * vx + c * vy;
-    }
 }
 
 // The stereo members of one feature and its keyframe (DESIGN.md "Stereo LocalMapping")

@@ -1492,3 +1492,74 @@ def synthetic_essential_graph(n_kf=100, k_covis=3, loop_span=5, drift=0.01, scal
     prob = EssentialGraphProblem(np.array(S), fixed, np.array(ij, np.int32).reshape(-1, 2),
                                  np.array(Sji).reshape(-1, 8), bool(fix_scale), 20, 1e-16, pts, ref)
     return prob, dict(true=np.array(true), tracked=np.array(tracked), corrected=corrected)
+
+
+# ---------------------------------------------------------------------------
+# TwoViewReconstruction problems (monocular initialisation)
+# ---------------------------------------------------------------------------
+def synthetic_two_view_scene(kind="general", n=300, seed=0, outlier_frac=0.1, noise_px=0.3, unmatched_frac=0.0,
+                             n_hyp=200, sigma=1.0, cam=None, doubled=False, plane=(5.0, 0.25, -0.15),
+                             t_mean=(0.45, 0.05, 0.08)):
+    """What Tracking::MonocularInitialization hands to TwoViewReconstruction::Reconstruct: the
+    undistorted keypoints of two frames (x, y; float32), vMatches12 (n1 entries, -1 = unmatched), K
+    as (fx, fy, cx, cy), and n_hyp 8-sets drawn by draw_sets from a seeded generator. n matches; kind:
+    "general" (points in a volume, a sideways baseline), "planar" (points on a tilted plane),
+    "mixed" (half on the plane, half in the volume), "rotation" (no baseline) or "low_parallax" (a
+    baseline of a thousandth of the depth). A share outlier_frac of the matches point at unrelated
+    places of frame 2, the inliers carry noise_px pixels of noise, and a share unmatched_frac of extra
+    keypoints of frame 1 have no match. Also the true (R21, t21 with unit norm) and the outlier flags
+    per match.
+
+    doubled: every match occurs twice (matches 2k and 2k + 1 have equal coordinates, as keypoints
+    found on two pyramid levels do) and every set holds four such twins. Four distinct points fix a
+    homography but leave the fundamental matrix's system five null directions, so its hypotheses are
+    poor: with upstream's RH > 0.50 this is how a homography wins, which it never does when both
+    models are fitted to sound sets (CheckFundamental rejects less than CheckHomography)."""
+    from .two_view import draw_sets
+    rng = np.random.default_rng(seed)
+    c = dict(D435I) if cam is None else dict(cam)
+    fx, fy, cx, cy = (float(c[k]) for k in ("fx", "fy", "cx", "cy"))
+    X = np.stack([rng.uniform(-2.0, 2.0, n), rng.uniform(-1.5, 1.5, n), rng.uniform(3.0, 9.0, n)], 1)
+    plane = plane[0] + plane[1] * X[:, 0] + plane[2] * X[:, 1]   # z = z0 + a x + b y
+    if kind == "planar":
+        X[:, 2] = plane
+    elif kind == "mixed":
+        X[::2, 2] = plane[::2]
+    R = _rodrigues(np.array([0.02, -0.05, 0.03]) + rng.normal(size=3) * 0.01)
+    t = np.array(t_mean, float) + rng.normal(size=3) * 0.02
+    if kind == "rotation":
+        t = np.zeros(3)
+    elif kind == "low_parallax":
+        t = t * 0.01
+    elif kind not in ("general", "planar", "mixed"):
+        raise ValueError(f"unknown kind {kind!r}")
+    X2 = X @ R.T + t
+    p1 = np.stack([fx * X[:, 0] / X[:, 2] + cx, fy * X[:, 1] / X[:, 2] + cy], 1)
+    p2 = np.stack([fx * X2[:, 0] / X2[:, 2] + cx, fy * X2[:, 1] / X2[:, 2] + cy], 1)
+    p1 += rng.normal(size=p1.shape) * noise_px
+    p2 += rng.normal(size=p2.shape) * noise_px
+    out = rng.random(n) < outlier_frac
+    p2[out] = np.stack([rng.uniform(20.0, 2 * cx - 20.0, n), rng.uniform(20.0, 2 * cy - 20.0, n)], 1)[out]
+    if doubled:
+        if n % 2 or n < 8:
+            raise ValueError("doubled needs an even n >= 8")
+        p1[1::2], p2[1::2], out[1::2] = p1[0::2], p2[0::2], out[0::2]
+    n_extra = int(round(unmatched_frac * n))
+    n1 = n + n_extra
+    slots = np.sort(rng.choice(n1, n, replace=False))          # the matched keypoints of frame 1
+    kps1 = np.stack([rng.uniform(20.0, 2 * cx - 20.0, n1), rng.uniform(20.0, 2 * cy - 20.0, n1)], 1)
+    kps1[slots] = p1
+    perm = rng.permutation(n)                                   # frame 2 holds them in another order
+    kps2 = np.empty((n, 2))
+    kps2[perm] = p2
+    matches12 = np.full(n1, -1, np.int32)
+    matches12[slots] = perm
+    draw = np.random.default_rng(seed + 7919)
+    sets = draw_sets(n, n_hyp, lambda lo, hi: int(draw.integers(lo, hi + 1)))
+    if doubled:
+        twins = draw_sets(n // 2, n_hyp, lambda lo, hi: int(draw.integers(lo, hi + 1)))[:, :4]
+        sets = np.stack([2 * twins, 2 * twins + 1], 2).reshape(n_hyp, 8).astype(np.int32)
+    nt = np.linalg.norm(t)
+    return dict(kps1=kps1.astype(np.float32), kps2=kps2.astype(np.float32), matches12=matches12,
+                K=np.array([fx, fy, cx, cy], np.float32), sigma=float(sigma), sets=sets, outlier=out,
+                true_R=R, true_t=t / nt if nt > 0 else t, kind=kind)
